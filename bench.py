@@ -8,7 +8,7 @@ rank, i.e. over the whole 1e5-site workload at N = 1 (25 calls of bvc_lrt_dense:
 EM/LRT kernel -> result records in HBM).  A tile (8 GB) is 30x the 256 MiB Infinity Cache, so every call
 streams from HBM.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 N > 1 (BASELINE.json configs[3]): the SAME 1e5 x 1e6 workload is split by site, rank r owns
@@ -16,9 +16,12 @@ shard_range(1e5, r, N) (basevarc_amd/sharding.py) -- strong scaling, no collecti
 torch.distributed (nccl = RCCL) is used only for the barriers and the max-over-ranks of the time.
 `--scaling weak` gives every rank its own 1e5 sites instead.
 
-After the headline region rank 0 (N = 1 only) runs short legs over the other single-GPU configurations, each
-reported as a sub-record of "legs" with its own roofline: configs[1] (1e4 x 1e4, EM-bound), configs[4]
-(k = 5 groups, both sample orders) and the ragged (CSR) entry point at 10 % coverage; then the CPU baseline.
+A plain run sets up, warms up, times the K steps, writes the last step's records if --dump-outputs is given
+(DIR/site_<field>.npy, float64) and prints the result line.  Everything else is measured only with --full:
+the streaming-read ceiling of the roofline, the same steps with every subset run, and (rank 0, N = 1 only)
+short legs over the other single-GPU configurations, each reported as a sub-record of "legs" with its own
+roofline: configs[1] (1e4 x 1e4, EM-bound), configs[4] (k = 5 groups, both sample orders) and the ragged
+(CSR) entry point at 10 % coverage; then the CPU baseline.
 """
 import argparse
 import hashlib
@@ -65,9 +68,14 @@ def parse():
     p.add_argument("--row-align", type=int, default=128, help="row stride of the tiles is a multiple of this many bytes")
     p.add_argument("--scaling", choices=("strong", "weak"), default="strong")
     p.add_argument("--seed", type=int, default=1)
-    p.add_argument("--cpu-sites", type=int, default=-1, help="sites for the CPU baseline (-1: one per core, 0: skip)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: the streaming-read ceiling, the steps with every subset "
+                        "run, the legs and the CPU baseline (off: set up, warm up, time the steps, print the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the records of the last step as DIR/<name>.npy (float64; rank 0's sites)")
+    p.add_argument("--cpu-sites", type=int, default=-1, help="--full: sites for the CPU baseline (-1: one per core, 0: skip)")
     p.add_argument("--no-verify", action="store_true", help="CPU leg: time the baseline only, skip the wider check")
-    p.add_argument("--no-legs", action="store_true", help="skip the configs[1] / configs[4] / CSR legs")
+    p.add_argument("--no-legs", action="store_true", help="--full: skip the configs[1] / configs[4] / CSR legs")
     p.add_argument("--packed", action="store_true",
                    help="headline region on packed tiles (one byte per sample, bvc_lrt_dense_packed): an additive layout, "
                         "NOT the BASELINE metric's -- for profiling that kernel")
@@ -225,13 +233,16 @@ def main():
         t = tiles[i][0]
         return t.as_strided((tile_sizes[i], t.stride(0)), (t.stride(0), 1))
     probe = sorted({0, n_tiles // 2, n_tiles - 1})
-    reads_before = [ctx.stream_read_gbs(whole(i), repeats=3) for i in probe for _ in range(2)]
+    if a.full:
+        reads_before = [ctx.stream_read_gbs(whole(i), repeats=3) for i in probe for _ in range(2)]
     for _ in range(a.warmup):
         step()
     barrier()
-    reads = sorted(ctx.stream_read_gbs(whole(i), repeats=3) for i in probe for _ in range(3))
-    empirical_gbs, empirical_median = max(reads[-1], max(reads_before)), reads[len(reads) // 2]
-    barrier()
+    empirical_gbs = empirical_median = None                      # (--full only)
+    if a.full:
+        reads = sorted(ctx.stream_read_gbs(whole(i), repeats=3) for i in probe for _ in range(3))
+        empirical_gbs, empirical_median = max(reads[-1], max(reads_before)), reads[len(reads) // 2]
+        barrier()
     log("timed region")
     ctx.set_profiling(a.profile_every <= 1)
     ctx.profile(reset=True)
@@ -267,10 +278,12 @@ def main():
 
     log(f"timed region done: {dt * 1e3:.1f} ms for {a.steps} steps")
     value = a.steps * sites_per_step_all / dt
-    # For the record, outside the timed region and on one GPU only: the same steps with every subset of every level run
+    if a.dump_outputs and rank == 0:        # the records of the last timed step, before anything else reuses the buffers
+        dump_outputs(a.dump_outputs, results, grp_results, a.groups, lo, np)
+    # For the record (--full), outside the timed region and on one GPU only: the same steps with every subset of every level run
     # (em_prune = 0, the E+M passes the reference runs).  The headline is bound by the histogram pass either way.
     value_all_run = None
-    if world == 1:
+    if world == 1 and a.full:
         ctx.join(); ctx.set_tuning("em_prune", 0)
         extra = max(2, a.steps // 4)
         step(); ctx.join(); torch.cuda.synchronize()
@@ -338,9 +351,9 @@ def main():
         last = results_from_tensor(results[0])
         out["em_passes_per_site"] = float(last["n_passes"].mean())
         out["called_fraction"] = float(last["called"].mean())
-    if rank == 0 and world == 1 and not a.no_legs and a.groups == 0 and a.coverage >= 1 and not a.packed:
+    if rank == 0 and world == 1 and a.full and not a.no_legs and a.groups == 0 and a.coverage >= 1 and not a.packed:
         out["legs"] = run_legs(ctx, a, tiles, tile_sizes, stride, min_af, np, torch, dev)
-    if rank == 0 and world == 1 and a.cpu_sites != 0:
+    if rank == 0 and world == 1 and a.full and a.cpu_sites != 0:
         # CPU leg (the only place the oracle is used here): the reference path's CPU port timed on a bounded sample
         # of the same workload, and -- since its answers are at hand -- checked against the GPU records of those
         # sites and of a wider sample through the oracle's histogram form.
@@ -368,6 +381,37 @@ def main():
         dist.barrier()
         dist.destroy_process_group()
     ctx.close()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(path, results, grp_results, k, lo, np):
+    """--dump-outputs: the records the timed path handed back in its last step, one float64 array per field of bvc_site_result
+    (site_<field>.npy, a row per site) and in group mode of bvc_group_result (group_<field>.npy, sites x k), with the sites'
+    indices in the workload (site_index.npy).  The inputs depend only on the arguments (--seed), so two builds can be compared
+    array by array.  Above 64 MB in all, a fixed sample of the sites (seed 0, in site order) is written instead of every site."""
+    from basevarc_amd.lib import GROUP_DTYPE, SITE_DTYPE
+    rec = np.concatenate([r.cpu().numpy().view(SITE_DTYPE) for r in results])
+    grp = None
+    if grp_results is not None:
+        grp = np.concatenate([g.cpu().numpy().view(GROUP_DTYPE).reshape(-1, k) for g in grp_results])
+    gfields = [f for f in GROUP_DTYPE.names if f != "pad"]
+    per_site = 1 + sum(int(np.prod(SITE_DTYPE[f].shape)) for f in SITE_DTYPE.names)
+    if grp is not None:
+        per_site += k * sum(int(np.prod(GROUP_DTYPE[f].shape)) for f in gfields)
+    keep = (DUMP_LIMIT_BYTES - 64 * 128) // (8 * per_site)         # (128 bytes of .npy header per file)
+    pick = np.arange(len(rec))
+    if len(rec) > keep:
+        pick = np.sort(np.random.default_rng(0).choice(len(rec), keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "site_index.npy"), (lo + pick).astype(np.float64))
+    for f in SITE_DTYPE.names:
+        np.save(os.path.join(path, f"site_{f}.npy"), rec[f][pick].astype(np.float64))
+    if grp is not None:
+        for f in gfields:
+            np.save(os.path.join(path, f"group_{f}.npy"), grp[f][pick].astype(np.float64))
+    log(f"outputs of the last step: {len(pick)} of {len(rec)} sites written to {path}")
 
 
 # ------------------------------------------------------------------------------------------------ legs

@@ -261,7 +261,7 @@ def region_reference(ref_at, rg_s, rg_e, buf=1000):
 
 def main():
     from oracle import orc
-    from tests.golden.golden_io import save_golden
+    from tests.golden.golden_io import save_golden, savez
     chrom, start, end = REGION
     rg_s, rg_e = start, end - 1
     pv = list(range(rg_s, rg_e + 1))
@@ -293,7 +293,7 @@ def main():
     # positions kept alongside (small)
     z = dict(np.load(os.path.join(os.path.dirname(__file__), "testdata_pileup.npz")))
     z["positions"] = np.array(positions, dtype=np.int32)
-    np.savez_compressed(os.path.join(os.path.dirname(__file__), "testdata_pileup.npz"), **z)
+    savez(os.path.join(os.path.dirname(__file__), "testdata_pileup.npz"), **z)
     depth = np.array([len(b) for b, _, _ in sites])
     print(f"{len(sites)} sites from {n_samples} samples ({names[0]} ...), depth {depth.min()}..{depth.max()} "
           f"(mean {depth.mean():.1f}), {sum(e['called'] for e in exp)} called, "

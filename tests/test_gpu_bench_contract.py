@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_prints_one_json_line_with_the_contract_keys():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "1",
-                        "--samples", "200000", "--total-sites", "8000", "--tile-sites", "2000", "--cpu-sites", "2"],
+                        "--samples", "200000", "--total-sites", "8000", "--tile-sites", "2000", "--cpu-sites", "2", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -87,6 +87,50 @@ def test_bench_prints_one_json_line_with_the_contract_keys():
     # the ragged histogram pass is reported twice: underneath stage 2 and with the chip to itself (faster alone)
     hr = legs["csr_coverage10pct"]["hist_roofline"]
     assert 0 < hr["frac"] <= hr["alone"]["frac"] * 1.05 and hr["alone"]["launches_timed"] >= 8
+
+
+def test_plain_bench_times_only_the_headline_and_dumps_the_last_step(tmp_path):
+    """Without --full the line has the headline and nothing that takes runs of its own; --dump-outputs writes the records of the
+    last timed step, the same arrays from run to run, and they are the oracle's records of the generator's sites."""
+    import numpy as np
+    from oracle import orc
+
+    def run(d):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--samples", "200000", "--total-sites", "8000", "--tile-sites", "2000", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, lines
+        return json.loads(lines[0])
+    d = run(tmp_path / "a")
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in d, k
+    assert d["steps"] == 3 and d["unit"] == "sites/s" and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(8000 / (d["ms_per_step"] / 1e3), rel=1e-3)
+    assert "legs" not in d and "cpu_baseline" not in d and d["value_with_every_subset_run"] is None
+    assert d["roofline"]["empirical_stream_read_GBs"] is None and 0 < d["roofline"]["frac"] < 1
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert "site_index.npy" in files and "site_var_qual.npy" in files and "site_called.npy" in files
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64_000_000
+    a = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 and len(v) == 8000 for v in a.values())
+    assert np.array_equal(a["site_index.npy"], np.arange(8000))
+    run(tmp_path / "b")
+    for f in files:
+        assert np.array_equal(a[f], np.load(tmp_path / "b" / f), equal_nan=True), f
+    n = 200000
+    min_af = min(0.001, 100.0 / n)
+    called = [int(i) for i in np.flatnonzero(a["site_called.npy"] == 1)[:3]]
+    assert called
+    for s in [0, 1999, 2000, 7999] + called:
+        b, q, r = orc.synth_tile(1, s, 1, n)
+        e = orc.hist_lrt(orc.dense_hist(b[0], q[0]), int(r[0]), min_af)
+        na = int(a["site_n_alt.npy"][s])
+        assert int(a["site_called.npy"][s]) == e["called"] and [int(x) for x in a["site_depth.npy"][s]] == e["depth"], s
+        assert [int(x) for x in a["site_alt_base.npy"][s][:na]] == e["alt_base"], s
+        assert np.allclose(a["site_af.npy"][s][:na], e["af"], rtol=0, atol=1e-6), s
+        assert abs(a["site_var_qual.npy"][s] - e["var_qual"]) <= max(1e-6, 1e-6 * abs(e["var_qual"])), s
 
 
 def test_bench_under_the_drivers_multi_gpu_launcher_two_ranks_sharing_the_card():

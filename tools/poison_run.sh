@@ -22,7 +22,7 @@ tail -3 $O/pytest_gpu.log
 echo "pytest rc=$rc" > $O/verdict
 if [ $rc = 0 ]; then
   # the bench's phases (headline warm-up included) under the same build; short, once
-  timeout -k 10 600 python bench.py --steps 2 --warmup 1 --cpu-sites 0 > $O/bench.json 2> $O/bench.err || rc=$?
+  timeout -k 10 600 python bench.py --full --steps 2 --warmup 1 --cpu-sites 0 > $O/bench.json 2> $O/bench.err || rc=$?
   echo "bench rc=$rc" >> $O/verdict
   python -c "import json,sys; d=json.loads(open('$O/bench.json').read().strip().split('\n')[-1]); print('bench lds_violations:', d.get('diagnostic_build'))" >> $O/verdict 2>&1
 fi

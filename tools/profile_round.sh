@@ -15,13 +15,13 @@ O=$R/gpurun_out/$TAG/${PART}_$(date +%m%d_%H%M%S)
 mkdir -p $O
 cd $R
 if [ $PART = all ] || [ $PART = trace ]; then
-python bench.py > $O/bench_overlap.json 2> $O/bench_overlap.err
-python bench.py --no-overlap --cpu-sites 0 --no-legs > $O/bench_serial.json 2> $O/bench_serial.err
+python bench.py --full > $O/bench_overlap.json 2> $O/bench_overlap.err
+python bench.py --full --no-overlap --cpu-sites 0 --no-legs > $O/bench_serial.json 2> $O/bench_serial.err
 cd /tmp && export TMPDIR=/tmp
 Q="--cpu-sites 0 --no-verify --no-legs"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_overlap -- python3 $R/bench.py --steps 4 --warmup 1 $Q > $O/trace_overlap.log 2>&1
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_serial -- python3 $R/bench.py --steps 4 --warmup 1 $Q --no-overlap > $O/trace_serial.log 2>&1
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_legs -- python3 $R/bench.py --steps 1 --warmup 1 --cpu-sites 0 --no-verify > $O/trace_legs.log 2>&1
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_legs -- python3 $R/bench.py --full --steps 1 --warmup 1 --cpu-sites 0 --no-verify > $O/trace_legs.log 2>&1
 fi
 cd /tmp && export TMPDIR=/tmp
 Q="--cpu-sites 0 --no-verify --no-legs"

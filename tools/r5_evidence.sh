@@ -4,11 +4,11 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${1:-r05_evidence}; mkdir -p $O   # (one attempt per tag: a second one goes to <tag>_<time>, never over a log)
 [ -f $O/seeds.jsonl ] && O=${O}_$(date +%H%M%S) && mkdir -p $O
-python bench.py --verify-all --no-legs --cpu-sites 32 > $O/verify_all_config3.json 2> $O/verify_all_config3.err
+python bench.py --full --verify-all --no-legs --cpu-sites 32 > $O/verify_all_config3.json 2> $O/verify_all_config3.err
 python bench.py --groups 5 --verify-all --no-legs --cpu-sites 0 --steps 4 > $O/verify_groups_interleaved.json 2> $O/verify_groups_interleaved.err
 python bench.py --groups 5 --group-layout ordered --verify-all --no-legs --cpu-sites 0 --steps 4 > $O/verify_groups_ordered.json 2> $O/verify_groups_ordered.err
 for s in 1 2 3; do python bench.py --seed $s --cpu-sites 0 --no-legs 2>/dev/null >> $O/seeds.jsonl; done
-for r in 1 2 3 4 5; do python bench.py --cpu-sites 0 2>/dev/null >> $O/repeat5.jsonl; done
+for r in 1 2 3 4 5; do python bench.py --full --cpu-sites 0 2>/dev/null >> $O/repeat5.jsonl; done
 python tools/verify_packed.py > $O/packed_equals_two_byte_all_sites.json 2> $O/packed_equals_two_byte.err
 O=$O python - <<'PY'
 import json, os
