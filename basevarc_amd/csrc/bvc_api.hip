@@ -3,6 +3,7 @@
 // compute entry point launches the HIP kernels or fails with an error code.
 #include <hip/hip_runtime.h>
 
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,33 @@
 #include "bvc_internal.h"
 
 using namespace bvc;
+
+// Device scratch of a context: grown by ensure(), freed with the context.
+struct DevBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// bvc_pileup_begin / bvc_pileup_begin_bgzf / bvc_pileup_finish: their device buffers and the tile between the calls.
+struct PileupState {
+    DevBuf text, meta, out, called;    // the tile's text, its line tables and counts, its parsed columns and records, the called entries
+    // tiles inflated on the device (bvc_pileup_begin_bgzf): two text buffers (what a tile leaves of a batch is carried from one to the
+    // other), the compressed bytes, what the calls left of every batch
+    DevBuf pz_text[2], pz_comp;
+    int pz_cur = 0;                    // the buffer that holds the leftovers
+    std::vector<uint32_t> left_src, left_len;
+    struct Tile {                      // what a begin call leaves for the finish call; every begin starts from Tile{}
+        PileupTile P;
+        bool begun = false;
+        int64_t entries = 0, obs = 0, indels = 0;
+        int64_t text_bytes = 0, indel_bytes = 0;
+        bool on_device_text = false;
+    } tile;
+};
 
 struct bvc_ctx {
     int device = -1;
@@ -30,8 +58,7 @@ struct bvc_ctx {
     // histogram pass of call i+1 waits only for the EM of call i-2 (long finished), never for the one running
     // beside it, so both streams run back to back.
     static constexpr int kRing = 4;
-    uint32_t *d_cnt[kRing] = {};
-    size_t cnt_cap[kRing] = {};
+    DevBuf d_cnt[kRing];
     // overlap mode: stage 2 of call i runs on `side` while stage 1 of call i+1 streams on `stream`
     bool overlap = false;
     hipStream_t side = nullptr;        // stage 2 of even calls
@@ -41,43 +68,25 @@ struct bvc_ctx {
     hipEvent_t ev_hist_done[kRing] = {};
     hipEvent_t ev_em_done[kRing] = {};
     bool em_pending[kRing] = {};
-    uint32_t *d_grp[kRing] = {};   // [sites][groups + 1][512] in group mode
-    size_t grp_cap[kRing] = {};
+    DevBuf d_grp[kRing];               // [sites][groups + 1][512] in group mode
     // item-engine scratch of stage 2 (em_items.hip), one per ring buffer (the stage 2 of consecutive calls may run
     // side by side); the last one serves bvc_lrt_hist on the context's own stream
-    void *d_em[kRing + 1] = {};
-    size_t em_cap[kRing + 1] = {};
-    void *d_emg[kRing] = {};      // the same for the (site, group) pseudo-sites of group calls
-    size_t emg_cap[kRing] = {};
+    DevBuf d_em[kRing + 1];
+    DevBuf d_emg[kRing];               // the same for the (site, group) pseudo-sites of group calls
     uint32_t *d_sink = nullptr;        // 256 bytes: sink of the streaming-read measurement kernel; bvc_pack_dense's counter at byte 64
-    uint8_t *d_grp_labels = nullptr;   // group mode: the call's group vector clamped to 0..n_groups (hist_kernel.hip)
-    size_t grp_labels_cap = 0;
+    DevBuf d_grp_labels;               // group mode: the call's group vector clamped to 0..n_groups (hist_kernel.hip)
     int64_t *d_grp_scratch = nullptr;  // group mode: "samples ordered by group" flag + column bounds (hist_kernel.hip)
     // staging for BVC_PTR_HOST calls: two sets, so that the upload of chunk i+1 (copy stream) runs under the kernels
     // of chunk i
-    char *d_stage[2] = {nullptr, nullptr};
-    size_t stage_cap[2] = {0, 0};
+    DevBuf d_stage[2];
     hipStream_t copy = nullptr;
     hipEvent_t ev_upload[2] = {nullptr, nullptr};
     hipEvent_t ev_set_free[2] = {nullptr, nullptr};   // ragged host calls: the kernels that read staging set k have finished
-    // bvc_pileup_begin / bvc_pileup_finish: the tile's text, its line tables and counts, its parsed columns and records
-    char *d_pl_text = nullptr, *d_pl_meta = nullptr, *d_pl_out = nullptr, *d_pl_called = nullptr;
-    size_t pl_text_cap = 0, pl_meta_cap = 0, pl_out_cap = 0, pl_called_cap = 0;
-    // tiles inflated on the device (bvc_pileup_begin_bgzf): two text buffers (what a tile leaves of a batch is carried from one to the
-    // other), the compressed bytes, what the calls left of every batch
-    char *d_pz_text[2] = {nullptr, nullptr}, *d_pz_comp = nullptr;
-    size_t pz_text_cap[2] = {0, 0}, pz_comp_cap = 0;
-    int pz_cur = 0;                    // the buffer that holds the leftovers
-    std::vector<uint32_t> pz_left_src, pz_left_len;
-    int64_t pl_text_bytes = 0, pl_indel_bytes = 0;
-    bool pl_on_device_text = false;
+    PileupState pile;
     // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
     // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
     char *h_up = nullptr, *h_down = nullptr;
     size_t up_cap = 0, down_cap = 0;
-    PileupTile pl;                     // the tile between the two calls
-    bool pl_begun = false;
-    int64_t pl_entries = 0, pl_obs = 0, pl_indels = 0;
     LaunchState ls;                    // launch policy + one-time kernel setup of this context
     bool profiling = false;
     std::vector<hipEvent_t> ev_pool;   // free events
@@ -111,24 +120,45 @@ inline hipError_t wait_stream(bvc_ctx *ctx)
         if (e__ != hipSuccess) return fail((ctx), BVC_ERR_DEVICE, #call, e__);     \
     } while (0)
 
-int ensure(bvc_ctx *ctx, void **buf, size_t *cap, size_t need)
+// Every stream a context enqueues work on.
+std::array<hipStream_t, 5> streams_of(const bvc_ctx *ctx) { return {ctx->stream, ctx->copy, ctx->side, ctx->side_b, ctx->side_c}; }
+
+// A failed call must not leave an upload or a kernel running on the context's buffers: the next call may free or refill
+// them, and stage 2 of what was already launched may still run on the side streams.  Returns `code`.
+int drain_on_error(bvc_ctx *ctx, int code)
 {
-    if (need <= *cap) return BVC_OK;
-    if (*buf) {
+    for (hipStream_t s : streams_of(ctx)) (void)hipStreamSynchronize(s);
+    for (bool &p : ctx->em_pending) p = false;
+    (void)hipGetLastError();
+    return code;
+}
+
+#define BVC_HIP_D(ctx, call)                                                                         \
+    do {                                                                                             \
+        hipError_t e__ = (call);                                                                     \
+        if (e__ != hipSuccess) return drain_on_error((ctx), fail((ctx), BVC_ERR_DEVICE, #call, e__)); \
+    } while (0)
+
+int ensure(bvc_ctx *ctx, DevBuf &buf, size_t need)
+{
+    if (need <= buf.cap) return BVC_OK;
+    if (buf.p) {
         // nothing may still be reading or writing the old buffer: the context's stream, and the copy stream (a staging
         // set may have an upload in flight after a failed host-pointer call)
         BVC_HIP(ctx, hipStreamSynchronize(ctx->stream));
         if (ctx->copy) BVC_HIP(ctx, hipStreamSynchronize(ctx->copy));
-        BVC_HIP(ctx, hipFree(*buf));
-        *buf = nullptr; *cap = 0;
+        BVC_HIP(ctx, hipFree(buf.p));
+        buf.p = nullptr; buf.cap = 0;
     }
     size_t want = need + need / 4;
-    if (hipMalloc(buf, want) != hipSuccess) {
+    void *p = nullptr;
+    if (hipMalloc(&p, want) != hipSuccess) {
         (void)hipGetLastError();
-        if (hipMalloc(buf, need) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, BVC_ERR_ALLOC, "device scratch allocation failed"); }
+        if (hipMalloc(&p, need) != hipSuccess) { (void)hipGetLastError(); return fail(ctx, BVC_ERR_ALLOC, "device scratch allocation failed"); }
         want = need;
     }
-    *cap = want;
+    buf.p = static_cast<char *>(p);
+    buf.cap = want;
     // Fresh device memory holds whatever its last owner left.  No kernel of the library is meant to read scratch it has not
     // written, and so that a slip there can never read another call's (or another process's) leftovers the new buffer is
     // cleared before anything can touch it -- to 0xFF bytes in the -DBVC_POISON build, which makes such a slip loud.
@@ -138,8 +168,36 @@ int ensure(bvc_ctx *ctx, void **buf, size_t *cap, size_t need)
 #else
     constexpr int kFill = 0;
 #endif
-    BVC_HIP(ctx, hipMemsetAsync(*buf, kFill, want, ctx->stream));
+    BVC_HIP(ctx, hipMemsetAsync(buf.p, kFill, want, ctx->stream));
     BVC_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return BVC_OK;
+}
+
+inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+
+// Slices of a device buffer, each starting on a 256-byte boundary: take<T>(count, pad) hands out count elements + pad bytes.
+struct Layout {
+    uintptr_t base = 0;
+    size_t at = 0;
+    template <class T> T *take(size_t count, size_t pad = 0)
+    {
+        T *p = reinterpret_cast<T *>(base + at);
+        at += round256(count * sizeof(T) + pad);
+        return p;
+    }
+};
+
+// Grows `buf` to the slices of `list` (a function of a Layout &) + `slack` bytes and carves it: the one list of take() calls runs
+// once to size the buffer and once to hand out the pointers, so the two cannot disagree.
+template <class List>
+int carve(bvc_ctx *ctx, DevBuf &buf, size_t slack, List list)
+{
+    Layout size;
+    list(size);
+    const int rc = ensure(ctx, buf, size.at + slack);
+    if (rc != BVC_OK) return rc;
+    Layout slices{reinterpret_cast<uintptr_t>(buf.p)};
+    list(slices);
     return BVC_OK;
 }
 
@@ -153,13 +211,18 @@ hipEvent_t take_event(bvc_ctx *ctx)
 
 void give_back(bvc_ctx *ctx, hipEvent_t e) { if (e) ctx->ev_pool.push_back(e); }
 
+void give_back(bvc_ctx *ctx, bvc_ctx::Triple &t)
+{
+    give_back(ctx, t.a); give_back(ctx, t.b); give_back(ctx, t.c); give_back(ctx, t.d);
+    t.a = t.b = t.c = t.d = nullptr;
+}
+
 // Four timing events for one call, or none at all (never a partial set).
 bool take_timing_events(bvc_ctx *ctx, bvc_ctx::Triple &t)
 {
     t.a = take_event(ctx); t.b = take_event(ctx); t.c = take_event(ctx); t.d = take_event(ctx);
     if (t.a && t.b && t.c && t.d) return true;
-    give_back(ctx, t.a); give_back(ctx, t.b); give_back(ctx, t.c); give_back(ctx, t.d);
-    t.a = t.b = t.c = t.d = nullptr;
+    give_back(ctx, t);
     return false;
 }
 
@@ -202,88 +265,101 @@ int em_scratch_for(bvc_ctx *ctx, int slot, int64_t n_sites, double min_af, void 
     *out = nullptr;
     if (ctx->ls.em_engine == 1 || !(min_af > 0.0)) return BVC_OK;
     const size_t need = n_groups > 0 ? em_group_scratch_bytes(n_sites, n_groups) : em_items_scratch_bytes(n_sites);
-    void **buf = n_groups > 0 ? &ctx->d_emg[slot] : &ctx->d_em[slot];
-    size_t *cap = n_groups > 0 ? &ctx->emg_cap[slot] : &ctx->em_cap[slot];
-    if (need > *cap) {
+    DevBuf &buf = n_groups > 0 ? ctx->d_emg[slot] : ctx->d_em[slot];
+    if (need > buf.cap) {
         int rcj = join_side(ctx);
         if (rcj != BVC_OK) return rcj;
     }
-    int rc = ensure(ctx, buf, cap, need);
+    int rc = ensure(ctx, buf, need);
     if (rc != BVC_OK) return rc;
-    *out = *buf;
+    *out = buf.p;
     return BVC_OK;
 }
 
-// The two stages on device pointers.  `stage1(counts)` launches the histogram pass of the call (dense, ragged, ...)
-// on the context's stream into a [n_sites][512] buffer of the ring; stage 2 (EM/LRT) follows on the same stream, or
-// on the side stream behind an event in overlap mode.
+// The ring buffers of one call: [n_sites][512] counts, the [n_sites][n_groups + 1][512] group histograms (group calls)
+// and the item-engine scratch of both (null when stage 2 does not use the engine).
+struct RingSlot {
+    uint32_t *counts = nullptr, *grp = nullptr;
+    void *em = nullptr, *emg = nullptr;
+};
+
+// The two stages of one call on device pointers.  `stage1(hist)` launches the histogram pass (dense, ragged, ...) on the
+// context's stream into a buffer of the ring -- the counts, or with n_groups > 0 the group histograms; `stage2(s2, slot)`
+// launches the EM/LRT on the same stream, or in overlap mode on a side stream (of em_stream(ctx, em_streams)) behind an event.
+template <class Stage1, class Stage2>
+int run_stages(bvc_ctx *ctx, int64_t n_sites, int n_groups, bool zero_counts, double min_af, int em_streams, Stage1 stage1,
+               Stage2 stage2)
+{
+    const size_t cbytes = (size_t)n_sites * BVC_NCLASS * sizeof(uint32_t), gbytes = cbytes * (size_t)(n_groups + 1);
+    const int buf = ctx->overlap ? ctx->flip : 0;
+    if (ctx->overlap) ctx->flip = (ctx->flip + 1) % bvc_ctx::kRing;
+    DevBuf &cnt = ctx->d_cnt[buf], &grp = ctx->d_grp[buf];
+    if (cbytes > cnt.cap || (n_groups > 0 && gbytes > grp.cap)) {   // growing a buffer: nothing may still be reading it
+        int rcj = join_side(ctx);
+        if (rcj != BVC_OK) return rcj;
+    }
+    int rc = ensure(ctx, cnt, cbytes);
+    if (rc == BVC_OK && n_groups > 0) rc = ensure(ctx, grp, gbytes);
+    RingSlot slot;
+    if (rc == BVC_OK) rc = em_scratch_for(ctx, buf, n_sites, min_af, &slot.em);
+    if (rc == BVC_OK && n_groups > 0) rc = em_scratch_for(ctx, buf, n_sites, min_af, &slot.emg, n_groups);
+    if (rc != BVC_OK) return rc;
+    slot.counts = reinterpret_cast<uint32_t *>(cnt.p);
+    if (n_groups > 0) slot.grp = reinterpret_cast<uint32_t *>(grp.p);
+    bvc_ctx::Triple t{nullptr, nullptr, nullptr, nullptr, n_sites};
+    const bool timed = ctx->profiling && take_timing_events(ctx, t);
+    auto enqueue = [&]() -> int {
+        // stage 1 on the context's stream; the histogram buffer is free once the EM that read it has finished
+        if (ctx->overlap && ctx->em_pending[buf]) {
+            BVC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_em_done[buf], 0));
+            ctx->em_pending[buf] = false;
+        }
+        if (zero_counts) BVC_HIP(ctx, hipMemsetAsync(slot.counts, 0, cbytes, ctx->stream));
+        if (timed) BVC_HIP(ctx, hipEventRecord(t.a, ctx->stream));
+        BVC_HIP(ctx, stage1(n_groups > 0 ? slot.grp : slot.counts));
+        if (timed) BVC_HIP(ctx, hipEventRecord(t.b, ctx->stream));
+        // stage 2: same stream, or a side stream behind an event
+        hipStream_t s2 = ctx->stream;
+        if (ctx->overlap) {
+            s2 = em_stream(ctx, em_streams);
+            BVC_HIP(ctx, hipEventRecord(ctx->ev_hist_done[buf], ctx->stream));
+            BVC_HIP(ctx, hipStreamWaitEvent(s2, ctx->ev_hist_done[buf], 0));
+        }
+        if (timed) BVC_HIP(ctx, hipEventRecord(t.c, s2));
+        const int rc2 = stage2(s2, slot);
+        if (rc2 != BVC_OK) return rc2;
+        if (timed) {
+            BVC_HIP(ctx, hipEventRecord(t.d, s2));
+            ctx->ev_pending.push_back(t);
+            t = bvc_ctx::Triple{nullptr, nullptr, nullptr, nullptr, 0};
+            if (ctx->ev_pending.size() > 256) reap_timing(ctx, false);
+        }
+        if (ctx->overlap) {
+            BVC_HIP(ctx, hipEventRecord(ctx->ev_em_done[buf], s2));
+            ctx->em_pending[buf] = true;
+        }
+        return BVC_OK;
+    };
+    rc = enqueue();
+    give_back(ctx, t);                          // an early exit returns the timing events to the pool
+    return rc;
+}
+
+// The two stages of a plain call: stage 2 is the EM/LRT of the counts.
 template <class Stage1>
 int run_two_stages(bvc_ctx *ctx, int64_t n_sites, bool zero_counts, bool long_rows, Stage1 stage1,
                    const int8_t *ref_base, double min_af, const int8_t *comb, const uint8_t *n_comb,
                    bvc_site_result *results, int em_streams_long_rows = 1)
 {
-    const size_t cbytes = (size_t)n_sites * BVC_NCLASS * sizeof(uint32_t);
-    const int buf = ctx->overlap ? ctx->flip : 0;
-    if (ctx->overlap) ctx->flip = (ctx->flip + 1) % bvc_ctx::kRing;
-    uint32_t **counts_p = &ctx->d_cnt[buf];
-    size_t *cap_p = &ctx->cnt_cap[buf];
-    if (cbytes > *cap_p) {                      // growing a buffer: nothing may still be reading it
-        int rcj = join_side(ctx);
-        if (rcj != BVC_OK) return rcj;
-    }
-    int rc = ensure(ctx, reinterpret_cast<void **>(counts_p), cap_p, cbytes);
-    if (rc != BVC_OK) return rc;
-    uint32_t *counts = *counts_p;
-    void *em_scratch = nullptr;
-    rc = em_scratch_for(ctx, buf, n_sites, min_af, &em_scratch);
-    if (rc != BVC_OK) return rc;
-    bvc_ctx::Triple t{nullptr, nullptr, nullptr, nullptr, n_sites};
-    const bool timed = ctx->profiling && take_timing_events(ctx, t);
-    auto bail = [&](int code) {                 // an early exit returns the timing events to the pool
-        give_back(ctx, t.a); give_back(ctx, t.b); give_back(ctx, t.c); give_back(ctx, t.d);
-        return code;
-    };
-#define BVC_HIP_T(call)                                                                     \
-    do {                                                                                    \
-        hipError_t e__ = (call);                                                            \
-        if (e__ != hipSuccess) return bail(fail(ctx, BVC_ERR_DEVICE, #call, e__));          \
-    } while (0)
-
-    // stage 1 on the context's stream; the histogram buffer is free once the EM that read it has finished
-    if (ctx->overlap && ctx->em_pending[buf]) {
-        BVC_HIP_T(hipStreamWaitEvent(ctx->stream, ctx->ev_em_done[buf], 0));
-        ctx->em_pending[buf] = false;
-    }
-    if (zero_counts) BVC_HIP_T(hipMemsetAsync(counts, 0, cbytes, ctx->stream));
-    if (timed) BVC_HIP_T(hipEventRecord(t.a, ctx->stream));
-    BVC_HIP_T(stage1(counts));
-    if (timed) BVC_HIP_T(hipEventRecord(t.b, ctx->stream));
-
-    // stage 2: same stream, or the side stream behind an event
-    hipStream_t s2 = ctx->stream;
-    if (ctx->overlap) {
-        s2 = em_stream(ctx, long_rows ? em_streams_long_rows : 2);
-        BVC_HIP_T(hipEventRecord(ctx->ev_hist_done[buf], ctx->stream));
-        BVC_HIP_T(hipStreamWaitEvent(s2, ctx->ev_hist_done[buf], 0));
-    }
-    if (timed) BVC_HIP_T(hipEventRecord(t.c, s2));
-    // underneath a long streaming pass the EM kernel keeps to a few wave slots; with short rows it is the longer
-    // kernel and takes the chip
-    const bool shared = ctx->overlap && long_rows;
-    BVC_HIP_T(launch_lrt(ctx->ls, s2, n_sites, counts, BVC_NCLASS, ref_base, min_af, ctx->d_lut, comb, n_comb, results, shared, 0,
-                         em_scratch));
-    if (timed) {
-        BVC_HIP_T(hipEventRecord(t.d, s2));
-        ctx->ev_pending.push_back(t);
-        t = bvc_ctx::Triple{nullptr, nullptr, nullptr, nullptr, 0};
-        if (ctx->ev_pending.size() > 256) reap_timing(ctx, false);
-    }
-    if (ctx->overlap) {
-        BVC_HIP_T(hipEventRecord(ctx->ev_em_done[buf], s2));
-        ctx->em_pending[buf] = true;
-    }
-#undef BVC_HIP_T
-    return BVC_OK;
+    return run_stages(ctx, n_sites, 0, zero_counts, min_af, long_rows ? em_streams_long_rows : 2, stage1,
+                      [&](hipStream_t s2, const RingSlot &slot) -> int {
+                          // underneath a long streaming pass the EM kernel keeps to a few wave slots; with short rows it is the
+                          // longer kernel and takes the chip
+                          const bool shared = ctx->overlap && long_rows;
+                          BVC_HIP(ctx, launch_lrt(ctx->ls, s2, n_sites, slot.counts, BVC_NCLASS, ref_base, min_af, ctx->d_lut, comb,
+                                                  n_comb, results, shared, 0, slot.em));
+                          return BVC_OK;
+                      });
 }
 
 int run_dense_device(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride,
@@ -346,47 +422,89 @@ void reap_timing(bvc_ctx *ctx, bool all)
 template <class Upload, class Compute>
 int run_chunks(bvc_ctx *ctx, int64_t n_sites, int64_t chunk, Upload upload, Compute compute)
 {
-    // an early exit must not leave an upload or a kernel running on the staging sets: the next call may free or refill them
-    auto drained = [&](int code) {
-        if (code != BVC_OK) {
-            // stage 2 of the chunks already launched may still run on the side streams and it reads / writes the staging sets
-            (void)hipStreamSynchronize(ctx->copy);
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipStreamSynchronize(ctx->side);
-            (void)hipStreamSynchronize(ctx->side_b);
-            (void)hipStreamSynchronize(ctx->side_c);
-            for (bool &p : ctx->em_pending) p = false;
-            (void)hipGetLastError();
-        }
-        return code;
-    };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
     int set = 0;
     int rc = upload(set, (int64_t)0, n_sites < chunk ? n_sites : chunk);
-    if (rc != BVC_OK) return drained(rc);
-    BVC_HIP_D(hipEventRecord(ctx->ev_upload[set], ctx->copy));
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipEventRecord(ctx->ev_upload[set], ctx->copy));
     for (int64_t s0 = 0; s0 < n_sites; s0 += chunk, set ^= 1) {
         const int64_t ns = n_sites - s0 < chunk ? n_sites - s0 : chunk;
-        BVC_HIP_D(hipStreamWaitEvent(ctx->stream, ctx->ev_upload[set], 0));
+        BVC_HIP_D(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload[set], 0));
         rc = compute(set, s0, ns, /*download=*/false);
-        if (rc != BVC_OK) return drained(rc);
+        if (rc != BVC_OK) return drain_on_error(ctx, rc);
         const int64_t s1 = s0 + chunk;
         if (s1 < n_sites) {
             // the other set's previous chunk (i-1) has been downloaded synchronously below: it is free
             rc = upload(set ^ 1, s1, n_sites - s1 < chunk ? n_sites - s1 : chunk);
-            if (rc != BVC_OK) return drained(rc);
-            BVC_HIP_D(hipEventRecord(ctx->ev_upload[set ^ 1], ctx->copy));
+            if (rc != BVC_OK) return drain_on_error(ctx, rc);
+            BVC_HIP_D(ctx, hipEventRecord(ctx->ev_upload[set ^ 1], ctx->copy));
         }
         rc = compute(set, s0, ns, /*download=*/true);
-        if (rc != BVC_OK) return drained(rc);
-        BVC_HIP_D(hipStreamSynchronize(ctx->stream));
+        if (rc != BVC_OK) return drain_on_error(ctx, rc);
+        BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
     }
-#undef BVC_HIP_D
     return BVC_OK;
+}
+
+// One staging set of a host-pointer dense call (run_dense_host).
+struct DenseSet {
+    int8_t *rows[2] = {nullptr, nullptr};
+    int8_t *ref = nullptr;
+    uint8_t *labels = nullptr;
+    bvc_site_result *res = nullptr;
+    bvc_group_result *gres = nullptr;
+};
+
+// Host-pointer dense tiles (bvc_lrt_dense, bvc_lrt_dense_packed, the group calls): site chunks of at most host_chunk_bytes per
+// array through two staging sets.  `n_rows` row arrays (2: bases and quals, 1: packed rows); with n_groups > 0 the group vector
+// `labels` goes up and the group records come down too.  `device(ns, set)` runs the two stages on a chunk staged in `set`.
+template <class Device>
+int run_dense_host(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride, int n_rows, const int8_t *const rows[2],
+                   const int8_t *ref_base, const uint8_t *labels, int n_groups, bvc_site_result *results, bvc_group_result *grp_results,
+                   Device device)
+{
+    const int64_t row_bytes = row_stride > 0 ? row_stride : 1;
+    int64_t chunk = ctx->ls.host_chunk_bytes / row_bytes;
+    if (chunk < 1) chunk = 1;
+    if (chunk > n_sites) chunk = n_sites;
+    DenseSet sets[2];
+    const int n_sets = n_sites > chunk ? 2 : 1;
+    for (int k = 0; k < n_sets; ++k) {
+        DenseSet &d = sets[k];
+        int rc = carve(ctx, ctx->d_stage[k], 256, [&](Layout &L) {
+            for (int a = 0; a < n_rows; ++a) d.rows[a] = L.take<int8_t>((size_t)chunk * (size_t)row_stride);
+            d.ref = L.take<int8_t>((size_t)chunk);
+            if (n_groups > 0) d.labels = L.take<uint8_t>((size_t)n_samples);
+            d.res = L.take<bvc_site_result>((size_t)chunk);
+            if (n_groups > 0) d.gres = L.take<bvc_group_result>((size_t)chunk * n_groups);
+        });
+        if (rc != BVC_OK) return rc;
+        if (n_rows == 1) d.rows[1] = d.rows[0];
+    }
+    return run_chunks(ctx, n_sites, chunk,
+        [&](int set, int64_t s0, int64_t ns) -> int {
+            const DenseSet &d = sets[set];
+            // the last row may be shorter than row_stride in the caller's allocation: copy exactly what is addressed
+            const size_t bytes = n_samples ? (size_t)(ns - 1) * (size_t)row_stride + (size_t)n_samples : 0;
+            // the group vector travels with the first chunk of each staging set
+            if (n_groups > 0 && s0 < 2 * chunk && n_samples)
+                BVC_HIP(ctx, hipMemcpyAsync(d.labels, labels, (size_t)n_samples, hipMemcpyHostToDevice, ctx->copy));
+            for (int a = 0; a < n_rows && bytes; ++a)
+                BVC_HIP(ctx, hipMemcpyAsync(d.rows[a], rows[a] + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
+            BVC_HIP(ctx, hipMemcpyAsync(d.ref, ref_base + s0, (size_t)ns, hipMemcpyHostToDevice, ctx->copy));
+            return BVC_OK;
+        },
+        [&](int set, int64_t s0, int64_t ns, bool download) -> int {
+            const DenseSet &d = sets[set];
+            if (!download) {
+                int rc = device(ns, d);
+                return rc == BVC_OK ? join_side(ctx) : rc;
+            }
+            BVC_HIP(ctx, hipMemcpyAsync(results + s0, d.res, (size_t)ns * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+            if (n_groups > 0)
+                BVC_HIP(ctx, hipMemcpyAsync(grp_results + s0 * n_groups, d.gres, (size_t)ns * n_groups * sizeof(bvc_group_result),
+                                            hipMemcpyDeviceToHost, ctx->stream));
+            return BVC_OK;
+        });
 }
 
 // Group calls: stage 1 (`stage1(grp_counts)`: one pass, n_groups + 1 histograms per site, [site][n_groups + 1][512]) on the
@@ -396,63 +514,15 @@ template <class Stage1>
 int run_group_stages(bvc_ctx *ctx, int64_t ns, int n_groups, bool long_rows, Stage1 stage1, const int8_t *r, double min_af,
                      bvc_site_result *res, bvc_group_result *gres)
 {
-    const int n_hist = n_groups + 1;
-    const int buf = ctx->overlap ? ctx->flip : 0;
-    if (ctx->overlap) ctx->flip = (ctx->flip + 1) % bvc_ctx::kRing;
-    uint32_t **cp = &ctx->d_cnt[buf];
-    size_t *ccap = &ctx->cnt_cap[buf];
-    uint32_t **gp = &ctx->d_grp[buf];
-    size_t *gcap = &ctx->grp_cap[buf];
-    const size_t cbytes = (size_t)ns * BVC_NCLASS * sizeof(uint32_t), gbytes = cbytes * (size_t)n_hist;
-    if (cbytes > *ccap || gbytes > *gcap) { int rj = join_side(ctx); if (rj != BVC_OK) return rj; }
-    int rc2 = ensure(ctx, reinterpret_cast<void **>(cp), ccap, cbytes);
-    if (rc2 != BVC_OK) return rc2;
-    rc2 = ensure(ctx, reinterpret_cast<void **>(gp), gcap, gbytes);
-    if (rc2 != BVC_OK) return rc2;
-    void *em_scratch = nullptr, *emg_scratch = nullptr;
-    rc2 = em_scratch_for(ctx, buf, ns, min_af, &em_scratch);
-    if (rc2 != BVC_OK) return rc2;
-    rc2 = em_scratch_for(ctx, buf, ns, min_af, &emg_scratch, n_groups);
-    if (rc2 != BVC_OK) return rc2;
-    if (ctx->overlap && ctx->em_pending[buf]) {
-        BVC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_em_done[buf], 0));
-        ctx->em_pending[buf] = false;
-    }
-    bvc_ctx::Triple t{nullptr, nullptr, nullptr, nullptr, ns};
-    const bool timed = ctx->profiling && take_timing_events(ctx, t);
-    auto bail = [&](int code) { give_back(ctx, t.a); give_back(ctx, t.b); give_back(ctx, t.c); give_back(ctx, t.d); return code; };
-#define BVC_HIP_T(call)                                                                     \
-    do {                                                                                    \
-        hipError_t e__ = (call);                                                            \
-        if (e__ != hipSuccess) return bail(fail(ctx, BVC_ERR_DEVICE, #call, e__));          \
-    } while (0)
-    if (timed) BVC_HIP_T(hipEventRecord(t.a, ctx->stream));
-    BVC_HIP_T(stage1(*gp));
-    if (timed) BVC_HIP_T(hipEventRecord(t.b, ctx->stream));
-    hipStream_t s2 = ctx->stream;
-    if (ctx->overlap) {
-        s2 = em_stream(ctx, 2);
-        BVC_HIP_T(hipEventRecord(ctx->ev_hist_done[buf], ctx->stream));
-        BVC_HIP_T(hipStreamWaitEvent(s2, ctx->ev_hist_done[buf], 0));
-    }
-    if (timed) BVC_HIP_T(hipEventRecord(t.c, s2));
-    BVC_HIP_T(launch_sum_groups(s2, ns, n_hist, *gp, *cp));
-    const bool shared = ctx->overlap && long_rows;
-    const int per_launch = kGroupSharedWavesPerCu / em_stream_count(ctx, 2) > 2 ? kGroupSharedWavesPerCu / em_stream_count(ctx, 2) : 2;
-    BVC_HIP_T(launch_lrt(ctx->ls, s2, ns, *cp, BVC_NCLASS, r, min_af, ctx->d_lut, nullptr, nullptr, res, shared, per_launch, em_scratch));
-    BVC_HIP_T(launch_lrt_groups(ctx->ls, s2, ns, n_groups, *gp, r, min_af, ctx->d_lut, res, gres, shared, per_launch, emg_scratch));
-    if (timed) {
-        BVC_HIP_T(hipEventRecord(t.d, s2));
-        ctx->ev_pending.push_back(t);
-        t = bvc_ctx::Triple{nullptr, nullptr, nullptr, nullptr, 0};
-        if (ctx->ev_pending.size() > 256) reap_timing(ctx, false);
-    }
-    if (ctx->overlap) {
-        BVC_HIP_T(hipEventRecord(ctx->ev_em_done[buf], s2));
-        ctx->em_pending[buf] = true;
-    }
-#undef BVC_HIP_T
-    return BVC_OK;
+    return run_stages(ctx, ns, n_groups, false, min_af, 2, stage1, [&](hipStream_t s2, const RingSlot &slot) -> int {
+        BVC_HIP(ctx, launch_sum_groups(s2, ns, n_groups + 1, slot.grp, slot.counts));
+        const bool shared = ctx->overlap && long_rows;
+        const int per_launch = kGroupSharedWavesPerCu / em_stream_count(ctx, 2) > 2 ? kGroupSharedWavesPerCu / em_stream_count(ctx, 2) : 2;
+        BVC_HIP(ctx, launch_lrt(ctx->ls, s2, ns, slot.counts, BVC_NCLASS, r, min_af, ctx->d_lut, nullptr, nullptr, res, shared, per_launch,
+                                slot.em));
+        BVC_HIP(ctx, launch_lrt_groups(ctx->ls, s2, ns, n_groups, slot.grp, r, min_af, ctx->d_lut, res, gres, shared, per_launch, slot.emg));
+        return BVC_OK;
+    });
 }
 
 // bvc_host_alloc's allocations: a transfer from / to a buffer inside one of them needs no bounce buffer
@@ -668,33 +738,19 @@ void bvc_destroy(bvc_ctx *ctx)
     for (int b = 0; b < bvc_ctx::kRing; ++b) {
         if (ctx->ev_hist_done[b]) (void)hipEventDestroy(ctx->ev_hist_done[b]);
         if (ctx->ev_em_done[b]) (void)hipEventDestroy(ctx->ev_em_done[b]);
-        if (ctx->d_cnt[b]) (void)hipFree(ctx->d_cnt[b]);
-        if (ctx->d_grp[b]) (void)hipFree(ctx->d_grp[b]);
     }
-    for (int b = 0; b <= bvc_ctx::kRing; ++b)
-        if (ctx->d_em[b]) (void)hipFree(ctx->d_em[b]);
-    for (int b = 0; b < bvc_ctx::kRing; ++b)
-        if (ctx->d_emg[b]) (void)hipFree(ctx->d_emg[b]);
     for (int b = 0; b < 2; ++b) {
         if (ctx->ev_upload[b]) (void)hipEventDestroy(ctx->ev_upload[b]);
         if (ctx->ev_set_free[b]) (void)hipEventDestroy(ctx->ev_set_free[b]);
-        if (ctx->d_stage[b]) (void)hipFree(ctx->d_stage[b]);
     }
     for (auto &t : ctx->ev_pending) { (void)hipEventDestroy(t.a); (void)hipEventDestroy(t.b); (void)hipEventDestroy(t.c); (void)hipEventDestroy(t.d); }
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     if (ctx->d_lut) (void)hipFree(ctx->d_lut);
     if (ctx->d_grp_scratch) (void)hipFree(ctx->d_grp_scratch);
-    if (ctx->d_grp_labels) (void)hipFree(ctx->d_grp_labels);
     if (ctx->d_sink) (void)hipFree(ctx->d_sink);
-    if (ctx->d_pl_text) (void)hipFree(ctx->d_pl_text);
-    if (ctx->d_pl_meta) (void)hipFree(ctx->d_pl_meta);
-    if (ctx->d_pl_out) (void)hipFree(ctx->d_pl_out);
-    if (ctx->d_pl_called) (void)hipFree(ctx->d_pl_called);
     if (ctx->h_up) (void)hipHostFree(ctx->h_up);
     if (ctx->h_down) (void)hipHostFree(ctx->h_down);
-    for (int k = 0; k < 2; ++k) if (ctx->d_pz_text[k]) (void)hipFree(ctx->d_pz_text[k]);
-    if (ctx->d_pz_comp) (void)hipFree(ctx->d_pz_comp);
-    delete ctx;
+    delete ctx;                        // frees the device scratch (DevBuf)
 }
 
 const char *bvc_last_error(const bvc_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -716,12 +772,8 @@ int bvc_synchronize(bvc_ctx *ctx)
 {
     if (!ctx) return BVC_ERR_ARG;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    BVC_HIP(ctx, hipStreamSynchronize(ctx->side));
-    BVC_HIP(ctx, hipStreamSynchronize(ctx->side_b));
-    BVC_HIP(ctx, hipStreamSynchronize(ctx->side_c));
-    BVC_HIP(ctx, hipStreamSynchronize(ctx->copy));
+    for (hipStream_t s : streams_of(ctx)) BVC_HIP(ctx, hipStreamSynchronize(s));
     for (bool &p : ctx->em_pending) p = false;
-    BVC_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return BVC_OK;
 }
 
@@ -775,41 +827,11 @@ int bvc_lrt_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_
     if (flags & BVC_PTR_DEVICE)
         return run_dense_device(ctx, n_sites, n_samples, row_stride, bases, quals, ref_base, min_af, results);
 
-    // host pointers: site chunks of at most ~512 MiB per array through two staging sets
-    const int64_t row_bytes = row_stride > 0 ? row_stride : 1;
-    int64_t chunk = ctx->ls.host_chunk_bytes / row_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_sites) chunk = n_sites;
-    const size_t arr_al = ((size_t)chunk * (size_t)row_stride + 255) & ~(size_t)255;
-    const size_t ref_al = ((size_t)chunk + 255) & ~(size_t)255;
-    const size_t need = 2 * arr_al + ref_al + (size_t)chunk * sizeof(bvc_site_result) + 256;
-    const int n_sets = n_sites > chunk ? 2 : 1;
-    for (int k = 0; k < n_sets; ++k) {
-        rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[k]), &ctx->stage_cap[k], need);
-        if (rc != BVC_OK) return rc;
-    }
-    auto d_b = [&](int set) { return reinterpret_cast<int8_t *>(ctx->d_stage[set]); };
-    auto d_q = [&](int set) { return d_b(set) + arr_al; };
-    auto d_r = [&](int set) { return d_q(set) + arr_al; };
-    auto d_res = [&](int set) { return reinterpret_cast<bvc_site_result *>(d_r(set) + ref_al); };
-    return run_chunks(ctx, n_sites, chunk,
-        [&](int set, int64_t s0, int64_t ns) -> int {
-            // the last row may be shorter than row_stride in the caller's allocation: copy exactly what is addressed
-            const size_t bytes = n_samples ? (size_t)(ns - 1) * (size_t)row_stride + (size_t)n_samples : 0;
-            if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_b(set), bases + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
-            if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_q(set), quals + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
-            BVC_HIP(ctx, hipMemcpyAsync(d_r(set), ref_base + s0, (size_t)ns, hipMemcpyHostToDevice, ctx->copy));
-            return BVC_OK;
-        },
-        [&](int set, int64_t s0, int64_t ns, bool download) -> int {
-            if (!download) {
-                int rc2 = run_dense_device(ctx, ns, n_samples, row_stride, d_b(set), d_q(set), d_r(set), min_af, d_res(set));
-                return rc2 == BVC_OK ? join_side(ctx) : rc2;
-            }
-            BVC_HIP(ctx, hipMemcpyAsync(results + s0, d_res(set), (size_t)ns * sizeof(bvc_site_result),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-            return BVC_OK;
-        });
+    const int8_t *rows[2] = {bases, quals};
+    return run_dense_host(ctx, n_sites, n_samples, row_stride, 2, rows, ref_base, nullptr, 0, results, nullptr,
+                          [&](int64_t ns, const DenseSet &d) {
+                              return run_dense_device(ctx, ns, n_samples, row_stride, d.rows[0], d.rows[1], d.ref, min_af, d.res);
+                          });
 }
 
 int bvc_lrt_dense_packed(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride, const uint8_t *packed,
@@ -821,38 +843,12 @@ int bvc_lrt_dense_packed(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64
     if (n_sites == 0) return BVC_OK;
     if (flags & BVC_PTR_DEVICE) return run_packed_device(ctx, n_sites, n_samples, row_stride, packed, ref_base, min_af, results);
 
-    // host pointers: the chunked staging of bvc_lrt_dense with one array instead of two
-    const int64_t row_bytes = row_stride > 0 ? row_stride : 1;
-    int64_t chunk = ctx->ls.host_chunk_bytes / row_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_sites) chunk = n_sites;
-    const size_t arr_al = ((size_t)chunk * (size_t)row_stride + 255) & ~(size_t)255;
-    const size_t ref_al = ((size_t)chunk + 255) & ~(size_t)255;
-    const size_t need = arr_al + ref_al + (size_t)chunk * sizeof(bvc_site_result) + 256;
-    const int n_sets = n_sites > chunk ? 2 : 1;
-    for (int k = 0; k < n_sets; ++k) {
-        rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[k]), &ctx->stage_cap[k], need);
-        if (rc != BVC_OK) return rc;
-    }
-    auto d_p = [&](int set) { return reinterpret_cast<uint8_t *>(ctx->d_stage[set]); };
-    auto d_r = [&](int set) { return reinterpret_cast<int8_t *>(d_p(set) + arr_al); };
-    auto d_res = [&](int set) { return reinterpret_cast<bvc_site_result *>(d_r(set) + ref_al); };
-    return run_chunks(ctx, n_sites, chunk,
-        [&](int set, int64_t s0, int64_t ns) -> int {
-            const size_t bytes = n_samples ? (size_t)(ns - 1) * (size_t)row_stride + (size_t)n_samples : 0;
-            if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_p(set), packed + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
-            BVC_HIP(ctx, hipMemcpyAsync(d_r(set), ref_base + s0, (size_t)ns, hipMemcpyHostToDevice, ctx->copy));
-            return BVC_OK;
-        },
-        [&](int set, int64_t s0, int64_t ns, bool download) -> int {
-            if (!download) {
-                int rc2 = run_packed_device(ctx, ns, n_samples, row_stride, d_p(set), d_r(set), min_af, d_res(set));
-                return rc2 == BVC_OK ? join_side(ctx) : rc2;
-            }
-            BVC_HIP(ctx, hipMemcpyAsync(results + s0, d_res(set), (size_t)ns * sizeof(bvc_site_result),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-            return BVC_OK;
-        });
+    const int8_t *rows[2] = {reinterpret_cast<const int8_t *>(packed), nullptr};
+    return run_dense_host(ctx, n_sites, n_samples, row_stride, 1, rows, ref_base, nullptr, 0, results, nullptr,
+                          [&](int64_t ns, const DenseSet &d) {
+                              return run_packed_device(ctx, ns, n_samples, row_stride, reinterpret_cast<const uint8_t *>(d.rows[0]), d.ref,
+                                                       min_af, d.res);
+                          });
 }
 
 int bvc_pack_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride, const int8_t *bases,
@@ -907,12 +903,14 @@ int bvc_hist_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row
         return BVC_OK;
     }
     const size_t bytes = n_samples ? (size_t)(n_sites - 1) * (size_t)row_stride + (size_t)n_samples : 0;
-    const size_t arr_al = (bytes + 255) & ~(size_t)255;
-    rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[0]), &ctx->stage_cap[0], 2 * arr_al + cbytes + 256);
+    int8_t *d_b, *d_q;
+    uint32_t *d_c;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_b = L.take<int8_t>(bytes);
+        d_q = L.take<int8_t>(bytes);
+        d_c = L.take<uint32_t>((size_t)n_sites * BVC_NCLASS);
+    });
     if (rc != BVC_OK) return rc;
-    int8_t *d_b = reinterpret_cast<int8_t *>(ctx->d_stage[0]);
-    int8_t *d_q = d_b + arr_al;
-    uint32_t *d_c = reinterpret_cast<uint32_t *>(d_q + arr_al);
     if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_b, bases, bytes, hipMemcpyHostToDevice, ctx->stream));
     if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_q, quals, bytes, hipMemcpyHostToDevice, ctx->stream));
     if (split > 1) BVC_HIP(ctx, hipMemsetAsync(d_c, 0, cbytes, ctx->stream));
@@ -950,16 +948,15 @@ int bvc_lrt_hist(bvc_ctx *ctx, int64_t n_sites, const uint32_t *counts, const in
     }
     if (base_comb && (rc = check_comb_host(ctx, n_sites, base_comb, n_comb)) != BVC_OK) return rc;
     const size_t cbytes = (size_t)n_sites * BVC_NCLASS * sizeof(uint32_t);
-    const size_t sa = ((size_t)n_sites + 255) & ~(size_t)255;
-    const size_t ca = ((size_t)n_sites * 4 + 255) & ~(size_t)255;
-    rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[0]), &ctx->stage_cap[0],
-                cbytes + 2 * sa + ca + (size_t)n_sites * sizeof(bvc_site_result) + 256);
+    uint32_t *d_c; int8_t *d_r, *d_cb; uint8_t *d_nc; bvc_site_result *d_res;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_c = L.take<uint32_t>((size_t)n_sites * BVC_NCLASS);
+        d_r = L.take<int8_t>((size_t)n_sites);
+        d_nc = L.take<uint8_t>((size_t)n_sites);
+        d_cb = L.take<int8_t>((size_t)n_sites * 4);
+        d_res = L.take<bvc_site_result>((size_t)n_sites);
+    });
     if (rc != BVC_OK) return rc;
-    uint32_t *d_c = reinterpret_cast<uint32_t *>(ctx->d_stage[0]);
-    int8_t *d_r = reinterpret_cast<int8_t *>(ctx->d_stage[0] + cbytes);
-    uint8_t *d_nc = reinterpret_cast<uint8_t *>(d_r + sa);
-    int8_t *d_cb = reinterpret_cast<int8_t *>(d_nc + sa);
-    bvc_site_result *d_res = reinterpret_cast<bvc_site_result *>(d_cb + ca);
     BVC_HIP(ctx, hipMemcpyAsync(d_c, counts, cbytes, hipMemcpyHostToDevice, ctx->stream));
     BVC_HIP(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
     if (base_comb) {
@@ -1000,55 +997,37 @@ static int run_csr_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, c
         const int64_t s1 = s0 + chunk < n_sites ? s0 + chunk : n_sites;
         if (offsets[s1] - offsets[s0] > widest) widest = offsets[s1] - offsets[s0];
     }
-    const int arrays = quals ? 2 : 1;
-    const size_t arr_al = ((size_t)widest + 256 + 255) & ~(size_t)255;       // + the lead
-    const size_t off_al = ((size_t)(n_sites + 1) * 8 + 255) & ~(size_t)255;
-    const size_t site_al = ((size_t)n_sites + 255) & ~(size_t)255;
-    const size_t comb_al = ((size_t)n_sites * 4 + 255) & ~(size_t)255;
-    const size_t res_al = ((size_t)n_sites * sizeof(bvc_site_result) + 255) & ~(size_t)255;
-    const size_t head = off_al + 2 * site_al + comb_al + res_al;             // set 0 carries the per-site arrays in front
+    // set 0 carries the per-site arrays in front of its observations
+    int64_t *d_o; int8_t *d_r, *d_cb; uint8_t *d_nc; bvc_site_result *d_res;
+    int8_t *d_b[2] = {nullptr, nullptr}, *d_q[2] = {nullptr, nullptr};
     const int n_sets = n_sites > chunk ? 2 : 1;
-    int rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[0]), &ctx->stage_cap[0], head + (size_t)arrays * arr_al + 256);
-    if (rc == BVC_OK && n_sets > 1) rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[1]), &ctx->stage_cap[1], (size_t)arrays * arr_al + 256);
+    int rc = BVC_OK;
+    for (int k = 0; k < n_sets && rc == BVC_OK; ++k)
+        rc = carve(ctx, ctx->d_stage[k], 256, [&](Layout &L) {
+            if (k == 0) {
+                d_o = L.take<int64_t>((size_t)n_sites + 1);
+                d_r = L.take<int8_t>((size_t)n_sites);
+                d_nc = L.take<uint8_t>((size_t)n_sites);
+                d_cb = L.take<int8_t>((size_t)n_sites * 4);
+                d_res = L.take<bvc_site_result>((size_t)n_sites);
+            }
+            d_b[k] = L.take<int8_t>((size_t)widest, 256);                  // + the lead
+            if (quals) d_q[k] = L.take<int8_t>((size_t)widest, 256);
+        });
     if (rc != BVC_OK) return rc;
-    int64_t *d_o = reinterpret_cast<int64_t *>(ctx->d_stage[0]);
-    int8_t *d_r = reinterpret_cast<int8_t *>(ctx->d_stage[0] + off_al);
-    uint8_t *d_nc = reinterpret_cast<uint8_t *>(d_r + site_al);
-    int8_t *d_cb = reinterpret_cast<int8_t *>(d_nc + site_al);
-    bvc_site_result *d_res = reinterpret_cast<bvc_site_result *>(d_cb + comb_al);
-    auto d_b = [&](int set) { return reinterpret_cast<int8_t *>(ctx->d_stage[set]) + (set == 0 ? head : 0); };
-    // an early exit must not leave an upload or a kernel running on the staging sets: the next call may free or refill them
-    auto drained = [&](int code) {
-        if (code != BVC_OK) {
-            // stage 2 of the chunks already launched may still run on the side streams and it reads / writes the staging sets
-            (void)hipStreamSynchronize(ctx->copy);
-            (void)hipStreamSynchronize(ctx->stream);
-            (void)hipStreamSynchronize(ctx->side);
-            (void)hipStreamSynchronize(ctx->side_b);
-            (void)hipStreamSynchronize(ctx->side_c);
-            for (bool &p : ctx->em_pending) p = false;
-            (void)hipGetLastError();
-        }
-        return code;
-    };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
-    BVC_HIP_D(hipMemcpyAsync(d_o, offsets, (size_t)(n_sites + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_o, offsets, (size_t)(n_sites + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
     if (base_comb) {
-        BVC_HIP_D(hipMemcpyAsync(d_nc, n_comb, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_cb, base_comb, (size_t)n_sites * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_nc, n_comb, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_cb, base_comb, (size_t)n_sites * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     auto upload = [&](int set, int64_t s0, int64_t ns, bool reuse) -> int {
         const int64_t o0 = offsets[s0];
         const size_t bytes = (size_t)(offsets[s0 + ns] - o0), lead = (size_t)(o0 & 255);
-        if (reuse) BVC_HIP_D(hipStreamWaitEvent(ctx->copy, ctx->ev_set_free[set], 0));   // the kernels of chunk i - 2 are done with it
-        if (bytes) BVC_HIP_D(hipMemcpyAsync(d_b(set) + lead, bases + o0, bytes, hipMemcpyHostToDevice, ctx->copy));
-        if (bytes && quals) BVC_HIP_D(hipMemcpyAsync(d_b(set) + arr_al + lead, quals + o0, bytes, hipMemcpyHostToDevice, ctx->copy));
-        BVC_HIP_D(hipEventRecord(ctx->ev_upload[set], ctx->copy));
+        if (reuse) BVC_HIP_D(ctx, hipStreamWaitEvent(ctx->copy, ctx->ev_set_free[set], 0));   // the kernels of chunk i - 2 are done with it
+        if (bytes) BVC_HIP_D(ctx, hipMemcpyAsync(d_b[set] + lead, bases + o0, bytes, hipMemcpyHostToDevice, ctx->copy));
+        if (bytes && quals) BVC_HIP_D(ctx, hipMemcpyAsync(d_q[set] + lead, quals + o0, bytes, hipMemcpyHostToDevice, ctx->copy));
+        BVC_HIP_D(ctx, hipEventRecord(ctx->ev_upload[set], ctx->copy));
         return BVC_OK;
     };
     int set = 0;
@@ -1059,26 +1038,33 @@ static int run_csr_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, c
         const int64_t ns = n_sites - s0 < chunk ? n_sites - s0 : chunk;
         const int64_t o0 = offsets[s0];
         const uintptr_t shift = (uintptr_t)(o0 - (o0 & 255));                // array base = staging + lead - o0
-        const int8_t *pb = reinterpret_cast<const int8_t *>(reinterpret_cast<uintptr_t>(d_b(set)) - shift);
-        const int8_t *pq = quals ? reinterpret_cast<const int8_t *>(reinterpret_cast<uintptr_t>(d_b(set) + arr_al) - shift) : nullptr;
-        BVC_HIP_D(hipStreamWaitEvent(ctx->stream, ctx->ev_upload[set], 0));
+        const int8_t *pb = reinterpret_cast<const int8_t *>(reinterpret_cast<uintptr_t>(d_b[set]) - shift);
+        const int8_t *pq = quals ? reinterpret_cast<const int8_t *>(reinterpret_cast<uintptr_t>(d_q[set]) - shift) : nullptr;
+        BVC_HIP_D(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_upload[set], 0));
         rc = run_csr_device(ctx, ns, d_o + s0, pb, pq, d_r + s0, min_af, base_comb ? d_cb + s0 * 4 : nullptr,
                             base_comb ? d_nc + s0 : nullptr, d_res + s0);
-        if (rc != BVC_OK) return drained(rc);
+        if (rc != BVC_OK) return drain_on_error(ctx, rc);
         // the histogram kernels are the only readers of the set and they run on the context's stream
-        BVC_HIP_D(hipEventRecord(ctx->ev_set_free[set], ctx->stream));
+        BVC_HIP_D(ctx, hipEventRecord(ctx->ev_set_free[set], ctx->stream));
         const int64_t s1 = s0 + chunk;
         if (s1 < n_sites) {
             rc = upload(set ^ 1, s1, n_sites - s1 < chunk ? n_sites - s1 : chunk, i >= 1);
-            if (rc != BVC_OK) return drained(rc);
+            if (rc != BVC_OK) return rc;
         }
     }
     rc = join_side(ctx);
-    if (rc != BVC_OK) return drained(rc);
-    BVC_HIP_D(hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(hipStreamSynchronize(ctx->stream));
-#undef BVC_HIP_D
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
     return BVC_OK;
+}
+
+// Host-pointer ragged calls: the chunking and the uploads index the observations with offsets[0..n_sites].
+static int check_offsets_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets)
+{
+    bool ok = offsets[0] == 0;
+    for (int64_t s = 0; s < n_sites && ok; ++s) ok = offsets[s + 1] >= offsets[s];
+    return ok ? BVC_OK : fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
 }
 
 int bvc_lrt_csr_comb(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets,
@@ -1094,10 +1080,8 @@ int bvc_lrt_csr_comb(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets,
         if (!bases || !quals) return fail(ctx, BVC_ERR_ARG, "null data pointer");
         return run_csr_device(ctx, n_sites, offsets, bases, quals, ref_base, min_af, base_comb, n_comb, results);
     }
+    if ((rc = check_offsets_host(ctx, n_sites, offsets)) != BVC_OK) return rc;
     const int64_t total = offsets[n_sites];
-    if (offsets[0] != 0 || total < 0) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
-    for (int64_t s = 0; s < n_sites; ++s)
-        if (offsets[s + 1] < offsets[s]) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
     if (total > 0 && (!bases || !quals)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if (base_comb && (rc = check_comb_host(ctx, n_sites, base_comb, n_comb)) != BVC_OK) return rc;
     return run_csr_host(ctx, n_sites, offsets, bases, quals, ref_base, min_af, base_comb, n_comb, results);
@@ -1114,10 +1098,8 @@ int bvc_lrt_csr_packed(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, co
         if (!packed) return fail(ctx, BVC_ERR_ARG, "null data pointer");
         return run_csr_device(ctx, n_sites, offsets, obs, nullptr, ref_base, min_af, nullptr, nullptr, results);
     }
+    if ((rc = check_offsets_host(ctx, n_sites, offsets)) != BVC_OK) return rc;
     const int64_t total = offsets[n_sites];
-    if (offsets[0] != 0 || total < 0) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
-    for (int64_t s = 0; s < n_sites; ++s)
-        if (offsets[s + 1] < offsets[s]) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
     if (total > 0 && !packed) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     // half the bytes of bvc_lrt_csr over the host link
     return run_csr_host(ctx, n_sites, offsets, obs, nullptr, ref_base, min_af, nullptr, nullptr, results);
@@ -1144,8 +1126,6 @@ static int run_csr_groups_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *o
                             ref_base, min_af, results, grp_results);
 }
 
-static inline size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
-
 int bvc_lrt_csr_groups(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
                        const int32_t *sample_of_obs, const int8_t *ref_base, double min_af,
                        const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
@@ -1161,56 +1141,36 @@ int bvc_lrt_csr_groups(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, co
         return run_csr_groups_device(ctx, n_sites, offsets, bases, quals, sample_of_obs, ref_base, min_af, group_of_sample, n_samples,
                                      n_groups, results, grp_results);
     }
+    if ((rc = check_offsets_host(ctx, n_sites, offsets)) != BVC_OK) return rc;
     const int64_t total = offsets[n_sites];
-    if (offsets[0] != 0 || total < 0) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
-    for (int64_t s = 0; s < n_sites; ++s)
-        if (offsets[s + 1] < offsets[s]) return fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
     if (total > 0 && (!bases || !quals || !sample_of_obs)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
-    // one piece through staging set 0: offsets | ref | labels | bases | quals | samples | records | group records
-    const size_t off_al = al256((size_t)(n_sites + 1) * 8), ref_al = al256((size_t)n_sites), g_al = al256((size_t)n_samples + 1);
-    const size_t arr_al = al256((size_t)total + 16), smp_al = al256((size_t)total * 4 + 16);
-    const size_t res_al = al256((size_t)n_sites * sizeof(bvc_site_result));
-    const size_t need = off_al + ref_al + g_al + 2 * arr_al + smp_al + res_al + (size_t)n_sites * n_groups * sizeof(bvc_group_result) + 256;
-    rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[0]), &ctx->stage_cap[0], need);
+    // one piece through staging set 0
+    int64_t *d_o; int8_t *d_r, *d_b, *d_q; uint8_t *d_g; int32_t *d_s; bvc_site_result *d_res; bvc_group_result *d_gres;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_o = L.take<int64_t>((size_t)n_sites + 1);
+        d_r = L.take<int8_t>((size_t)n_sites);
+        d_g = L.take<uint8_t>((size_t)n_samples, 1);
+        d_b = L.take<int8_t>((size_t)total, 16);
+        d_q = L.take<int8_t>((size_t)total, 16);
+        d_s = L.take<int32_t>((size_t)total, 16);
+        d_res = L.take<bvc_site_result>((size_t)n_sites);
+        d_gres = L.take<bvc_group_result>((size_t)n_sites * n_groups);
+    });
     if (rc != BVC_OK) return rc;
-    char *p = ctx->d_stage[0];
-    int64_t *d_o = reinterpret_cast<int64_t *>(p); p += off_al;
-    int8_t *d_r = reinterpret_cast<int8_t *>(p); p += ref_al;
-    uint8_t *d_g = reinterpret_cast<uint8_t *>(p); p += g_al;
-    int8_t *d_b = reinterpret_cast<int8_t *>(p); p += arr_al;
-    int8_t *d_q = reinterpret_cast<int8_t *>(p); p += arr_al;
-    int32_t *d_s = reinterpret_cast<int32_t *>(p); p += smp_al;
-    bvc_site_result *d_res = reinterpret_cast<bvc_site_result *>(p); p += res_al;
-    bvc_group_result *d_gres = reinterpret_cast<bvc_group_result *>(p);
-    auto drained = [&](int code) {
-        if (code != BVC_OK) {
-            (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->side); (void)hipStreamSynchronize(ctx->side_b);
-            (void)hipStreamSynchronize(ctx->side_c);
-            for (bool &pnd : ctx->em_pending) pnd = false;
-            (void)hipGetLastError();
-        }
-        return code;
-    };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
-    BVC_HIP_D(hipMemcpyAsync(d_o, offsets, (size_t)(n_sites + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
-    if (n_samples) BVC_HIP_D(hipMemcpyAsync(d_g, group_of_sample, (size_t)n_samples, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_o, offsets, (size_t)(n_sites + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+    if (n_samples) BVC_HIP_D(ctx, hipMemcpyAsync(d_g, group_of_sample, (size_t)n_samples, hipMemcpyHostToDevice, ctx->stream));
     if (total) {
-        BVC_HIP_D(hipMemcpyAsync(d_b, bases, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_q, quals, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_s, sample_of_obs, (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_b, bases, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_q, quals, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_s, sample_of_obs, (size_t)total * 4, hipMemcpyHostToDevice, ctx->stream));
     }
     rc = run_csr_groups_device(ctx, n_sites, d_o, d_b, d_q, d_s, d_r, min_af, d_g, n_samples, n_groups, d_res, d_gres);
     if (rc == BVC_OK) rc = join_side(ctx);
-    if (rc != BVC_OK) return drained(rc);
-    BVC_HIP_D(hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(hipMemcpyAsync(grp_results, d_gres, (size_t)n_sites * n_groups * sizeof(bvc_group_result), hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(hipStreamSynchronize(ctx->stream));
-#undef BVC_HIP_D
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(grp_results, d_gres, (size_t)n_sites * n_groups * sizeof(bvc_group_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
     return BVC_OK;
 }
 
@@ -1233,37 +1193,54 @@ int bvc_inflate_blocks(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, co
             b.out_off + b.isize > out_bytes)
             return fail(ctx, BVC_ERR_ARG, "block outside its buffer");
     }
-    const size_t c_al = al256((size_t)comp_bytes + 16), b_al = al256((size_t)n_blocks * sizeof(bvc_bgzf_block)), s_al = al256((size_t)n_blocks * 4);
-    int rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[0]), &ctx->stage_cap[0], c_al + b_al + s_al + (size_t)out_bytes + 256);
+    uint8_t *d_c, *d_o; bvc_bgzf_block *d_b; uint32_t *d_s;
+    int rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_c = L.take<uint8_t>((size_t)comp_bytes, 16);
+        d_b = L.take<bvc_bgzf_block>((size_t)n_blocks);
+        d_s = L.take<uint32_t>((size_t)n_blocks);
+        d_o = L.take<uint8_t>((size_t)out_bytes);
+    });
     if (rc != BVC_OK) return rc;
-    char *p = ctx->d_stage[0];
-    uint8_t *d_c = reinterpret_cast<uint8_t *>(p); p += c_al;
-    bvc_bgzf_block *d_b = reinterpret_cast<bvc_bgzf_block *>(p); p += b_al;
-    uint32_t *d_s = reinterpret_cast<uint32_t *>(p); p += s_al;
-    uint8_t *d_o = reinterpret_cast<uint8_t *>(p);
-    auto drained = [&](int code) { if (code != BVC_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); } return code; };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
-    BVC_HIP_D(hipMemcpyAsync(d_c, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(hipMemcpyAsync(d_b, blocks, (size_t)n_blocks * sizeof(bvc_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(launch_inflate(ctx->stream, d_c, d_b, n_blocks, d_o, d_s));
-    BVC_HIP_D(hipMemcpyAsync(status, d_s, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, ctx->stream));
-    if (out_bytes) BVC_HIP_D(hipMemcpyAsync(out, d_o, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(hipStreamSynchronize(ctx->stream));
-#undef BVC_HIP_D
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_c, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_b, blocks, (size_t)n_blocks * sizeof(bvc_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, launch_inflate(ctx->stream, d_c, d_b, n_blocks, d_o, d_s));
+    BVC_HIP_D(ctx, hipMemcpyAsync(status, d_s, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(out, d_o, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
     return BVC_OK;
 }
 
 // ---- temp-batch pileup text -> columns -> records (pileup_kernel.hip) -------------------------------------------------------
+// The slices of a tile's meta buffer that both begin calls lay out alike: the line table, the first sample and the size of every
+// batch (each slice batch_pad bytes longer), the per-line words, 256 bytes of status (the totals at +64), the two offset arrays
+// and the tallies.  Returns the bytes from the status to the end of the tallies: what a begin call clears.
+static size_t carve_tile(Layout &L, PileupTile &P, int32_t n_batches, int32_t n_pos, size_t batch_pad, uint32_t *&line_start,
+                         int32_t *&sample0, int32_t *&n_in_batch)
+{
+    const size_t T = (size_t)n_pos, nb = (size_t)n_batches;
+    P.n_batches = n_batches; P.n_pos = n_pos; P.line_stride = n_pos + 1;
+    P.n_lines_cap = (int64_t)n_batches * n_pos;
+    P.line_start = line_start = L.take<uint32_t>(nb * (T + 1));
+    P.sample0 = sample0 = L.take<int32_t>(nb, batch_pad);
+    P.n_in_batch = n_in_batch = L.take<int32_t>(nb, batch_pad);
+    P.line_words = L.take<uint32_t>((size_t)P.n_lines_cap * 4);
+    const size_t from = L.at;
+    char *st = L.take<char>(256);
+    P.status = reinterpret_cast<uint32_t *>(st);
+    P.totals = reinterpret_cast<int64_t *>(st + 64);
+    P.entry_off = L.take<int64_t>(T + 1);
+    P.obs_off = L.take<int64_t>(T + 1);
+    P.tally = L.take<int32_t>(T * 32);
+    return L.at - from;
+}
+
 int bvc_pileup_begin(bvc_ctx *ctx, const char *text, int64_t text_bytes, const uint32_t *line_start,
                      const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
                      int64_t *n_entries, int64_t *n_indels)
 {
     if (!ctx) return BVC_ERR_ARG;
-    ctx->pl_begun = false;
+    PileupState::Tile &tile = ctx->pile.tile;
+    tile = PileupState::Tile{};
     if (n_batches < 0 || n_positions < 0 || text_bytes < 0 || !n_entries || !n_indels) return fail(ctx, BVC_ERR_ARG, "bad argument");
     if (text_bytes > (int64_t)0xFFFFFF00) return fail(ctx, BVC_ERR_ARG, "more than 4 GiB of text in one tile (use fewer positions)");
     const int64_t n_lines = (int64_t)n_batches * n_positions;
@@ -1280,50 +1257,30 @@ int bvc_pileup_begin(bvc_ctx *ctx, const char *text, int64_t text_bytes, const u
         if (n_positions > 0 && (int64_t)ls[n_positions] > text_bytes) return fail(ctx, BVC_ERR_ARG, "line_start points outside the text");
     }
     const size_t T = (size_t)n_positions, nb = (size_t)n_batches;
-    const size_t ls_al = al256(nb * (T + 1) * 4), b_al = al256(nb * 4), lw_al = al256((size_t)n_lines * 16), st_al = 256;
-    const size_t off_al = al256((T + 1) * 8), tal_al = al256(T * 32 * 4);
-    int rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pl_text), &ctx->pl_text_cap, (size_t)text_bytes + 64);
-    if (rc == BVC_OK) rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pl_meta), &ctx->pl_meta_cap, ls_al + 2 * b_al + lw_al + st_al + 2 * off_al + tal_al);
+    PileupTile &P = tile.P;
+    uint32_t *d_ls; int32_t *d_s0, *d_nib;
+    size_t clear = 0;
+    int rc = ensure(ctx, ctx->pile.text, (size_t)text_bytes + 64);
+    if (rc == BVC_OK)
+        rc = carve(ctx, ctx->pile.meta, 0, [&](Layout &L) { clear = carve_tile(L, P, n_batches, n_positions, 0, d_ls, d_s0, d_nib); });
     if (rc != BVC_OK) return rc;
-    char *p = ctx->d_pl_meta;
-    PileupTile &P = ctx->pl;
-    P = PileupTile{};
-    P.text = reinterpret_cast<const uint8_t *>(ctx->d_pl_text);
-    uint32_t *d_ls = reinterpret_cast<uint32_t *>(p); p += ls_al;
-    int32_t *d_s0 = reinterpret_cast<int32_t *>(p); p += b_al;
-    int32_t *d_nib = reinterpret_cast<int32_t *>(p); p += b_al;
-    P.line_start = d_ls; P.sample0 = d_s0; P.n_in_batch = d_nib;
-    P.line_words = reinterpret_cast<uint32_t *>(p); p += lw_al;
-    P.status = reinterpret_cast<uint32_t *>(p);
-    P.totals = reinterpret_cast<int64_t *>(p + 64); p += st_al;
-    P.entry_off = reinterpret_cast<int64_t *>(p); p += off_al;
-    P.obs_off = reinterpret_cast<int64_t *>(p); p += off_al;
-    P.tally = reinterpret_cast<int32_t *>(p);
-    P.n_batches = n_batches; P.n_pos = n_positions; P.n_lines_cap = n_lines; P.line_stride = n_positions + 1;
-    auto drained = [&](int code) { if (code != BVC_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); } return code; };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
-    BVC_HIP_D(hipMemsetAsync(P.status, 0, st_al + 2 * off_al + tal_al, ctx->stream));     // status, totals, offsets of an empty tile, tallies
+    P.text = reinterpret_cast<const uint8_t *>(ctx->pile.text.p);
+    BVC_HIP_D(ctx, hipMemsetAsync(P.status, 0, clear, ctx->stream));     // status, totals, offsets of an empty tile, tallies
     if (n_lines > 0) {
-        BVC_HIP_D(hipMemcpyAsync(ctx->d_pl_text, text, (size_t)text_bytes, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_ls, line_start, nb * (T + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_s0, sample0, nb * 4, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(hipMemcpyAsync(d_nib, n_in_batch, nb * 4, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(launch_pileup_count(ctx->stream, P));
+        BVC_HIP_D(ctx, hipMemcpyAsync(ctx->pile.text.p, text, (size_t)text_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_ls, line_start, nb * (T + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_s0, sample0, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_nib, n_in_batch, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
     }
     uint32_t st[4] = {0, 0, 0, 0};
     int64_t tot[2] = {0, 0};
-    BVC_HIP_D(hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(wait_stream(ctx));
-#undef BVC_HIP_D
+    BVC_HIP_D(ctx, hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
     if (st[0] != 0) return BVC_PILEUP_IRREGULAR;
-    ctx->pl_entries = tot[0]; ctx->pl_obs = tot[1]; ctx->pl_indels = st[1];
-    ctx->pl_begun = true;
-    ctx->pl_on_device_text = false; ctx->pl_indel_bytes = 0;
+    tile.entries = tot[0]; tile.obs = tot[1]; tile.indels = st[1];
+    tile.begun = true;
     *n_entries = tot[0]; *n_indels = st[1];
     return BVC_OK;
 }
@@ -1334,7 +1291,8 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
                           int64_t *n_entries, int64_t *n_indels, int64_t *indel_text_bytes)
 {
     if (!ctx) return BVC_ERR_ARG;
-    ctx->pl_begun = false;
+    PileupState &pile = ctx->pile;
+    pile.tile = PileupState::Tile{};
     if (n_batches < 0 || max_positions < 0 || comp_bytes < 0 || !n_positions || !n_entries || !n_indels || !indel_text_bytes)
         return fail(ctx, BVC_ERR_ARG, "bad argument");
     if (n_batches > 0 && (!blocks_of_batch || !sample0 || !n_in_batch || !lines_of_batch)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
@@ -1342,7 +1300,7 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     *n_positions = 0; *n_entries = 0; *n_indels = 0; *indel_text_bytes = 0;
     const size_t nb = (size_t)n_batches;
-    if (reset || ctx->pz_left_len.size() != nb) { ctx->pz_left_len.assign(nb, 0u); ctx->pz_left_src.assign(nb, 0u); }
+    if (reset || pile.left_len.size() != nb) { pile.left_len.assign(nb, 0u); pile.left_src.assign(nb, 0u); }
     int64_t n_blocks = 0;
     for (size_t b = 0; b < nb; ++b) { if (blocks_of_batch[b] < 0 || n_in_batch[b] < 0) return fail(ctx, BVC_ERR_ARG, "negative count"); n_blocks += blocks_of_batch[b]; }
     if (n_blocks > 0 && (!comp || !blocks)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
@@ -1356,7 +1314,7 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
     uint32_t segs = 0;
     for (size_t b = 0; b < nb; ++b) {
         at = (at + 15) & ~(uint64_t)15;
-        const uint32_t left = ctx->pz_left_len[b];
+        const uint32_t left = pile.left_len[b];
         uint64_t fresh = 0;
         for (int32_t k = 0; k < blocks_of_batch[b]; ++k, ++bi) {
             const bvc_bgzf_block &in = blocks[bi];
@@ -1370,7 +1328,7 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
         if (skip_bytes && left == 0 && skip_bytes[b] > 0) skip = (uint32_t)skip_bytes[b];
         if (skip > fresh) return fail(ctx, BVC_ERR_ARG, "skip_bytes beyond the batch's first blocks");
         if (at + left + fresh > (uint64_t)0xFFFFFF00u) return fail(ctx, BVC_ERR_ARG, "more than 4 GiB of text in one tile (send fewer blocks)");
-        reg[b].start = (uint32_t)at + skip; reg[b].len = left + (uint32_t)fresh - skip; reg[b].left_src = ctx->pz_left_src[b]; reg[b].left_len = left;
+        reg[b].start = (uint32_t)at + skip; reg[b].len = left + (uint32_t)fresh - skip; reg[b].left_src = pile.left_src[b]; reg[b].left_len = left;
         region_end[b] = reg[b].start + reg[b].len;
         seg_base[b] = segs;
         segs += (reg[b].len + 1023u) / 1024u;
@@ -1378,54 +1336,34 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
     }
     seg_base[nb] = segs;
     const uint64_t text_bytes = at;
-    const int nw = 1 - ctx->pz_cur;
-    const size_t T = (size_t)max_positions;
-    const int64_t n_lines_cap = (int64_t)max_positions * n_batches;
-    const size_t ls_al = al256(nb * (T + 1) * 4), b_al = al256(nb * 4 + 4), lw_al = al256((size_t)n_lines_cap * 16), st_al = 256;
-    const size_t off_al = al256((T + 1) * 8), tal_al = al256(T * 32 * 4);
-    const size_t blk_al = al256((size_t)n_blocks * sizeof(bvc_bgzf_block)), bst_al = al256((size_t)n_blocks * 4), reg_al = al256(nb * sizeof(bvc_pileup_region));
-    const size_t sb_al = al256((nb + 1) * 4), sn_al = al256((size_t)segs * 4 + 4);
-    int rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pz_text[nw]), &ctx->pz_text_cap[nw], (size_t)text_bytes + 64);
-    if (rc == BVC_OK) rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pz_comp), &ctx->pz_comp_cap, (size_t)comp_bytes + 64);
+    const int nw = 1 - pile.pz_cur;
+    PileupTile &P = pile.tile.P;
+    int32_t *d_s0, *d_nib, *d_lines; uint32_t *d_ls, *d_bst, *d_sb, *d_sn, *d_ends; bvc_bgzf_block *d_blk; bvc_pileup_region *d_reg;
+    size_t clear = 0;
+    int rc = ensure(ctx, pile.pz_text[nw], (size_t)text_bytes + 64);
+    if (rc == BVC_OK) rc = ensure(ctx, pile.pz_comp, (size_t)comp_bytes + 64);
     if (rc == BVC_OK)
-        rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pl_meta), &ctx->pl_meta_cap,
-                    ls_al + 2 * b_al + lw_al + st_al + 2 * off_al + tal_al + blk_al + bst_al + reg_al + sb_al + sn_al + 3 * b_al);
+        rc = carve(ctx, pile.meta, 0, [&](Layout &L) {
+            clear = carve_tile(L, P, n_batches, max_positions, 4, d_ls, d_s0, d_nib);
+            d_blk = L.take<bvc_bgzf_block>((size_t)n_blocks);
+            d_bst = L.take<uint32_t>((size_t)n_blocks);
+            d_reg = L.take<bvc_pileup_region>(nb);
+            d_sb = L.take<uint32_t>(nb + 1);
+            d_sn = L.take<uint32_t>(segs, 4);
+            d_lines = L.take<int32_t>(nb, 4);
+            d_ends = L.take<uint32_t>(nb, 4);
+        });
     if (rc != BVC_OK) return rc;
-    char *p = ctx->d_pl_meta;
-    PileupTile &P = ctx->pl;
-    P = PileupTile{};
-    P.text = reinterpret_cast<const uint8_t *>(ctx->d_pz_text[nw]);
-    uint32_t *d_ls = reinterpret_cast<uint32_t *>(p); p += ls_al;
-    int32_t *d_s0 = reinterpret_cast<int32_t *>(p); p += b_al;
-    int32_t *d_nib = reinterpret_cast<int32_t *>(p); p += b_al;
-    P.line_start = d_ls; P.sample0 = d_s0; P.n_in_batch = d_nib;
-    P.line_words = reinterpret_cast<uint32_t *>(p); p += lw_al;
-    P.status = reinterpret_cast<uint32_t *>(p);
-    P.totals = reinterpret_cast<int64_t *>(p + 64);
-    int32_t *d_T = reinterpret_cast<int32_t *>(p + 128); p += st_al;
-    P.entry_off = reinterpret_cast<int64_t *>(p); p += off_al;
-    P.obs_off = reinterpret_cast<int64_t *>(p); p += off_al;
-    P.tally = reinterpret_cast<int32_t *>(p); p += tal_al;
-    bvc_bgzf_block *d_blk = reinterpret_cast<bvc_bgzf_block *>(p); p += blk_al;
-    uint32_t *d_bst = reinterpret_cast<uint32_t *>(p); p += bst_al;
-    bvc_pileup_region *d_reg = reinterpret_cast<bvc_pileup_region *>(p); p += reg_al;
-    uint32_t *d_sb = reinterpret_cast<uint32_t *>(p); p += sb_al;
-    uint32_t *d_sn = reinterpret_cast<uint32_t *>(p); p += sn_al;
-    int32_t *d_lines = reinterpret_cast<int32_t *>(p); p += b_al;
-    uint32_t *d_ends = reinterpret_cast<uint32_t *>(p); p += b_al;
-    P.n_batches = n_batches; P.n_pos = max_positions; P.n_lines_cap = n_lines_cap; P.line_stride = max_positions + 1; P.n_pos_dev = d_T;
-    auto drained = [&](int code) { if (code != BVC_OK) { (void)hipStreamSynchronize(ctx->stream); (void)hipGetLastError(); } return code; };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
+    uint8_t *text_out = reinterpret_cast<uint8_t *>(pile.pz_text[nw].p);
+    P.text = text_out;
+    int32_t *d_T = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(P.status) + 128);
+    P.n_pos_dev = d_T;
     PinIO io(ctx);
     rc = io.reserve((n_blocks > 0 && in_pinned(comp, (size_t)comp_bytes) ? 0 : (size_t)comp_bytes) + (size_t)n_blocks * sizeof(bvc_bgzf_block) +
                         nb * (sizeof(bvc_pileup_region) + 12) + 1024,
                     (size_t)n_blocks * 4 + nb * 8 + 1024);
     if (rc != BVC_OK) return rc;
-    BVC_HIP_D(hipMemsetAsync(P.status, 0, st_al + 2 * off_al + tal_al, ctx->stream));
+    BVC_HIP_D(ctx, hipMemsetAsync(P.status, 0, clear, ctx->stream));
     std::vector<uint32_t> bst((size_t)n_blocks);
     std::vector<uint32_t> ends(nb);
     uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1433,48 +1371,46 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
     int32_t Tgot = 0;
     if (nb > 0) {
         if (n_blocks > 0) {
-            BVC_HIP_D(io.h2d(ctx->d_pz_comp, comp, (size_t)comp_bytes));
-            BVC_HIP_D(io.h2d(d_blk, blk.data(), (size_t)n_blocks * sizeof(bvc_bgzf_block)));
+            BVC_HIP_D(ctx, io.h2d(pile.pz_comp.p, comp, (size_t)comp_bytes));
+            BVC_HIP_D(ctx, io.h2d(d_blk, blk.data(), (size_t)n_blocks * sizeof(bvc_bgzf_block)));
         }
-        BVC_HIP_D(io.h2d(d_reg, reg.data(), nb * sizeof(bvc_pileup_region)));
-        BVC_HIP_D(io.h2d(d_sb, seg_base.data(), (nb + 1) * 4));
-        BVC_HIP_D(io.h2d(d_s0, sample0, nb * 4));
-        BVC_HIP_D(io.h2d(d_nib, n_in_batch, nb * 4));
-        BVC_HIP_D(launch_region_carry(ctx->stream, reinterpret_cast<const uint8_t *>(ctx->d_pz_text[ctx->pz_cur]),
-                                      reinterpret_cast<uint8_t *>(ctx->d_pz_text[nw]), d_reg, n_batches));
+        BVC_HIP_D(ctx, io.h2d(d_reg, reg.data(), nb * sizeof(bvc_pileup_region)));
+        BVC_HIP_D(ctx, io.h2d(d_sb, seg_base.data(), (nb + 1) * 4));
+        BVC_HIP_D(ctx, io.h2d(d_s0, sample0, nb * 4));
+        BVC_HIP_D(ctx, io.h2d(d_nib, n_in_batch, nb * 4));
+        BVC_HIP_D(ctx, launch_region_carry(ctx->stream, reinterpret_cast<const uint8_t *>(pile.pz_text[pile.pz_cur].p), text_out, d_reg,
+                                           n_batches));
         if (n_blocks > 0)
-            BVC_HIP_D(launch_inflate(ctx->stream, reinterpret_cast<const uint8_t *>(ctx->d_pz_comp), d_blk, n_blocks,
-                                     reinterpret_cast<uint8_t *>(ctx->d_pz_text[nw]), d_bst));
-        BVC_HIP_D(launch_region_index(ctx->stream, P, d_reg, d_sb, (int64_t)segs, d_sn, d_lines, max_positions));
-        BVC_HIP_D(launch_region_ends(ctx->stream, P, d_ends));
-        BVC_HIP_D(launch_pileup_count(ctx->stream, P));
-        if (n_blocks > 0) BVC_HIP_D(io.d2h(bst.data(), d_bst, (size_t)n_blocks * 4));
-        BVC_HIP_D(io.d2h(lines_of_batch, d_lines, nb * 4));
-        BVC_HIP_D(io.d2h(ends.data(), d_ends, nb * 4));
-        BVC_HIP_D(io.d2h(&Tgot, d_T, 4));
+            BVC_HIP_D(ctx, launch_inflate(ctx->stream, reinterpret_cast<const uint8_t *>(pile.pz_comp.p), d_blk, n_blocks, text_out, d_bst));
+        BVC_HIP_D(ctx, launch_region_index(ctx->stream, P, d_reg, d_sb, (int64_t)segs, d_sn, d_lines, max_positions));
+        BVC_HIP_D(ctx, launch_region_ends(ctx->stream, P, d_ends));
+        BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
+        if (n_blocks > 0) BVC_HIP_D(ctx, io.d2h(bst.data(), d_bst, (size_t)n_blocks * 4));
+        BVC_HIP_D(ctx, io.d2h(lines_of_batch, d_lines, nb * 4));
+        BVC_HIP_D(ctx, io.d2h(ends.data(), d_ends, nb * 4));
+        BVC_HIP_D(ctx, io.d2h(&Tgot, d_T, 4));
     }
-    BVC_HIP_D(io.d2h(st, P.status, sizeof st));
-    BVC_HIP_D(io.d2h(tot, P.totals, sizeof tot));
-    BVC_HIP_D(wait_stream(ctx));
+    BVC_HIP_D(ctx, io.d2h(st, P.status, sizeof st));
+    BVC_HIP_D(ctx, io.d2h(tot, P.totals, sizeof tot));
+    BVC_HIP_D(ctx, wait_stream(ctx));
     io.deliver();
-#undef BVC_HIP_D
     for (int64_t i = 0; i < n_blocks; ++i)
         if (bst[(size_t)i] != 0) {
-            ctx->pz_left_len.assign(nb, 0u);                     // the stream of this window is broken: nothing to carry on with
+            pile.left_len.assign(nb, 0u);                        // the stream of this window is broken: nothing to carry on with
             return fail(ctx, BVC_ERR_DATA, bst[(size_t)i] == 10 ? "a BGZF block of a temp batch fails its CRC32"
                                                                 : "a BGZF block of a temp batch is not valid deflate of its ISIZE bytes");
         }
     // what this tile leaves of every batch: from the end of its last line to the end of its region
-    for (size_t b = 0; b < nb; ++b) { ctx->pz_left_src[b] = ends[b]; ctx->pz_left_len[b] = region_end[b] - ends[b]; }
-    ctx->pz_cur = nw;
+    for (size_t b = 0; b < nb; ++b) { pile.left_src[b] = ends[b]; pile.left_len[b] = region_end[b] - ends[b]; }
+    pile.pz_cur = nw;
     P.n_pos = Tgot; P.n_pos_dev = nullptr;
-    ctx->pl_text_bytes = (int64_t)text_bytes;
-    ctx->pl_on_device_text = true;
+    pile.tile.text_bytes = (int64_t)text_bytes;
+    pile.tile.on_device_text = true;
     *n_positions = Tgot;
     if (Tgot == 0) return BVC_OK;
     if (st[0] != 0) return BVC_PILEUP_IRREGULAR;
-    ctx->pl_entries = tot[0]; ctx->pl_obs = tot[1]; ctx->pl_indels = st[1]; ctx->pl_indel_bytes = st[4];
-    ctx->pl_begun = true;
+    pile.tile.entries = tot[0]; pile.tile.obs = tot[1]; pile.tile.indels = st[1]; pile.tile.indel_bytes = st[4];
+    pile.tile.begun = true;
     *n_entries = tot[0]; *n_indels = st[1]; *indel_text_bytes = st[4];
     return BVC_OK;
 }
@@ -1482,13 +1418,14 @@ int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes,
 int bvc_pileup_text(bvc_ctx *ctx, char *text, int64_t text_cap, int64_t *text_bytes_needed, uint32_t *line_start)
 {
     if (!ctx || !text_bytes_needed) return BVC_ERR_ARG;
-    if (!ctx->pl_on_device_text) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_text without a tile from bvc_pileup_begin_bgzf");
-    *text_bytes_needed = ctx->pl_text_bytes;
+    const PileupState::Tile &tile = ctx->pile.tile;
+    if (!tile.on_device_text) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_text without a tile from bvc_pileup_begin_bgzf");
+    *text_bytes_needed = tile.text_bytes;
     if (!text) return BVC_OK;
-    if (text_cap < ctx->pl_text_bytes || !line_start) return fail(ctx, BVC_ERR_ARG, "text buffer too small / null line table");
+    if (text_cap < tile.text_bytes || !line_start) return fail(ctx, BVC_ERR_ARG, "text buffer too small / null line table");
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    const PileupTile &P = ctx->pl;
-    if (ctx->pl_text_bytes) BVC_HIP(ctx, hipMemcpyAsync(text, P.text, (size_t)ctx->pl_text_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    const PileupTile &P = tile.P;
+    if (tile.text_bytes) BVC_HIP(ctx, hipMemcpyAsync(text, P.text, (size_t)tile.text_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (P.n_batches > 0)
         BVC_HIP(ctx, hipMemcpy2DAsync(line_start, (size_t)(P.n_pos + 1) * 4, P.line_start, (size_t)P.line_stride * 4, (size_t)(P.n_pos + 1) * 4,
                                       (size_t)P.n_batches, hipMemcpyDeviceToHost, ctx->stream));
@@ -1505,11 +1442,13 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
                               bvc_group_result *grp_results)
 {
     if (!ctx) return BVC_ERR_ARG;
-    if (!ctx->pl_begun) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_finish without a bvc_pileup_begin that returned BVC_OK");
-    if (ctx->pl_on_device_text && ctx->pl_indels > 0 && !indel_text) return fail(ctx, BVC_ERR_ARG, "indel_text is needed: the tile's text is on the device only");
-    ctx->pl_begun = false;
-    PileupTile &P = ctx->pl;
-    const int64_t T = P.n_pos, n_e = ctx->pl_entries, n_o = ctx->pl_obs, n_i = ctx->pl_indels;
+    PileupState &pile = ctx->pile;
+    PileupState::Tile &tile = pile.tile;
+    if (!tile.begun) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_finish without a bvc_pileup_begin that returned BVC_OK");
+    if (tile.on_device_text && tile.indels > 0 && !indel_text) return fail(ctx, BVC_ERR_ARG, "indel_text is needed: the tile's text is on the device only");
+    tile.begun = false;
+    PileupTile &P = tile.P;
+    const int64_t T = P.n_pos, n_e = tile.entries, n_o = tile.obs, n_i = tile.indels, n_it = tile.indel_bytes;
     if (!carry_in || !carry_out || !entry_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
     if (T > 0 && (!ref_base || !tally || !results)) return fail(ctx, BVC_ERR_ARG, "null pointer");
     const bool called_only = called_off != nullptr;
@@ -1518,104 +1457,84 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
     if (n_groups > 0 && (!grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t e_al = al256((size_t)n_e * sizeof(bvc_pileup_entry) + 16), s_al = al256((size_t)n_e * 4 + 16), o_al = al256((size_t)n_o + 16);
-    const size_t os_al = al256((size_t)n_o * 4 + 16), i_al = al256((size_t)n_i * sizeof(bvc_pileup_indel) + 16), r_al = al256((size_t)T + 16);
-    const size_t res_al = al256((size_t)T * sizeof(bvc_site_result)), g_al = al256((size_t)(n_groups ? n_samples : 0) + 16);
-    const size_t gres_al = al256((size_t)T * (size_t)n_groups * sizeof(bvc_group_result));
-    const size_t it_al = al256((size_t)(indel_text ? ctx->pl_indel_bytes : 0) + 16);
-    const size_t co_al = al256(called_only ? (size_t)(T + 1) * 8 : 0);
-    int rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pl_out), &ctx->pl_out_cap,
-                    e_al + s_al + 2 * o_al + os_al + i_al + r_al + res_al + g_al + gres_al + it_al + co_al + 256);
+    int8_t *d_ref; bvc_site_result *d_res; uint8_t *d_g, *d_itext; bvc_group_result *d_gres; int64_t *d_called_off;
+    int rc = carve(ctx, pile.out, 256, [&](Layout &L) {
+        P.entries = L.take<bvc_pileup_entry>((size_t)n_e, 16);
+        P.samples = L.take<int32_t>((size_t)n_e, 16);
+        P.obs_base = L.take<int8_t>((size_t)n_o, 16);
+        P.obs_qual = L.take<int8_t>((size_t)n_o, 16);
+        P.obs_sample = L.take<int32_t>((size_t)n_o, 16);
+        P.indels = L.take<bvc_pileup_indel>((size_t)n_i, 16);
+        d_ref = L.take<int8_t>((size_t)T, 16);
+        d_res = L.take<bvc_site_result>((size_t)T);
+        d_g = L.take<uint8_t>((size_t)(n_groups ? n_samples : 0), 16);
+        d_gres = L.take<bvc_group_result>((size_t)T * (size_t)n_groups);
+        d_itext = L.take<uint8_t>((size_t)(indel_text ? n_it : 0), 16);
+        d_called_off = L.take<int64_t>(called_only ? (size_t)(T + 1) : 0);
+    });
     if (rc != BVC_OK) return rc;
-    char *p = ctx->d_pl_out;
-    P.entries = reinterpret_cast<bvc_pileup_entry *>(p); p += e_al;
-    P.samples = reinterpret_cast<int32_t *>(p); p += s_al;
-    P.obs_base = reinterpret_cast<int8_t *>(p); p += o_al;
-    P.obs_qual = reinterpret_cast<int8_t *>(p); p += o_al;
-    P.obs_sample = reinterpret_cast<int32_t *>(p); p += os_al;
-    P.indels = reinterpret_cast<bvc_pileup_indel *>(p); p += i_al;
     P.indel_cap = (uint32_t)n_i;
-    int8_t *d_ref = reinterpret_cast<int8_t *>(p); p += r_al;
-    bvc_site_result *d_res = reinterpret_cast<bvc_site_result *>(p); p += res_al;
-    uint8_t *d_g = reinterpret_cast<uint8_t *>(p); p += g_al;
-    bvc_group_result *d_gres = reinterpret_cast<bvc_group_result *>(p); p += gres_al;
-    uint8_t *d_itext = reinterpret_cast<uint8_t *>(p); p += it_al;
-    int64_t *d_called_off = reinterpret_cast<int64_t *>(p);
     const uint32_t cin = (uint32_t)(carry_in[0] & 7u) | ((uint32_t)(carry_in[4] & 1u) << 3) | 0x80u | ((uint32_t)carry_in[1] << 8) |
                          ((uint32_t)carry_in[2] << 16) | ((uint32_t)carry_in[3] << 24);
-    auto drained = [&](int code) {
-        if (code != BVC_OK) {
-            (void)hipStreamSynchronize(ctx->stream); (void)hipStreamSynchronize(ctx->side); (void)hipStreamSynchronize(ctx->side_b);
-            (void)hipStreamSynchronize(ctx->side_c);
-            for (bool &pnd : ctx->em_pending) pnd = false;
-            (void)hipGetLastError();
-        }
-        return code;
-    };
-#define BVC_HIP_D(call)                                                                   \
-    do {                                                                                  \
-        hipError_t e__ = (call);                                                          \
-        if (e__ != hipSuccess) return drained(fail(ctx, BVC_ERR_DEVICE, #call, e__));     \
-    } while (0)
     uint32_t cout = cin;
     PinIO io(ctx);
     rc = io.reserve((size_t)T + (size_t)(n_groups > 0 ? n_samples : 0) + 1024,
                     (size_t)T * (sizeof(bvc_site_result) + 32 * 4 + 8 + (size_t)n_groups * sizeof(bvc_group_result)) +
                         (size_t)(called_only ? 0 : n_e) * (sizeof(bvc_pileup_entry) + 4) + (called_only ? (size_t)(T + 1) * 8 : 0) +
-                        (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)ctx->pl_indel_bytes + 4096);
+                        (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)n_it + 4096);
     if (rc != BVC_OK) return rc;
     if (T > 0) {
-        BVC_HIP_D(io.h2d(d_ref, ref_base, (size_t)T));
-        if (n_groups > 0 && n_samples > 0) BVC_HIP_D(io.h2d(d_g, group_of_sample, (size_t)n_samples));
-        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(launch_pileup_write(ctx->stream, P, cin));
+        BVC_HIP_D(ctx, io.h2d(d_ref, ref_base, (size_t)T));
+        if (n_groups > 0 && n_samples > 0) BVC_HIP_D(ctx, io.h2d(d_g, group_of_sample, (size_t)n_samples));
+        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, launch_pileup_write(ctx->stream, P, cin));
         if (n_groups > 0)
             rc = run_csr_groups_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, P.obs_sample, d_ref, min_af, d_g, n_samples, n_groups, d_res, d_gres);
         else
             rc = run_csr_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, d_ref, min_af, nullptr, nullptr, d_res);
         if (rc == BVC_OK) rc = join_side(ctx);
-        if (rc != BVC_OK) return drained(rc);
-        BVC_HIP_D(io.d2h(results, d_res, (size_t)T * sizeof(bvc_site_result)));
+        if (rc != BVC_OK) return drain_on_error(ctx, rc);
+        BVC_HIP_D(ctx, io.d2h(results, d_res, (size_t)T * sizeof(bvc_site_result)));
         if (n_groups > 0)
-            BVC_HIP_D(io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
-        BVC_HIP_D(io.d2h(tally, P.tally, (size_t)T * 32 * 4));
+            BVC_HIP_D(ctx, io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
+        BVC_HIP_D(ctx, io.d2h(tally, P.tally, (size_t)T * 32 * 4));
         if (n_e && !called_only) {
-            BVC_HIP_D(io.d2h(entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
-            BVC_HIP_D(io.d2h(samples, P.samples, (size_t)n_e * 4));
+            BVC_HIP_D(ctx, io.d2h(entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
+            BVC_HIP_D(ctx, io.d2h(samples, P.samples, (size_t)n_e * 4));
         }
         if (called_only) {
-            BVC_HIP_D(launch_called_scan(ctx->stream, P, d_res, d_called_off));
-            BVC_HIP_D(io.d2h(called_off, d_called_off, (size_t)(T + 1) * 8));
+            BVC_HIP_D(ctx, launch_called_scan(ctx->stream, P, d_res, d_called_off));
+            BVC_HIP_D(ctx, io.d2h(called_off, d_called_off, (size_t)(T + 1) * 8));
         }
         if (n_i && indel_text) {
-            BVC_HIP_D(launch_indel_text(ctx->stream, P, d_itext, (uint32_t)ctx->pl_indel_bytes, P.status + 5));
-            if (ctx->pl_indel_bytes) BVC_HIP_D(io.d2h(indel_text, d_itext, (size_t)ctx->pl_indel_bytes));
+            BVC_HIP_D(ctx, launch_indel_text(ctx->stream, P, d_itext, (uint32_t)n_it, P.status + 5));
+            if (n_it) BVC_HIP_D(ctx, io.d2h(indel_text, d_itext, (size_t)n_it));
         }
-        if (n_i) BVC_HIP_D(io.d2h(indels, P.indels, (size_t)n_i * sizeof(bvc_pileup_indel)));
-        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(io.d2h(&cout, P.status + 3, 4));
+        if (n_i) BVC_HIP_D(ctx, io.d2h(indels, P.indels, (size_t)n_i * sizeof(bvc_pileup_indel)));
+        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, io.d2h(&cout, P.status + 3, 4));
     }
-    BVC_HIP_D(io.d2h(entry_off, P.entry_off, (size_t)(T + 1) * 8));
-    BVC_HIP_D(wait_stream(ctx));
+    BVC_HIP_D(ctx, io.d2h(entry_off, P.entry_off, (size_t)(T + 1) * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
     io.deliver();
     if (called_only && T == 0) called_off[0] = 0;
     if (called_only && T > 0 && called_off[T] > 0) {
         // the second trip: the called positions' entries, gathered on the device (typically a few per cent of the tile's)
         const int64_t n_c = called_off[T];
         if (n_c > called_cap) return fail(ctx, BVC_ERR_ARG, "called_cap is smaller than the entries of the called positions (n_entries of the begin call always suffices)");
-        const size_t ce_al = al256((size_t)n_c * sizeof(bvc_pileup_entry));
-        rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_pl_called), &ctx->pl_called_cap, ce_al + al256((size_t)n_c * 4));
+        bvc_pileup_entry *d_ce; int32_t *d_cs;
+        rc = carve(ctx, pile.called, 0, [&](Layout &L) {
+            d_ce = L.take<bvc_pileup_entry>((size_t)n_c);
+            d_cs = L.take<int32_t>((size_t)n_c);
+        });
         if (rc != BVC_OK) return rc;
-        bvc_pileup_entry *d_ce = reinterpret_cast<bvc_pileup_entry *>(ctx->d_pl_called);
-        int32_t *d_cs = reinterpret_cast<int32_t *>(ctx->d_pl_called + ce_al);
         io.down_used = 0;
         rc = io.reserve(0, (size_t)n_c * (sizeof(bvc_pileup_entry) + 4) + 4096);
         if (rc != BVC_OK) return rc;
-        BVC_HIP_D(launch_called_gather(ctx->stream, P, d_called_off, d_ce, d_cs));
-        BVC_HIP_D(io.d2h(entries, d_ce, (size_t)n_c * sizeof(bvc_pileup_entry)));
-        BVC_HIP_D(io.d2h(samples, d_cs, (size_t)n_c * 4));
-        BVC_HIP_D(wait_stream(ctx));
+        BVC_HIP_D(ctx, launch_called_gather(ctx->stream, P, d_called_off, d_ce, d_cs));
+        BVC_HIP_D(ctx, io.d2h(entries, d_ce, (size_t)n_c * sizeof(bvc_pileup_entry)));
+        BVC_HIP_D(ctx, io.d2h(samples, d_cs, (size_t)n_c * 4));
+        BVC_HIP_D(ctx, wait_stream(ctx));
         io.deliver();
     }
-#undef BVC_HIP_D
     carry_out[0] = (uint8_t)(cout & 7u); carry_out[1] = (uint8_t)(cout >> 8); carry_out[2] = (uint8_t)(cout >> 16);
     carry_out[3] = (uint8_t)(cout >> 24); carry_out[4] = (uint8_t)((cout >> 3) & 1u);
     return BVC_OK;
@@ -1659,17 +1578,18 @@ static int lrt_groups_impl(bvc_ctx *ctx, bool packed, int64_t n_sites, int64_t n
     auto run_device = [&](int64_t ns, const int8_t *b, const int8_t *q, const int8_t *r, const uint8_t *g,
                           bvc_site_result *res, bvc_group_result *gres) -> int {
         const size_t lbytes = group_labels_bytes(n_samples, ns);       // the call's labels clamped to 0..n_groups + a flag per site
-        if (lbytes > ctx->grp_labels_cap) { int rj = join_side(ctx); if (rj != BVC_OK) return rj; }
-        int rc2 = ensure(ctx, reinterpret_cast<void **>(&ctx->d_grp_labels), &ctx->grp_labels_cap, lbytes);
+        if (lbytes > ctx->d_grp_labels.cap) { int rj = join_side(ctx); if (rj != BVC_OK) return rj; }
+        int rc2 = ensure(ctx, ctx->d_grp_labels, lbytes);
         if (rc2 != BVC_OK) return rc2;
+        uint8_t *labels = reinterpret_cast<uint8_t *>(ctx->d_grp_labels.p);
         return run_group_stages(ctx, ns, n_groups, n_samples >= 200000,
                                 [&](uint32_t *gp) {
                                     if (packed)
                                         return launch_hist_packed_groups(ctx->ls, ctx->stream, ns, n_samples, row_stride,
                                                                          reinterpret_cast<const uint8_t *>(b), g, n_groups, gp,
-                                                                         ctx->d_grp_scratch, ctx->d_grp_labels);
+                                                                         ctx->d_grp_scratch, labels);
                                     return launch_hist_dense(ctx->ls, ctx->stream, ns, n_samples, row_stride, b, q, g, n_groups, gp, 1,
-                                                             ctx->d_grp_scratch, ctx->d_grp_labels);
+                                                             ctx->d_grp_scratch, labels);
                                 },
                                 r, min_af, res, gres);
     };
@@ -1677,48 +1597,11 @@ static int lrt_groups_impl(bvc_ctx *ctx, bool packed, int64_t n_sites, int64_t n
     if (flags & BVC_PTR_DEVICE)
         return run_device(n_sites, bases, quals, ref_base, group_of_sample, results, grp_results);
 
-    const int64_t row_bytes = row_stride > 0 ? row_stride : 1;
-    int64_t chunk = ctx->ls.host_chunk_bytes / row_bytes;
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_sites) chunk = n_sites;
-    const size_t arr_al = ((size_t)chunk * (size_t)row_stride + 255) & ~(size_t)255;
-    const size_t ref_al = ((size_t)chunk + 255) & ~(size_t)255;
-    const size_t g_al = ((size_t)n_samples + 255) & ~(size_t)255;
-    const size_t res_al = ((size_t)chunk * sizeof(bvc_site_result) + 255) & ~(size_t)255;
-    const size_t need = (packed ? 1 : 2) * arr_al + ref_al + g_al + res_al + (size_t)chunk * n_groups * sizeof(bvc_group_result) + 256;
-    const int n_sets = n_sites > chunk ? 2 : 1;
-    for (int k = 0; k < n_sets; ++k) {
-        rc = ensure(ctx, reinterpret_cast<void **>(&ctx->d_stage[k]), &ctx->stage_cap[k], need);
-        if (rc != BVC_OK) return rc;
-    }
-    auto d_b = [&](int set) { return reinterpret_cast<int8_t *>(ctx->d_stage[set]); };
-    auto d_q = [&](int set) { return packed ? d_b(set) : d_b(set) + arr_al; };
-    auto d_r = [&](int set) { return d_q(set) + arr_al; };
-    auto d_g = [&](int set) { return reinterpret_cast<uint8_t *>(d_r(set) + ref_al); };
-    auto d_res = [&](int set) { return reinterpret_cast<bvc_site_result *>(d_g(set) + g_al); };
-    auto d_gres = [&](int set) { return reinterpret_cast<bvc_group_result *>(reinterpret_cast<char *>(d_res(set)) + res_al); };
-    return run_chunks(ctx, n_sites, chunk,
-        [&](int set, int64_t s0, int64_t ns) -> int {
-            const size_t bytes = n_samples ? (size_t)(ns - 1) * (size_t)row_stride + (size_t)n_samples : 0;
-            // the group vector travels with the first chunk of each staging set
-            if (s0 < 2 * chunk && n_samples)
-                BVC_HIP(ctx, hipMemcpyAsync(d_g(set), group_of_sample, (size_t)n_samples, hipMemcpyHostToDevice, ctx->copy));
-            if (bytes) BVC_HIP(ctx, hipMemcpyAsync(d_b(set), bases + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
-            if (bytes && !packed) BVC_HIP(ctx, hipMemcpyAsync(d_q(set), quals + s0 * row_stride, bytes, hipMemcpyHostToDevice, ctx->copy));
-            BVC_HIP(ctx, hipMemcpyAsync(d_r(set), ref_base + s0, (size_t)ns, hipMemcpyHostToDevice, ctx->copy));
-            return BVC_OK;
-        },
-        [&](int set, int64_t s0, int64_t ns, bool download) -> int {
-            if (!download) {
-                int rc2 = run_device(ns, d_b(set), d_q(set), d_r(set), d_g(set), d_res(set), d_gres(set));
-                return rc2 == BVC_OK ? join_side(ctx) : rc2;
-            }
-            BVC_HIP(ctx, hipMemcpyAsync(results + s0, d_res(set), (size_t)ns * sizeof(bvc_site_result), hipMemcpyDeviceToHost,
-                                        ctx->stream));
-            BVC_HIP(ctx, hipMemcpyAsync(grp_results + s0 * n_groups, d_gres(set), (size_t)ns * n_groups * sizeof(bvc_group_result),
-                                        hipMemcpyDeviceToHost, ctx->stream));
-            return BVC_OK;
-        });
+    const int8_t *rows[2] = {bases, quals};
+    return run_dense_host(ctx, n_sites, n_samples, row_stride, packed ? 1 : 2, rows, ref_base, group_of_sample, n_groups, results,
+                          grp_results, [&](int64_t ns, const DenseSet &d) {
+                              return run_device(ns, d.rows[0], d.rows[1], d.ref, d.labels, d.res, d.gres);
+                          });
 }
 
 int bvc_lrt_dense_groups(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride,

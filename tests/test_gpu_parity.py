@@ -719,8 +719,11 @@ def test_host_pointer_calls_pipeline_their_chunks(ctx):
     B[:, n:] = 7                                                 # junk in the row padding
     m = caller_min_af(n)
     g = rng.integers(0, k + 1, n + 48).astype(np.uint8)
+    P = _pack_numpy(B, Q)                                        # the packed forms: one row array instead of two
     one = ctx.lrt_dense(B, Q, R, m)
     one_g = ctx.lrt_dense_groups(B, Q, R, m, g, k)
+    one_p = ctx.lrt_dense_packed(P, R, m)
+    one_gp = ctx.lrt_dense_groups_packed(P, R, m, g, k)
     for overlap in (False, True):
         for kib in (20, 137, 1000):                              # 1, 6 and 51 sites per chunk
             with Context(0) as c:
@@ -729,6 +732,9 @@ def test_host_pointer_calls_pipeline_their_chunks(ctx):
                 assert c.lrt_dense(B, Q, R, m).tobytes() == one.tobytes(), (overlap, kib)
                 res, gres = c.lrt_dense_groups(B, Q, R, m, g, k)
                 assert res.tobytes() == one_g[0].tobytes() and gres.tobytes() == one_g[1].tobytes(), (overlap, kib)
+                assert c.lrt_dense_packed(P, R, m).tobytes() == one_p.tobytes(), (overlap, kib)
+                res, gres = c.lrt_dense_groups_packed(P, R, m, g, k)
+                assert res.tobytes() == one_gp[0].tobytes() and gres.tobytes() == one_gp[1].tobytes(), (overlap, kib)
     exp = orc.basetype_lrt(sites[7][0], sites[7][1], sites[7][2], m)
     assert_site_matches(one[7], exp, where="chunked host call, site 7")
 
@@ -983,6 +989,13 @@ def test_error_behaviour_of_the_c_abi(ctx):
     assert L.bvc_pack_dense(hh, 2, 8, 8, vp(B), vp(B), 8, vp(P), C.byref(bad), 0) == -1 and b"device pointers" in L.bvc_last_error(hh)
     assert L.bvc_pack_dense(hh, 2, 8, 8, vp(B), vp(B), 4, vp(P), C.byref(bad), 1) == -1     # packed stride < n_samples
     assert L.bvc_hist_dense_packed(hh, 2, 8, 8, vp(P), vp(cnt), 0) == -1
+    # the ragged packed and group calls check their offsets as bvc_lrt_csr does
+    smp = np.zeros(8, dtype=np.int32)
+    for offsets in ([1, 4, 8], [0, 6, 4]):
+        with pytest.raises(BvcError, match="offsets must start at 0"):
+            ctx.lrt_csr_packed(offsets, P.reshape(-1)[:8], R, 0.001)
+        with pytest.raises(BvcError, match="offsets must start at 0"):
+            ctx.lrt_csr_groups(offsets, B.reshape(-1)[:8], B.reshape(-1)[:8], smp, R, 0.001, g, 2)
     # the context is still good, and a site without a call is a record, not an error
     rec = ctx.lrt_dense(np.full((1, 50), 2, dtype=np.int8), np.full((1, 50), 30, dtype=np.int8), [2], 0.001)
     assert int(rec[0]["called"]) == 0 and int(rec[0]["status"]) == 0 and rec[0]["depth"].tolist() == [0, 0, 50, 0]
