@@ -1285,6 +1285,68 @@ int bvc_pileup_begin(bvc_ctx *ctx, const char *text, int64_t text_bytes, const u
     return BVC_OK;
 }
 
+// The binary records of the same content (host/pileup.h): the records go where the text goes, rec_start where line_start goes, and the
+// tile is marked so that the count and write passes launch pileup_bin_kernel; bvc_pileup_finish[_called] serve it as they serve text.
+int bvc_pileup_begin_bin(bvc_ctx *ctx, const uint8_t *records, int64_t records_bytes, const uint32_t *rec_start,
+                         const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
+                         int64_t *n_entries, int64_t *n_indels)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    PileupState::Tile &tile = ctx->pile.tile;
+    tile = PileupState::Tile{};
+    if (n_batches < 0 || n_positions < 0 || records_bytes < 0 || !n_entries || !n_indels) return fail(ctx, BVC_ERR_ARG, "bad argument");
+    if (records_bytes > (int64_t)0xFFFFFF00) return fail(ctx, BVC_ERR_ARG, "more than 4 GiB of records in one tile (use fewer positions)");
+    const int64_t n_recs = (int64_t)n_batches * n_positions;
+    if (n_recs > 0 && (!records || !rec_start || !sample0 || !n_in_batch)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n_positions > (int32_t)(0x7FFFFFFF / 64)) return fail(ctx, BVC_ERR_ARG, "too many positions in one call (split the tile)");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    *n_entries = 0; *n_indels = 0;
+    // the record table is what the kernel bounds every load with: every record inside the buffer, as long as its length word says
+    for (int32_t b = 0; b < n_batches; ++b) {
+        const uint32_t *rs = rec_start + (int64_t)b * (n_positions + 1);
+        if (n_in_batch[b] < 0) return fail(ctx, BVC_ERR_ARG, "negative batch size");
+        for (int32_t t = 0; t < n_positions; ++t) {
+            const int64_t r0 = rs[t], r1 = rs[t + 1];
+            if (r1 < r0 + 4 || r1 > records_bytes) return fail(ctx, BVC_ERR_ARG, "rec_start: records of a batch ascend, each holds its length word, all lie inside records_bytes");
+            const uint8_t *q = records + r0;
+            const int64_t len = (int64_t)((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24));
+            if (r1 - r0 != 4 + len) return fail(ctx, BVC_ERR_ARG, "rec_start disagrees with a record's length word");
+        }
+    }
+    const size_t T = (size_t)n_positions, nb = (size_t)n_batches;
+    PileupTile &P = tile.P;
+    uint32_t *d_rs; int32_t *d_s0, *d_nib;
+    size_t clear = 0;
+    int rc = ensure(ctx, ctx->pile.text, (size_t)records_bytes + 64);
+    if (rc == BVC_OK)
+        rc = carve(ctx, ctx->pile.meta, 0, [&](Layout &L) { clear = carve_tile(L, P, n_batches, n_positions, 0, d_rs, d_s0, d_nib); });
+    if (rc != BVC_OK) return rc;
+    P.text = reinterpret_cast<const uint8_t *>(ctx->pile.text.p);
+    P.bin = true;
+    BVC_HIP_D(ctx, hipMemsetAsync(P.status, 0, clear, ctx->stream));     // status, totals, offsets of an empty tile, tallies
+    if (n_recs > 0) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(ctx->pile.text.p, records, (size_t)records_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_rs, rec_start, nb * (T + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_s0, sample0, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_nib, n_in_batch, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
+    }
+    uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t tot[2] = {0, 0};
+    BVC_HIP_D(ctx, hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    if (st[0] != 0) {
+        const std::string what = std::to_string(st[0]) + " malformed record(s) in the tile (an entry or an indel text runs past its record's end, or a "
+                                 "sample index is not below the batch's size)";
+        return fail(ctx, BVC_ERR_DATA, what.c_str());
+    }
+    tile.entries = tot[0]; tile.obs = tot[1]; tile.indels = st[1]; tile.indel_bytes = st[4];
+    tile.begun = true;
+    *n_entries = tot[0]; *n_indels = st[1];
+    return BVC_OK;
+}
+
 int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks,
                           const int32_t *blocks_of_batch, const int32_t *skip_bytes, const int32_t *sample0, const int32_t *n_in_batch,
                           int32_t n_batches, int32_t max_positions, int32_t reset, int32_t *n_positions, int32_t *lines_of_batch,

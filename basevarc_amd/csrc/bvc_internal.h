@@ -125,6 +125,8 @@ hipError_t launch_synth_dense(hipStream_t stream, uint64_t seed, int64_t site0, 
 // Device buffers of one tile between bvc_pileup_begin and bvc_pileup_finish (all owned by the context).
 struct PileupTile {
     const uint8_t *text = nullptr;
+    bool bin = false;                        // the tile is binary records (bvc_pileup_begin_bin): text = the records, line_start = where each
+                                             // begins; the count and write passes launch pileup_bin_kernel
     const uint32_t *line_start = nullptr;    // [n_batches][line_stride]
     const int32_t *sample0 = nullptr, *n_in_batch = nullptr;
     int32_t n_batches = 0, n_pos = 0;        // n_pos: the tile's positions (an upper bound while n_pos_dev decides)

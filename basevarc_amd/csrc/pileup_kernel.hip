@@ -1,5 +1,5 @@
-// pileup_kernel.hip -- the producer side of the hot path on the device: temp-batch pileup TEXT -> ragged pileup columns,
-// and the per-group histograms of ragged columns.
+// pileup_kernel.hip -- the producer side of the hot path on the device: temp-batch pileup TEXT (or the binary records of the same
+// content, pileup_bin_kernel) -> ragged pileup columns, and the per-group histograms of ragged columns.
 //
 // Reference (paths under /root/reference): the position loop of bt_s parses one line of every temp batch per position with
 // strtok_r / atoi (src/BaseVarC.cpp:403-441; writer :509-527), bt_f then walks the position's entries for the depth and strand
@@ -265,6 +265,140 @@ __global__ __launch_bounds__(kParseWaves * kWave) void pileup_parse_kernel(Parse
     }
 }
 
+// ---- the binary form of the temp batches (host/pileup.h: `--tmp-format bin` and `raw`) -----------------------------------------
+// A record = u32 payload bytes | payload; the payload = entries, entry = u32 sample-in-batch | u8 base mapq qual rpr flags
+// [| u16 n | n bytes of indel text] (flags: bit 0 strand, bit 1 indel).  The behaviour is that of parse_pileup_bin (host/pileup.cpp):
+// base = byte & 7, strand = flags & 1, a base entry with base 4 is dropped but stays "the last base token", an indel entry carries
+// the fields of the last base entry before it.  Same two passes and the same per-record words as the text kernel above (A.text = the
+// records, A.line_start = where each begins, at its length word; the host has checked that table against the length words and the
+// buffer's size), so the scan, the patch kernel and everything behind them serve both forms.
+//
+// One WAVEFRONT per record.  Entries are nine bytes except where an indel entry sits (a few per thousand), so per step lane i takes
+// the candidate entry at p + 9 i: the first lane whose flags say "indel" ends the step -- the lanes in front of it are base entries,
+// it is the indel entry, and the next step starts behind its text.  Ranks from ballots.  Every offset is compared with the record's
+// end before the bytes behind it are read, whatever the bytes say: a record that does not add up (fewer than 9 bytes left, fewer
+// than 11 for an indel entry, indel text past the end, a sample index that is not below the batch's size -- the index feeds the
+// group lookup) is counted in status[0] and followed no further.
+// The nine bytes of an entry start anywhere: two aligned 8-byte loads and shifts (the buffer is allocated 64 bytes longer than the
+// records); only the length of an indel entry, one lane per step, is read by bytes.
+template <bool WRITE>
+__global__ __launch_bounds__(kParseWaves * kWave) void pileup_bin_kernel(ParseArgs A)
+{
+    BVC_POISON_LDS();
+    __shared__ uint32_t tal_all[kParseWaves][32];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t *tal = tal_all[wave];
+    if (lane < 32) tal[lane] = 0u;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+    __builtin_amdgcn_wave_barrier();
+    const uint8_t *__restrict__ text = A.text;
+    const uint64_t below = (1ull << lane) - 1ull;
+    const int64_t n_lines = (int64_t)A.n_pos * A.n_batches;
+    for (int64_t line = (int64_t)blockIdx.x * kParseWaves + wave; line < n_lines; line += (int64_t)gridDim.x * kParseWaves) {
+        const int t = (int)(line / A.n_batches), b = (int)(line - (int64_t)t * A.n_batches);
+        const uint32_t s = A.line_start[(int64_t)b * A.line_stride + t];
+        const uint32_t e = A.line_start[(int64_t)b * A.line_stride + t + 1];       // the payload is [s + 4, e)
+        bool bad = e < s || e - s < 4u;                                             // (wave-uniform, as everything that steers the walk)
+        const int32_t smp0 = A.sample0[b];
+        const uint32_t n_in = (uint32_t)A.n_in_batch[b];
+        uint32_t ent_at = 0, obs_at = 0;
+        if (WRITE) { ent_at = A.line_entries[line]; obs_at = A.line_obs[line]; }
+        uint32_t ent_run = 0, obs_run = 0, need = 0, n_ind_line = 0, ind_bytes = 0;
+        uint32_t prev_tok = 0;                                   // last base entry of the record so far (packed)
+        uint32_t p = s + 4u;
+        while (!bad && p < e) {
+            const uint32_t rem = e - p, mine = 9u * (uint32_t)lane;
+            const bool in = mine + 9u <= rem;                    // nine bytes of an entry lie inside the record at p + mine
+            const uint32_t q = p + mine;
+            uint32_t smp = 0, hi = 0, flags = 0;
+            if (in) {
+                const uint64_t *w = reinterpret_cast<const uint64_t *>(text + (q & ~7u));
+                const uint64_t w0 = w[0], w1 = w[1];
+                const uint32_t sh = 8u * (q & 7u);
+                const uint64_t lo8 = sh ? (w0 >> sh) | (w1 << (64u - sh)) : w0;    // bytes 0..7 of the entry
+                smp = (uint32_t)lo8; hi = (uint32_t)(lo8 >> 32);
+                flags = (uint32_t)(w1 >> sh) & 0xFFu;            // byte 8
+            }
+            const uint64_t in_m = __ballot(in);                  // lanes 0 .. n_whole - 1
+            const uint64_t ind_m = __ballot(in && (flags & 2u));
+            const int n_whole = __builtin_popcountll(in_m);
+            const int k = ind_m ? __builtin_ctzll(ind_m) : kWave;                 // the step's indel entry, if any
+            const int n_base = k < n_whole ? k : n_whole;        // lanes [0, n_base) are base entries
+            uint32_t n_txt = 0;
+            if (k < kWave) {
+                const uint32_t at = 9u * (uint32_t)k;            // the indel entry: 11 bytes and its text inside the record
+                if (at + 11u > rem) bad = true;
+                else {
+                    uint32_t v = 0;
+                    if (lane == k) v = (uint32_t)text[q + 9u] | ((uint32_t)text[q + 10u] << 8);
+                    n_txt = (uint32_t)__shfl((int)v, k, kWave);
+                    if (n_txt > rem - at - 11u) bad = true;
+                }
+            } else if (n_whole < kWave && 9u * (uint32_t)n_whole != rem) bad = true;          // fewer than nine bytes left
+            const bool is_base = lane < n_base, is_ind = lane == k;
+            if (__ballot((is_base || is_ind) && smp >= n_in)) bad = true;
+            if (bad) break;
+            const uint32_t tok = (hi & 7u) | ((flags & 1u) << 3) | kTokValid | (hi & 0xFFFFFF00u);
+            const bool is_ent = is_base && (hi & 7u) != 4u;      // N base: dropped, but the last base entry all the same
+            const uint64_t ent_m = __ballot(is_ent);
+            const uint32_t rank = (uint32_t)__builtin_popcountll(ent_m & below);
+            const uint32_t n_ent = (uint32_t)__builtin_popcountll(ent_m);
+            uint32_t src = prev_tok;                             // what an indel entry of this step inherits
+            if (n_base > 0) { prev_tok = (uint32_t)__shfl((int)tok, n_base - 1, kWave); if (k < kWave) src = prev_tok; }
+            if (WRITE) {
+                if (is_ent) {
+                    const uint32_t ent_i = ent_at + ent_run + rank, obs_i = obs_at + obs_run + rank;
+                    *reinterpret_cast<u32x2 *>(&A.entries[ent_i]) = u32x2{(tok & 7u) | (tok & 0xFFFFFF00u), (tok >> 3) & 1u};
+                    A.samples[ent_i] = smp0 + (int32_t)smp;
+                    A.obs_base[obs_i] = (int8_t)(tok & 7u);
+                    A.obs_qual[obs_i] = (int8_t)((tok >> 16) & 0xFFu);
+                    A.obs_sample[obs_i] = smp0 + (int32_t)smp;
+                    atomicAdd(&tal[tok & 15u], 1u);
+                }
+                if (is_ind) {
+                    // (src == 0: no base entry in front of it in this record -- pileup_patch_kernel fills the fields in)
+                    const uint32_t ent_i = ent_at + ent_run + n_ent;
+                    *reinterpret_cast<u32x2 *>(&A.entries[ent_i]) = u32x2{(src & 7u) | (src & 0xFFFFFF00u), ((src >> 3) & 1u) | 0x100u};
+                    A.samples[ent_i] = smp0 + (int32_t)smp;
+                    if (src) atomicAdd(&tal[16u + (src & 15u)], 1u);
+                    const uint32_t r = atomicAdd(&A.status[2], 1u);
+                    if (r < A.indel_cap) A.indels[r] = bvc_pileup_indel{(int64_t)ent_i, (int64_t)q + 11, (int32_t)n_txt, 0};
+                }
+            }
+            ent_run += n_ent; obs_run += n_ent;
+            if (k < kWave) {
+                ent_run += 1u; n_ind_line += 1u; ind_bytes += n_txt;
+                if (src == 0u) need += 1u;
+                p += 9u * (uint32_t)k + 11u + n_txt;
+            } else {
+                p += 9u * (uint32_t)n_base;
+            }
+        }
+        if (!WRITE) {
+            if (lane == 0) {
+                if (ind_bytes && !bad) atomicAdd(&A.status[4], ind_bytes);
+                A.line_entries[line] = bad ? 0u : ent_run;
+                A.line_obs[line] = bad ? 0u : obs_run;
+                A.line_last[line] = prev_tok;
+                A.line_need[line] = need;
+                if (bad) atomicAdd(&A.status[0], 1u);
+                if (n_ind_line) atomicAdd(&A.status[1], n_ind_line);
+            }
+        } else {
+            __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+            if (lane < 32) {
+                const uint32_t v = tal[lane];
+                if (v) atomicAdd(&A.tally[(int64_t)t * 32 + lane], (int32_t)v);
+                tal[lane] = 0u;
+            }
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
+}
+
 // Exclusive prefix sums of the lines' entry and observation counts, in place, position-major; the positions' offsets; the totals.
 // One workgroup walks the arrays 4096 lines at a time: four consecutive lines per thread (one 16-byte load per array: coalesced), a
 // scan of the 1024 thread sums by wave shuffles and one LDS exchange, the running base carried in registers.  (Round 5: a contiguous
@@ -440,7 +574,9 @@ hipError_t launch_pileup_count(hipStream_t stream, const PileupTile &P)
     const int64_t n_lines = (int64_t)P.n_pos * P.n_batches;       // (an upper bound when the device decides the positions)
     if (n_lines <= 0) return hipSuccess;
     const int64_t blocks = (n_lines + kParseWaves - 1) / kParseWaves;
-    hipLaunchKernelGGL(pileup_parse_kernel<false>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kParseWaves * kWave), 0, stream, A);
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(kParseWaves * kWave);
+    if (P.bin) hipLaunchKernelGGL(pileup_bin_kernel<false>, grid, block, 0, stream, A);
+    else hipLaunchKernelGGL(pileup_parse_kernel<false>, grid, block, 0, stream, A);
     hipLaunchKernelGGL(pileup_scan_kernel, dim3(1), dim3(1024), 0, stream, n_lines, P.n_batches, P.n_pos, P.n_pos_dev, A.line_entries,
                        A.line_obs, P.entry_off, P.obs_off, P.totals);
     return hipGetLastError();
@@ -453,7 +589,9 @@ hipError_t launch_pileup_write(hipStream_t stream, const PileupTile &P, uint32_t
     const int64_t n_lines = (int64_t)P.n_pos * P.n_batches;
     if (n_lines <= 0) return hipSuccess;
     const int64_t blocks = (n_lines + kParseWaves - 1) / kParseWaves;
-    hipLaunchKernelGGL(pileup_parse_kernel<true>, dim3((unsigned)(blocks < 65536 ? blocks : 65536)), dim3(kParseWaves * kWave), 0, stream, A);
+    const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(kParseWaves * kWave);
+    if (P.bin) hipLaunchKernelGGL(pileup_bin_kernel<true>, grid, block, 0, stream, A);
+    else hipLaunchKernelGGL(pileup_parse_kernel<true>, grid, block, 0, stream, A);
     const int64_t threads = n_lines + 1;
     hipLaunchKernelGGL(pileup_patch_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, stream, n_lines, P.n_batches,
                        A.line_entries, A.line_last, A.line_need, carry_in, P.entries, P.tally, P.status + 3);

@@ -244,6 +244,7 @@ struct Tile {
     // -- a tile whose text the DEVICE parses (bvc_pileup_begin / bvc_pileup_finish): the inflated lines of its positions, batch
     //    after batch, as they came out of the temp files; what comes back are the columns and tallies the CPU parser would have built
     bool dev = false;
+    bool bin = false;                    // ... as binary records (bvc_pileup_begin_bin): text = the records, line_start = where each begins
     size_t n_pos = 0;                    // positions of the tile (with or without entries)
     std::vector<int32_t> pos;            // their coordinates
     std::vector<char> text;
@@ -254,7 +255,7 @@ struct Tile {
     std::vector<bvc_pileup_entry> ent;
     std::vector<bvc_pileup_indel> indels;
     bool dev_parsed = false;             // false after the call: a line was not regular and the tile went through the CPU parser (sites)
-    void reset() { n_used = 0; entries = 0; refs.clear(); dev = false; dev_parsed = false; n_pos = 0; pos.clear(); }
+    void reset() { n_used = 0; entries = 0; refs.clear(); dev = false; bin = false; dev_parsed = false; n_pos = 0; pos.clear(); }
 };
 static_assert(sizeof(bvc_pileup_entry) == sizeof(Entry), "the device parser's entry is the host's");
 
@@ -304,7 +305,7 @@ struct TileRunner {
     std::string err;                     // first failure of stage 2 or 3
     bool started = false;
     int64_t tiles_one_byte = 0, tiles_two_byte = 0;   // library calls by tile form (stage 2's thread; read after finish())
-    int64_t tiles_dev_parsed = 0, tiles_cpu_parsed = 0;   // tiles of text: parsed on the device / handed back (a line was not regular)
+    int64_t tiles_dev_parsed = 0, tiles_cpu_parsed = 0;   // tiles of text or records: parsed on the device / handed back (a line was not regular)
     std::vector<int32_t> sample0, n_in_batch;         // per temp batch: its first sample and its samples (device-parsed tiles)
     uint8_t carry[5] = {0, 0, 0, 0, 0};               // the parser's long-lived AlleleInfo between tiles (stage 2's thread)
     std::atomic<int64_t> sites_done{0};
@@ -322,7 +323,7 @@ struct TileRunner {
         cur = free_q.pop();
         dev_thread = std::thread([this] {
             for (Tile *t; (t = dev_q.pop()) != nullptr;) {
-                if (!failed()) { try { if (t->dev) run_device_text(*t); else run_device(*t); } catch (const std::exception &e) { fail(e.what()); } }
+                if (!failed()) { try { if (t->dev && t->bin) run_device_bin(*t); else if (t->dev) run_device_text(*t); else run_device(*t); } catch (const std::exception &e) { fail(e.what()); } }
                 out_q.push(t);
             }
             out_q.close();
@@ -437,6 +438,20 @@ struct TileRunner {
         const int rc = bvc_pileup_begin(ctx, T.text.data(), (int64_t)T.text.size(), T.line_start.data(), sample0.data(), n_in_batch.data(),
                                         (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind);
         if (rc == BVC_PILEUP_IRREGULAR) { cpu_parse_tile(T); return; }
+        if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
+        finish_tile(T, n_ent, n_ind, 0, false);
+        clk_dev.gpu += StageClock::now() - t0;
+    }
+
+    // stage 2 of a tile of binary RECORDS: the same on the device; a record that does not add up is an error (the CPU parser would
+    // refuse it too: binary records have no second meaning)
+    void run_device_bin(Tile &T)
+    {
+        const double t0 = StageClock::now();
+        int64_t n_ent = 0, n_ind = 0;
+        const int rc = bvc_pileup_begin_bin(ctx, reinterpret_cast<const uint8_t *>(T.text.data()), (int64_t)T.text.size(), T.line_start.data(),
+                                            sample0.data(), n_in_batch.data(), (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind);
+        if (rc == BVC_ERR_DATA) throw std::runtime_error(std::string("ERROR: malformed temp batch record (") + bvc_last_error(ctx) + ")");
         if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
         finish_tile(T, n_ent, n_ind, 0, false);
         clk_dev.gpu += StageClock::now() - t0;
@@ -862,18 +877,22 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     thread_window(pv.size(), thread, ithread, lo, hi);
     int32_t count = 0;
     tr.ithread = ithread;
-    // Tiles of TEXT for the device parser (the default with the reference's text batches): BVC_HOST_DEVICE_PARSE=0 keeps the CPU
-    // parser (A/B runs, and what the quality-shift test hook and the binary batch forms use)
+    // Tiles of TEXT, or of binary RECORDS when every batch file is binary, for the device parser (the default): BVC_HOST_DEVICE_PARSE=0
+    // keeps the CPU parser (A/B runs, and what the quality-shift test hook and a mix of text and binary files use)
     bool dev_parse = !qual_shift && !(getenv("BVC_HOST_DEVICE_PARSE") && atoi(getenv("BVC_HOST_DEVICE_PARSE")) == 0);
-    for (auto fp : fpiv) if (fp->bin) dev_parse = false;
+    size_t n_bin_files = 0;
+    for (auto fp : fpiv) if (fp->bin) ++n_bin_files;
+    if (n_bin_files != 0 && n_bin_files != fpiv.size()) dev_parse = false;
+    const bool dev_bin = dev_parse && n_bin_files != 0;
     const double t_loop = StageClock::now();
-    // ... and with the blocks of the temp batches inflated on the device too (the default): BVC_HOST_DEVICE_INFLATE=0 inflates on the CPU
-    const bool dev_inflate = dev_parse && !(getenv("BVC_HOST_DEVICE_INFLATE") && atoi(getenv("BVC_HOST_DEVICE_INFLATE")) == 0);
+    // ... and with the blocks of the text batches inflated on the device too (the default): BVC_HOST_DEVICE_INFLATE=0 inflates on the CPU
+    const bool dev_inflate = dev_parse && !dev_bin && !(getenv("BVC_HOST_DEVICE_INFLATE") && atoi(getenv("BVC_HOST_DEVICE_INFLATE")) == 0);
     if (dev_parse) {
-        // per batch: its first sample and its samples, from the names line (tab-terminated names, src/BaseVarC.cpp:495, 503)
+        // per batch: its first sample and its samples, from the binary header or the names line (tab-terminated names,
+        // src/BaseVarC.cpp:495, 503)
         int32_t j0 = 0;
         for (auto fp : fpiv) {
-            const int32_t n_in = (int32_t)std::count(fp->names.begin(), fp->names.end(), '\t');
+            const int32_t n_in = fp->bin ? (int32_t)fp->n_in_batch : (int32_t)std::count(fp->names.begin(), fp->names.end(), '\t');
             tr.sample0.push_back(j0); tr.n_in_batch.push_back(n_in);
             j0 += n_in;
         }
@@ -1049,6 +1068,51 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
                    << t[4] * 1e3 << ", " << t[5] * 1e3 << ")";
             std::cerr << os.str() << std::endl;
         }
+    } else if (dev_bin) {
+        // a tile of records: --tile positions at most, and about BVC_HOST_TILE_MB of records (default 32) going by the tile before it;
+        // the records of a batch one after the other as they come out of its stream (inflated on the CPU, or copied: the raw form)
+        const double target = 1048576.0 * (getenv("BVC_HOST_TILE_MB") ? std::max(1, atoi(getenv("BVC_HOST_TILE_MB"))) : 32);
+        double bytes_per_pos = 0;
+        const size_t nb = fpiv.size();
+        for (size_t ip = lo; ip < hi;) {
+            size_t T = (size_t)std::min<int64_t>(tile, (int64_t)(hi - ip));
+            if (bytes_per_pos > 0) T = std::min(T, (size_t)std::max(1.0, target / bytes_per_pos));
+            else T = std::min<size_t>(T, 64);
+            Tile &tl = *tr.cur;
+            tl.dev = true; tl.bin = true; tl.n_pos = T;
+            tl.text.clear();
+            tl.line_start.resize(nb * (T + 1));
+            double t0 = StageClock::now();
+            for (size_t b = 0; b < nb; ++b) {
+                BgzfReader &rd = fpiv[b]->rd;
+                tl.text.resize((tl.text.size() + 7) & ~(size_t)7, 0);          // every batch's records from an 8-byte boundary
+                uint32_t *rs = &tl.line_start[b * (T + 1)];
+                for (size_t t = 0; t < T; ++t) {
+                    unsigned char b4[4];
+                    if (rd.read(b4, 4) != 4) throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
+                    const size_t n = (size_t)b4[0] | ((size_t)b4[1] << 8) | ((size_t)b4[2] << 16) | ((size_t)b4[3] << 24);
+                    const size_t at = tl.text.size();
+                    if (at + 4 + n > (size_t)0xF0000000u) throw std::runtime_error("ERROR: more than 3.75 GiB of records in one tile: lower --tile");
+                    rs[t] = (uint32_t)at;
+                    tl.text.resize(at + 4 + n);
+                    std::memcpy(&tl.text[at], b4, 4);
+                    if (n && rd.read(&tl.text[at + 4], n) != n) throw std::runtime_error("ERROR: truncated temp batch record");
+                }
+                rs[T] = (uint32_t)tl.text.size();
+            }
+            tr.clk.read += StageClock::now() - t0;
+            tl.refs.resize(T);
+            tl.pos.resize(T);
+            for (size_t k = 0; k < T; ++k) {
+                const int32_t p = pv[ip + k];
+                const char rc = refseq[(size_t)(p - rg_s)];
+                tl.pos[k] = p;
+                tl.refs[k] = rc == 'A' ? 0 : rc == 'C' ? 1 : rc == 'G' ? 2 : rc == 'T' ? 3 : -1;
+            }
+            bytes_per_pos = (double)tl.text.size() / (double)T;
+            tr.flush();
+            ip += T;
+        }
     } else if (dev_parse) {
         // a tile: --tile positions at most, and about BVC_HOST_TILE_MB of text (default 32) going by the tile before it
         const double target = 1048576.0 * (getenv("BVC_HOST_TILE_MB") ? std::max(1, atoi(getenv("BVC_HOST_TILE_MB"))) : 32);
@@ -1110,7 +1174,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     const double loop_s = StageClock::now() - t_loop, setup_s = t_loop - t_start;
     if (getenv("BVC_HOST_PROFILE")) {
         std::cerr << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
-                  << tr.tiles_two_byte << "; tiles of text parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
+                  << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
                   << tr.tiles_cpu_parsed << std::endl;
         const StageClock &c = tr.clk, &d = tr.clk_dev, &o = tr.clk_out;
         std::cerr << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "

@@ -14,7 +14,8 @@ NCLASS = 512
 
 
 class BvcError(RuntimeError):
-    pass
+    """status: the library's return code (BVC_ERR_*, include/bvc.h) where the error came from a call, else None."""
+    status = None
 
 
 class SiteResult(C.Structure):          # bvc_site_result, 120 bytes
@@ -52,6 +53,7 @@ EXPORTS = [
     "bvc_lrt_csr", "bvc_lrt_csr_comb", "bvc_hist_dense", "bvc_lrt_hist", "bvc_synth_dense", "bvc_stream_read_ms", "bvc_set_tuning",
     "bvc_lrt_dense_packed", "bvc_pack_dense", "bvc_hist_dense_packed", "bvc_lrt_dense_groups_packed",
     "bvc_lrt_csr_packed", "bvc_lrt_csr_groups", "bvc_pileup_begin", "bvc_pileup_finish", "bvc_pileup_finish_called", "bvc_inflate_blocks", "bvc_pileup_begin_bgzf", "bvc_pileup_text",
+    "bvc_pileup_begin_bin",
     "bvc_host_alloc", "bvc_host_free",
 ]
 
@@ -118,6 +120,8 @@ def load_library():
     L.bvc_lrt_csr_groups.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, vp, i64, i32, vp, vp, u32]
     L.bvc_pileup_begin.restype = C.c_int
     L.bvc_pileup_begin.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
+    L.bvc_pileup_begin_bin.restype = C.c_int
+    L.bvc_pileup_begin_bin.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.bvc_pileup_finish.restype = C.c_int
     L.bvc_pileup_finish.argtypes = [vp, vp, dbl, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.bvc_pileup_finish_called.restype = C.c_int
@@ -175,7 +179,9 @@ class Context:
 
     def _check(self, rc):
         if rc != 0:
-            raise BvcError(f"libbvc error {rc}: {self._L.bvc_last_error(self._h).decode()}")
+            err = BvcError(f"libbvc error {rc}: {self._L.bvc_last_error(self._h).decode()}")
+            err.status = rc
+            raise err
 
     # ---- plumbing
     def set_stream(self, stream):
@@ -297,6 +303,25 @@ class Context:
         if rc == 1:
             return None
         self._check(rc)
+        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only)
+
+    def pileup_tile_bin(self, records, rec_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
+                        n_groups=0, called_only=False):
+        """bvc_pileup_begin_bin + bvc_pileup_finish on one tile of binary temp-batch records (include/bvc.h).  records: bytes;
+        rec_start: uint32 [n_batches, n_positions + 1].  Returns the dict of pileup_tile (indels' text_off are offsets into records);
+        raises BvcError (status BVC_ERR_DATA = -5: a malformed record, BVC_ERR_ARG = -1: a rec_start that does not fit)."""
+        rs = np.ascontiguousarray(rec_start, dtype=np.uint32)
+        if rs.ndim != 2 or rs.shape[1] < 1:
+            raise ValueError("rec_start must be [n_batches, n_positions + 1]")
+        nb, T = rs.shape[0], rs.shape[1] - 1
+        s0 = np.ascontiguousarray(sample0, dtype=np.int32)
+        nib = np.ascontiguousarray(n_in_batch, dtype=np.int32)
+        if s0.shape != (nb,) or nib.shape != (nb,):
+            raise ValueError("sample0 / n_in_batch must be [n_batches]")
+        buf = np.frombuffer(bytes(records), dtype=np.uint8)
+        ne, ni = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.bvc_pileup_begin_bin(self._h, _np_ptr(buf) if len(buf) else None, len(buf), _np_ptr(rs), _np_ptr(s0), _np_ptr(nib),
+                                                 nb, T, C.byref(ne), C.byref(ni)))
         return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only)
 
     def _pileup_finish(self, T, n_entries, n_indels, indel_text_bytes, ref_base, min_af, carry_in, group_of_sample, n_groups,

@@ -40,7 +40,8 @@ extern "C" {
 #define BVC_ERR_DEVICE      -2   /* HIP runtime error; text in bvc_last_error */
 #define BVC_ERR_NO_DEVICE   -3   /* no gfx950 device / device index out of range */
 #define BVC_ERR_ALLOC       -4   /* device or host allocation failed */
-#define BVC_ERR_DATA        -5   /* bvc_pileup_begin_bgzf: a BGZF block is not valid deflate of its ISIZE bytes */
+#define BVC_ERR_DATA        -5   /* bvc_pileup_begin_bgzf: a BGZF block is not valid deflate of its ISIZE bytes;
+                                    bvc_pileup_begin_bin: a binary record is malformed.  The context stays usable */
 #define BVC_PILEUP_IRREGULAR 1   /* bvc_pileup_begin only, not an error: a line of the tile is not of the shape the reference's
                                     writer produces; nothing was computed, parse this tile with the reference's own rules */
 
@@ -248,7 +249,8 @@ int bvc_inflate_blocks(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, co
  * tokenises it with strtok_r / atoi into the position's entries; bt_f then tallies depths and strands (:548-590), builds the
  * (base, qual) vectors (:550-559) and calls BaseType on them (:612-613; per group :617-661).  These two calls do all of that for
  * a TILE of positions from the inflated TEXT of the temp batches (format: writer :509-527): the text goes to the device as it is,
- * the parsed columns feed the LRT there, and what bt_f and WriteVcf read afterwards comes back.
+ * the parsed columns feed the LRT there, and what bt_f and WriteVcf read afterwards comes back.  (bvc_pileup_begin_bin below takes
+ * the tile as binary records instead; bvc_pileup_begin_bgzf takes the text still compressed.)
  *
  *   text         the tile's text: for every temp batch the lines of the tile's positions ('\n' after each), anywhere in the buffer
  *   line_start   [n_batches][n_positions + 1] offsets into text: line t of batch b starts at line_start[b * (n_positions + 1) + t];
@@ -288,6 +290,33 @@ int bvc_pileup_finish(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const
                       const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
                       int64_t *entry_off, int32_t *tally, bvc_pileup_entry *entries, int32_t *samples,
                       bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results, bvc_group_result *grp_results);
+/*
+ * The same from the BINARY form of the temp batches (additive; the host program's `--tmp-format bin` and `raw`): per position and
+ * batch one record
+ *   record  = u32 payload bytes | payload                                                        (little-endian)
+ *   payload = entries; entry = u32 sample-in-batch | u8 base mapq qual rpr flags | [u16 n | n bytes of indel text]
+ *             flags: bit 0 strand, bit 1 "indel entry" (only then the u16 and the text follow)
+ * with the meaning the text form has: base = byte & 7, strand = flags & 1, a base entry with base 4 (N) is dropped but remains the
+ * "last base token", an indel entry shows the fields of the last base entry before it (carry, above).
+ *   records      the tile's records: for every temp batch the records of the tile's positions, one after the other, anywhere in the buffer
+ *   rec_start    [n_batches][n_positions + 1] offsets into records, the twin of line_start: record t of batch b begins -- at its
+ *                length word -- at rec_start[b * (n_positions + 1) + t]; entry n_positions of a batch = one past its last record
+ *   sample0, n_in_batch   as above; a sample-in-batch index must be below n_in_batch[b]
+ * The call checks on the host that every rec_start[t + 1] - rec_start[t] equals 4 + the record's length word and that all of it lies
+ * inside records_bytes (<= 0xFFFFFF00): BVC_ERR_ARG otherwise.  It returns BVC_OK and the sizes, or BVC_ERR_DATA when some record is
+ * malformed: fewer than 9 bytes left for an entry, fewer than 11 for an indel entry, an indel text that runs past the payload's
+ * end -- what the host program's CPU parser refuses too -- or a sample-in-batch index >= n_in_batch[b], which that parser does
+ * not check and this call must, because the index feeds the group lookup on the device.  The kernel bounds every load by the
+ * record's end whatever the bytes say; a malformed record is counted (bvc_last_error says how many), never followed; the tile is
+ * not begun and the context stays usable.  There is no BVC_PILEUP_IRREGULAR here: binary records have no second meaning.
+ * bvc_pileup_finish / bvc_pileup_finish_called then serve the tile as they serve text: indel_text NULL leaves the indel records'
+ * text_off as offsets into `records` (at the text bytes, len = n); given, it receives the texts gathered on the device and
+ * text_off become offsets into it (room for the sum of the records' len is needed; records_bytes always suffices).
+ * Host pointers only; synchronises the context's stream.
+ */
+int bvc_pileup_begin_bin(bvc_ctx *ctx, const uint8_t *records, int64_t records_bytes, const uint32_t *rec_start,
+                         const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
+                         int64_t *n_entries, int64_t *n_indels);
 /*
  * bvc_pileup_finish with the entries of the CALLED positions only (results[t].called != 0).  Of a position that is not called the
  * reference reads the tallies and the indel strings alone (the CVG line, src/BaseVarC.cpp:560-610); the entries themselves are read

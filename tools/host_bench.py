@@ -8,6 +8,9 @@ BVC_HOST_BENCH_FORMATS=text,raw restricts the forms; BVC_HOST_BENCH_INFLATE=1,2,
 BVC_HOST_INFLATE_THREADS on the same files (default: the program's own default only).
 BVC_HOST_BENCH_VARIANTS="A=1,B=2;A=0" runs the compute phase once per ';'-separated set of environment settings on the same files
 (e.g. "BVC_HOST_DEVICE_PARSE=1;BVC_HOST_DEVICE_PARSE=0"); the outputs of all variants must be identical.
+BVC_HOST_BENCH_REPEATS=n runs the whole sweep n times on the same files, variants interleaved (run-to-run spread: A B A B A B).
+The binary forms take both feeds -- records parsed on the device (bvc_pileup_begin_bin) and on the CPU -- through
+BVC_HOST_BENCH_VARIANTS="BVC_HOST_DEVICE_PARSE=0;BVC_HOST_DEVICE_PARSE=1" with BVC_HOST_BENCH_FORMATS=bin,raw.
 BVC_HOST_BENCH_GROUPS=k adds --group with k population groups (sample j in group j mod k, every 10th sample in none).
 """
 import ctypes as C
@@ -63,7 +66,8 @@ def main():
         formats = os.environ.get("BVC_HOST_BENCH_FORMATS", "text,bin,raw").split(",")
         inflates = os.environ.get("BVC_HOST_BENCH_INFLATE", "").split(",")
         variants = [dict(kv.split("=", 1) for kv in v.split(",") if kv) for v in os.environ.get("BVC_HOST_BENCH_VARIANTS", "").split(";")]
-        runs = [(infl, var) for infl in inflates for var in variants]
+        repeats = max(1, int(os.environ.get("BVC_HOST_BENCH_REPEATS", "1")))
+        runs = [(infl, var) for _ in range(repeats) for infl in inflates for var in variants]
         group_args = []
         k_groups = int(os.environ.get("BVC_HOST_BENCH_GROUPS", "0"))
         if k_groups > 0:
@@ -102,7 +106,7 @@ def main():
                 body = [gzip.decompress(open(out + k, "rb").read()) for k in (".cvg.gz", ".vcf.gz")]
                 variant_outputs.setdefault(fmt, body)
                 assert variant_outputs[fmt] == body, f"variant {var} writes other outputs than the first run"
-                print(json.dumps({"tmp_format": fmt, "inflate_threads": infl or "default", "variant": var, "groups": k_groups, "positions_per_s_in_the_position_loops": round(npos / max(loops), 1) if loops else None, "n_samples": n, "positions": npos, "threads": thread, "coverage": cov,
+                print(json.dumps({"tmp_format": fmt, "inflate_threads": infl or "default", "variant": var, "repeat": ii // max(1, len(runs) // repeats), "groups": k_groups, "positions_per_s_in_the_position_loops": round(npos / max(loops), 1) if loops else None, "n_samples": n, "positions": npos, "threads": thread, "coverage": cov,
                                   "entries": entries, "batch_files_MB": round(size / 1e6, 1), "generate_s": round(gen_s, 2),
                                   "seconds": round(dt, 3), "positions_per_s": round(npos / dt, 1),
                                   "entries_per_s": round(entries / dt), "cvg_lines": n_cvg, "vcf_lines": n_vcf,
