@@ -147,6 +147,58 @@ static std::string tmp_name(int ithread, int ibatch)
     return opt::output + ".tmp.thread." + std::to_string(ithread) + "/batch." + std::to_string(ibatch);
 }
 
+static uint32_t le32(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+// a reference letter as libbvc takes it
+static int8_t ref_code(char c) { return c == 'A' ? 0 : c == 'C' ? 1 : c == 'G' ? 2 : c == 'T' ? 3 : -1; }
+// (a temp batch holds one line or record per position of the thread's window)
+static const char *const kTruncatedBatch = "ERROR: truncated temp batch (it ends before the thread's window does)";
+static void bvc_check(bvc_ctx *ctx, int rc) { if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx)); }
+
+// CPUs this process may use: the cgroup's quota when it has one (cpu.max: "<quota> <period>"), else the CPUs of its affinity mask.
+// A position loop runs helper threads beside its own (the tile formatter, the deflaters of its two outputs, the call that finishes a
+// tile while the next one's blocks are gathered); how many it starts goes by the CPUs per loop -- past the quota they only get the
+// whole process throttled (round 5, 16 CPUs: three VCF deflaters per loop +50 % with one loop, +18 % with four, -15 % with eight).
+static double cpus_per_loop()
+{
+    static const double cpus = [] {
+        double c = (double)std::max(1u, std::thread::hardware_concurrency());
+        cpu_set_t set;
+        if (sched_getaffinity(0, sizeof set, &set) == 0) c = (double)CPU_COUNT(&set);
+        std::ifstream f("/sys/fs/cgroup/cpu.max");
+        std::string q; double period = 0;
+        if (f >> q >> period && q != "max" && period > 0) c = std::min(c, std::max(1.0, atof(q.c_str()) / period));
+        return c;
+    }();
+    return cpus / (double)std::max(1, opt::thread);
+}
+
+// ---- the compute phase's knobs in the environment: every name, default and meaning once (none changes an output) ----------------
+static bool env_set(const char *name) { return getenv(name) != nullptr; }
+static int env_int(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+namespace knob {
+static bool profile() { return env_set("BVC_HOST_PROFILE"); }                          // set: the stage clocks of every thread and of main
+static bool profile_tiles() { return env_int("BVC_HOST_PROFILE", 0) >= 2; }           // 2: and what every tile of the BGZF feed cost its thread
+static bool device_parse() { return env_int("BVC_HOST_DEVICE_PARSE", 1) != 0; }       // 0: the CPU parser, not the device's (A/B runs)
+static bool device_inflate() { return env_int("BVC_HOST_DEVICE_INFLATE", 1) != 0; }   // 0: the text batches are inflated on the CPU
+// 0: a device-parsed tile's entries come back for every position, not for the called ones only (WriteVcf is their one reader,
+// src/BaseVarC.cpp:664; as up to round 5's first form of this feed)
+static bool called_only() { return env_int("BVC_HOST_CALLED_ONLY", 1) != 0; }
+static bool two_byte_tiles() { return env_set("BVC_HOST_TWO_BYTE_TILES"); }            // set: never one byte per observation in the CPU parser's tiles
+static bool no_crc() { return env_set("BVC_HOST_NO_CRC"); }                            // set: the device does not check the CRC32 of the blocks it inflates
+// tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
+// fit one byte per observation (quality >= 63)
+static int qual_shift() { return env_int("BVC_HOST_QUAL_SHIFT", 0); }
+// threads that inflate the blocks of the temp batches ahead of a position loop that reads them on the CPU (the loop takes a line of
+// every batch per position; inflating was 70 % of it with the text form); 0 = none
+static int inflate_threads() { return env_int("BVC_HOST_INFLATE_THREADS", 2); }
+// MB a tile should hold: of compressed blocks in the BGZF feed, of text or records in the tiles staged on the host
+static int tile_mb(bool staged_on_host) { return std::max(1, env_int("BVC_HOST_TILE_MB", staged_on_host ? 32 : 128)); }
+static int device_slots() { return std::max(1, env_int("BVC_HOST_DEVICE_SLOTS", 8)); } // threads per device inside its part of a tile at a time
+// the BGZF feed gathers the next tile's blocks beside the call that finishes this one; threads that deflate a loop's VCF text
+static bool gather_ahead() { return env_int("BVC_HOST_GATHER_AHEAD", cpus_per_loop() >= 3 ? 1 : 0) != 0; }
+static int vcf_deflaters() { return std::max(1, env_int("BVC_HOST_VCF_DEFLATERS", cpus_per_loop() >= 4 ? 3 : (cpus_per_loop() >= 3 ? 2 : 1))); }
+}  // namespace knob
+
 // ---- phase 1: BAM -> temp-batch pileup text (bt_r, src/BaseVarC.cpp:467-534) ------------------------------------
 static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
                  const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread)
@@ -177,13 +229,13 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
     // --rerun check looks for, but reading them back is a copy instead of an inflate (half of the compute phase's
     // host time once the tokenising is gone)
     const int level = opt::tmp_format == "raw" ? 0 : 6;
-    std::vector<BgzfWriter *> fpv;
+    std::deque<BgzfWriter> fpv;                 // (a deque: a writer owns its file and its threads and does not move)
     for (int i = 0; i < thread; ++i) {
-        BgzfWriter *fp = new BgzfWriter(tmp_name(i, ib), level);
-        if (!fp->ok()) throw std::runtime_error("ERROR: fail to write " + tmp_name(i, ib));
-        if (bin) { std::string h; bin_batch_header((uint32_t)(b1 - b0), names, h); fp->write(h); }
-        else fp->write(names);
-        fpv.push_back(fp);
+        fpv.emplace_back(tmp_name(i, ib), level);
+        BgzfWriter &fp = fpv.back();
+        if (!fp.ok()) throw std::runtime_error("ERROR: fail to write " + tmp_name(i, ib));
+        if (bin) { std::string h; bin_batch_header((uint32_t)(b1 - b0), names, h); fp.write(h); }
+        else fp.write(names);
     }
     const size_t psize = pv.size();
     const size_t window = psize % thread + psize / thread;
@@ -208,12 +260,10 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
             out += "\n";
         }
         if (i == (j + 1) * window && j + 1 < (size_t)thread) ++j;
-        fpv[j]->write(out);
+        fpv[j].write(out);
     }
-    for (auto fp : fpv) {
-        if (!fp->close()) std::cerr << "warning: file cannot be closed" << std::endl;
-        delete fp;
-    }
+    for (auto &fp : fpv)
+        if (!fp.close()) std::cerr << "warning: file cannot be closed" << std::endl;
 }
 
 // ---- phase 2: temp-batch text -> tiles -> libbvc -> CVG/VCF (successor of bt_s + bt_f) ------------------------
@@ -223,8 +273,24 @@ struct StageClock {
     static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 };
 
+// What every feed of a thread's compute phase works on: the positions of the region with the reference's bases, the thread's share
+// of them and the positions a tile holds at most.
+struct Window {
+    const std::vector<int32_t> &pv;
+    const std::string &refseq;
+    int32_t rg_s;
+    size_t lo, hi;
+    int64_t tile;
+    int8_t ref_at(int32_t p) const { return ref_code(refseq[(size_t)(p - rg_s)]); }
+};
+
+// What stage 1 put into a tile: the columns the CPU parser built, or what the device parses -- the lines of its positions, or their
+// binary records (bvc_pileup_begin / bvc_pileup_begin_bin)
+enum class TileForm { Sites, Text, Records };
+
 // One tile of positions on its way through a runner: parsed (stage 1), handed to libbvc (stage 2), written out (stage 3).
 struct Tile {
+    TileForm form = TileForm::Sites;
     // the tile's positions: slots [0, n_used) of `sites` (the slots and their vectors are reused from tile to tile)
     std::vector<SiteColumn> sites;
     size_t n_used = 0;
@@ -241,10 +307,9 @@ struct Tile {
     std::vector<int64_t> offsets;
     std::vector<int8_t> bases, quals;
     std::vector<uint8_t> packed;
-    // -- a tile whose text the DEVICE parses (bvc_pileup_begin / bvc_pileup_finish): the inflated lines of its positions, batch
-    //    after batch, as they came out of the temp files; what comes back are the columns and tallies the CPU parser would have built
-    bool dev = false;
-    bool bin = false;                    // ... as binary records (bvc_pileup_begin_bin): text = the records, line_start = where each begins
+    // -- a tile whose text or records the DEVICE parses (bvc_pileup_begin[_bin] / bvc_pileup_finish): the inflated lines of its
+    //    positions (the records: text = the records, line_start = where each begins), batch after batch, as they came out of the temp
+    //    files; what comes back are the columns and tallies the CPU parser would have built
     size_t n_pos = 0;                    // positions of the tile (with or without entries)
     std::vector<int32_t> pos;            // their coordinates
     std::vector<char> text;
@@ -254,8 +319,27 @@ struct Tile {
     std::vector<int32_t> tally, samples;
     std::vector<bvc_pileup_entry> ent;
     std::vector<bvc_pileup_indel> indels;
-    bool dev_parsed = false;             // false after the call: a line was not regular and the tile went through the CPU parser (sites)
-    void reset() { n_used = 0; entries = 0; refs.clear(); dev = false; bin = false; dev_parsed = false; n_pos = 0; pos.clear(); }
+    bool handed_back = false;            // a line was not regular: the tile went through the CPU parser and its columns are in `sites`
+    void reset() { form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); }
+    bool empty() const { return form == TileForm::Sites ? n_used == 0 : n_pos == 0; }     // nothing for stage 2 to do
+    bool device_parsed() const { return form != TileForm::Sites && !handed_back; }        // (once stage 2 is through with it)
+    // the tile is the T positions from w.pv[ip] on: their coordinates and reference bases
+    void set_positions(const Window &w, size_t ip, size_t T)
+    {
+        n_pos = T; pos.resize(T); refs.resize(T);
+        for (size_t k = 0; k < T; ++k) { pos[k] = w.pv[ip + k]; refs[k] = w.ref_at(pos[k]); }
+    }
+    // position t's slice of the arrays the device returned: its entries and their samples
+    SiteView view(size_t t) const
+    {
+        const int64_t a0 = called_off.empty() ? entry_off[t] : called_off[t];
+        SiteView v;
+        v.pos = pos[t];
+        v.aiv = reinterpret_cast<const Entry *>(&ent[(size_t)a0]);
+        v.sample = &samples[(size_t)a0];
+        v.n = (size_t)(entry_off[t + 1] - entry_off[t]);
+        return v;
+    }
 };
 static_assert(sizeof(bvc_pileup_entry) == sizeof(Entry), "the device parser's entry is the host's");
 
@@ -283,8 +367,6 @@ class TileQueue {
     std::deque<Tile *> q_;
     bool closed_ = false;
 };
-
-static double cpus_per_loop();
 
 struct TileRunner {
     StageClock clk;                      // stage 1 (the caller's thread): read, parse
@@ -316,6 +398,12 @@ struct TileRunner {
         // let every stage run dry: tiles still flow back to the parser, which sees the error at its next flush
     }
     bool failed() { std::lock_guard<std::mutex> g(err_mu); return !err.empty(); }
+    // stage 1 throws the first failure of a later stage
+    void rethrow_if_failed()
+    {
+        std::lock_guard<std::mutex> g(err_mu);
+        if (!err.empty()) throw std::runtime_error(err);
+    }
 
     void start()
     {
@@ -323,7 +411,7 @@ struct TileRunner {
         cur = free_q.pop();
         dev_thread = std::thread([this] {
             for (Tile *t; (t = dev_q.pop()) != nullptr;) {
-                if (!failed()) { try { if (t->dev && t->bin) run_device_bin(*t); else if (t->dev) run_device_text(*t); else run_device(*t); } catch (const std::exception &e) { fail(e.what()); } }
+                if (!failed()) { try { if (t->form == TileForm::Sites) run_device(*t); else run_device_parsed(*t); } catch (const std::exception &e) { fail(e.what()); } }
                 out_q.push(t);
             }
             out_q.close();
@@ -343,23 +431,22 @@ struct TileRunner {
     // stage 1 hands its tile on and takes a free one (waits when both later stages are still busy)
     void flush()
     {
-        if (cur->n_used == 0 && !(cur->dev && cur->n_pos)) return;
+        if (cur->empty()) return;
         dev_q.push(cur);
         cur = free_q.pop();
-        if (failed()) { std::lock_guard<std::mutex> g(err_mu); throw std::runtime_error(err); }
+        rethrow_if_failed();
     }
 
     // end of the window: drain the pipeline; rethrows the first failure of a later stage
     void finish()
     {
         if (!started) return;
-        if (cur && (cur->n_used || (cur->dev && cur->n_pos))) dev_q.push(cur);
+        if (cur && !cur->empty()) dev_q.push(cur);
         dev_q.close();
         dev_thread.join();
         out_thread.join();
         started = false;
-        std::lock_guard<std::mutex> g(err_mu);
-        if (!err.empty()) throw std::runtime_error(err);
+        rethrow_if_failed();
     }
     ~TileRunner()
     {
@@ -372,6 +459,7 @@ struct TileRunner {
     {
         const double t0 = StageClock::now();
         tiles_cpu_parsed += 1;
+        T.handed_back = true;
         set_parser_carry(carry);
         const size_t nb = sample0.size();
         for (size_t t = 0; t < T.n_pos; ++t) {
@@ -405,11 +493,8 @@ struct TileRunner {
         T.gres.resize(T.n_pos * (size_t)ng);
         if (text_on_device) T.text.resize((size_t)ind_bytes + 1);
         uint8_t carry_out[5];
-        // the entries come back for the called positions only (WriteVcf is their one reader, src/BaseVarC.cpp:664; BVC_HOST_CALLED_ONLY=0:
-        // for every position, as up to round 5's first form of this feed)
-        static const bool called_only = !(getenv("BVC_HOST_CALLED_ONLY") && atoi(getenv("BVC_HOST_CALLED_ONLY")) == 0);
         int rc;
-        if (called_only) {
+        if (knob::called_only()) {
             T.called_off.resize(T.n_pos + 1);
             rc = bvc_pileup_finish_called(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
                                           ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(), T.called_off.data(),
@@ -422,37 +507,28 @@ struct TileRunner {
                                    T.samples.data(), T.indels.data(), text_on_device ? T.text.data() : nullptr, T.res.data(),
                                    ng ? T.gres.data() : nullptr);
         }
-        if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
+        bvc_check(ctx, rc);
         std::memcpy(carry, carry_out, 5);
         T.indels.resize((size_t)n_ind);
         std::sort(T.indels.begin(), T.indels.end(), [](const bvc_pileup_indel &a, const bvc_pileup_indel &b) { return a.entry < b.entry; });
-        T.dev_parsed = true;
         tiles_dev_parsed += 1;
     }
 
-    // stage 2 of a tile of TEXT: parse and LRT on the device; the CPU parser only when a line is not what the writer produces
-    void run_device_text(Tile &T)
+    // stage 2 of a tile of TEXT or of binary RECORDS: parse and LRT on the device.  Text goes to the CPU parser when a line is not what
+    // the writer produces; a record that does not add up is an error (the CPU parser would refuse it too: binary records have no
+    // second meaning)
+    void run_device_parsed(Tile &T)
     {
         const double t0 = StageClock::now();
+        const bool records = T.form == TileForm::Records;
         int64_t n_ent = 0, n_ind = 0;
-        const int rc = bvc_pileup_begin(ctx, T.text.data(), (int64_t)T.text.size(), T.line_start.data(), sample0.data(), n_in_batch.data(),
-                                        (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind);
-        if (rc == BVC_PILEUP_IRREGULAR) { cpu_parse_tile(T); return; }
-        if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
-        finish_tile(T, n_ent, n_ind, 0, false);
-        clk_dev.gpu += StageClock::now() - t0;
-    }
-
-    // stage 2 of a tile of binary RECORDS: the same on the device; a record that does not add up is an error (the CPU parser would
-    // refuse it too: binary records have no second meaning)
-    void run_device_bin(Tile &T)
-    {
-        const double t0 = StageClock::now();
-        int64_t n_ent = 0, n_ind = 0;
-        const int rc = bvc_pileup_begin_bin(ctx, reinterpret_cast<const uint8_t *>(T.text.data()), (int64_t)T.text.size(), T.line_start.data(),
-                                            sample0.data(), n_in_batch.data(), (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind);
-        if (rc == BVC_ERR_DATA) throw std::runtime_error(std::string("ERROR: malformed temp batch record (") + bvc_last_error(ctx) + ")");
-        if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
+        const int rc = records ? bvc_pileup_begin_bin(ctx, reinterpret_cast<const uint8_t *>(T.text.data()), (int64_t)T.text.size(), T.line_start.data(),
+                                                      sample0.data(), n_in_batch.data(), (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind)
+                               : bvc_pileup_begin(ctx, T.text.data(), (int64_t)T.text.size(), T.line_start.data(), sample0.data(), n_in_batch.data(),
+                                                  (int32_t)sample0.size(), (int32_t)T.n_pos, &n_ent, &n_ind);
+        if (!records && rc == BVC_PILEUP_IRREGULAR) { cpu_parse_tile(T); return; }
+        if (records && rc == BVC_ERR_DATA) throw std::runtime_error(std::string("ERROR: malformed temp batch record (") + bvc_last_error(ctx) + ")");
+        bvc_check(ctx, rc);
         finish_tile(T, n_ent, n_ind, 0, false);
         clk_dev.gpu += StageClock::now() - t0;
     }
@@ -466,7 +542,7 @@ struct TileRunner {
         const int ng = groups ? (int)groups->names.size() : 0;
         int rc;
         double t0 = StageClock::now(), t1;
-        static const bool two_byte_only = getenv("BVC_HOST_TWO_BYTE_TILES") != nullptr;
+        const bool two_byte_only = knob::two_byte_tiles();
         if (ng == 0) {
             // ragged form: exactly the vectors bt_f builds (src/BaseVarC.cpp:550-559) -- as ONE byte per observation
             // (base << 6 | qual, bvc_lrt_csr_packed: half the bytes over the host link) while every base quality of the
@@ -542,7 +618,7 @@ struct TileRunner {
                                           groups->of_column.data(), ng, T.res.data(), T.gres.data(), BVC_PTR_HOST);
             }
         }
-        if (rc != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(ctx));
+        bvc_check(ctx, rc);
         clk_dev.gpu += StageClock::now() - t0;
     }
 
@@ -552,7 +628,7 @@ struct TileRunner {
         const int ng = groups ? (int)groups->names.size() : 0;
         StageClock &c = clk_out;
         double t0 = StageClock::now(), t1;
-        if (T.dev && T.dev_parsed) {
+        if (T.device_parsed()) {
             // the position's slice of the arrays the device returned; its tallies (src/BaseVarC.cpp:560-590) from the 32 counters
             size_t ii = 0;                                   // next indel record (sorted by entry)
             std::vector<std::string> ind_text;
@@ -564,16 +640,9 @@ struct TileRunner {
             auto format_share = [&](size_t k0, size_t k1) {
                 for (size_t k = k0; k < k1; ++k) {
                     const size_t t = called_t[k];
-                    const int64_t e0 = T.entry_off[t], e1 = T.entry_off[t + 1];
-                    const int64_t a0 = T.called_off.empty() ? e0 : T.called_off[t];
-                    SiteView v;
-                    v.pos = T.pos[t];
-                    v.aiv = reinterpret_cast<const Entry *>(&T.ent[(size_t)a0]);
-                    v.sample = &T.samples[(size_t)a0];
-                    v.n = (size_t)(e1 - e0);
                     std::map<std::string, std::string> info;
                     if (ng) group_af_info(T.res[t], &T.gres[t * (size_t)ng], *groups, info);
-                    vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], v, info, n_samples);
+                    vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], T.view(t), info, n_samples);
                 }
             };
             {
@@ -597,13 +666,7 @@ struct TileRunner {
                 ind_text.clear();
                 for (; ii < T.indels.size() && T.indels[ii].entry < e1; ++ii)
                     ind_text.emplace_back(T.text.data() + T.indels[ii].text_off, (size_t)T.indels[ii].len);
-                SiteView v;
-                v.pos = T.pos[t];
-                // (a position that is not called: the CVG line reads the tallies and the indel strings only)
-                const int64_t a0 = T.called_off.empty() ? e0 : T.called_off[t];
-                v.aiv = reinterpret_cast<const Entry *>(&T.ent[(size_t)a0]);
-                v.sample = &T.samples[(size_t)a0];
-                v.n = (size_t)(e1 - e0);
+                SiteView v = T.view(t);             // (a position that is not called: the CVG line reads the tallies and the indel strings only)
                 v.cnt = cnt; v.fwd = fwd; v.rev = rev;
                 v.indels = ind_text.data(); v.n_indels = ind_text.size();
                 const bvc_group_result *g = ng ? &T.gres[t * (size_t)ng] : nullptr;
@@ -647,7 +710,7 @@ class DeviceSlots {
     void acquire(int device)
     {
         std::unique_lock<std::mutex> g(mu_);
-        if (limit_ < 0) limit_ = getenv("BVC_HOST_DEVICE_SLOTS") ? std::max(1, atoi(getenv("BVC_HOST_DEVICE_SLOTS"))) : 8;
+        if (limit_ < 0) limit_ = knob::device_slots();
         if ((size_t)device >= used_.size()) used_.resize((size_t)device + 1, 0);
         cv_.wait(g, [&] { return used_[(size_t)device] < limit_; });
         used_[(size_t)device] += 1;
@@ -664,12 +727,17 @@ class DeviceSlots {
     int limit_ = -1;
 };
 static DeviceSlots g_device_slots;
+// one of a device's slots, held for as long as this lives
+struct DeviceSlot {
+    const int device;
+    explicit DeviceSlot(int d) : device(d) { g_device_slots.acquire(d); }
+    ~DeviceSlot() { g_device_slots.release(device); }
+};
 
 // ---- temp batches as RAW BGZF blocks (the device inflates them: bvc_pileup_begin_bgzf) ------------------------------------------
-// One block of a temp-batch file as it is on disk: its deflate payload and the size it inflates to.
-// A BGZF block of a temp-batch file as it lies in the file's pages (the file is mapped: nothing is copied before the one copy into the
-// tile's page-locked buffer, and no thread reads ahead -- round 5: a read-ahead thread that fread one block at a time into a vector of
-// its own delivered 1.2 GB/s and was what a position loop waited for).
+// A BGZF block of a temp-batch file as it lies in the file's pages: its deflate payload, the size it inflates to and its CRC32 (the
+// file is mapped: nothing is copied before the one copy into the tile's page-locked buffer, and no thread reads ahead -- round 5: a
+// read-ahead thread that fread one block at a time into a vector of its own delivered 1.2 GB/s and was what a position loop waited for).
 struct RawBlock { const unsigned char *payload = nullptr; size_t len = 0; uint32_t isize = 0, crc32 = 0; };
 
 class MappedBlocks {
@@ -709,8 +777,8 @@ class MappedBlocks {
             if (m.n - m.at < bsize) throw std::runtime_error("ERROR: truncated temp batch (it ends inside a BGZF block)");
             const unsigned char *t = h + bsize - 8;
             out.payload = h + 18; out.len = bsize - 18 - 8;
-            out.crc32 = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-            out.isize = (uint32_t)t[4] | ((uint32_t)t[5] << 8) | ((uint32_t)t[6] << 16) | ((uint32_t)t[7] << 24);
+            out.crc32 = le32(t);
+            out.isize = le32(t + 4);
             m.at += bsize;
             if (out.isize > 65536) throw std::runtime_error("ERROR: a temp batch is not BGZF (a block of more than 64 KiB)");
             if (out.isize != 0) return true;                      // (empty blocks: the EOF marker)
@@ -744,8 +812,8 @@ struct BatchInput {
         if (got == 8 && std::memcmp(head, kBinBatchMagic, 8) == 0) {
             bin = true;
             if (rd.read(head, 8) != 8) throw std::runtime_error("ERROR: truncated temp batch " + path);
-            n_in_batch = (uint32_t)head[0] | ((uint32_t)head[1] << 8) | ((uint32_t)head[2] << 16) | ((uint32_t)head[3] << 24);
-            const uint32_t l = (uint32_t)head[4] | ((uint32_t)head[5] << 8) | ((uint32_t)head[6] << 16) | ((uint32_t)head[7] << 24);
+            n_in_batch = le32(head);
+            const uint32_t l = le32(head + 4);
             names.resize(l);
             if (l && rd.read(&names[0], l) != l) throw std::runtime_error("ERROR: truncated temp batch " + path);
             if (!names.empty() && names.back() == '\n') names.pop_back();
@@ -761,10 +829,8 @@ struct BatchInput {
         double t0 = StageClock::now();
         if (bin) {
             unsigned char b4[4];
-            // a temp batch holds one record per position of the thread's window: running out of records before the window
-            // is exhausted means the file was cut short (both forms: the text form below)
-            if (rd.read(b4, 4) != 4) throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
-            const uint32_t n = (uint32_t)b4[0] | ((uint32_t)b4[1] << 8) | ((uint32_t)b4[2] << 16) | ((uint32_t)b4[3] << 24);
+            if (rd.read(b4, 4) != 4) throw std::runtime_error(kTruncatedBatch);
+            const uint32_t n = le32(b4);
             rec.resize(n);
             if (n && rd.read(rec.data(), n) != n) throw std::runtime_error("ERROR: truncated temp batch record");
             double t1 = StageClock::now();
@@ -774,7 +840,7 @@ struct BatchInput {
             return (int32_t)n_in_batch;
         }
         const bool got = rd.getline(line);
-        if (!got) throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
+        if (!got) throw std::runtime_error(kTruncatedBatch);
         double t1 = StageClock::now();
         clk.read += t1 - t0;
         const int32_t adv = parse_pileup_line(line.data(), line.size(), j0, site);
@@ -783,70 +849,331 @@ struct BatchInput {
     }
 };
 
-// CPUs this process may use: the cgroup's quota when it has one (cpu.max: "<quota> <period>"), else the CPUs of its affinity mask.
-// A position loop runs helper threads beside its own (the tile formatter, the deflaters of its two outputs, the call that finishes a
-// tile while the next one's blocks are gathered); how many it starts goes by the CPUs per loop -- past the quota they only get the
-// whole process throttled (round 5, 16 CPUs: three VCF deflaters per loop +50 % with one loop, +18 % with four, -15 % with eight).
-static double cpus_per_loop()
+typedef std::deque<BatchInput> BatchInputs;     // a thread's temp-batch files, batch by batch (a deque: an input owns its file and does not move)
+
+// ---- the feeds of the compute phase: each takes a thread's window through its runner, tile by tile ---------------------------------
+
+// The CPU parser, position by position (BVC_HOST_DEVICE_PARSE=0, the quality-shift hook, a mix of text and binary files): a line or
+// record of every batch per position into the tile's next column.
+static void feed_cpu_parser(TileRunner &tr, const Window &w, BatchInputs &in, int qual_shift)
 {
-    static const double cpus = [] {
-        double c = (double)std::max(1u, std::thread::hardware_concurrency());
-        cpu_set_t set;
-        if (sched_getaffinity(0, sizeof set, &set) == 0) c = (double)CPU_COUNT(&set);
-        std::ifstream f("/sys/fs/cgroup/cpu.max");
-        std::string q; double period = 0;
-        if (f >> q >> period && q != "max" && period > 0) c = std::min(c, std::max(1.0, atof(q.c_str()) / period));
-        return c;
-    }();
-    return cpus / (double)std::max(1, opt::thread);
+    std::string line;
+    int32_t count = 0;
+    for (size_t ip = w.lo; ip < w.hi; ++ip) {
+        const int32_t p = w.pv[ip];
+        SiteColumn &site = tr.slot();                                   // parsed in place: no copy into the tile
+        site.clear();
+        site.pos = p;
+        int32_t j = 0;
+        for (auto &fp : in) j += fp.next(j, site, line, tr.clk);
+        if (qual_shift)                                                 // test hook (knob::qual_shift)
+            for (auto &a : site.aiv)
+                if (a.is_indel == 0) a.qual = (uint32_t)std::min(127, (int)a.qual + qual_shift);
+        if (!site.aiv.empty()) {
+            ++tr.cur->n_used;
+            tr.cur->entries += site.aiv.size();
+            tr.cur->refs.push_back(w.ref_at(p));
+            // a tile is full at --tile positions or at 1M observations (16 MB of per-sample records held for the
+            // CVG/VCF lines; three tiles are in flight per thread): at 1e5 samples that is a hundred positions, still far
+            // more than the device needs, and short enough for the three stages to overlap within a thread's window
+            if ((int64_t)tr.cur->n_used >= w.tile || tr.cur->entries >= ((size_t)1 << 20)) tr.flush();
+            if (!(++count % 1000)) std::cerr << "basetype completed " << count << " sites -- thread" << tr.ithread << std::endl;
+        }
+    }
+}
+
+// One batch's share of a tile of TEXT: its next T lines, from a 16-byte boundary.
+static void stage_lines(BgzfReader &rd, size_t T, std::vector<char> &text, uint32_t *starts)
+{
+    text.resize((text.size() + 15) & ~(size_t)15, '\n');
+    if (rd.read_lines(T, text, starts) != T) throw std::runtime_error(kTruncatedBatch);
+    if (text.size() > (size_t)0xF0000000u) throw std::runtime_error("ERROR: more than 3.75 GiB of text in one tile: lower --tile");
+}
+
+// One batch's share of a tile of RECORDS: its next T records one after the other as they come out of its stream (inflated on the
+// CPU, or copied: the raw form), from an 8-byte boundary.
+static void stage_records(BgzfReader &rd, size_t T, std::vector<char> &text, uint32_t *starts)
+{
+    text.resize((text.size() + 7) & ~(size_t)7, 0);
+    for (size_t t = 0; t < T; ++t) {
+        unsigned char b4[4];
+        if (rd.read(b4, 4) != 4) throw std::runtime_error(kTruncatedBatch);
+        const size_t n = le32(b4);
+        const size_t at = text.size();
+        if (at + 4 + n > (size_t)0xF0000000u) throw std::runtime_error("ERROR: more than 3.75 GiB of records in one tile: lower --tile");
+        starts[t] = (uint32_t)at;
+        text.resize(at + 4 + n);
+        std::memcpy(&text[at], b4, 4);
+        if (n && rd.read(&text[at + 4], n) != n) throw std::runtime_error("ERROR: truncated temp batch record");
+    }
+    starts[T] = (uint32_t)text.size();
+}
+
+// Tiles staged on the host for the device parser: text inflated on the CPU (BVC_HOST_DEVICE_INFLATE=0), or binary records when every
+// batch file is binary.  A tile: --tile positions at most, and about BVC_HOST_TILE_MB of text or records going by the tile before it
+// (the first: 64 positions at most); every batch's share of it one after the other.
+static void feed_staged_tiles(TileRunner &tr, const Window &w, BatchInputs &in, TileForm form)
+{
+    const double target = 1048576.0 * knob::tile_mb(true);
+    double bytes_per_pos = 0;
+    const size_t nb = in.size();
+    for (size_t ip = w.lo; ip < w.hi;) {
+        size_t T = (size_t)std::min<int64_t>(w.tile, (int64_t)(w.hi - ip));
+        if (bytes_per_pos > 0) T = std::min(T, (size_t)std::max(1.0, target / bytes_per_pos));
+        else T = std::min<size_t>(T, 64);
+        Tile &tl = *tr.cur;
+        tl.form = form;
+        tl.text.clear();
+        tl.line_start.resize(nb * (T + 1));
+        const double t0 = StageClock::now();
+        for (size_t b = 0; b < nb; ++b) {
+            uint32_t *starts = &tl.line_start[b * (T + 1)];
+            if (form == TileForm::Records) stage_records(in[b].rd, T, tl.text, starts);
+            else stage_lines(in[b].rd, T, tl.text, starts);
+        }
+        tr.clk.read += StageClock::now() - t0;
+        tl.set_positions(w, ip, T);
+        bytes_per_pos = (double)tl.text.size() / (double)T;
+        tr.flush();
+        ip += T;
+    }
+}
+
+// the tile's compressed blocks, one after the other, in page-locked memory of the library's: they go over the link from here
+struct PinnedBytes {
+    unsigned char *p = nullptr;
+    size_t n = 0, cap = 0;
+    ~PinnedBytes() { bvc_host_free(p); }
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    unsigned char *data() { return p; }
+    void clear() { n = 0; }
+    void append(const unsigned char *src, size_t len)
+    {
+        const size_t need = ((n + len + 3) & ~(size_t)3) + 16;
+        if (need > cap) {
+            const size_t want = std::max(need + need / 2, (size_t)1 << 20);
+            unsigned char *q = static_cast<unsigned char *>(bvc_host_alloc(want));
+            if (!q) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
+            if (n) std::memcpy(q, p, n);
+            bvc_host_free(p);
+            p = q; cap = want;
+        }
+        std::memcpy(p + n, src, len);
+        n += len;
+        while (n & 3) p[n++] = 0;                                // every payload from a 4-byte boundary
+    }
+};
+
+// The blocks of one bvc_pileup_begin_bgzf call, gathered and not yet sent.
+struct Staged {
+    PinnedBytes comp;
+    std::vector<bvc_bgzf_block> blocks;
+    std::vector<int32_t> send;                                   // per batch: how many of them are its
+    bool any_new = false, ready = false;
+    double seconds = 0;                                          // what gathering them took
+};
+
+// Raw BGZF blocks, inflated and parsed on the device (text batches, the default).  The files go to the device as they are: this thread
+// takes the raw blocks out of the mapped files, hands every batch's next blocks to bvc_pileup_begin_bgzf -- as many as its lines are
+// short of the tile's target, counted from what the calls report back -- and the tile is the positions every batch has whole.  The
+// thread does stage 2's work itself; stage 3 (CVG / VCF lines) runs beside it.
+class BgzfFeed {
+ public:
+    // skip: per batch, the bytes of its names line (the BatchInputs that read them are closed by now: the files are mapped here)
+    BgzfFeed(TileRunner &tr, const Window &w, const std::vector<std::string> &paths, const std::vector<int32_t> &skip, int device)
+        : tr_(tr), w_(w), skip_(skip), device_(device), nb_(paths.size()),
+          blocks_per_batch_(std::max(1.0, knob::tile_mb(false) * 1048576.0 / (65280.0 * (double)std::max<size_t>(1, nb_)))),
+          check_crc_(!knob::no_crc()), feed_(paths), lines_per_block_(nb_, 0.0), blocks_sent_(nb_, 0), lines_seen_(nb_, 0),
+          left_lines_(nb_, 0), lines_(nb_, 0), ended_(nb_, 0)
+    {
+        stg_[0].send.assign(nb_, 0); stg_[1].send.assign(nb_, 0);
+    }
+
+    void run()
+    {
+        // BVC_HOST_PROFILE=2: what every tile cost this thread (positions, compressed bytes, gathering its blocks, waiting for a device
+        // slot, bvc_pileup_begin_bgzf, bvc_pileup_finish)
+        const bool tile_log = knob::profile_tiles();
+        const bool overlap_gather = knob::gather_ahead();
+        std::vector<std::array<double, 6>> tile_times;
+        int cur = 0;                                                    // of the two sets of blocks: the one this tile's call takes
+        for (size_t ip = w_.lo; ip < w_.hi;) {
+            Staged &S = stg_[cur];
+            if (!S.ready) gather(S);
+            const double t_wait = StageClock::now();
+            DeviceSlot slot(device_);                                   // (held to the end of the loop's body)
+            const double t1 = StageClock::now();
+            Tile &tl = *tr_.cur;
+            const int32_t max_pos = (int32_t)std::min<int64_t>((int64_t)(w_.hi - ip), std::max<int64_t>(2 * target_, 64));
+            int32_t T = 0;
+            int64_t n_ent = 0, n_ind = 0, ind_bytes = 0;
+            const int rc = bvc_pileup_begin_bgzf(tr_.ctx, S.comp.empty() ? nullptr : S.comp.data(), (int64_t)S.comp.size(), S.blocks.data(), S.send.data(),
+                                                 first_ ? skip_.data() : nullptr, tr_.sample0.data(), tr_.n_in_batch.data(), (int32_t)nb_, max_pos,
+                                                 first_ ? 1 : 0, &T, lines_.data(), &n_ent, &n_ind, &ind_bytes);
+            first_ = false;
+            S.ready = false;
+            const double t_begun = StageClock::now();
+            if (rc < 0) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(tr_.ctx) + " (BVC_HOST_DEVICE_INFLATE=0 inflates on the CPU)");
+            note_lines(T);
+            if (T == 0) {
+                // some batch has no whole line yet: it gets more blocks next time round (left_lines < target); nothing new and nothing
+                // whole means its file has ended before the window has
+                if (!S.any_new) throw std::runtime_error(kTruncatedBatch);
+                continue;
+            }
+            tl.form = TileForm::Text;
+            tl.set_positions(w_, ip, (size_t)T);
+            if (rc == BVC_PILEUP_IRREGULAR) {
+                int64_t need = 0;
+                bvc_check(tr_.ctx, bvc_pileup_text(tr_.ctx, nullptr, 0, &need, nullptr));
+                tl.text.resize((size_t)need + 1);
+                tl.line_start.resize(nb_ * ((size_t)T + 1));
+                bvc_check(tr_.ctx, bvc_pileup_text(tr_.ctx, tl.text.data(), need, &need, tl.line_start.data()));
+                tr_.cpu_parse_tile(tl);
+            } else if (overlap_gather && ip + (size_t)T < w_.hi) {
+                // the blocks of the next tile are gathered (out of the mapped files into the other page-locked buffer) beside the call
+                // that parses this one, runs its LRT and brings its records back: what the next call needs is known since the begin
+                std::future<void> fin = std::async(std::launch::async, [&] { tr_.finish_tile(tl, n_ent, n_ind, ind_bytes, true); });
+                gather(stg_[1 - cur]);                                  // (should it throw, fin's destructor waits for the call)
+                fin.get();
+                cur = 1 - cur;
+            } else {
+                tr_.finish_tile(tl, n_ent, n_ind, ind_bytes, true);
+            }
+            tr_.clk_dev.gpu += StageClock::now() - t1;
+            if (tile_log) tile_times.push_back({(double)T, (double)S.comp.size(), S.seconds, t1 - t_wait, t_begun - t1, StageClock::now() - t_begun});
+            ip += (size_t)T;
+            // straight to stage 3 (this thread did stage 2's work itself)
+            tr_.rethrow_if_failed();
+            tr_.out_q.push(tr_.cur);
+            tr_.cur = tr_.free_q.pop();
+        }
+        if (tile_log) {
+            std::ostringstream os;
+            os << "[profile] thread " << tr_.ithread << " tiles (positions, comp MB, gather ms, slot wait ms, begin ms, finish ms):";
+            for (auto const &t : tile_times)
+                os << " (" << t[0] << ", " << std::fixed << std::setprecision(1) << t[1] / 1048576.0 << ", " << t[2] * 1e3 << ", " << t[3] * 1e3 << ", "
+                   << t[4] * 1e3 << ", " << t[5] * 1e3 << ")";
+            std::cerr << os.str() << std::endl;
+        }
+    }
+
+ private:
+    // every batch's new blocks: enough for `target` lines going by its lines per block so far (the first call: the names line and
+    // one block of positions); a batch found without a whole line gets one block more than that
+    void gather(Staged &S)
+    {
+        const double t0 = StageClock::now();
+        S.comp.clear(); S.blocks.clear();
+        S.any_new = false;
+        for (size_t b = 0; b < nb_; ++b) {
+            int64_t want = 0;
+            if (first_) { want = 1 + skip_[b] / 60000; }
+            else if (left_lines_[b] < target_) {
+                const double lpb = lines_per_block_[b] > 0 ? lines_per_block_[b] : 1.0;
+                want = (int64_t)std::ceil((double)(target_ - left_lines_[b]) / lpb);
+                if (want < 1) want = 1;
+            }
+            int32_t took = 0;
+            RawBlock rb;
+            while (took < want && !ended_[b]) {
+                if (!feed_.pop(b, rb)) { ended_[b] = 1; break; }
+                bvc_bgzf_block blk;
+                blk.comp_off = (int64_t)S.comp.size(); blk.out_off = 0; blk.comp_len = (int32_t)rb.len; blk.isize = (int32_t)rb.isize;
+                blk.crc32 = rb.crc32; blk.check_crc = check_crc_ ? 1u : 0u;
+                S.comp.append(rb.payload, rb.len);
+                S.blocks.push_back(blk);
+                ++took;
+            }
+            S.send[b] = took;
+            blocks_sent_[b] += took;
+            S.any_new = S.any_new || took > 0;
+        }
+        S.ready = true;
+        S.seconds = StageClock::now() - t0;
+        tr_.clk.read += S.seconds;
+    }
+
+    // after a begin that made a tile of T positions (lines_: the whole lines it found of every batch): the lines every batch has left
+    // for the next tile and its lines per block so far; and the tile after this one: the positions that ~BVC_HOST_TILE_MB of blocks
+    // hold, going by the batch with the fewest lines per block
+    void note_lines(int32_t T)
+    {
+        double lpb_min = 1e30;
+        for (size_t b = 0; b < nb_; ++b) {
+            lines_seen_[b] += lines_[b] - left_lines_[b];
+            if (blocks_sent_[b] > 0) lines_per_block_[b] = (double)lines_seen_[b] / (double)blocks_sent_[b];
+            left_lines_[b] = lines_[b] - T;
+            if (lines_per_block_[b] > 0) lpb_min = std::min(lpb_min, lines_per_block_[b]);
+        }
+        if (T > 0 && lpb_min < 1e30) target_ = std::max<int64_t>(1, std::min<int64_t>(w_.tile, (int64_t)(blocks_per_batch_ * lpb_min)));
+    }
+
+    TileRunner &tr_;
+    const Window &w_;
+    const std::vector<int32_t> &skip_;
+    const int device_;
+    const size_t nb_;
+    const double blocks_per_batch_;     // the blocks of a batch that a tile of BVC_HOST_TILE_MB holds
+    const bool check_crc_;
+    MappedBlocks feed_;
+    std::vector<double> lines_per_block_;                               // running estimate per batch
+    std::vector<int64_t> blocks_sent_, lines_seen_;
+    std::vector<int32_t> left_lines_, lines_;
+    std::vector<char> ended_;
+    Staged stg_[2];                     // two sets: the blocks of the tile after this one are gathered while bvc_pileup_finish works on this one
+    bool first_ = true;
+    int64_t target_ = 1;                // positions the next tile should hold
+};
+
+// population groups (src/BaseVarC.cpp:335-369): name-sorted, a sample not listed belongs to no group
+static Groups read_groups(const std::vector<std::string> &names, int32_t N)
+{
+    Groups groups;
+    if (opt::group.empty()) return groups;
+    std::ifstream ifg(opt::group);
+    std::unordered_map<std::string, std::string> popg_m;
+    std::string id, grp;
+    while (ifg >> id >> grp) popg_m.insert({id, grp});
+    std::map<std::string, std::vector<int>> popg_idx;
+    for (size_t i = 0; i < names.size(); ++i) {
+        auto it = popg_m.find(names[i]);
+        if (it != popg_m.end()) popg_idx[it->second].push_back((int)i);
+    }
+    if (popg_idx.size() > BVC_MAX_GROUPS) throw std::runtime_error("ERROR: more than 32 population groups");
+    groups.of_sample.assign((size_t)N, 255);
+    for (auto const &kv : popg_idx) {
+        for (int i : kv.second) groups.of_sample[(size_t)i] = (uint8_t)groups.names.size();
+        groups.names.push_back(kv.first);
+    }
+    groups.order_columns();
+    return groups;
 }
 
 static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32_t> &pv, const std::string &refseq,
                  const std::string &chr, int32_t rg_s, int32_t N, int thread, int ithread, int device)
 {
     const double t_start = StageClock::now();
-    // the outputs (a VCF line carries a field per SAMPLE: a megabyte at 1e5 samples) are deflated by threads of their
-    // writers' own
-    // (the VCF text is one field per SAMPLE and called position: up to three threads deflate it, BVC_HOST_VCF_DEFLATERS)
-    static const int vcf_deflaters = getenv("BVC_HOST_VCF_DEFLATERS") ? std::max(1, atoi(getenv("BVC_HOST_VCF_DEFLATERS")))
-                                                                          : (cpus_per_loop() >= 4 ? 3 : (cpus_per_loop() >= 3 ? 2 : 1));
-    BgzfWriter fpv(opt::output + "." + std::to_string(ithread) + ".vcf.gz", 6, true, vcf_deflaters);
+    // the outputs are deflated by threads of their writers' own (a VCF line carries a field per SAMPLE, a megabyte at 1e5 samples: up
+    // to three threads deflate the VCF text)
+    BgzfWriter fpv(opt::output + "." + std::to_string(ithread) + ".vcf.gz", 6, true, knob::vcf_deflaters());
     BgzfWriter fpc(opt::output + "." + std::to_string(ithread) + ".cvg.gz", 6, true);
-    // the blocks of the temp batches are inflated ahead of the position loop by threads of their own (the loop takes a
-    // line of every batch per position; inflating was 70 % of it with the text form): BVC_HOST_INFLATE_THREADS, 0 = none
-    const int n_inflate = getenv("BVC_HOST_INFLATE_THREADS") ? atoi(getenv("BVC_HOST_INFLATE_THREADS")) : 2;
-    std::unique_ptr<InflatePool> inflate_pool(n_inflate > 0 ? new InflatePool(n_inflate) : nullptr);
-    std::vector<BatchInput *> fpiv;
-    for (auto const &f : ftmp_v) fpiv.push_back(new BatchInput(f));
-    if (inflate_pool) for (auto fp : fpiv) fp->rd.attach(inflate_pool.get());
+    std::deque<InflatePool> inflate_pool;                               // (none with BVC_HOST_INFLATE_THREADS=0; outlives the inputs)
+    const int n_inflate = knob::inflate_threads();
+    if (n_inflate > 0) inflate_pool.emplace_back(n_inflate);
+    BatchInputs in;
+    for (auto const &f : ftmp_v) in.emplace_back(f);
+    if (!inflate_pool.empty()) for (auto &fp : in) fp.rd.attach(&inflate_pool.front());
     // (BVC_HOST_PROFILE: on a GPU box the first ~0.5 s of every worker thread go to process-wide stalls while the HIP
     // runtime, started by bvc_device_count in main, finishes coming up -- whatever the thread does first pays them.)
     const double t_opened = StageClock::now();
-    std::string sams, line;
-    for (auto fp : fpiv) sams += fp->names;
+    std::string sams;
+    for (auto const &fp : in) sams += fp.names;
     if (!sams.empty()) sams.pop_back();                                 // names are tab-terminated
     std::vector<std::string> names;
     { std::istringstream iss(sams); std::string id; while (std::getline(iss, id, '\t')) names.push_back(id); }
-    // population groups (src/BaseVarC.cpp:335-369): name-sorted, a sample not listed belongs to no group
-    Groups groups;
-    if (!opt::group.empty()) {
-        std::ifstream ifg(opt::group);
-        std::unordered_map<std::string, std::string> popg_m;
-        std::string id, grp;
-        while (ifg >> id >> grp) popg_m.insert({id, grp});
-        std::map<std::string, std::vector<int>> popg_idx;
-        for (size_t i = 0; i < names.size(); ++i) {
-            auto it = popg_m.find(names[i]);
-            if (it != popg_m.end()) popg_idx[it->second].push_back((int)i);
-        }
-        if (popg_idx.size() > BVC_MAX_GROUPS) throw std::runtime_error("ERROR: more than 32 population groups");
-        groups.of_sample.assign((size_t)N, 255);
-        for (auto const &kv : popg_idx) {
-            for (int i : kv.second) groups.of_sample[(size_t)i] = (uint8_t)groups.names.size();
-            groups.names.push_back(kv.first);
-        }
-        groups.order_columns();
-    }
+    const Groups groups = read_groups(names, N);
     if (ithread == 0) {
         fpc.write(cvg_header(groups));
         fpv.write(vcf_header(groups, opt::reference, names));
@@ -860,6 +1187,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     tr.groups = groups.empty() ? nullptr : &groups;
     tr.chr = chr;
     tr.n_samples = N;
+    tr.ithread = ithread;
     double min_af = 100.0 / N;                                          // src/BaseVarC.cpp:541-543
     if (min_af > 0.001) min_af = 0.001;
     if (opt::maf < min_af) min_af = opt::maf;
@@ -867,312 +1195,44 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     tr.fvcf = &fpv;
     tr.fcvg = &fpc;
     tr.start();
-    int64_t tile = opt::tile > 0 ? opt::tile : 4096;
-    if (!groups.empty()) tile = std::max<int64_t>(1, std::min<int64_t>(tile, ((int64_t)256 << 20) / std::max(1, N)));
+    Window w = {pv, refseq, rg_s, 0, 0, opt::tile > 0 ? opt::tile : 4096};
+    if (!groups.empty()) w.tile = std::max<int64_t>(1, std::min<int64_t>(w.tile, ((int64_t)256 << 20) / std::max(1, N)));
+    thread_window(pv.size(), thread, ithread, w.lo, w.hi);
     reset_parser_carry();
-    // BVC_HOST_QUAL_SHIFT=k (tests only): k is added to every base quality as it is read, so that data whose qualities
-    // stop at 41 can exercise the tiles that do not fit one byte per observation (quality >= 63)
-    const int qual_shift = getenv("BVC_HOST_QUAL_SHIFT") ? atoi(getenv("BVC_HOST_QUAL_SHIFT")) : 0;
-    size_t lo, hi;
-    thread_window(pv.size(), thread, ithread, lo, hi);
-    int32_t count = 0;
-    tr.ithread = ithread;
-    // Tiles of TEXT, or of binary RECORDS when every batch file is binary, for the device parser (the default): BVC_HOST_DEVICE_PARSE=0
-    // keeps the CPU parser (A/B runs, and what the quality-shift test hook and a mix of text and binary files use)
-    bool dev_parse = !qual_shift && !(getenv("BVC_HOST_DEVICE_PARSE") && atoi(getenv("BVC_HOST_DEVICE_PARSE")) == 0);
+    // The feed.  Tiles of TEXT, or of binary RECORDS when every batch file is binary, for the device parser (the default);
+    // BVC_HOST_DEVICE_PARSE=0 keeps the CPU parser (A/B runs, and what the quality-shift test hook and a mix of text and binary files
+    // use) ...
+    const int qual_shift = knob::qual_shift();
+    bool dev_parse = !qual_shift && knob::device_parse();
     size_t n_bin_files = 0;
-    for (auto fp : fpiv) if (fp->bin) ++n_bin_files;
-    if (n_bin_files != 0 && n_bin_files != fpiv.size()) dev_parse = false;
+    for (auto const &fp : in) if (fp.bin) ++n_bin_files;
+    if (n_bin_files != 0 && n_bin_files != in.size()) dev_parse = false;
     const bool dev_bin = dev_parse && n_bin_files != 0;
     const double t_loop = StageClock::now();
     // ... and with the blocks of the text batches inflated on the device too (the default): BVC_HOST_DEVICE_INFLATE=0 inflates on the CPU
-    const bool dev_inflate = dev_parse && !dev_bin && !(getenv("BVC_HOST_DEVICE_INFLATE") && atoi(getenv("BVC_HOST_DEVICE_INFLATE")) == 0);
+    const bool dev_inflate = dev_parse && !dev_bin && knob::device_inflate();
     if (dev_parse) {
         // per batch: its first sample and its samples, from the binary header or the names line (tab-terminated names,
         // src/BaseVarC.cpp:495, 503)
         int32_t j0 = 0;
-        for (auto fp : fpiv) {
-            const int32_t n_in = fp->bin ? (int32_t)fp->n_in_batch : (int32_t)std::count(fp->names.begin(), fp->names.end(), '\t');
+        for (auto const &fp : in) {
+            const int32_t n_in = fp.bin ? (int32_t)fp.n_in_batch : (int32_t)std::count(fp.names.begin(), fp.names.end(), '\t');
             tr.sample0.push_back(j0); tr.n_in_batch.push_back(n_in);
             j0 += n_in;
         }
         get_parser_carry(tr.carry);                                     // (zeros: reset_parser_carry above)
     }
     if (dev_inflate) {
-        // The files go to the device as they are: this thread takes the raw blocks out of the mapped files,
-        // hands every batch's next blocks to bvc_pileup_begin_bgzf -- as many as its lines are short of the tile's target, counted from what
-        // the calls report back -- and the tile is the positions every batch has whole.  Stage 3 (CVG / VCF lines) runs beside it.
-        const size_t nb = fpiv.size();
-        std::vector<int32_t> skip(nb);
-        for (size_t b = 0; b < nb; ++b) skip[b] = (int32_t)fpiv[b]->names.size() + 1;      // the names line and its newline
-        for (auto fp : fpiv) delete fp;
-        fpiv.clear();
-        const double tile_mb = getenv("BVC_HOST_TILE_MB") ? std::max(1, atoi(getenv("BVC_HOST_TILE_MB"))) : 128;
-        const double blocks_per_batch = std::max(1.0, tile_mb * 1048576.0 / (65280.0 * (double)std::max<size_t>(1, nb)));
-        MappedBlocks feed(ftmp_v);
-        static const bool check_crc = getenv("BVC_HOST_NO_CRC") == nullptr;     // (the CRC32 of every block is compared on the device, as htslib does)
-        std::vector<double> lines_per_block(nb, 0.0);                   // running estimate per batch
-        std::vector<int64_t> blocks_sent(nb, 0), lines_seen(nb, 0);
-        std::vector<int32_t> left_lines(nb, 0), lines(nb, 0), send(nb, 0);
-        std::vector<char> ended(nb, 0);
-        // the tile's compressed blocks, one after the other, in page-locked memory of the library's: they go over the link from here
-        struct PinnedBytes {
-            unsigned char *p = nullptr;
-            size_t n = 0, cap = 0;
-            ~PinnedBytes() { bvc_host_free(p); }
-            size_t size() const { return n; }
-            bool empty() const { return n == 0; }
-            unsigned char *data() { return p; }
-            void clear() { n = 0; }
-            void append(const unsigned char *src, size_t len)
-            {
-                const size_t need = ((n + len + 3) & ~(size_t)3) + 16;
-                if (need > cap) {
-                    const size_t want = std::max(need + need / 2, (size_t)1 << 20);
-                    unsigned char *q = static_cast<unsigned char *>(bvc_host_alloc(want));
-                    if (!q) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
-                    if (n) std::memcpy(q, p, n);
-                    bvc_host_free(p);
-                    p = q; cap = want;
-                }
-                std::memcpy(p + n, src, len);
-                n += len;
-                while (n & 3) p[n++] = 0;                                // every payload from a 4-byte boundary
-            }
-        };
-        // two sets of them: the blocks of the tile after this one are gathered while bvc_pileup_finish works on this one
-        struct Staged {
-            PinnedBytes comp;
-            std::vector<bvc_bgzf_block> blocks;
-            std::vector<int32_t> send;
-            bool any_new = false, ready = false;
-            double seconds = 0;
-        } stg[2];
-        stg[0].send.assign(nb, 0); stg[1].send.assign(nb, 0);
-        int cur = 0;
-        bool first = true;
-        int64_t target = 1;                                             // positions the next tile should hold
-        // BVC_HOST_PROFILE=2: what every tile cost this thread (positions, compressed bytes, gathering its blocks, waiting for a device
-        // slot, bvc_pileup_begin_bgzf, bvc_pileup_finish)
-        const bool tile_log = getenv("BVC_HOST_PROFILE") && atoi(getenv("BVC_HOST_PROFILE")) >= 2;
-        static const bool overlap_gather = getenv("BVC_HOST_GATHER_AHEAD") ? atoi(getenv("BVC_HOST_GATHER_AHEAD")) != 0 : cpus_per_loop() >= 3;
-        std::vector<std::array<double, 6>> tile_times;
-        // every batch's new blocks: enough for `target` lines going by its lines per block so far (the first call: the names line and
-        // one block of positions); a batch found without a whole line gets one block more than that
-        auto gather = [&](Staged &S) {
-            const double t0 = StageClock::now();
-            S.comp.clear(); S.blocks.clear();
-            S.any_new = false;
-            for (size_t b = 0; b < nb; ++b) {
-                int64_t want = 0;
-                if (first) { want = 1 + skip[b] / 60000; }
-                else if (left_lines[b] < target) {
-                    const double lpb = lines_per_block[b] > 0 ? lines_per_block[b] : 1.0;
-                    want = (int64_t)std::ceil((double)(target - left_lines[b]) / lpb);
-                    if (want < 1) want = 1;
-                }
-                int32_t took = 0;
-                RawBlock rb;
-                while (took < want && !ended[b]) {
-                    if (!feed.pop(b, rb)) { ended[b] = 1; break; }
-                    bvc_bgzf_block blk;
-                    blk.comp_off = (int64_t)S.comp.size(); blk.out_off = 0; blk.comp_len = (int32_t)rb.len; blk.isize = (int32_t)rb.isize;
-                    blk.crc32 = rb.crc32; blk.check_crc = check_crc ? 1u : 0u;
-                    S.comp.append(rb.payload, rb.len);
-                    S.blocks.push_back(blk);
-                    ++took;
-                }
-                S.send[b] = took;
-                blocks_sent[b] += took;
-                S.any_new = S.any_new || took > 0;
-            }
-            S.ready = true;
-            S.seconds = StageClock::now() - t0;
-            tr.clk.read += S.seconds;
-        };
-        for (size_t ip = lo; ip < hi;) {
-            Staged &S = stg[cur];
-            if (!S.ready) gather(S);
-            const double t_wait = StageClock::now();
-            g_device_slots.acquire(device);
-            struct SlotGuard { int d; ~SlotGuard() { g_device_slots.release(d); } } slot_guard{device};
-            const double t1 = StageClock::now();
-            Tile &tl = *tr.cur;
-            const int32_t max_pos = (int32_t)std::min<int64_t>((int64_t)(hi - ip), std::max<int64_t>(2 * target, 64));
-            int32_t T = 0;
-            int64_t n_ent = 0, n_ind = 0, ind_bytes = 0;
-            const int rc = bvc_pileup_begin_bgzf(tr.ctx, S.comp.empty() ? nullptr : S.comp.data(), (int64_t)S.comp.size(), S.blocks.data(), S.send.data(),
-                                                 first ? skip.data() : nullptr, tr.sample0.data(), tr.n_in_batch.data(), (int32_t)nb, max_pos,
-                                                 first ? 1 : 0, &T, lines.data(), &n_ent, &n_ind, &ind_bytes);
-            first = false;
-            S.ready = false;
-            const double t_begun = StageClock::now();
-            if (rc < 0) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(tr.ctx) + " (BVC_HOST_DEVICE_INFLATE=0 inflates on the CPU)");
-            for (size_t b = 0; b < nb; ++b) {
-                lines_seen[b] += lines[b] - left_lines[b];
-                if (blocks_sent[b] > 0) lines_per_block[b] = (double)lines_seen[b] / (double)blocks_sent[b];
-                left_lines[b] = lines[b] - T;
-            }
-            if (T == 0) {
-                // some batch has no whole line yet: it gets more blocks next time round (left_lines < target); nothing new and nothing
-                // whole means its file has ended before the window has
-                if (!S.any_new) throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
-                continue;
-            }
-            // the tile after this one: the positions that ~tile_mb of text hold, going by the batch with the fewest lines per block
-            {
-                double lpb_min = 1e30;
-                for (size_t b = 0; b < nb; ++b) if (lines_per_block[b] > 0) lpb_min = std::min(lpb_min, lines_per_block[b]);
-                if (lpb_min < 1e30) target = std::max<int64_t>(1, std::min<int64_t>(tile, (int64_t)(blocks_per_batch * lpb_min)));
-            }
-            tl.dev = true; tl.n_pos = (size_t)T;
-            tl.refs.resize((size_t)T);
-            tl.pos.resize((size_t)T);
-            for (int32_t k = 0; k < T; ++k) {
-                const int32_t p = pv[ip + (size_t)k];
-                const char rcc = refseq[(size_t)(p - rg_s)];
-                tl.pos[(size_t)k] = p;
-                tl.refs[(size_t)k] = rcc == 'A' ? 0 : rcc == 'C' ? 1 : rcc == 'G' ? 2 : rcc == 'T' ? 3 : -1;
-            }
-            if (rc == BVC_PILEUP_IRREGULAR) {
-                int64_t need = 0;
-                if (bvc_pileup_text(tr.ctx, nullptr, 0, &need, nullptr) != BVC_OK) throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(tr.ctx));
-                tl.text.resize((size_t)need + 1);
-                tl.line_start.resize(nb * ((size_t)T + 1));
-                if (bvc_pileup_text(tr.ctx, tl.text.data(), need, &need, tl.line_start.data()) != BVC_OK)
-                    throw std::runtime_error(std::string("libbvc: ") + bvc_last_error(tr.ctx));
-                tr.cpu_parse_tile(tl);
-            } else if (overlap_gather && ip + (size_t)T < hi) {
-                // the blocks of the next tile are gathered (out of the mapped files into the other page-locked buffer) beside the call
-                // that parses this one, runs its LRT and brings its records back: what the next call needs is known since the begin
-                std::future<void> fin = std::async(std::launch::async, [&] { tr.finish_tile(tl, n_ent, n_ind, ind_bytes, true); });
-                gather(stg[1 - cur]);                                   // (should it throw, fin's destructor waits for the call)
-                fin.get();
-                cur = 1 - cur;
-            } else {
-                tr.finish_tile(tl, n_ent, n_ind, ind_bytes, true);
-            }
-            tr.clk_dev.gpu += StageClock::now() - t1;
-            if (tile_log) tile_times.push_back({(double)T, (double)S.comp.size(), S.seconds, t1 - t_wait, t_begun - t1, StageClock::now() - t_begun});
-            ip += (size_t)T;
-            // straight to stage 3 (this thread did stage 2's work itself)
-            if (tr.failed()) { std::lock_guard<std::mutex> g(tr.err_mu); throw std::runtime_error(tr.err); }
-            tr.out_q.push(tr.cur);
-            tr.cur = tr.free_q.pop();
-        }
-        if (tile_log) {
-            std::ostringstream os;
-            os << "[profile] thread " << ithread << " tiles (positions, comp MB, gather ms, slot wait ms, begin ms, finish ms):";
-            for (auto const &t : tile_times)
-                os << " (" << t[0] << ", " << std::fixed << std::setprecision(1) << t[1] / 1048576.0 << ", " << t[2] * 1e3 << ", " << t[3] * 1e3 << ", "
-                   << t[4] * 1e3 << ", " << t[5] * 1e3 << ")";
-            std::cerr << os.str() << std::endl;
-        }
-    } else if (dev_bin) {
-        // a tile of records: --tile positions at most, and about BVC_HOST_TILE_MB of records (default 32) going by the tile before it;
-        // the records of a batch one after the other as they come out of its stream (inflated on the CPU, or copied: the raw form)
-        const double target = 1048576.0 * (getenv("BVC_HOST_TILE_MB") ? std::max(1, atoi(getenv("BVC_HOST_TILE_MB"))) : 32);
-        double bytes_per_pos = 0;
-        const size_t nb = fpiv.size();
-        for (size_t ip = lo; ip < hi;) {
-            size_t T = (size_t)std::min<int64_t>(tile, (int64_t)(hi - ip));
-            if (bytes_per_pos > 0) T = std::min(T, (size_t)std::max(1.0, target / bytes_per_pos));
-            else T = std::min<size_t>(T, 64);
-            Tile &tl = *tr.cur;
-            tl.dev = true; tl.bin = true; tl.n_pos = T;
-            tl.text.clear();
-            tl.line_start.resize(nb * (T + 1));
-            double t0 = StageClock::now();
-            for (size_t b = 0; b < nb; ++b) {
-                BgzfReader &rd = fpiv[b]->rd;
-                tl.text.resize((tl.text.size() + 7) & ~(size_t)7, 0);          // every batch's records from an 8-byte boundary
-                uint32_t *rs = &tl.line_start[b * (T + 1)];
-                for (size_t t = 0; t < T; ++t) {
-                    unsigned char b4[4];
-                    if (rd.read(b4, 4) != 4) throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
-                    const size_t n = (size_t)b4[0] | ((size_t)b4[1] << 8) | ((size_t)b4[2] << 16) | ((size_t)b4[3] << 24);
-                    const size_t at = tl.text.size();
-                    if (at + 4 + n > (size_t)0xF0000000u) throw std::runtime_error("ERROR: more than 3.75 GiB of records in one tile: lower --tile");
-                    rs[t] = (uint32_t)at;
-                    tl.text.resize(at + 4 + n);
-                    std::memcpy(&tl.text[at], b4, 4);
-                    if (n && rd.read(&tl.text[at + 4], n) != n) throw std::runtime_error("ERROR: truncated temp batch record");
-                }
-                rs[T] = (uint32_t)tl.text.size();
-            }
-            tr.clk.read += StageClock::now() - t0;
-            tl.refs.resize(T);
-            tl.pos.resize(T);
-            for (size_t k = 0; k < T; ++k) {
-                const int32_t p = pv[ip + k];
-                const char rc = refseq[(size_t)(p - rg_s)];
-                tl.pos[k] = p;
-                tl.refs[k] = rc == 'A' ? 0 : rc == 'C' ? 1 : rc == 'G' ? 2 : rc == 'T' ? 3 : -1;
-            }
-            bytes_per_pos = (double)tl.text.size() / (double)T;
-            tr.flush();
-            ip += T;
-        }
-    } else if (dev_parse) {
-        // a tile: --tile positions at most, and about BVC_HOST_TILE_MB of text (default 32) going by the tile before it
-        const double target = 1048576.0 * (getenv("BVC_HOST_TILE_MB") ? std::max(1, atoi(getenv("BVC_HOST_TILE_MB"))) : 32);
-        double bytes_per_pos = 0;
-        const size_t nb = fpiv.size();
-        for (size_t ip = lo; ip < hi;) {
-            size_t T = (size_t)std::min<int64_t>(tile, (int64_t)(hi - ip));
-            if (bytes_per_pos > 0) T = std::min(T, (size_t)std::max(1.0, target / bytes_per_pos));
-            else T = std::min<size_t>(T, 64);
-            Tile &tl = *tr.cur;
-            tl.dev = true; tl.n_pos = T;
-            tl.text.clear();
-            tl.line_start.resize(nb * (T + 1));
-            double t0 = StageClock::now();
-            for (size_t b = 0; b < nb; ++b) {
-                tl.text.resize((tl.text.size() + 15) & ~(size_t)15, '\n');    // every batch's lines from a 16-byte boundary
-                if (fpiv[b]->rd.read_lines(T, tl.text, &tl.line_start[b * (T + 1)]) != T)
-                    throw std::runtime_error("ERROR: truncated temp batch (it ends before the thread's window does)");
-                if (tl.text.size() > (size_t)0xF0000000u) throw std::runtime_error("ERROR: more than 3.75 GiB of text in one tile: lower --tile");
-            }
-            tr.clk.read += StageClock::now() - t0;
-            tl.refs.resize(T);
-            tl.pos.resize(T);
-            for (size_t k = 0; k < T; ++k) {
-                const int32_t p = pv[ip + k];
-                const char rc = refseq[(size_t)(p - rg_s)];
-                tl.pos[k] = p;
-                tl.refs[k] = rc == 'A' ? 0 : rc == 'C' ? 1 : rc == 'G' ? 2 : rc == 'T' ? 3 : -1;
-            }
-            bytes_per_pos = (double)tl.text.size() / (double)T;
-            tr.flush();
-            ip += T;
-        }
-    } else
-    for (size_t ip = lo; ip < hi; ++ip) {
-        const int32_t p = pv[ip];
-        SiteColumn &site = tr.slot();                                   // parsed in place: no copy into the tile
-        site.clear();
-        site.pos = p;
-        int32_t j = 0;
-        for (auto fp : fpiv) j += fp->next(j, site, line, tr.clk);
-        if (qual_shift)                                                 // test hook, see above
-            for (auto &a : site.aiv)
-                if (a.is_indel == 0) a.qual = (uint32_t)std::min(127, (int)a.qual + qual_shift);
-        if (!site.aiv.empty()) {
-            const char rc = refseq[(size_t)(p - rg_s)];
-            const int8_t ref_base = rc == 'A' ? 0 : rc == 'C' ? 1 : rc == 'G' ? 2 : rc == 'T' ? 3 : -1;
-            ++tr.cur->n_used;
-            tr.cur->entries += site.aiv.size();
-            tr.cur->refs.push_back(ref_base);
-            // a tile is full at --tile positions or at 1M observations (16 MB of per-sample records held for the
-            // CVG/VCF lines; three tiles are in flight per thread): at 1e5 samples that is a hundred positions, still far
-            // more than the device needs, and short enough for the three stages to overlap within a thread's window
-            if ((int64_t)tr.cur->n_used >= tile || tr.cur->entries >= ((size_t)1 << 20)) tr.flush();
-            if (!(++count % 1000)) std::cerr << "basetype completed " << count << " sites -- thread" << ithread << std::endl;
-        }
-    }
+        std::vector<int32_t> skip;
+        for (auto const &fp : in) skip.push_back((int32_t)fp.names.size() + 1);      // the names line and its newline
+        in.clear();                                                     // closed before the feed maps the same files
+        BgzfFeed(tr, w, ftmp_v, skip, device).run();
+    } else if (dev_bin) feed_staged_tiles(tr, w, in, TileForm::Records);
+    else if (dev_parse) feed_staged_tiles(tr, w, in, TileForm::Text);
+    else feed_cpu_parser(tr, w, in, qual_shift);
     tr.finish();
     const double loop_s = StageClock::now() - t_loop, setup_s = t_loop - t_start;
-    if (getenv("BVC_HOST_PROFILE")) {
+    if (knob::profile()) {
         std::cerr << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
                   << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
                   << tr.tiles_cpu_parsed << std::endl;
@@ -1186,7 +1246,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     bvc_destroy(tr.ctx);
     if (!fpv.close()) std::cerr << "warning: file cannot be closed" << std::endl;
     if (!fpc.close()) std::cerr << "warning: file cannot be closed" << std::endl;
-    for (auto fp : fpiv) delete fp;
+    in.clear();
     if (!opt::keep_tmp)
         for (auto const &f : ftmp_v) std::remove(f.c_str());
 }
@@ -1294,7 +1354,7 @@ static void run_basetype(int argc, char **argv)                          // src/
         std::cout << "merge subfiles done" << std::endl;
         if (!fov.close()) std::cerr << "warning: file cannot be closed" << std::endl;
         if (!foc.close()) std::cerr << "warning: file cannot be closed" << std::endl;
-        if (getenv("BVC_HOST_PROFILE")) {
+        if (knob::profile()) {
             // CPU time the whole process has consumed so far (all threads, the HIP runtime's included): on a box that grants a quota of
             // CPUs this, not the thread count, is what the feed is bounded by
             struct rusage ru;
