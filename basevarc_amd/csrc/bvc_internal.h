@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <vector>
+
 #include "../../include/bvc.h"
 
 namespace bvc {
@@ -35,8 +37,13 @@ struct LaunchState {
                                    // log-likelihood shows that it cannot be the level's first minimum (em_items.hip, site_decide); 0 = it always runs
     int dbg_levels = 0;            // BVC_DBG_LEVELS (timing only, records wrong): cut region_kernel short after a phase; 0 = run all
     mutable uint32_t em_epoch = 0; // stage-2 launches of this context so far (em_items.hip: the narrow launch tells the wide one)
-    mutable uint64_t attr_done = 0;    // kernels whose dynamic-LDS attribute has been raised on this context's device
+    struct RaisedLds { const void *kernel; size_t bytes; };
+    mutable std::vector<RaisedLds> lds_raised;     // kernels whose dynamic-LDS attribute has been raised on this context's device, and to what
 };
+
+// Kernels with more than 48 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised before their first
+// launch: done once per kernel and context (hist_kernel.hip).
+hipError_t raise_lds(const LaunchState &st, const void *kernel, size_t bytes);
 
 // Base-quality -> likelihood table, built on the HOST with the same libm exp() the CPU path uses
 // (src/BaseType.cpp:13,15) and uploaded once per context:

@@ -1165,13 +1165,8 @@ hipError_t launch_lrt_items(const LaunchState &st, hipStream_t stream, int64_t n
     A.prune = st.em_prune;
     A.region0 = 0;
     // the wide kernels' dynamic LDS (4 x 14 KB) is beyond the 48 KiB a launch may ask for without the attribute
-    constexpr uint32_t kSlotRegionWide = 60;
-    if (!(st.attr_done & ((uint64_t)1 << kSlotRegionWide))) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(region_kernel<kWide>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(kMaxTeams * sizeof(Region<kWide>)));
-        if (e != hipSuccess) return e;
-        st.attr_done |= (uint64_t)1 << kSlotRegionWide;
-    }
+    const hipError_t e = raise_lds(st, reinterpret_cast<const void *>(region_kernel<kWide>), kMaxTeams * sizeof(Region<kWide>));
+    if (e != hipSuccess) return e;
     const dim3 block(64 * teams * kTeam);
     auto sequence = [&](auto kernel, size_t lds_per_team) {
         for (int64_t w0 = 0; w0 < wgs; w0 += per_launch) {

@@ -13,6 +13,8 @@
 #include "bvc_device.h"
 #include "bvc_internal.h"
 
+#include <utility>
+
 namespace bvc {
 namespace {
 
@@ -90,6 +92,78 @@ __device__ __forceinline__ void lds_barrier()
     asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
 }
 
+// Zero `words` (a multiple of four) LDS words, 16 bytes per lane and trip; the caller's barrier follows.
+template <int THREADS = kHistThreads>
+__device__ __forceinline__ void clear_lds(uint32_t *hist, int words, int tid)
+{
+    for (int i = tid * 4; i < words; i += THREADS * 4)
+        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+}
+
+// Sum and clear the COPIES copies of counter `slot` (layout [slot][copy]), 16 bytes at a time.  The quad a lane starts
+// with is rotated by the slot so that the 16 lanes of a ds_read_b128 group (consecutive slots) spread over the banks.
+template <int COPIES>
+__device__ __forceinline__ uint32_t fold_class(uint32_t *hist, int slot)
+{
+    uint32_t sum = 0;
+#pragma unroll
+    for (int v = 0; v < COPIES; v += 4) {
+        const int cc = (v + 4 * (slot & 7)) & (COPIES - 1);
+        u32x4 *p = reinterpret_cast<u32x4 *>(&hist[slot * COPIES + cc]);
+        const u32x4 x = *p;
+        sum += x.x + x.y + x.z + x.w;
+        *p = u32x4{0u, 0u, 0u, 0u};
+    }
+    return sum;
+}
+
+// kUnroll (U) independent non-temporal 16-byte loads per lane and array: chunks c, c + kHistThreads, ... of a row (I: the
+// kernel's index type).  The partial form is for the last block of a run [.., c1): a lane past the end loads nothing and
+// carries "no observation" (base bytes 0xFF, or the packed byte 0xFF), which the counting skips.
+template <int U, class I>
+__device__ __forceinline__ void load_block(const u32x4 *bv, const u32x4 *qv, I c, u32x4 (&b)[U], u32x4 (&q)[U])
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        b[u] = __builtin_nontemporal_load(&bv[c + (I)u * kHistThreads]);
+        q[u] = __builtin_nontemporal_load(&qv[c + (I)u * kHistThreads]);
+    }
+}
+
+template <int U, class I>
+__device__ __forceinline__ void load_block(const u32x4 *rv, I c, u32x4 (&v)[U])
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) v[u] = __builtin_nontemporal_load(&rv[c + (I)u * kHistThreads]);
+}
+
+template <int U, class I>
+__device__ __forceinline__ void load_partial_block(const u32x4 *bv, const u32x4 *qv, I c, I c1, u32x4 (&b)[U],
+                                                   u32x4 (&q)[U])
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const I cu = c + (I)u * kHistThreads;
+        b[u] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        q[u] = u32x4{0u, 0u, 0u, 0u};
+        if (cu < c1) {
+            b[u] = __builtin_nontemporal_load(&bv[cu]);
+            q[u] = __builtin_nontemporal_load(&qv[cu]);
+        }
+    }
+}
+
+template <int U, class I>
+__device__ __forceinline__ void load_partial_block(const u32x4 *rv, I c, I c1, u32x4 (&v)[U])
+{
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const I cu = c + (I)u * kHistThreads;
+        v[u] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+        if (cu < c1) v[u] = __builtin_nontemporal_load(&rv[cu]);
+    }
+}
+
 // (Tried: a scheduling fence after each batch of independent loads, so that all 2 * kUnroll loads issue back to back --
 // the compiler otherwise hoists the first use of the first load above the last two.  The compiler's order measures 1 %
 // FASTER on the headline, 0.5 % slower on the column-range kernel: profiles/r02_hist_load_scheduling.txt.)
@@ -144,16 +218,27 @@ __device__ __forceinline__ void count_word(uint32_t lane_base, uint32_t bw, uint
     lds_add_one(shl_byte<3>(bw, 14u) + shl_byte<3>(qw, 7u) + lane_base);   // disjoint bits: + is |, and one v_add3_u32
 }
 
+// One sample behind the "covered?" test, into the lane's copy of its class (layout [class][COPIES]).
+template <int COPIES = kCopies>
+__device__ __forceinline__ void count_sample(uint32_t *hist, uint32_t b, uint32_t q, uint32_t copy)
+{
+    if (b < 4u && q < 128u)                                       // covered sample
+        hist_add(hist, ((b << 7) | q) * COPIES + copy);
+}
+
+// Samples [i0, i1) of a row one by one: unaligned rows, and the head and tail around a run of 16-sample chunks.
+__device__ __forceinline__ void count_bytes(uint32_t *hist, const int8_t *brow,
+                                            const int8_t *qrow, int64_t i0, int64_t i1, int tid, uint32_t lane_off)
+{
+    for (int64_t i = i0 + tid; i < i1; i += kHistThreads)
+        count_sample(hist, (uint8_t)brow[i], (uint8_t)qrow[i], lane_off);
+}
+
 __device__ __forceinline__ void count_word_checked(uint32_t *__restrict__ hist, uint32_t bw, uint32_t qw,
                                                    uint32_t lane_off)
 {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t b = (bw >> (8 * i)) & 0xFFu;
-        const uint32_t q = (qw >> (8 * i)) & 0xFFu;
-        if (b < 4u && q < 128u)                                   // covered sample
-            hist_add(hist, ((b << 7) | q) * kCopies + lane_off);
-    }
+    for (int i = 0; i < 4; ++i) count_sample(hist, (bw >> (8 * i)) & 0xFFu, (qw >> (8 * i)) & 0xFFu, lane_off);
 }
 
 // 16 samples of one lane.  The common case (every sample of the wave covered) skips the per-sample test.
@@ -210,8 +295,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_kernel(
     // (overlap mode): its few instructions go first so the memory pipeline never waits on the VALU.
     __builtin_amdgcn_s_setprio(3);
 
-    for (int i = tid * 4; i < kLdsWords; i += kHistThreads * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds(hist, kLdsWords, tid);
     __syncthreads();
 
     const int64_t n_work = n_sites * split;
@@ -231,15 +315,10 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_kernel(
             const u32x4 *bv = reinterpret_cast<const u32x4 *>(brow);
             const u32x4 *qv = reinterpret_cast<const u32x4 *>(qrow);
             for (int64_t cb = (int64_t)part * kBlockChunks; cb < n16; cb += (int64_t)split * kBlockChunks) {
-                const int64_t c = cb + tid;
                 if (cb + kBlockChunks <= n16) {
                     // kUnroll independent 16-byte loads per array in flight, then the LDS updates
                     u32x4 b[kUnroll], q[kUnroll];
-#pragma unroll
-                    for (int u = 0; u < kUnroll; ++u) {
-                        b[u] = __builtin_nontemporal_load(&bv[c + (int64_t)u * kHistThreads]);
-                        q[u] = __builtin_nontemporal_load(&qv[c + (int64_t)u * kHistThreads]);
-                    }
+                    load_block(bv, qv, cb + tid, b, q);
 #pragma unroll
                     for (int u = 0; u < kUnroll; ++u) count_chunk(hist, b[u], q[u], lane_off);
                 } else {
@@ -249,34 +328,15 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_kernel(
         } else {
             for (int64_t cb = (int64_t)part * kBlockChunks; cb < n16; cb += (int64_t)split * kBlockChunks) {
                 const int64_t i1 = (cb + kBlockChunks < n16 ? cb + kBlockChunks : n16) * 16;
-                for (int64_t i = cb * 16 + tid; i < i1; i += kHistThreads) {
-                    const uint32_t b = (uint8_t)brow[i], q = (uint8_t)qrow[i];
-                    if (b < 4u && q < 128u)
-                        hist_add(hist, ((b << 7) | q) * kCopies + lane_off);
-                }
+                count_bytes(hist, brow, qrow, cb * 16, i1, tid, lane_off);
             }
         }
-        if (part == split - 1) {
-            for (int64_t i = (n16 << 4) + tid; i < n_samples; i += kHistThreads) {
-                const uint32_t b = (uint8_t)brow[i], q = (uint8_t)qrow[i];
-                if (b < 4u && q < 128u)
-                    hist_add(hist, ((b << 7) | q) * kCopies + lane_off);
-            }
-        }
+        if (part == split - 1) count_bytes(hist, brow, qrow, n16 << 4, n_samples, tid, lane_off);
         __syncthreads();
 
         // fold the copies of each class, publish, and clear for the next site
         for (int key = tid; key < BVC_NCLASS; key += kHistThreads) {
-            uint32_t s = 0;
-#pragma unroll
-            for (int v = 0; v < kCopies; v += 4) {
-                // rotate the starting copy by the key so that the 16 lanes of a ds_read_b128 group spread over banks
-                const int cc = (v + 4 * (key & 7)) & (kCopies - 1);
-                u32x4 *p = reinterpret_cast<u32x4 *>(&hist[key * kCopies + cc]);
-                const u32x4 x = *p;
-                s += x.x + x.y + x.z + x.w;
-                *p = u32x4{0u, 0u, 0u, 0u};
-            }
+            const uint32_t s = fold_class<kCopies>(hist, key);
             if (split == 1) counts[site * BVC_NCLASS + key] = s;
             else if (s) atomicAdd(&counts[site * BVC_NCLASS + key], s);
         }
@@ -398,8 +458,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_groups_kernel(
     const int words = (n_hist * BVC_NCLASS) << LOG2C;
     const uint32_t lane_off = (uint32_t)tid & ((1u << LOG2C) - 1u);
     const uint32_t lane_base = lds_address(hist) + (lane_off << 2);
-    for (int i = tid * 4; i < words; i += kHistThreads * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds(hist, words, tid);
     __syncthreads();
 
     auto add_checked = [&](uint32_t b, uint32_t q, uint32_t h) {
@@ -519,13 +578,6 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_ranges_kernel(
     }
     if (n_real == 0) return;
 
-    auto scalar = [&](const int8_t *brow, const int8_t *qrow, int64_t i0, int64_t i1) {
-        for (int64_t i = i0 + tid; i < i1; i += kHistThreads) {
-            const uint32_t b = (uint8_t)brow[i], q = (uint8_t)qrow[i];
-            if (b < 4u && q < 128u)
-                hist_add(hist, ((b << 7) | q) * kCopies + lane_off);
-        }
-    };
     // A work item is one (site, histogram) = one column range of one row.  The loads of the NEXT item's first block are
     // issued before the barrier that ends the current one, so the workgroup has bytes in flight while it folds its
     // copies: with k = 5 a range is a fifth of a row and the fold comes five times as often as in hist_dense_kernel.
@@ -584,28 +636,17 @@ __global__ __launch_bounds__(kHistThreads) void hist_dense_ranges_kernel(
                 for (int u = 0; u < kUnroll; ++u) count_chunk(hist, b[u], q[u], lane_off);
             }
             if (cb < r.c1) count_partial_block(hist, bv, qv, cb, r.c1, tid, lane_off);
-            scalar(brow, qrow, r.s0, r.c0 << 4);
-            scalar(brow, qrow, r.c1 << 4, r.s1);
+            count_bytes(hist, brow, qrow, r.s0, r.c0 << 4, tid, lane_off);
+            count_bytes(hist, brow, qrow, r.c1 << 4, r.s1, tid, lane_off);
         } else {
-            scalar(brow, qrow, r.s0, r.s1);
+            count_bytes(hist, brow, qrow, r.s0, r.s1, tid, lane_off);
         }
         const int64_t wn = w + gridDim.x;
         const int64_t out = r.out;
         have = false;
         if (wn < n_work) { r = range_of(wn); prefetch(r); }
         lds_barrier();
-        for (int key = tid; key < BVC_NCLASS; key += kHistThreads) {
-            uint32_t sum = 0;
-#pragma unroll
-            for (int v = 0; v < kCopies; v += 4) {
-                const int cc = (v + 4 * (key & 7)) & (kCopies - 1);
-                u32x4 *p = reinterpret_cast<u32x4 *>(&hist[key * kCopies + cc]);
-                const u32x4 x = *p;
-                sum += x.x + x.y + x.z + x.w;
-                *p = u32x4{0u, 0u, 0u, 0u};
-            }
-            grp_counts[out + key] = sum;
-        }
+        for (int key = tid; key < BVC_NCLASS; key += kHistThreads) grp_counts[out + key] = fold_class<kCopies>(hist, key);
         lds_barrier();
         w = wn;
     }
@@ -740,7 +781,7 @@ __global__ __launch_bounds__(kHistThreads) BVC_WAVES_PER_EU(6, 8) void hist_csr_
     // one observation given as the two-byte kernels see it (PACKED: the byte decoded first)
     auto one = [&](uint32_t b, uint32_t q) {
         if (PACKED) { q = b & 63u; b = q == 63u ? 0xFFu : b >> 6; }
-        if (b < 4u && q < 128u) hist_add(hist, ((b << 7) | q) * kCopies + lane_off);
+        count_sample(hist, b, q, lane_off);
     };
     auto scalar = [&](int64_t i0, int64_t i1) {
         for (int64_t i = i0 + tid; i < i1; i += kHistThreads) one((uint8_t)bases[i], PACKED ? 0u : (uint32_t)(uint8_t)quals[i]);
@@ -748,26 +789,14 @@ __global__ __launch_bounds__(kHistThreads) BVC_WAVES_PER_EU(6, 8) void hist_csr_
     constexpr int64_t kBlockChunks = (int64_t)kUnroll * kHistThreads;
     const u32x4 *bv = reinterpret_cast<const u32x4 *>(bases);
     const u32x4 *qv = reinterpret_cast<const u32x4 *>(quals);
-    const u32x4 kSkip = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};   // "no observation" in either form
     // chunks [cb, cb + kBlockChunks) of a site's whole chunks [0, nc) (32-bit indices relative to the site's first chunk):
     // whole blocks load without a test
     auto fetch = [&](const u32x4 *sb, const u32x4 *sq, uint32_t cb, uint32_t nc, u32x4 (&b)[kUnroll], u32x4 (&q)[kUnroll]) {
+        const uint32_t c = cb + (uint32_t)tid;
         if (cb + (uint32_t)kBlockChunks <= nc) {
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                b[u] = __builtin_nontemporal_load(&sb[cb + (uint32_t)tid + (uint32_t)u * kHistThreads]);
-                if (!PACKED) q[u] = __builtin_nontemporal_load(&sq[cb + (uint32_t)tid + (uint32_t)u * kHistThreads]);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kUnroll; ++u) {
-                const uint32_t c = cb + (uint32_t)tid + (uint32_t)u * kHistThreads;
-                b[u] = kSkip; q[u] = u32x4{0u, 0u, 0u, 0u};
-                if (c < nc) {
-                    b[u] = __builtin_nontemporal_load(&sb[c]);
-                    if (!PACKED) q[u] = __builtin_nontemporal_load(&sq[c]);
-                }
-            }
+            if (PACKED) load_block(sb, c, b); else load_block(sb, sq, c, b, q);
+        } else {                                                   // 0xFF is "no observation" in either form
+            if (PACKED) load_partial_block(sb, c, nc, b); else load_partial_block(sb, sq, c, nc, b, q);
         }
     };
     auto count = [&](uint32_t cb, uint32_t nc, const u32x4 (&b)[kUnroll], const u32x4 (&q)[kUnroll]) {
@@ -821,18 +850,7 @@ __global__ __launch_bounds__(kHistThreads) BVC_WAVES_PER_EU(6, 8) void hist_csr_
                 scalar(s0, s1);
             }
             __syncthreads();
-            for (int key = tid; key < BVC_NCLASS; key += kHistThreads) {
-                uint32_t sum = 0;
-#pragma unroll
-                for (int v = 0; v < kCopies; v += 4) {
-                    const int cc = (v + 4 * (key & 7)) & (kCopies - 1);      // rotated: the lanes of a ds_read_b128 group spread over banks
-                    u32x4 *p = reinterpret_cast<u32x4 *>(&hist[key * kCopies + cc]);
-                    const u32x4 x = *p;
-                    sum += x.x + x.y + x.z + x.w;
-                    *p = u32x4{0u, 0u, 0u, 0u};
-                }
-                counts[site * BVC_NCLASS + key] = sum;
-            }
+            for (int key = tid; key < BVC_NCLASS; key += kHistThreads) counts[site * BVC_NCLASS + key] = fold_class<kCopies>(hist, key);
             __syncthreads();
         }
         site = next; s0 = n0; s1 = n1;
@@ -875,6 +893,29 @@ __device__ __forceinline__ void count_packed_word(uint32_t &a0, uint32_t &a1, ui
     put_slot<3>(a3, w); lds_add_one(a3);
 }
 
+// the 16 samples of one lane's chunk
+__device__ __forceinline__ void count_packed_chunk(uint32_t &a0, uint32_t &a1, uint32_t &a2, uint32_t &a3, const u32x4 v)
+{
+    count_packed_word(a0, a1, a2, a3, v.x); count_packed_word(a0, a1, a2, a3, v.y);
+    count_packed_word(a0, a1, a2, a3, v.z); count_packed_word(a0, a1, a2, a3, v.w);
+}
+
+// Samples [i0, i1) of a packed row one by one (unaligned rows, heads and tails): the byte is the slot.
+__device__ __forceinline__ void count_packed_bytes(const uint8_t *row, int64_t i0, int64_t i1, int tid, uint32_t lane_base)
+{
+    for (int64_t i = i0 + tid; i < i1; i += kHistThreads) lds_add_one(((uint32_t)row[i] << 8) + lane_base);
+}
+
+// Sum and clear the copies of class `key` of a packed histogram: the result is in the [base][128 quals] form of the
+// two-byte path (qualities 64..127 have no slot; qual bits 63 are "no observation", counted and thrown away here).
+__device__ __forceinline__ uint32_t fold_packed_class(uint32_t *hist, int key)
+{
+    const int q = key & 127;
+    if (q >= 64) return 0;
+    const uint32_t sum = fold_class<kPackedCopies>(hist, ((key >> 7) << 6) | q);
+    return q == 63 ? 0u : sum;
+}
+
 template <bool ALIGNED>
 __global__ __launch_bounds__(kHistThreads) void hist_packed_kernel(
     int64_t n_sites, int64_t n_samples, int64_t row_stride, const uint8_t *__restrict__ packed,
@@ -887,8 +928,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_packed_kernel(
     // the one-instruction address needs bits 8..15 of the array's address to be zero (they are: see above)
     const bool at_zero = (lds_address(hist) & 0xFFFFu) == 0u;
     __builtin_amdgcn_s_setprio(3);                // as in hist_dense_kernel; priorities 0 and 1 measure 12 % and 1 % slower under the EM (profiles/r02_packed_sweep.txt)
-    for (int i = tid * 4; i < kPackedLdsWords; i += kHistThreads * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds(hist, kPackedLdsWords, tid);
     __syncthreads();
 
     uint32_t a0 = lane_base, a1 = lane_base, a2 = lane_base, a3 = lane_base;
@@ -904,20 +944,13 @@ __global__ __launch_bounds__(kHistThreads) void hist_packed_kernel(
             for (int64_t cb = (int64_t)part * kBlockChunks; cb < n16; cb += (int64_t)split * kBlockChunks) {
                 u32x4 v[kPackedUnroll];
                 if (cb + kBlockChunks <= n16) {                  // a whole block: plain loads
-#pragma unroll
-                    for (int u = 0; u < kPackedUnroll; ++u) v[u] = __builtin_nontemporal_load(&rv[cb + tid + (int64_t)u * kHistThreads]);
+                    load_block(rv, cb + tid, v);
                 } else {                                         // the last, partial block: lanes past the end count "no observation"
-#pragma unroll
-                    for (int u = 0; u < kPackedUnroll; ++u) {
-                        const int64_t c = cb + tid + (int64_t)u * kHistThreads;
-                        v[u] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-                        if (c < n16) v[u] = __builtin_nontemporal_load(&rv[c]);
-                    }
+                    load_partial_block(rv, cb + tid, n16, v);
                 }
 #pragma unroll
                 for (int u = 0; u < kPackedUnroll; ++u) {
-                    count_packed_word(a0, a1, a2, a3, v[u].x); count_packed_word(a0, a1, a2, a3, v[u].y);
-                    count_packed_word(a0, a1, a2, a3, v[u].z); count_packed_word(a0, a1, a2, a3, v[u].w);
+                    count_packed_chunk(a0, a1, a2, a3, v[u]);
                 }
             }
         }
@@ -927,20 +960,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_packed_kernel(
         __syncthreads();
         // fold the copies, publish in the [base][128 quals] form of the two-byte path, clear for the next site
         for (int key = tid; key < BVC_NCLASS; key += kHistThreads) {
-            const int q = key & 127;
-            uint32_t sum = 0;
-            if (q < 64) {
-                const int slot = ((key >> 7) << 6) | q;
-#pragma unroll
-                for (int c = 0; c < kPackedCopies; c += 4) {
-                    const int cc = (c + 4 * (slot & 7)) & (kPackedCopies - 1);
-                    u32x4 *p = reinterpret_cast<u32x4 *>(&hist[slot * kPackedCopies + cc]);
-                    const u32x4 x = *p;
-                    sum += x.x + x.y + x.z + x.w;
-                    *p = u32x4{0u, 0u, 0u, 0u};
-                }
-                if (q == 63) sum = 0;                            // qual bits 63: no observation
-            }
+            const uint32_t sum = fold_packed_class(hist, key);
             if (split == 1) counts[site * BVC_NCLASS + key] = sum;
             else if (sum) atomicAdd(&counts[site * BVC_NCLASS + key], sum);
         }
@@ -993,54 +1013,31 @@ __global__ __launch_bounds__(kHistThreads) void hist_packed_ranges_kernel(
         const int h = real_h[w % n_real];
         const uint8_t *row = packed + site * row_stride;
         const int64_t s0 = scratch[1 + h], s1 = scratch[2 + h];
-        auto scalar = [&](int64_t i0, int64_t i1) {
-            for (int64_t i = i0 + tid; i < i1; i += kHistThreads) lds_add_one(((uint32_t)row[i] << 8) + lane_base);
-        };
         const int64_t c0 = (s0 + 15) >> 4, c1 = s1 >> 4;          // [s0, s1) = head, whole 16-sample chunks [c0, c1), tail
         if (ALIGNED && at_zero && c0 < c1) {
-            scalar(s0, c0 << 4);
+            count_packed_bytes(row, s0, c0 << 4, tid, lane_base);
             const u32x4 *rv = reinterpret_cast<const u32x4 *>(row);
             constexpr int64_t kBlockChunks = (int64_t)kPackedUnroll * kHistThreads;
             for (int64_t cb = c0; cb < c1; cb += kBlockChunks) {
                 u32x4 v[kPackedUnroll];
                 if (cb + kBlockChunks <= c1) {
-#pragma unroll
-                    for (int u = 0; u < kPackedUnroll; ++u) v[u] = __builtin_nontemporal_load(&rv[cb + tid + (int64_t)u * kHistThreads]);
+                    load_block(rv, cb + tid, v);
                 } else {
-#pragma unroll
-                    for (int u = 0; u < kPackedUnroll; ++u) {
-                        const int64_t c = cb + tid + (int64_t)u * kHistThreads;
-                        v[u] = u32x4{0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
-                        if (c < c1) v[u] = __builtin_nontemporal_load(&rv[c]);
-                    }
+                    load_partial_block(rv, cb + tid, c1, v);
                 }
 #pragma unroll
                 for (int u = 0; u < kPackedUnroll; ++u) {
-                    count_packed_word(a0, a1, a2, a3, v[u].x); count_packed_word(a0, a1, a2, a3, v[u].y);
-                    count_packed_word(a0, a1, a2, a3, v[u].z); count_packed_word(a0, a1, a2, a3, v[u].w);
+                    count_packed_chunk(a0, a1, a2, a3, v[u]);
                 }
             }
-            scalar(c1 << 4, s1);
+            count_packed_bytes(row, c1 << 4, s1, tid, lane_base);
         } else {
-            scalar(s0, s1);
+            count_packed_bytes(row, s0, s1, tid, lane_base);
         }
         __syncthreads();
         const int64_t out = (site * n_hist + h) * BVC_NCLASS;
         for (int key = tid; key < BVC_NCLASS; key += kHistThreads) {
-            const int q = key & 127;
-            uint32_t sum = 0;
-            if (q < 64) {
-                const int slot = ((key >> 7) << 6) | q;
-#pragma unroll
-                for (int c = 0; c < kPackedCopies; c += 4) {
-                    const int cc = (c + 4 * (slot & 7)) & (kPackedCopies - 1);
-                    u32x4 *p = reinterpret_cast<u32x4 *>(&hist[slot * kPackedCopies + cc]);
-                    const u32x4 x = *p;
-                    sum += x.x + x.y + x.z + x.w;
-                    *p = u32x4{0u, 0u, 0u, 0u};
-                }
-                if (q == 63) sum = 0;
-            }
+            const uint32_t sum = fold_packed_class(hist, key);
             grp_counts[out + key] = sum;
         }
         __syncthreads();
@@ -1138,8 +1135,7 @@ __global__ __launch_bounds__(kH16Threads) void hist_packed_groups_h16_kernel(
     const uint32_t copy4 = lds_address(hist) + (((uint32_t)tid & 31u) << 2);
     uint32_t one = 1u;
     asm volatile("" : "+v"(one));                                 // a VGPR for the SDWA shifts
-    for (int i = tid * 4; i < words; i += THREADS * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds<THREADS>(hist, words, tid);
     __syncthreads();
     const int64_t n16 = n_samples >> 4;
     const u32x4 *gv = reinterpret_cast<const u32x4 *>(hist_of_sample);
@@ -1200,8 +1196,7 @@ __global__ __launch_bounds__(THREADS) void hist_packed_groups_kernel(
     const int words = (n_hist * kPackedSlots) << LOG2C;
     const uint32_t lane_off = (uint32_t)tid & ((1u << LOG2C) - 1u);
     const uint32_t lane_base = lds_address(hist) + (lane_off << 2);
-    for (int i = tid * 4; i < words; i += THREADS * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds<THREADS>(hist, words, tid);
     __syncthreads();
     constexpr uint32_t SH = 2 + LOG2C;
     // round 5: each sample's 16-bit (label, byte) key by ONE v_perm_b32 ([0 0 g p], the zero bytes from selector 0x0C) and its counter
@@ -1286,8 +1281,7 @@ __global__ __launch_bounds__(1024) void hist_dense_groups_slots_kernel(
     const uint32_t redo_at = lds_address(hist) + ((uint32_t)words << 2);
     const uint32_t lane_off = (uint32_t)tid & ((1u << LOG2C) - 1u);
     const uint32_t lane_base = lds_address(hist) + (lane_off << 2);
-    for (int i = tid * 4; i < words; i += THREADS * 4)
-        *reinterpret_cast<u32x4 *>(&hist[i]) = u32x4{0u, 0u, 0u, 0u};
+    clear_lds<THREADS>(hist, words, tid);
     if (tid == 0) lds_store(redo_at, 0u);
     __syncthreads();
     constexpr uint32_t SH = 2 + LOG2C;
@@ -1448,27 +1442,97 @@ int choose_hist_split(const LaunchState &st, int64_t n_sites, int64_t n_samples)
     return (int)split;
 }
 
-// Kernels with more than 48 KiB of dynamic LDS need the attribute raised once per device; the context remembers
-// which of its kernels have been done (no process-wide state).
-enum KernelSlot : uint32_t {
-    kSlotDense0 = 0, kSlotDense1, kSlotRanges0, kSlotRanges1, kSlotCsr0, kSlotCsr1, kSlotGroupByte,
-    kSlotGroup = 8,            // + log2c (0..5)
-    kSlotGroupPipe = 16,       // + log2c (0..5)
-    kSlotPacked0 = 24, kSlotPacked1 = 25, kSlotPackedRanges0 = 26, kSlotPackedRanges1 = 27,
-    kSlotPackedGroups = 32,    // + 6 * aligned + log2c (0..5)
-    kSlotCsrPacked0 = 44, kSlotCsrPacked1 = 45,
-    kSlotPackedGroupsBig = 46,  // + (4 - log2 copies): 46..48
-    kSlotGroupSlots = 49,       // + (4 - log2 copies): 49..51
-    kSlotPackedGroupsH16 = 52, kSlotGroupSlotsH16 = 53,
-};
-constexpr size_t kBigLdsBytes = 144 * 1024;      // a workgroup may take the CU's whole LDS (160 KiB); stage 2 keeps 16 KiB beside it
-
-static hipError_t raise_lds(LaunchState &st, uint32_t slot, const void *kernel, size_t bytes)
+// Kernels with more than 48 KiB of dynamic LDS need the attribute raised once per device; the context remembers, by
+// address, which kernels it has done (no process-wide state, and no hipFuncSetAttribute on the steady-state path).
+hipError_t raise_lds(const LaunchState &st, const void *kernel, size_t bytes)
 {
-    if (st.attr_done & ((uint64_t)1 << slot)) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e == hipSuccess) st.attr_done |= (uint64_t)1 << slot;
+    for (LaunchState::RaisedLds &done : st.lds_raised)
+        if (done.kernel == kernel) {
+            if (done.bytes >= bytes) return hipSuccess;
+            // (every caller raises a kernel to one constant today; a larger request is not skipped)
+            const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e == hipSuccess) done.bytes = bytes;
+            return e;
+        }
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) st.lds_raised.push_back({kernel, bytes});
     return e;
+}
+
+constexpr size_t kLdsBytes = (size_t)kLdsWords * sizeof(uint32_t);   // 64 KiB: the dense and the packed histogram alike
+static_assert(kPackedLdsWords == kLdsWords, "kLdsBytes serves the packed kernels too");
+constexpr size_t kBigLdsBytes = 144 * 1024;      // a workgroup may take the CU's whole LDS (160 KiB); stage 2 keeps 16 KiB beside it
+// 33 histograms (32 groups + "no group") of one copy each are 66 KiB: what the any-order two-byte kernels' attribute is raised to
+constexpr size_t kGroupLdsMax = (size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t);
+
+static unsigned grid_cap(int64_t n, int64_t cap = 4096) { return (unsigned)(n < cap ? n : cap); }
+
+// Raise the kernel's LDS attribute to attr_bytes if this context has not done so yet (0: the kernel needs none), launch, report.
+template <class... P, class... A>
+static hipError_t launch(const LaunchState &st, hipStream_t stream, void (*kernel)(P...), unsigned grid, int block, size_t lds,
+                         size_t attr_bytes, A... args)
+{
+    if (attr_bytes) {
+        const hipError_t e = raise_lds(st, reinterpret_cast<const void *>(kernel), attr_bytes);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, stream, static_cast<P>(args)...);
+    return hipGetLastError();
+}
+
+// The instance for `log2c` (0..5) copies of the any-order group kernels
+using Log2cs = std::make_integer_sequence<int, 6>;
+template <bool PIPE, int... L>
+static auto dense_groups_instance(int log2c, std::integer_sequence<int, L...>)
+{
+    static constexpr decltype(&hist_dense_groups_kernel<0, PIPE>) table[] = {hist_dense_groups_kernel<L, PIPE>...};
+    return table[log2c];
+}
+template <bool ALIGNED, int... L>
+static auto packed_groups_instance(int log2c, std::integer_sequence<int, L...>)
+{
+    static constexpr decltype(&hist_packed_groups_kernel<0, ALIGNED>) table[] = {hist_packed_groups_kernel<L, ALIGNED>...};
+    return table[log2c];
+}
+
+// How the any-order kernels of a group call lay out their LDS: [histogram][slot][copy] with 1 << log2c copies, as many as
+// fit 64 KiB (st.group_log2c caps them), `lds` bytes; and the one-workgroup-per-CU form of 256 slots x 16 / 8 / 4 copies
+// (1 << big; up to 9 / 18 / 36 histograms) + big_tail bytes = big_lds, big = -1 when st.group_big_lds is off or not even
+// four copies fit.
+struct GroupPlan { int log2c, big; size_t lds, big_lds; };
+
+static GroupPlan plan_group_copies(const LaunchState &st, int n_hist, int slots, size_t big_tail)
+{
+    GroupPlan g;
+    g.log2c = 0;
+    while (g.log2c < 5 && (size_t)n_hist * slots * (2u << g.log2c) <= (size_t)kLdsWords) ++g.log2c;
+    if (st.group_log2c >= 0 && st.group_log2c < g.log2c) g.log2c = st.group_log2c;
+    g.lds = ((size_t)n_hist * slots << g.log2c) * sizeof(uint32_t);
+    auto big_bytes = [&](int l) { return ((size_t)n_hist * kPackedSlots << l) * sizeof(uint32_t) + big_tail; };
+    g.big = 4;
+    while (g.big > 2 && big_bytes(g.big) > kBigLdsBytes) --g.big;
+    g.big_lds = big_bytes(g.big);
+    if (!st.group_big_lds || g.big_lds > kBigLdsBytes) g.big = -1;
+    return g;
+}
+
+// What the two-byte and the packed group launcher share.  Decided on the device, without a host round trip: the bounds
+// kernel marks whether the samples are ordered by group (and writes the clamped labels); the range kernel
+// (launch_ranges) and the any-order kernel the caller launches next both run, and the one whose turn it is not returns
+// at once.
+template <class Ranges>
+static hipError_t group_prelude(const LaunchState &st, hipStream_t stream, const uint8_t *group_of_sample, int64_t n_samples,
+                                int n_groups, int64_t *group_scratch, uint8_t *hist_of_sample, int slots, size_t big_tail,
+                                Ranges launch_ranges, GroupPlan *plan)
+{
+    if (!group_scratch || !hist_of_sample) return hipErrorInvalidValue;
+    hipError_t e = hipMemsetAsync(group_scratch, 0, (size_t)kGroupScratchWords * sizeof(int64_t), stream);
+    if (e != hipSuccess) return e;
+    e = launch(st, stream, group_bounds_kernel, grid_cap((n_samples + 255) / 256, 1024), 256, 0, 0, group_of_sample, n_samples,
+               n_groups, group_scratch, hist_of_sample);
+    if (e != hipSuccess) return e;
+    *plan = plan_group_copies(st, n_groups + 1, slots, big_tail);
+    return launch_ranges();
 }
 
 hipError_t launch_hist_dense(LaunchState &st, hipStream_t stream, int64_t n_sites, int64_t n_samples, int64_t row_stride,
@@ -1478,90 +1542,43 @@ hipError_t launch_hist_dense(LaunchState &st, hipStream_t stream, int64_t n_site
     if (n_sites <= 0) return hipSuccess;
     const bool aligned = ((reinterpret_cast<uintptr_t>(bases) | reinterpret_cast<uintptr_t>(quals)) & 15u) == 0 &&
                          (row_stride & 15) == 0;
-    const size_t lds = (size_t)kLdsWords * sizeof(uint32_t);
     if (group_of_sample) {                       // counts = [site][n_groups + 1][512]
         const int n_hist = n_groups + 1;
         if (n_samples <= 0)                      // no columns at all: every histogram is empty
             return hipMemsetAsync(counts, 0, (size_t)n_sites * n_hist * BVC_NCLASS * sizeof(uint32_t), stream);
-        if (!group_scratch || !hist_of_sample) return hipErrorInvalidValue;
-        // Decided on the device, without a host round trip: the bounds kernel marks whether the samples are ordered by
-        // group (and writes the clamped labels); the range kernel and the any-order kernel are both launched and the
-        // one whose turn it is not returns at once.
-        auto rk = aligned ? hist_dense_ranges_kernel<true> : hist_dense_ranges_kernel<false>;
-        hipError_t e = raise_lds(st, aligned ? kSlotRanges1 : kSlotRanges0, reinterpret_cast<const void *>(rk), lds);
+        GroupPlan g;
+        hipError_t e = group_prelude(st, stream, group_of_sample, n_samples, n_groups, group_scratch, hist_of_sample, BVC_NCLASS, 16, [&] {
+            return launch(st, stream, aligned ? hist_dense_ranges_kernel<true> : hist_dense_ranges_kernel<false>,
+                          grid_cap(n_sites * n_hist), kHistThreads, kLdsBytes, kLdsBytes, n_sites, n_samples, row_stride, bases, quals,
+                          n_hist, group_scratch, counts);
+        }, &g);
         if (e != hipSuccess) return e;
-        e = hipMemsetAsync(group_scratch, 0, (size_t)kGroupScratchWords * sizeof(int64_t), stream);
-        if (e != hipSuccess) return e;
-        const int64_t bgrid = (n_samples + 255) / 256;
-        hipLaunchKernelGGL(group_bounds_kernel, dim3((unsigned)(bgrid < 1024 ? bgrid : 1024)), dim3(256), 0, stream,
-                           group_of_sample, n_samples, n_groups, group_scratch, hist_of_sample);
-        const int64_t n_work = n_sites * n_hist;
-        hipLaunchKernelGGL(rk, dim3((unsigned)(n_work < 4096 ? n_work : 4096)), dim3(kHistThreads), lds, stream,
-                           n_sites, n_samples, row_stride, bases, quals, n_hist, group_scratch, counts);
-        int log2c = 0;
-        while (log2c < 5 && (size_t)n_hist * BVC_NCLASS * (2u << log2c) <= (size_t)kLdsWords) ++log2c;
-        if (st.group_log2c >= 0 && st.group_log2c < log2c) log2c = st.group_log2c;
-        const size_t glds = ((size_t)n_hist * BVC_NCLASS << log2c) * sizeof(uint32_t);
-        // 33 histograms (32 groups + "no group") of one copy each are 66 KiB: the attribute is raised to that once
-        constexpr size_t kGroupLdsMax = (size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t);
-        const int64_t ggrid = n_sites < 4096 ? n_sites : 4096;
-        if (aligned) {                           // hist_of_sample is the context's own 256-byte aligned buffer
-            using FastKernel = void (*)(int64_t, int64_t, int64_t, const int8_t *, const int8_t *, const uint8_t *, int,
-                                        uint32_t *, const int64_t *, const uint8_t *);
-            static const FastKernel fast[2][6] = {
-                {hist_dense_groups_kernel<0, false>, hist_dense_groups_kernel<1, false>, hist_dense_groups_kernel<2, false>,
-                 hist_dense_groups_kernel<3, false>, hist_dense_groups_kernel<4, false>, hist_dense_groups_kernel<5, false>},
-                {hist_dense_groups_kernel<0, true>, hist_dense_groups_kernel<1, true>, hist_dense_groups_kernel<2, true>,
-                 hist_dense_groups_kernel<3, true>, hist_dense_groups_kernel<4, true>, hist_dense_groups_kernel<5, true>}};
-            const int pipe = st.group_pipe ? 1 : 0;
-            const FastKernel fk = fast[pipe][log2c];
-            e = raise_lds(st, (pipe ? kSlotGroupPipe : kSlotGroup) + log2c, reinterpret_cast<const void *>(fk), kGroupLdsMax);
+        if (!aligned)
+            return launch(st, stream, hist_dense_groups_bytes_kernel, grid_cap(n_sites), kHistThreads, g.lds, kGroupLdsMax, n_sites,
+                          n_samples, row_stride, bases, quals, group_of_sample, n_groups, g.log2c, counts, group_scratch);
+        // hist_of_sample is the context's own 256-byte aligned buffer.
+        // 4..8 groups: packed in registers and counted in 256 slots x 16 / 8 / 4 copies first (+ 16 bytes: the site's flag);
+        // the general kernel then takes the sites that kernel flags (a covered sample of quality 63 or more), all sites otherwise
+        const uint8_t *only = nullptr;
+        if (g.big >= 0 && g.log2c < 3) {
+            uint8_t *redo = hist_of_sample + group_redo_offset(n_samples);
+            e = launch(st, stream, g.big == 4 ? hist_dense_groups_slots_kernel<4> : (g.big == 3 ? hist_dense_groups_slots_kernel<3> : hist_dense_groups_slots_kernel<2>),
+                       grid_cap(n_sites), 1024, g.big_lds, kBigLdsBytes, n_sites, n_samples, row_stride, bases, quals, hist_of_sample,
+                       n_groups, counts, group_scratch, redo);
             if (e != hipSuccess) return e;
-            // 4..8 groups: packed in registers and counted in 256 slots x 16 copies first; the general kernel then takes the
-            // sites that kernel flags (a covered sample of quality 63 or more), all sites otherwise
-            const uint8_t *only = nullptr;
-            // 256 slots x 16 / 8 / 4 copies per histogram in one workgroup's LDS: up to 9 / 18 / 36 histograms
-            int sl = 4;
-            while (sl > 2 && ((size_t)n_hist * kPackedSlots << sl) * sizeof(uint32_t) + 16 > kBigLdsBytes) --sl;
-            const size_t slds = ((size_t)n_hist * kPackedSlots << sl) * sizeof(uint32_t) + 16;
-            if (st.group_big_lds && log2c < 3 && slds <= kBigLdsBytes) {
-                using SK = void (*)(int64_t, int64_t, int64_t, const int8_t *, const int8_t *, const uint8_t *, int, uint32_t *,
-                                    const int64_t *, uint8_t *);
-                const SK sk = sl == 4 ? hist_dense_groups_slots_kernel<4> : (sl == 3 ? hist_dense_groups_slots_kernel<3> : hist_dense_groups_slots_kernel<2>);
-                e = raise_lds(st, kSlotGroupSlots + (4 - sl), reinterpret_cast<const void *>(sk), kBigLdsBytes);
-                if (e != hipSuccess) return e;
-                uint8_t *redo = hist_of_sample + group_redo_offset(n_samples);
-                hipLaunchKernelGGL(sk, dim3((unsigned)ggrid), dim3(1024), slds, stream, n_sites, n_samples,
-                                   row_stride, bases, quals, hist_of_sample, n_groups, counts, group_scratch, redo);
-                only = redo;
-            }
-            hipLaunchKernelGGL(fk, dim3((unsigned)ggrid), dim3(kHistThreads), glds, stream, n_sites, n_samples, row_stride,
-                               bases, quals, hist_of_sample, n_groups, counts, group_scratch, only);
-        } else {
-            e = raise_lds(st, kSlotGroupByte, reinterpret_cast<const void *>(hist_dense_groups_bytes_kernel), kGroupLdsMax);
-            if (e != hipSuccess) return e;
-            hipLaunchKernelGGL(hist_dense_groups_bytes_kernel, dim3((unsigned)ggrid), dim3(kHistThreads), glds, stream,
-                               n_sites, n_samples, row_stride, bases, quals, group_of_sample, n_groups, log2c, counts,
-                               group_scratch);
+            only = redo;
         }
-        return hipGetLastError();
+        return launch(st, stream, st.group_pipe ? dense_groups_instance<true>(g.log2c, Log2cs{}) : dense_groups_instance<false>(g.log2c, Log2cs{}),
+                      grid_cap(n_sites), kHistThreads, g.lds, kGroupLdsMax, n_sites, n_samples, row_stride, bases, quals, hist_of_sample,
+                      n_groups, counts, group_scratch, only);
     }
-    if (split == 1 && n_samples <= kWaveRowMax && n_sites >= (int64_t)st.n_cu * 2 * kCsrWaves) {
+    if (split == 1 && n_samples <= kWaveRowMax && n_sites >= (int64_t)st.n_cu * 2 * kCsrWaves)
         // short rows, many sites: one wavefront per site (a 64 KiB fold per 10 KB row is what the block kernel would pay)
-        auto wk = aligned ? hist_wave_kernel<true, true> : hist_wave_kernel<false, true>;
-        const int64_t wgrid = (n_sites + kCsrWaves - 1) / kCsrWaves;
-        hipLaunchKernelGGL(wk, dim3((unsigned)(wgrid < 8192 ? wgrid : 8192)), dim3(kHistThreads), 0, stream, n_sites,
-                           (const int64_t *)nullptr, n_samples, row_stride, bases, quals, counts);
-        return hipGetLastError();
-    }
-    auto kern = aligned ? hist_dense_kernel<true> : hist_dense_kernel<false>;
-    hipError_t e = raise_lds(st, aligned ? kSlotDense1 : kSlotDense0, reinterpret_cast<const void *>(kern), lds);
-    if (e != hipSuccess) return e;
-    const int64_t n_work = n_sites * split;
-    const int64_t grid = n_work < 4096 ? n_work : 4096;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kHistThreads), lds, stream, n_sites, n_samples,
-                       row_stride, bases, quals, counts, split);
-    return hipGetLastError();
+        return launch(st, stream, aligned ? hist_wave_kernel<true, true> : hist_wave_kernel<false, true>,
+                      grid_cap((n_sites + kCsrWaves - 1) / kCsrWaves, 8192), kHistThreads, 0, 0, n_sites, nullptr, n_samples, row_stride,
+                      bases, quals, counts);
+    return launch(st, stream, aligned ? hist_dense_kernel<true> : hist_dense_kernel<false>, grid_cap(n_sites * split), kHistThreads,
+                  kLdsBytes, kLdsBytes, n_sites, n_samples, row_stride, bases, quals, counts, split);
 }
 
 hipError_t launch_hist_packed(LaunchState &st, hipStream_t stream, int64_t n_sites, int64_t n_samples, int64_t row_stride,
@@ -1569,14 +1586,8 @@ hipError_t launch_hist_packed(LaunchState &st, hipStream_t stream, int64_t n_sit
 {
     if (n_sites <= 0) return hipSuccess;
     const bool aligned = (reinterpret_cast<uintptr_t>(packed) & 15u) == 0 && (row_stride & 15) == 0;
-    auto kern = aligned ? hist_packed_kernel<true> : hist_packed_kernel<false>;
-    const size_t lds = (size_t)kPackedLdsWords * sizeof(uint32_t);
-    hipError_t e = raise_lds(st, aligned ? kSlotPacked1 : kSlotPacked0, reinterpret_cast<const void *>(kern), lds);
-    if (e != hipSuccess) return e;
-    const int64_t n_work = n_sites * split;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(n_work < 4096 ? n_work : 4096)), dim3(kHistThreads), lds, stream, n_sites,
-                       n_samples, row_stride, packed, counts, split);
-    return hipGetLastError();
+    return launch(st, stream, aligned ? hist_packed_kernel<true> : hist_packed_kernel<false>, grid_cap(n_sites * split), kHistThreads,
+                  kLdsBytes, kLdsBytes, n_sites, n_samples, row_stride, packed, counts, split);
 }
 
 hipError_t launch_hist_packed_groups(LaunchState &st, hipStream_t stream, int64_t n_sites, int64_t n_samples,
@@ -1587,63 +1598,32 @@ hipError_t launch_hist_packed_groups(LaunchState &st, hipStream_t stream, int64_
     const int n_hist = n_groups + 1;
     if (n_samples <= 0)
         return hipMemsetAsync(counts, 0, (size_t)n_sites * n_hist * BVC_NCLASS * sizeof(uint32_t), stream);
-    if (!group_scratch || !hist_of_sample) return hipErrorInvalidValue;
     const bool aligned = (reinterpret_cast<uintptr_t>(packed) & 15u) == 0 && (row_stride & 15) == 0;
-    // as launch_hist_dense in group mode: the bounds kernel decides on the device which of the two kernels has the call
-    hipError_t e = hipMemsetAsync(group_scratch, 0, (size_t)kGroupScratchWords * sizeof(int64_t), stream);
+    GroupPlan g;
+    hipError_t e = group_prelude(st, stream, group_of_sample, n_samples, n_groups, group_scratch, hist_of_sample, kPackedSlots, 0, [&] {
+        // + 256 bytes: the table of non-empty ranges behind the histogram
+        return launch(st, stream, aligned ? hist_packed_ranges_kernel<true> : hist_packed_ranges_kernel<false>, grid_cap(n_sites * n_hist),
+                      kHistThreads, kLdsBytes + 256, kLdsBytes + 256, n_sites, row_stride, packed, n_hist, group_scratch, counts);
+    }, &g);
     if (e != hipSuccess) return e;
-    const int64_t bgrid = (n_samples + 255) / 256;
-    hipLaunchKernelGGL(group_bounds_kernel, dim3((unsigned)(bgrid < 1024 ? bgrid : 1024)), dim3(256), 0, stream,
-                       group_of_sample, n_samples, n_groups, group_scratch, hist_of_sample);
-    auto rk = aligned ? hist_packed_ranges_kernel<true> : hist_packed_ranges_kernel<false>;
-    const size_t lds = (size_t)kPackedLdsWords * sizeof(uint32_t);
-    e = raise_lds(st, aligned ? kSlotPackedRanges1 : kSlotPackedRanges0, reinterpret_cast<const void *>(rk), lds + 256);
-    if (e != hipSuccess) return e;
-    const int64_t n_work = n_sites * n_hist;
-    hipLaunchKernelGGL(rk, dim3((unsigned)(n_work < 4096 ? n_work : 4096)), dim3(kHistThreads), lds + 256, stream, n_sites,
-                       row_stride, packed, n_hist, group_scratch, counts);
-    int log2c = 0;
-    while (log2c < 5 && (size_t)n_hist * kPackedSlots * (2u << log2c) <= (size_t)kLdsWords) ++log2c;
-    if (st.group_log2c >= 0 && st.group_log2c < log2c) log2c = st.group_log2c;
-    const size_t glds = ((size_t)n_hist * kPackedSlots << log2c) * sizeof(uint32_t);
-    using GK = void (*)(int64_t, int64_t, int64_t, const uint8_t *, const uint8_t *, int, uint32_t *, const int64_t *);
-    static const GK gk[2][6] = {
-        {hist_packed_groups_kernel<0, false>, hist_packed_groups_kernel<1, false>, hist_packed_groups_kernel<2, false>,
-         hist_packed_groups_kernel<3, false>, hist_packed_groups_kernel<4, false>, hist_packed_groups_kernel<5, false>},
-        {hist_packed_groups_kernel<0, true>, hist_packed_groups_kernel<1, true>, hist_packed_groups_kernel<2, true>,
-         hist_packed_groups_kernel<3, true>, hist_packed_groups_kernel<4, true>, hist_packed_groups_kernel<5, true>}};
+    // round 5: two 16-bit counters per word, 32 conflict-free copies (same LDS as 16 copies of words); st.group_h16 picks it
+    const size_t hlds = (size_t)n_hist * 128 * 32 * sizeof(uint32_t);
+    if (st.group_h16 && st.group_big_lds && aligned && g.log2c < 4 && hlds <= kBigLdsBytes && n_samples <= kH16MaxSamples)
+        return launch(st, stream, hist_packed_groups_h16_kernel, grid_cap(n_sites), kH16Threads, hlds, kBigLdsBytes, n_sites, n_samples,
+                      row_stride, packed, hist_of_sample, n_groups, counts, group_scratch);
     // One workgroup of 1024 threads with 16 copies per histogram (bank = copy + 16 * (slot & 1): exactly two lanes of a
     // 32-lane group on a bank) when that fits the CU's LDS and the 64 KiB form would have fewer copies: 4 <= k <= 8 groups.
     // Alone it is 3 % slower than three 512-thread workgroups with 8 copies (0.78 against 0.76 ms at k = 5, N = 1e6, 4000
     // sites), underneath stage 2 -- the way the calls run -- 5 % faster (0.90 against 0.95) and stage 2 itself a fifth
     // (profiles/r03_group_anyorder_experiments.txt).  The same form of the two-byte kernel (8 copies, 96 KiB) LOSES 15 %
     // underneath stage 2 and is not kept.
-    // round 5: two 16-bit counters per word, 32 conflict-free copies (same LDS as 16 copies of words); st.group_h16 picks it
-    const size_t hlds = (size_t)n_hist * 128 * 32 * sizeof(uint32_t);
-    if (st.group_h16 && st.group_big_lds && aligned && log2c < 4 && hlds <= kBigLdsBytes && n_samples <= kH16MaxSamples) {
-        e = raise_lds(st, kSlotPackedGroupsH16, reinterpret_cast<const void *>(hist_packed_groups_h16_kernel), kBigLdsBytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(hist_packed_groups_h16_kernel, dim3((unsigned)(n_sites < 4096 ? n_sites : 4096)), dim3(kH16Threads), hlds, stream,
-                           n_sites, n_samples, row_stride, packed, hist_of_sample, n_groups, counts, group_scratch);
-        return hipGetLastError();
-    }
-    int bl = 4;                                                  // 16 / 8 / 4 copies in one workgroup's LDS: up to 9 / 18 / 36 histograms
-    while (bl > 2 && ((size_t)n_hist * kPackedSlots << bl) * sizeof(uint32_t) > kBigLdsBytes) --bl;
-    if (st.group_big_lds && aligned && log2c < bl && ((size_t)n_hist * kPackedSlots << bl) * sizeof(uint32_t) <= kBigLdsBytes) {
-        const GK bk = bl == 4 ? hist_packed_groups_kernel<4, true, 1024> : (bl == 3 ? hist_packed_groups_kernel<3, true, 1024> : hist_packed_groups_kernel<2, true, 1024>);
-        const size_t blds = ((size_t)n_hist * kPackedSlots << bl) * sizeof(uint32_t);
-        e = raise_lds(st, kSlotPackedGroupsBig + (4 - bl), reinterpret_cast<const void *>(bk), kBigLdsBytes);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(bk, dim3((unsigned)(n_sites < 4096 ? n_sites : 4096)), dim3(1024), blds, stream, n_sites,
-                           n_samples, row_stride, packed, hist_of_sample, n_groups, counts, group_scratch);
-        return hipGetLastError();
-    }
-    const GK k = gk[aligned ? 1 : 0][log2c];
-    e = raise_lds(st, kSlotPackedGroups + (aligned ? 6 : 0) + log2c, reinterpret_cast<const void *>(k), (size_t)kLdsWords * sizeof(uint32_t));
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3((unsigned)(n_sites < 4096 ? n_sites : 4096)), dim3(kHistThreads), glds, stream, n_sites,
-                       n_samples, row_stride, packed, hist_of_sample, n_groups, counts, group_scratch);
-    return hipGetLastError();
+    if (g.big >= 0 && aligned && g.log2c < g.big)
+        return launch(st, stream, g.big == 4 ? hist_packed_groups_kernel<4, true, 1024> : (g.big == 3 ? hist_packed_groups_kernel<3, true, 1024> : hist_packed_groups_kernel<2, true, 1024>),
+                      grid_cap(n_sites), 1024, g.big_lds, kBigLdsBytes, n_sites, n_samples, row_stride, packed, hist_of_sample, n_groups,
+                      counts, group_scratch);
+    return launch(st, stream, aligned ? packed_groups_instance<true>(g.log2c, Log2cs{}) : packed_groups_instance<false>(g.log2c, Log2cs{}),
+                  grid_cap(n_sites), kHistThreads, g.lds, kLdsBytes, n_sites, n_samples, row_stride, packed, hist_of_sample, n_groups, counts,
+                  group_scratch);
 }
 
 hipError_t launch_pack_dense(hipStream_t stream, int64_t n_sites, int64_t n_samples, int64_t stride_in, const int8_t *bases,
@@ -1662,20 +1642,17 @@ hipError_t launch_hist_csr(LaunchState &st, hipStream_t stream, int64_t n_sites,
     const bool packed = quals == nullptr;                        // one byte per observation in `bases`
     // both arrays are indexed by the same element offsets, so one alignment test covers every site
     const bool aligned = ((reinterpret_cast<uintptr_t>(bases) | reinterpret_cast<uintptr_t>(quals)) & 15u) == 0;
-    const size_t lds = (size_t)kLdsWords * sizeof(uint32_t);
-    auto bk = packed ? (aligned ? hist_csr_block_kernel<true, true> : hist_csr_block_kernel<false, true>)
-                     : (aligned ? hist_csr_block_kernel<true> : hist_csr_block_kernel<false>);
-    hipError_t e = raise_lds(st, (aligned ? kSlotCsr1 : kSlotCsr0) + (packed ? kSlotCsrPacked0 - kSlotCsr0 : 0),
-                             reinterpret_cast<const void *>(bk), lds);
-    if (e != hipSuccess) return e;
-    const int64_t wgrid = (n_sites + kCsrWaves - 1) / kCsrWaves;
     auto wk = packed ? (aligned ? hist_wave_kernel<true, false, true> : hist_wave_kernel<false, false, true>)
                      : (aligned ? hist_wave_kernel<true, false> : hist_wave_kernel<false, false>);
-    hipLaunchKernelGGL(wk, dim3((unsigned)(wgrid < 8192 ? wgrid : 8192)), dim3(kHistThreads), 0, stream,
-                       n_sites, offsets, (int64_t)0, (int64_t)0, bases, quals, counts);
-    hipLaunchKernelGGL(bk, dim3((unsigned)(n_sites < 4096 ? n_sites : 4096)), dim3(kHistThreads), lds, stream, n_sites,
-                       offsets, bases, quals, counts);
-    return hipGetLastError();
+    auto bk = packed ? (aligned ? hist_csr_block_kernel<true, true> : hist_csr_block_kernel<false, true>)
+                     : (aligned ? hist_csr_block_kernel<true> : hist_csr_block_kernel<false>);
+    // the block kernel's attribute first: a failure leaves nothing of the call enqueued
+    hipError_t e = raise_lds(st, reinterpret_cast<const void *>(bk), kLdsBytes);
+    if (e != hipSuccess) return e;
+    e = launch(st, stream, wk, grid_cap((n_sites + kCsrWaves - 1) / kCsrWaves, 8192), kHistThreads, 0, 0, n_sites, offsets, 0, 0,
+               bases, quals, counts);
+    if (e != hipSuccess) return e;
+    return launch(st, stream, bk, grid_cap(n_sites), kHistThreads, kLdsBytes, kLdsBytes, n_sites, offsets, bases, quals, counts);
 }
 
 }  // namespace bvc

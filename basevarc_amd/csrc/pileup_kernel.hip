@@ -806,12 +806,10 @@ hipError_t launch_hist_csr_groups(LaunchState &st, hipStream_t stream, int64_t n
     int log2c = 0;                                               // copies: as many as fit 64 KiB
     while (log2c < 5 && ((size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << (log2c + 1)) <= 64 * 1024) ++log2c;
     const size_t lds = (size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << log2c;
-    constexpr uint32_t kSlotCsrGroups = 61;
-    if (lds > 48 * 1024 && !(st.attr_done & ((uint64_t)1 << kSlotCsrGroups))) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(hist_csr_groups_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                           (int)((size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t)));
+    if (lds > 48 * 1024) {
+        const hipError_t e = raise_lds(st, reinterpret_cast<const void *>(hist_csr_groups_kernel),
+                                       (size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t));
         if (e != hipSuccess) return e;
-        st.attr_done |= (uint64_t)1 << kSlotCsrGroups;
     }
     hipLaunchKernelGGL(hist_csr_groups_kernel, dim3((unsigned)(n_sites < 8192 ? n_sites : 8192)), dim3(kCsrGroupThreads), lds, stream, n_sites,
                        offsets, bases, quals, sample_of_obs, group_of_sample, n_samples, n_groups, log2c, counts);
