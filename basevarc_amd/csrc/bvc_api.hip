@@ -173,21 +173,7 @@ int ensure(bvc_ctx *ctx, DevBuf &buf, size_t need)
     return BVC_OK;
 }
 
-inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
-
-// Slices of a device buffer, each starting on a 256-byte boundary: take<T>(count, pad) hands out count elements + pad bytes.
-struct Layout {
-    uintptr_t base = 0;
-    size_t at = 0;
-    template <class T> T *take(size_t count, size_t pad = 0)
-    {
-        T *p = reinterpret_cast<T *>(base + at);
-        at += round256(count * sizeof(T) + pad);
-        return p;
-    }
-};
-
-// Grows `buf` to the slices of `list` (a function of a Layout &) + `slack` bytes and carves it: the one list of take() calls runs
+// Grows `buf` to the slices of `list` (a function of a Layout &, bvc_internal.h) + `slack` bytes and carves it: the one list of take() calls runs
 // once to size the buffer and once to hand out the pointers, so the two cannot disagree.
 template <class List>
 int carve(bvc_ctx *ctx, DevBuf &buf, size_t slack, List list)
@@ -263,7 +249,7 @@ hipStream_t em_stream(bvc_ctx *ctx, int by_default)
 int em_scratch_for(bvc_ctx *ctx, int slot, int64_t n_sites, double min_af, void **out, int n_groups = 0)
 {
     *out = nullptr;
-    if (ctx->ls.em_engine == 1 || !(min_af > 0.0)) return BVC_OK;
+    if (!uses_item_engine(ctx->ls, min_af)) return BVC_OK;
     const size_t need = n_groups > 0 ? em_group_scratch_bytes(n_sites, n_groups) : em_items_scratch_bytes(n_sites);
     DevBuf &buf = n_groups > 0 ? ctx->d_emg[slot] : ctx->d_em[slot];
     if (need > buf.cap) {

@@ -41,6 +41,23 @@ struct LaunchState {
     mutable std::vector<RaisedLds> lds_raised;     // kernels whose dynamic-LDS attribute has been raised on this context's device, and to what
 };
 
+inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
+
+// Slices of a device buffer, each starting on a 256-byte boundary: take<T>(count, pad) hands out count elements + pad bytes.
+// A list of take() calls written once as a function of a Layout & both sizes a buffer (base 0: `at` ends as the byte count)
+// and hands out its pointers, so the two cannot disagree (bvc_api.hip carve(); the stage-2 scratch of em_kernel.hip and
+// em_items.hip).
+struct Layout {
+    uintptr_t base = 0;
+    size_t at = 0;
+    template <class T> T *take(size_t count, size_t pad = 0)
+    {
+        T *p = reinterpret_cast<T *>(base + at);
+        at += round256(count * sizeof(T) + pad);
+        return p;
+    }
+};
+
 // Kernels with more than 48 KiB of dynamic LDS need hipFuncAttributeMaxDynamicSharedMemorySize raised before their first
 // launch: done once per kernel and context (hist_kernel.hip).
 hipError_t raise_lds(const LaunchState &st, const void *kernel, size_t bytes);
@@ -95,6 +112,10 @@ hipError_t launch_hist_csr(LaunchState &st, hipStream_t stream, int64_t n_sites,
 //   shared: the launch runs underneath a streaming histogram kernel (overlap mode) and keeps to a few wave slots.
 //   scratch: em_items_scratch_bytes(n_sites) of device memory for the item engine (em_items.hip), or null: every
 //            site then takes the one-wavefront-per-site kernels.
+// Does a stage 2 with this min_af go through the item engine (when it is given scratch)?  em_engine = 1 is the A/B switch;
+// min_af <= 0 lets zero-depth alleles through the filter and UpdateF skip subsets (src/BaseType.cpp:54), which is left to
+// the one-wavefront-per-site kernels.  The scratch is allocated, and the engine launched, by this one rule.
+inline bool uses_item_engine(const LaunchState &st, double min_af) { return st.em_engine != 1 && min_af > 0.0; }
 hipError_t launch_lrt(const LaunchState &st, hipStream_t stream, int64_t n_sites, const uint32_t *counts,
                       int64_t hist_stride, const int8_t *ref_base, double min_af, const QualLut *lut,
                       const int8_t *comb, const uint8_t *n_comb, bvc_site_result *results, bool shared = false,

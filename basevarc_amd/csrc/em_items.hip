@@ -23,7 +23,7 @@
 //     (src/BaseType.cpp:93-110, k = 2 and 1) run 16 items per wavefront;
 //   * the stop rule needs no per-class work: m' - m = (f' - f) d for every class of an allele, hence
 //        sum_c n_c |m'_c / m_c - 1| = sum_b |f'_b - f_b| * D_b(previous pass)          (d > 0: quality >= 2)
-//     and delta = sum_c n_c |log m'_c - log m_c| < 1e-3 is decided from that bracket exactly as in em_kernel.hip
+//     and delta = sum_c n_c |log m'_c - log m_c| < 1e-3 is decided from that bracket (em_common.h), as in em_kernel.hip
 //     (delta itself is evaluated only when the bracket straddles 1e-3);
 //   * 16 independent classes per lane hide the FP64 latency that one dependency chain per wavefront exposes;
 //   * a = 1 - 3e, so the class marginal f a + (1 - f) e is f + (1 - 4 f) e: one FMA on e alone, and with
@@ -42,6 +42,7 @@
 
 #include "bvc_device.h"
 #include "bvc_internal.h"
+#include "em_common.h"
 
 namespace bvc {
 namespace {
@@ -49,10 +50,8 @@ namespace {
 // -DBVC_CHECK_LDS (bvc_device.h): every LDS index the region kernels derive from LDS contents goes through BVC_LDS_OK, which
 // records a violation for the host (bvc_debug_report) and lets the code take a harmless path.  Check ids 11..16.
 
-constexpr double kLrtThreshold = 24.0;    // LRT_THRESHOLD, src/BaseType.h:9
-constexpr int kEmIters = 100;             // src/BaseType.cpp:46
-constexpr double kEmEpsilon = 0.001;      // src/BaseType.cpp:45
-constexpr double kVarQualPending = -1.0;  // as in em_kernel.hip: var_qual_kernel finishes these records
+// The reference's constants, the stop rule's bracket, subset_masks and the call / var_qual rule: em_common.h, shared with
+// em_kernel.hip.
 
 // Quality classes of one allele the engine holds: CPB = 32 (two lanes x 16, three waves per SIMD) for the regions whose
 // sites all fit; CPB = 48 (two lanes x 24, two waves per SIMD) for the regions with a wider site -- Illumina's unbinned 41
@@ -63,9 +62,6 @@ constexpr int kTiny = 8, kNarrow = 32, kWide = 48;
 template <int CPB> constexpr int site_table_bytes() { return 4 * CPB * 5; }
 
 constexpr int kEmptyQ = 128;               // quality index of an empty class place: QualLut::e_empty = 1/4
-constexpr uint32_t hi_word(double x) { return (uint32_t)(__builtin_bit_cast(uint64_t, x) >> 32); }
-constexpr uint32_t kSureBelowHi = hi_word(kEmEpsilon / (1.0 + 0.00390625));        // hi(A) <  this: converged
-constexpr uint32_t kSureAboveHi = hi_word(kEmEpsilon / (1.0 - 0.00390625)) + 1u;   // hi(A) >= this: not converged
 
 // One fit: the alleles of a subset in candidate order ("units"), their starting frequencies, and what the alleles
 // outside the subset add to E (a constant of the fit).  64 bytes.
@@ -126,30 +122,6 @@ constexpr int kRegionSites = BVC_REGION_SITES;
 // (n-1)-subsets that keep the deepest candidate); the lists of a round lie one behind the other
 constexpr int kPlaces = 4 * kRegionSites;
 
-// k-subsets of positions 0..n-1 in lexicographic order (what combs_ yields), as 4-bit position masks packed
-// least-significant first; count returned through `cnt`.
-__device__ __forceinline__ uint32_t subset_masks(int n, int k, int &cnt)
-{
-    switch (n * 8 + k) {
-    case 1 * 8 + 1: cnt = 1; return 0x1u;
-    case 2 * 8 + 2: cnt = 1; return 0x3u;
-    case 2 * 8 + 1: cnt = 2; return 0x21u;
-    case 3 * 8 + 3: cnt = 1; return 0x7u;
-    case 3 * 8 + 2: cnt = 3; return 0x653u;
-    case 3 * 8 + 1: cnt = 3; return 0x421u;
-    case 4 * 8 + 4: cnt = 1; return 0xFu;
-    case 4 * 8 + 3: cnt = 4; return 0xEDB7u;
-    case 4 * 8 + 2: cnt = 6; return 0xCA6953u;
-    case 4 * 8 + 1: cnt = 4; return 0x8421u;
-    default: cnt = 0; return 0u;
-    }
-}
-
-__device__ __forceinline__ int pick4i(const int32_t (&v)[4], int j)
-{
-    return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
-}
-
 // Log-likelihood of the model "allele b alone" (f_b = 1): every observation's marginal is its own likelihood of b, a for the
 // observations of b and e for the others -- no EM needed (site_decide).
 __device__ __forceinline__ double single_allele_loglik(const double (&lla)[4], const double (&lle)[4], int b)
@@ -192,7 +164,7 @@ __device__ __forceinline__ int deepest_position(const int32_t (&depth)[4], uint3
     int best = 0, best_depth = -1;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
-        const int dp = pick4i(depth, (int)((blist >> (4 * p)) & 3u));
+        const int dp = pick4(depth, (int)((blist >> (4 * p)) & 3u));
         if (p < n && dp > best_depth) { best_depth = dp; best = p; }
     }
     return best;
@@ -279,7 +251,7 @@ __device__ __forceinline__ void region_emit(RegionT &R, int lane, const int (&fi
             const int b = (blist >> (4 * p)) & 3u;
             bases = (bases & ~(0xFFu << (8 * u))) | ((uint32_t)b << (8 * u));
             in_set |= 1u << b;
-            depth_sum += pick4i(depth, b);
+            depth_sum += pick4(depth, b);
             ++u;
         }
     double ll_excl = 0.0;
@@ -292,7 +264,7 @@ __device__ __forceinline__ void region_emit(RegionT &R, int lane, const int (&fi
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                                // SetAlleleFreq (:25-39)
         const int b = (bases >> (8 * q)) & 0xFFu;
-        fi.f0[q] = q < u ? (double)pick4i(depth, b & 3) / (double)depth_sum : 0.0;
+        fi.f0[q] = q < u ? (double)pick4(depth, b & 3) / (double)depth_sum : 0.0;
     }
 }
 
@@ -309,7 +281,7 @@ __device__ __forceinline__ void store_record(bvc_site_result *dst, const ItemSit
     for (int p = 0; p < 4; ++p) {                                // src/BaseType.cpp:111-116
         const int b = (blist >> (4 * p)) & 3;
         if (p < n && b != ref && n_alt < 3) {
-            const double fr = b == 0 ? S.base_frq[0] : (b == 1 ? S.base_frq[1] : (b == 2 ? S.base_frq[2] : S.base_frq[3]));
+            const double fr = pick4(S.base_frq, b);
             if (n_alt == 0) { a0 = b; g0 = fr; } else if (n_alt == 1) { a1 = b; g1 = fr; } else { a2 = b; g2 = fr; }
             ++n_alt;
         }
@@ -325,10 +297,7 @@ __device__ __forceinline__ void store_record(bvc_site_result *dst, const ItemSit
     r.n_passes = S.passes; r.n_alt = (uint8_t)n_alt; r.called = 0;
     r.n_kept = (uint8_t)n; r.status = 0; r.n_fits = (uint8_t)S.fits;
     if (n_alt > 0) {                                             // src/BaseType.cpp:117-135
-        const double rr = (double)pick4i(S.depth, (int)(blist & 3u)) / depth_total;
-        if (n == 1 && depth_total > 10 && rr > 0.5) r.var_qual = 5000.0;
-        else if (S.chi <= 0) r.var_qual = 0.0;
-        else r.var_qual = kVarQualPending;                       // chisf(chi, 1): finished by var_qual_kernel
+        r.var_qual = call_var_qual(n, pick4(S.depth, (int)(blist & 3u)), depth_total, S.chi);
         r.called = 1;
     }
     *dst = r;
@@ -418,7 +387,7 @@ __device__ __forceinline__ int site_classes(Region<CPB> &R, int ls, int lane, in
         uint32_t seen = 0;
         for (int c = 0; c < nc; ++c) {                           // src/BaseType.cpp:77-83
             const int b = (list >> (4 * c)) & 3;
-            if ((double)pick4i(S.depth, b) / depth_total >= min_af) {
+            if ((double)pick4(S.depth, b) / depth_total >= min_af) {
                 dup |= ((seen >> b) & 1u) != 0;
                 seen |= 1u << b;
                 blist |= (uint32_t)b << (4 * n);
@@ -972,7 +941,7 @@ __device__ __forceinline__ void team_sync(RegionT &R, uint32_t &phase, int lane)
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <bool WALK, int CPB, int TEAM>
+template <int CPB, int TEAM>
 __device__ __forceinline__ void region_body(Region<CPB> *regions, const RegionArgs &A)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -990,12 +959,12 @@ __device__ __forceinline__ void region_body(Region<CPB> *regions, const RegionAr
         if (member == 0 && lane == 0) R.arrive = 0u;
         __syncthreads();                                         // the only workgroup barrier: once, before any team barrier
     }
-    // team t of workgroup b takes region region0 + b * teams + t.  WALK = false: exactly that one -- the launcher sizes the
-    // grid, or cuts the call into a sequence of launches when stage 2 may hold only a few wavefronts per CU -- and without a
-    // loop nothing is kept live across regions, which is what lets the narrow kernel hold three wavefronts per SIMD (168
-    // VGPRs; the walking form needs 257).  WALK = true (experiments only): + gridDim.x * teams, ... to the end.
-    int64_t region = A.region0 + (int64_t)blockIdx.x * teams + wave / TEAM;
-    for (bool first = true; region < n_regions && (WALK || first); first = false, region += (int64_t)gridDim.x * teams) {
+    // team t of workgroup b takes region region0 + b * teams + t and exactly that one -- the launcher sizes the grid, or cuts
+    // the call into a sequence of launches when stage 2 may hold only a few wavefronts per CU: nothing is kept live across
+    // regions, which is what lets the narrow kernel hold three wavefronts per SIMD (168 VGPRs; a form that walked on to region
+    // + gridDim.x * teams, ... needed 257).  (A loop of one trip: the `continue` and `break` below leave the region.)
+    const int64_t region = A.region0 + (int64_t)blockIdx.x * teams + wave / TEAM;
+    for (bool first = true; region < n_regions && first; first = false) {
         const int64_t site0 = region * kRegionSites;
         if (member == 0 && lane == 0) { R.need = 0; R.next_slot = 0; }
         if (TEAM > 1) team_sync<TEAM>(R, phase, lane);
@@ -1107,7 +1076,7 @@ __global__ __launch_bounds__(64 * kMaxRegionWaves) BVC_OCCUPANCY(CPB == kWide ? 
 {
     BVC_POISON_LDS();
     extern __shared__ __attribute__((aligned(16))) unsigned char region_lds[];
-    region_body<false, CPB, kTeam>(reinterpret_cast<Region<CPB> *>(region_lds), A);
+    region_body<CPB, kTeam>(reinterpret_cast<Region<CPB> *>(region_lds), A);
 }
 
 }  // namespace
@@ -1116,9 +1085,29 @@ __global__ __launch_bounds__(64 * kMaxRegionWaves) BVC_OCCUPANCY(CPB == kWide ? 
 BVC_DEFINE_DEBUG_READER(debug_read_items)
 #endif
 
+// The engine's device scratch: the `taken` flags and, on the 256-byte boundary behind them, the two kind_epoch words
+// (RegionArgs); everything else lives in LDS.  The one list sizes the buffer and hands out the pointers.  The size is a bound
+// that holds wherever the boundary falls (n_sites + 256) plus 64 bytes for the words, not a multiple of 256.
+struct ItemScratch {
+    uint8_t *taken;
+    uint32_t *kind_epoch;
+};
+
+static ItemScratch item_scratch(Layout &L, int64_t n_sites)
+{
+    const size_t start = L.at;
+    ItemScratch s;
+    s.taken = L.take<uint8_t>((size_t)n_sites);
+    s.kind_epoch = L.take<uint32_t>(0);
+    L.at = start + (size_t)n_sites + 256 + 64;
+    return s;
+}
+
 size_t em_items_scratch_bytes(int64_t n_sites)
 {
-    return (size_t)n_sites + 256 + 64;                            // the `taken` flags and the "wide regions seen" word; everything else lives in LDS
+    Layout size;
+    item_scratch(size, n_sites);
+    return size.at;
 }
 
 // Stage 2 with the item engine.  `scratch` holds em_items_scratch_bytes(n_sites).  Sites it does not take are left
@@ -1128,7 +1117,9 @@ hipError_t launch_lrt_items(const LaunchState &st, hipStream_t stream, int64_t n
                             const QualLut *lut, const int8_t *comb, const uint8_t *n_comb, bvc_site_result *results,
                             void *scratch, const uint8_t **taken_out, bool shared)
 {
-    uint8_t *taken = static_cast<uint8_t *>(scratch);
+    Layout slices{reinterpret_cast<uintptr_t>(scratch)};
+    const ItemScratch scr = item_scratch(slices, n_sites);
+    uint8_t *taken = scr.taken;
     const int64_t regions = (n_sites + kRegionSites - 1) / kRegionSites;
     // A team of wavefronts is a region's whole engine, so the shape of the launch is free:
     //  * the chip to itself: as many teams per workgroup (<= 4 wavefronts: one per SIMD) as leave every CU a workgroup, one
@@ -1157,7 +1148,7 @@ hipError_t launch_lrt_items(const LaunchState &st, hipStream_t stream, int64_t n
     RegionArgs A;
     A.n_sites = n_sites; A.n_groups = n_groups; A.counts = counts; A.hist_stride = hist_stride; A.lut = lut;
     A.ref_base = ref_base; A.min_af = min_af; A.comb = comb; A.n_comb = n_comb; A.taken = taken; A.results = results;
-    A.kind_epoch = reinterpret_cast<uint32_t *>(taken + (((size_t)n_sites + 255) & ~(size_t)255));
+    A.kind_epoch = scr.kind_epoch;
     A.epoch = ++st.em_epoch;                                     // never 0; a stale word can only cost the wide launch a scan
     if (A.epoch == 0) A.epoch = ++st.em_epoch;
     A.dbg_levels = st.dbg_levels > 0 ? st.dbg_levels : 2 * kRounds;

@@ -19,17 +19,10 @@
 // FP64 throughout; no MFMA (nothing here is a dense contraction).
 #include "bvc_device.h"
 #include "bvc_internal.h"
+#include "em_common.h"
 
 namespace bvc {
 namespace {
-
-constexpr double kLrtThreshold = 24.0;    // LRT_THRESHOLD, src/BaseType.h:9
-constexpr int kEmIters = 100;             // src/BaseType.cpp:46
-// var_qual is >= 0 or NaN; this marks records whose chi-square tail is still to be evaluated.  The libm-style
-// log/exp/log10 of that step live in their own small kernel so that their constants and registers stay out
-// of the EM kernel (hoisted into VGPRs across the site loop they cost it half its occupancy).
-constexpr double kVarQualPending = -1.0;
-constexpr double kEmEpsilon = 0.001;      // src/BaseType.cpp:45
 
 // Register-resident classes of one lane.  NS (slots per lane) is a template parameter: the kernel is
 // instantiated for NS = 2, 4 and 8 and each site is handled by the smallest variant that holds it, so the
@@ -41,35 +34,6 @@ struct Slots {
     double d[NS];    // (1 - eps) - eps / 3 : matching minus non-matching likelihood
     double yp[NS];   // 1 / (class marginal) from the previous pass
 };
-
-// k-subsets of positions 0..n-1 in lexicographic order (what combs_ yields), as 4-bit position masks
-// packed least-significant first; count returned through `cnt`.
-__device__ __forceinline__ uint32_t subset_masks(int n, int k, int &cnt)
-{
-    switch (n * 8 + k) {
-    case 1 * 8 + 1: cnt = 1; return 0x1u;
-    case 2 * 8 + 2: cnt = 1; return 0x3u;
-    case 2 * 8 + 1: cnt = 2; return 0x21u;
-    case 3 * 8 + 3: cnt = 1; return 0x7u;
-    case 3 * 8 + 2: cnt = 3; return 0x653u;
-    case 3 * 8 + 1: cnt = 3; return 0x421u;
-    case 4 * 8 + 4: cnt = 1; return 0xFu;
-    case 4 * 8 + 3: cnt = 4; return 0xEDB7u;
-    case 4 * 8 + 2: cnt = 6; return 0xCA6953u;
-    case 4 * 8 + 1: cnt = 4; return 0x8421u;
-    default: cnt = 0; return 0u;
-    }
-}
-
-__device__ __forceinline__ double pick4(const double (&v)[4], int j)
-{
-    return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
-}
-
-__device__ __forceinline__ int pick4(const int (&v)[4], int j)
-{
-    return j == 0 ? v[0] : (j == 1 ? v[1] : (j == 2 ? v[2] : v[3]));
-}
 
 // Frequencies live per lane: fb = frequency of the lane's own base.  The class marginal is the reference's
 // sum_j f_j * L_ij (src/Algorithm.cpp:74-78) with the three equal terms grouped and the other three
@@ -97,20 +61,9 @@ struct PassOut {
 //   1/m'  : yp / (1 + u) -> yp * (1 - u) refined by two Newton steps; v_rcp_f64 + two Newton steps only when some
 //           |u| > 2^-6 (the first passes of a fit)
 //   delta : sum_c n_c |log1p(u_c)| is used ONLY in the test delta < eps = 1e-3, so it is bracketed instead of
-//           evaluated: with A = sum_c n_c |u_c| (one FMA per class),
-//             A >= eps / (1 - 2^-8): not converged.  Either some |u| >= 2^-9, and that class alone (n_c >= 1) gives
-//                  delta > 1.9e-3; or every |u| < 2^-9, where |log1p(u)| >= |u| (1 - 2^-9), so delta >= eps.
-//             A <  eps / (1 + 2^-8): every n_c |u_c| < eps, so every |u| < 2^-9, |log1p(u)| <= |u| (1 + 2^-9) and
-//                  delta < eps: converged.
-//             in between (a few passes per fit at most): delta itself, log1p as a cubic (truncation 3e-12 relative),
-//                  with a reduction of its own.
-//           A is a sum of non-negative doubles (or NaN), so both comparisons are unsigned compares of its high
-//           word, done on the scalar unit; NaN and +inf compare high: "NaN never converges", as in the reference.
+//           evaluated, from A = sum_c n_c |u_c| (one FMA per class): kSureBelowHi / kSureAboveHi, em_common.h
 // Empty slots have d = 0, e = 1, so m = 1 and u = 0 to an ulp: they add nothing.
 // The NS slots are independent dependency chains with no branch between them, so they interleave.
-constexpr uint32_t hi_word(double x) { return (uint32_t)(__builtin_bit_cast(uint64_t, x) >> 32); }
-constexpr uint32_t kSureBelowHi = hi_word(kEmEpsilon / (1.0 + 0.00390625));        // hi(A) <  this: converged
-constexpr uint32_t kSureAboveHi = hi_word(kEmEpsilon / (1.0 - 0.00390625)) + 1u;   // hi(A) >= this: not converged
 
 // NA <= NS: slots that can hold a class at this site.  A site whose bases have at most 16 * NA quality values leaves
 // slots NA..NS-1 empty in every lane, and an empty slot adds exact zeros to every sum (n = 0) and 0 to max|u|
@@ -416,16 +369,7 @@ __device__ bool lrt_site(const uint32_t *__restrict__ hist, int ref, double min_
     out.af[0] = g0; out.af[1] = g1; out.af[2] = g2;
     out.n_alt = n_alt;
     if (n_alt > 0) {                                             // :117-135
-        const double r = (double)pick4(depth, (int)(blist & 3u)) / depth_total;
-        double vq;
-        if (n == 1 && depth_total > 10 && r > 0.5) {
-            vq = 5000.0;
-        } else if (chi <= 0) {
-            vq = 0.0;
-        } else {
-            vq = kVarQualPending;                                // chisf(chi, 1): finished by var_qual_kernel
-        }
-        out.var_qual = vq;
+        out.var_qual = call_var_qual(n, pick4(depth, (int)(blist & 3u)), depth_total, chi);
         out.called = 1;
     }
     return true;
@@ -440,6 +384,19 @@ __device__ __forceinline__ void store_result(bvc_site_result *dst, const SiteOut
     r.n_passes = o.n_passes; r.n_alt = (uint8_t)o.n_alt; r.called = (uint8_t)o.called;
     r.n_kept = (uint8_t)o.n_kept; r.status = (uint8_t)o.status; r.n_fits = (uint8_t)o.n_fits;
     *dst = r;
+}
+
+// The prelude of the two wave kernels: the workgroup's LDS scratch (512 class counts and their qualities per wave) and the
+// wave's index in the workgroup.
+template <int WPB>
+__device__ __forceinline__ int wave_scratch(uint32_t (*&s_n_all)[512], uint8_t (*&s_q_all)[512])
+{
+    __shared__ uint32_t s_n[WPB][512];
+    __shared__ uint8_t s_q[WPB][512];
+    s_n_all = s_n;
+    s_q_all = s_q;
+    // wave-uniform by construction: tell the compiler, so that the site state stays in scalar registers
+    return WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
 }
 
 // Workgroups of WPB independent wavefronts (4 by default): the dispatcher spreads a workgroup's waves over the
@@ -458,10 +415,9 @@ __global__ __launch_bounds__(64 * WPB) void lrt_kernel(int64_t n_sites, const ui
                                                  bvc_site_result *__restrict__ results)
 {
     BVC_POISON_LDS();
-    __shared__ uint32_t s_n_all[WPB][512];
-    __shared__ uint8_t s_q_all[WPB][512];
-    // wave-uniform by construction: tell the compiler, so that the site state stays in scalar registers
-    const int wave = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t (*s_n_all)[512];
+    uint8_t (*s_q_all)[512];
+    const int wave = wave_scratch<WPB>(s_n_all, s_q_all);
     // A bounded number of waves walks the sites: the launcher sizes the grid so that this FP64-bound kernel
     // holds only a few wave slots per SIMD and the HBM-bound histogram kernel of the next tile, which runs
     // at the same time in overlap mode, keeps its occupancy.
@@ -499,10 +455,9 @@ __global__ __launch_bounds__(64 * WPB) void lrt_groups_kernel(int64_t n_sites, i
                                                         bvc_group_result *__restrict__ grp_results)
 {
     BVC_POISON_LDS();
-    __shared__ uint32_t s_n_all[WPB][512];
-    __shared__ uint8_t s_q_all[WPB][512];
-    // wave-uniform by construction: tell the compiler, so that the site state stays in scalar registers
-    const int wave = WPB == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    uint32_t (*s_n_all)[512];
+    uint8_t (*s_q_all)[512];
+    const int wave = wave_scratch<WPB>(s_n_all, s_q_all);
     uint32_t *s_n = s_n_all[wave];
     uint8_t *s_q = s_q_all[wave];
     const int64_t n_work = n_sites * n_groups;
@@ -523,14 +478,7 @@ __global__ __launch_bounds__(64 * WPB) void lrt_groups_kernel(int64_t n_sites, i
                 d = row_sum(d);
                 const int d0 = __builtin_amdgcn_readlane(d, 0), d1 = __builtin_amdgcn_readlane(d, 16);
                 const int d2 = __builtin_amdgcn_readlane(d, 32), d3 = __builtin_amdgcn_readlane(d, 48);
-                if (lane == 0) {
-                    bvc_group_result r;
-                    for (int j = 0; j < 3; ++j) r.af[j] = 0.0;
-                    r.depth[0] = d0; r.depth[1] = d1; r.depth[2] = d2; r.depth[3] = d3;
-                    r.ran = 0; r.present = 0;
-                    for (int j = 0; j < 6; ++j) r.pad[j] = 0;
-                    grp_results[site * n_groups + g] = r;
-                }
+                if (lane == 0) grp_results[site * n_groups + g] = group_record_depths(d0, d1, d2, d3);
             }
             continue;
         }
@@ -666,27 +614,46 @@ static int64_t em_grid_cap(const LaunchState &st, bool shared, int shared_waves_
     return (int64_t)per_cu * st.n_cu;
 }
 
-template <int WPB>
-static void launch_lrt_variants(hipStream_t stream, int64_t want_waves, int64_t n_sites,
-                                const uint32_t *counts, int64_t hist_stride, const int8_t *ref_base, double min_af,
-                                const QualLut *lut, const int8_t *comb, const uint8_t *n_comb, const uint8_t *taken,
-                                bvc_site_result *results)
+// The two families of wave kernels, so that one launcher serves both.
+struct SiteKernels {
+    template <int NS, int WPB, bool ANY = false> static constexpr auto kernel() { return lrt_kernel<NS, WPB, ANY>; }
+};
+struct GroupKernels {
+    template <int NS, int WPB, bool ANY = false> static constexpr auto kernel() { return lrt_groups_kernel<NS, WPB, ANY>; }
+};
+
+template <class Family, int WPB, class... Args>
+static void launch_variants(hipStream_t stream, int64_t want_waves, const uint8_t *taken, Args... args)
 {
     const dim3 grid((unsigned)((want_waves + WPB - 1) / WPB)), block(64 * WPB);
     if (taken) {
         // behind the item engine: the few sites it left (wide quality spectra, qualities 0 and 1, ...) in ONE launch of
         // the widest variant, which narrows itself to the slots a site fills
-        hipLaunchKernelGGL((lrt_kernel<8, WPB, true>), grid, block, 0, stream, n_sites, counts, hist_stride, ref_base,
-                           min_af, lut, comb, n_comb, taken, results);
+        hipLaunchKernelGGL((Family::template kernel<8, WPB, true>()), grid, block, 0, stream, args...);
         return;
     }
     // Every variant visits every site; a wave skips a site at once when it belongs to another variant.
-    hipLaunchKernelGGL((lrt_kernel<2, WPB>), grid, block, 0, stream, n_sites, counts, hist_stride, ref_base,
-                       min_af, lut, comb, n_comb, taken, results);
-    hipLaunchKernelGGL((lrt_kernel<4, WPB>), grid, block, 0, stream, n_sites, counts, hist_stride, ref_base, min_af,
-                       lut, comb, n_comb, taken, results);
-    hipLaunchKernelGGL((lrt_kernel<8, WPB>), grid, block, 0, stream, n_sites, counts, hist_stride, ref_base, min_af,
-                       lut, comb, n_comb, taken, results);
+    hipLaunchKernelGGL((Family::template kernel<2, WPB>()), grid, block, 0, stream, args...);
+    hipLaunchKernelGGL((Family::template kernel<4, WPB>()), grid, block, 0, stream, args...);
+    hipLaunchKernelGGL((Family::template kernel<8, WPB>()), grid, block, 0, stream, args...);
+}
+
+// The wave kernels of one call over n_work histograms; `args` are the kernels' own (`taken` is among them).
+template <class Family, class... Args>
+static void launch_wave_kernels(const LaunchState &st, hipStream_t stream, int64_t n_work, bool shared, int shared_waves_per_cu,
+                                const uint8_t *taken, Args... args)
+{
+    const int64_t cap = em_grid_cap(st, shared, shared_waves_per_cu);
+    const int64_t want_waves = n_work < cap ? n_work : cap;
+    if (st.em_wpb == 1) launch_variants<Family, 1>(stream, want_waves, taken, args...);
+    else launch_variants<Family, 4>(stream, want_waves, taken, args...);
+}
+
+// One thread per element, 256 to a workgroup: `kernel`(n, args...).
+template <class Kernel, class... Args>
+static void launch_per_element(Kernel kernel, hipStream_t stream, int64_t n, Args... args)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, args...);
 }
 
 hipError_t launch_lrt(const LaunchState &st, hipStream_t stream, int64_t n_sites, const uint32_t *counts,
@@ -695,47 +662,45 @@ hipError_t launch_lrt(const LaunchState &st, hipStream_t stream, int64_t n_sites
                       int shared_waves_per_cu, void *scratch)
 {
     if (n_sites <= 0) return hipSuccess;
-    // The item engine takes the sites it can (em_items.hip); the kernels below take the rest.  min_af <= 0 lets
-    // zero-depth alleles through the filter and UpdateF skip subsets (src/BaseType.cpp:54): left to lrt_site.
+    // The item engine takes the sites it can (em_items.hip; uses_item_engine, bvc_internal.h); the kernels below take the rest.
     const uint8_t *taken = nullptr;
-    if (scratch && st.em_engine != 1 && min_af > 0.0) {
+    if (scratch && uses_item_engine(st, min_af)) {
         const hipError_t e = launch_lrt_items(st, stream, n_sites, 0, counts, hist_stride, ref_base, min_af, lut, comb, n_comb,
                                               results, scratch, &taken, shared);
         if (e != hipSuccess) return e;
     }
-    const int64_t cap = em_grid_cap(st, shared, shared_waves_per_cu);
-    const int64_t want_waves = n_sites < cap ? n_sites : cap;
-    if (st.em_wpb == 1) launch_lrt_variants<1>(stream, want_waves, n_sites, counts, hist_stride, ref_base, min_af, lut, comb, n_comb, taken, results);
-    else launch_lrt_variants<4>(stream, want_waves, n_sites, counts, hist_stride, ref_base, min_af, lut, comb, n_comb, taken, results);
-    hipLaunchKernelGGL(var_qual_kernel, dim3((unsigned)((n_sites + 255) / 256)), dim3(256), 0, stream, n_sites, results);
+    launch_wave_kernels<SiteKernels>(st, stream, n_sites, shared, shared_waves_per_cu, taken, n_sites, counts, hist_stride, ref_base,
+                                     min_af, lut, comb, n_comb, taken, results);
+    launch_per_element(var_qual_kernel, stream, n_sites, results);
     return hipGetLastError();
 }
 
-template <int WPB>
-static void launch_group_variants(hipStream_t stream, int64_t want_waves, int64_t n_sites, int n_groups,
-                                  const uint32_t *grp_counts, const int8_t *ref_base, double min_af,
-                                  const QualLut *lut, const bvc_site_result *overall, const uint8_t *taken,
-                                  bvc_group_result *grp_results)
+// Scratch of a group call that uses the item engine: every (site, group) is a pseudo-site with a candidate list and a
+// site-style record of its own; the engine's own scratch (em_items.hip carves it) comes last.  The one list of take() calls
+// sizes the buffer and hands out the pointers.
+struct GroupScratch {
+    int8_t *comb;
+    uint8_t *n_comb;
+    bvc_site_result *pseudo;
+    void *items;
+};
+
+static GroupScratch group_scratch(Layout &L, int64_t n_pseudo)
 {
-    const dim3 grid((unsigned)((want_waves + WPB - 1) / WPB)), block(64 * WPB);
-    if (taken) {                                                 // behind the item engine: what it left, in one launch
-        hipLaunchKernelGGL((lrt_groups_kernel<8, WPB, true>), grid, block, 0, stream, n_sites, n_groups, grp_counts,
-                           ref_base, min_af, lut, overall, taken, grp_results);
-        return;
-    }
-    hipLaunchKernelGGL((lrt_groups_kernel<2, WPB>), grid, block, 0, stream, n_sites, n_groups, grp_counts, ref_base,
-                       min_af, lut, overall, taken, grp_results);
-    hipLaunchKernelGGL((lrt_groups_kernel<4, WPB>), grid, block, 0, stream, n_sites, n_groups, grp_counts, ref_base,
-                       min_af, lut, overall, taken, grp_results);
-    hipLaunchKernelGGL((lrt_groups_kernel<8, WPB>), grid, block, 0, stream, n_sites, n_groups, grp_counts, ref_base,
-                       min_af, lut, overall, taken, grp_results);
+    GroupScratch s;
+    s.comb = L.take<int8_t>((size_t)n_pseudo * 4);
+    s.n_comb = L.take<uint8_t>((size_t)n_pseudo);
+    s.pseudo = L.take<bvc_site_result>((size_t)n_pseudo);
+    s.items = L.take<char>(0);
+    L.at += em_items_scratch_bytes(n_pseudo);
+    return s;
 }
 
 size_t em_group_scratch_bytes(int64_t n_sites, int n_groups)
 {
-    const size_t n_pseudo = (size_t)n_sites * (size_t)n_groups;
-    return ((n_pseudo * 4 + 255) & ~(size_t)255) + ((n_pseudo + 255) & ~(size_t)255) +
-           ((n_pseudo * sizeof(bvc_site_result) + 255) & ~(size_t)255) + em_items_scratch_bytes((int64_t)n_pseudo);
+    Layout size;
+    group_scratch(size, n_sites * n_groups);
+    return size.at;
 }
 
 hipError_t launch_lrt_groups(const LaunchState &st, hipStream_t stream, int64_t n_sites, int n_groups,
@@ -744,26 +709,20 @@ hipError_t launch_lrt_groups(const LaunchState &st, hipStream_t stream, int64_t 
                              int shared_waves_per_cu, void *scratch)
 {
     if (n_sites <= 0 || n_groups <= 0) return hipSuccess;
-    const int64_t cap = em_grid_cap(st, shared, shared_waves_per_cu);
     const int64_t n_work = n_sites * n_groups;
-    const int64_t want_waves = n_work < cap ? n_work : cap;
     const uint8_t *taken = nullptr;
-    if (scratch && st.em_engine != 1 && min_af > 0.0) {
+    if (scratch && uses_item_engine(st, min_af)) {
         // every (site, group) a pseudo-site of the item engine; its records become group records afterwards
-        char *p = static_cast<char *>(scratch);
-        auto take = [&](size_t bytes) { char *q = p; p += (bytes + 255) & ~(size_t)255; return q; };
-        int8_t *comb = reinterpret_cast<int8_t *>(take((size_t)n_work * 4));
-        uint8_t *n_comb = reinterpret_cast<uint8_t *>(take((size_t)n_work));
-        bvc_site_result *pseudo = reinterpret_cast<bvc_site_result *>(take((size_t)n_work * sizeof(bvc_site_result)));
-        const dim3 tgrid((unsigned)((n_work + 255) / 256)), tblock(256);
-        hipLaunchKernelGGL(group_comb_kernel, tgrid, tblock, 0, stream, n_work, n_groups, ref_base, overall, comb, n_comb);
-        const hipError_t e = launch_lrt_items(st, stream, n_work, n_groups, grp_counts, BVC_NCLASS, ref_base, min_af, lut, comb,
-                                              n_comb, pseudo, p, &taken, shared);
+        Layout slices{reinterpret_cast<uintptr_t>(scratch)};
+        const GroupScratch s = group_scratch(slices, n_work);
+        launch_per_element(group_comb_kernel, stream, n_work, n_groups, ref_base, overall, s.comb, s.n_comb);
+        const hipError_t e = launch_lrt_items(st, stream, n_work, n_groups, grp_counts, BVC_NCLASS, ref_base, min_af, lut, s.comb,
+                                              s.n_comb, s.pseudo, s.items, &taken, shared);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(group_records_kernel, tgrid, tblock, 0, stream, n_work, n_groups, overall, pseudo, taken, grp_results);
+        launch_per_element(group_records_kernel, stream, n_work, n_groups, overall, s.pseudo, taken, grp_results);
     }
-    if (st.em_wpb == 1) launch_group_variants<1>(stream, want_waves, n_sites, n_groups, grp_counts, ref_base, min_af, lut, overall, taken, grp_results);
-    else launch_group_variants<4>(stream, want_waves, n_sites, n_groups, grp_counts, ref_base, min_af, lut, overall, taken, grp_results);
+    launch_wave_kernels<GroupKernels>(st, stream, n_work, shared, shared_waves_per_cu, taken, n_sites, n_groups, grp_counts, ref_base,
+                                      min_af, lut, overall, taken, grp_results);
     return hipGetLastError();
 }
 
@@ -772,8 +731,7 @@ hipError_t launch_sum_groups(hipStream_t stream, int64_t n_sites, int n_hist, co
 {
     const int64_t total = n_sites * BVC_NCLASS;
     if (total <= 0) return hipSuccess;
-    hipLaunchKernelGGL(sum_groups_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, total,
-                       n_hist, grp_counts, counts);
+    launch_per_element(sum_groups_kernel, stream, total, n_hist, grp_counts, counts);
     return hipGetLastError();
 }
 
