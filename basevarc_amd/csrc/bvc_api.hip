@@ -1160,6 +1160,82 @@ int bvc_lrt_csr_groups(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, co
     return BVC_OK;
 }
 
+// ---- ragged group calls with one label byte per observation ------------------------------------------------------------------
+// obs = the bases, or with quals == nullptr the packed bytes (as run_csr_device takes them)
+static int run_csr_labels_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *obs, const uint8_t *quals,
+                                 const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                                 bvc_site_result *results, bvc_group_result *grp_results)
+{
+    return run_group_stages(ctx, n_sites, n_groups, false,
+                            [&](uint32_t *gp) {
+                                return launch_hist_csr_labels(ctx->ls, ctx->stream, n_sites, offsets, obs, quals, group_of_obs, n_groups, gp);
+                            },
+                            ref_base, min_af, results, grp_results);
+}
+
+// bvc_lrt_csr_group_labels (n_arrays = 2: obs = bases, quals) and bvc_lrt_csr_group_labels_packed (1: obs = packed, quals not used)
+static int lrt_csr_labels_impl(bvc_ctx *ctx, int n_arrays, int64_t n_sites, const int64_t *offsets, const uint8_t *obs, const uint8_t *quals,
+                               const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                               bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags)
+{
+    int rc = check_common(ctx, n_sites, offsets, ref_base, results, results);
+    if (rc != BVC_OK) return rc;
+    if (n_groups < 1 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 1..32");
+    if (!grp_results) return fail(ctx, BVC_ERR_ARG, "null group pointer");
+    if (n_sites == 0) return BVC_OK;
+    if (n_arrays == 1) quals = nullptr;
+    const bool have_all = obs && (n_arrays == 1 || quals) && group_of_obs;
+    if (flags & BVC_PTR_DEVICE) {
+        if (!have_all) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+        return run_csr_labels_device(ctx, n_sites, offsets, obs, quals, group_of_obs, ref_base, min_af, n_groups, results, grp_results);
+    }
+    if ((rc = check_offsets_host(ctx, n_sites, offsets)) != BVC_OK) return rc;
+    const int64_t total = offsets[n_sites];
+    if (total > 0 && !have_all) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    // one piece through staging set 0
+    int64_t *d_o; int8_t *d_r; uint8_t *d_b, *d_q = nullptr, *d_l; bvc_site_result *d_res; bvc_group_result *d_gres;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_o = L.take<int64_t>((size_t)n_sites + 1);
+        d_r = L.take<int8_t>((size_t)n_sites);
+        d_b = L.take<uint8_t>((size_t)total, 16);
+        if (n_arrays == 2) d_q = L.take<uint8_t>((size_t)total, 16);
+        d_l = L.take<uint8_t>((size_t)total, 16);
+        d_res = L.take<bvc_site_result>((size_t)n_sites);
+        d_gres = L.take<bvc_group_result>((size_t)n_sites * n_groups);
+    });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_o, offsets, (size_t)(n_sites + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+    if (total) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_b, obs, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+        if (n_arrays == 2) BVC_HIP_D(ctx, hipMemcpyAsync(d_q, quals, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_l, group_of_obs, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    rc = run_csr_labels_device(ctx, n_sites, d_o, d_b, d_q, d_l, d_r, min_af, n_groups, d_res, d_gres);
+    if (rc == BVC_OK) rc = join_side(ctx);
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(grp_results, d_gres, (size_t)n_sites * n_groups * sizeof(bvc_group_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
+    return BVC_OK;
+}
+
+int bvc_lrt_csr_group_labels(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
+                             const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                             bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags)
+{
+    return lrt_csr_labels_impl(ctx, 2, n_sites, offsets, reinterpret_cast<const uint8_t *>(bases), reinterpret_cast<const uint8_t *>(quals),
+                               group_of_obs, ref_base, min_af, n_groups, results, grp_results, flags);
+}
+
+int bvc_lrt_csr_group_labels_packed(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *packed, const uint8_t *group_of_obs,
+                                    const int8_t *ref_base, double min_af, int32_t n_groups,
+                                    bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags)
+{
+    return lrt_csr_labels_impl(ctx, 1, n_sites, offsets, packed, nullptr, group_of_obs, ref_base, min_af, n_groups, results, grp_results,
+                               flags);
+}
+
 // ---- BGZF blocks on the device (inflate_kernel.hip) ------------------------------------------------------------------------
 int bvc_inflate_blocks(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
                        uint8_t *out, int64_t out_bytes, uint32_t *status, uint32_t flags)
@@ -1511,7 +1587,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         P.samples = L.take<int32_t>((size_t)n_e, 16);
         P.obs_base = L.take<int8_t>((size_t)n_o, 16);
         P.obs_qual = L.take<int8_t>((size_t)n_o, 16);
-        P.obs_sample = L.take<int32_t>((size_t)n_o, 16);
+        P.obs_label = L.take<uint8_t>((size_t)(n_groups ? n_o : 0), 16);
         P.indels = L.take<bvc_pileup_indel>((size_t)n_i, 16);
         d_ref = L.take<int8_t>((size_t)T, 16);
         d_res = L.take<bvc_site_result>((size_t)T);
@@ -1522,6 +1598,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     });
     if (rc != BVC_OK) return rc;
     P.indel_cap = (uint32_t)n_i;
+    P.group_of_sample = d_g; P.n_samples = n_groups ? n_samples : 0; P.n_groups = n_groups;
     const uint32_t cin = (uint32_t)(carry_in[0] & 7u) | ((uint32_t)(carry_in[4] & 1u) << 3) | 0x80u | ((uint32_t)carry_in[1] << 8) |
                          ((uint32_t)carry_in[2] << 16) | ((uint32_t)carry_in[3] << 24);
     uint32_t cout = cin;
@@ -1533,10 +1610,12 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     if (rc != BVC_OK) return rc;
     if (T > 0) {
         BVC_HIP_D(ctx, io.h2d(d_ref, ref_base, (size_t)T));
+        // the label vector goes up in front of the write pass: that pass turns it into one label byte per observation (obs_label)
         if (n_groups > 0 && n_samples > 0) BVC_HIP_D(ctx, io.h2d(d_g, group_of_sample, (size_t)n_samples));
         if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, launch_pileup_write(ctx->stream, P, cin));
         if (n_groups > 0)
-            rc = run_csr_groups_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, P.obs_sample, d_ref, min_af, d_g, n_samples, n_groups, d_res, d_gres);
+            rc = run_csr_labels_device(ctx, T, P.obs_off, reinterpret_cast<const uint8_t *>(P.obs_base),
+                                       reinterpret_cast<const uint8_t *>(P.obs_qual), P.obs_label, d_ref, min_af, n_groups, d_res, d_gres);
         else
             rc = run_csr_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, d_ref, min_af, nullptr, nullptr, d_res);
         if (rc == BVC_OK) rc = join_side(ctx);

@@ -166,8 +166,14 @@ struct PileupTile {
                                              // [4] bytes of indel tokens [5] bytes of indel text gathered
     int64_t *entry_off = nullptr, *obs_off = nullptr, *totals = nullptr;    // [n_pos + 1], [n_pos + 1], [2]
     bvc_pileup_entry *entries = nullptr;
-    int32_t *samples = nullptr, *obs_sample = nullptr;
+    int32_t *samples = nullptr;
     int8_t *obs_base = nullptr, *obs_qual = nullptr;
+    // tiles finished with n_groups > 0: the write pass stores each observation's group (min(group_of_sample[sample], n_groups);
+    // n_groups for a sample outside the label vector) in obs_label, the third column launch_hist_csr_labels reads
+    const uint8_t *group_of_sample = nullptr;
+    int64_t n_samples = 0;
+    int32_t n_groups = 0;
+    uint8_t *obs_label = nullptr;
     int32_t *tally = nullptr;                // [n_pos][32]
     bvc_pileup_indel *indels = nullptr;
     uint32_t indel_cap = 0;
@@ -194,6 +200,10 @@ hipError_t launch_pileup_write(hipStream_t stream, const PileupTile &P, uint32_t
 hipError_t launch_hist_csr_groups(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const int8_t *bases,
                                   const int8_t *quals, const int32_t *sample_of_obs, const uint8_t *group_of_sample, int64_t n_samples,
                                   int n_groups, uint32_t *counts);
+// the same counts from one label byte per observation (group_of_obs[i] >= n_groups: in no group); quals == nullptr: obs is the
+// packed byte base << 6 | qual.  Any byte alignment of the three arrays
+hipError_t launch_hist_csr_labels(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
+                                  const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, uint32_t *counts);
 
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);

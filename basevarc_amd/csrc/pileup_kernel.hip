@@ -48,6 +48,15 @@ __device__ __forceinline__ uint32_t wave_sum(uint32_t v)
     return v;
 }
 
+// The group of sample `smp` as hist_csr_labels_kernel takes it: one byte, n_groups = "in no group".  A line's samples ascend, so
+// the gathers of a wavefront fall into a few cache lines of the L2-resident label vector.
+__device__ __forceinline__ uint8_t label_of_sample(const uint8_t *__restrict__ group_of_sample, int64_t n_samples, int32_t n_groups, int32_t smp)
+{
+    uint32_t g = (uint32_t)n_groups;
+    if (smp >= 0 && (int64_t)smp < n_samples) { g = group_of_sample[smp]; if (g > (uint32_t)n_groups) g = (uint32_t)n_groups; }
+    return (uint8_t)g;
+}
+
 // "b,m,q,r,s " at text[p..] (p < e): five fields of one to three decimal digits, four commas, a space.  Returns the packed token,
 // 0 for any other shape.  Three aligned 8-byte loads cover the 20 bytes of the longest such token wherever p falls (the text
 // buffer is allocated 32 bytes longer than the text).
@@ -95,7 +104,10 @@ struct ParseArgs {
     bvc_pileup_entry *entries;
     int32_t *samples;
     int8_t *obs_base, *obs_qual;
-    int32_t *obs_sample;
+    const uint8_t *group_of_sample;  // tiles finished with n_groups > 0: the write pass leaves each observation's group in obs_label
+    int64_t n_samples;
+    int32_t n_groups;
+    uint8_t *obs_label;              // min(group_of_sample[sample], n_groups); n_groups for a sample outside the label vector
     int32_t *tally;                  // [n_pos][32]: [strand << 3 | base] of the base entries, + 16 for the indel entries
     bvc_pileup_indel *indels;
     uint32_t indel_cap;
@@ -216,7 +228,7 @@ __global__ __launch_bounds__(kParseWaves * kWave) void pileup_parse_kernel(Parse
                         A.samples[ent_i] = smp;
                         A.obs_base[obs_i] = (int8_t)(tok & 7u);
                         A.obs_qual[obs_i] = (int8_t)((tok >> 16) & 0xFFu);
-                        A.obs_sample[obs_i] = smp;
+                        if (A.n_groups > 0) A.obs_label[obs_i] = label_of_sample(A.group_of_sample, A.n_samples, A.n_groups, smp);
                         atomicAdd(&tal[tok & 15u], 1u);
                         ++ent_i; ++obs_i;
                     } else {
@@ -353,7 +365,7 @@ __global__ __launch_bounds__(kParseWaves * kWave) void pileup_bin_kernel(ParseAr
                     A.samples[ent_i] = smp0 + (int32_t)smp;
                     A.obs_base[obs_i] = (int8_t)(tok & 7u);
                     A.obs_qual[obs_i] = (int8_t)((tok >> 16) & 0xFFu);
-                    A.obs_sample[obs_i] = smp0 + (int32_t)smp;
+                    if (A.n_groups > 0) A.obs_label[obs_i] = label_of_sample(A.group_of_sample, A.n_samples, A.n_groups, smp0 + (int32_t)smp);
                     atomicAdd(&tal[tok & 15u], 1u);
                 }
                 if (is_ind) {
@@ -490,6 +502,23 @@ __global__ void pileup_patch_kernel(int64_t n_lines, int32_t n_batches, const ui
 // 1e1-1e5 observations, far fewer than a dense row, and what bounds a site here is zeroing and folding (k + 1) x 512 counters.
 constexpr int kCsrGroupThreads = 512;
 
+// The two steps hist_csr_groups_kernel and hist_csr_labels_kernel share word for word: the counters to zero before the first
+// site, and a site's counters folded into counts[site][class] (the copies of a class summed in an order rotated by the class, so
+// that the lanes of a wavefront start on different banks) and left zero for the next site.
+__device__ __forceinline__ void csr_groups_zero(uint32_t *ghist, int words, int tid)
+{
+    for (int i = tid * 4; i < words; i += kCsrGroupThreads * 4) *reinterpret_cast<u32x4 *>(&ghist[i]) = u32x4{0u, 0u, 0u, 0u};
+}
+
+__device__ __forceinline__ void csr_groups_fold(uint32_t *ghist, uint32_t *__restrict__ dst, int classes, int log2c, int tid)
+{
+    for (int key = tid; key < classes; key += kCsrGroupThreads) {
+        uint32_t sum = 0;
+        for (int v = 0; v < (1 << log2c); ++v) { const int at = (key << log2c) + ((v + key) & ((1 << log2c) - 1)); sum += ghist[at]; ghist[at] = 0u; }
+        dst[key] = sum;
+    }
+}
+
 // One workgroup per site; LDS [histogram][class][copy] with as many copies (a power of two, copy = lane mod copies) as fit 64 KiB --
 // 4 at k = 5 -- so that the handful of hot classes of a pileup (the reference base at ~30 qualities, per group) are not ONE counter
 // each for 512 lanes.  6 algorithmic bytes per observation (base, quality, sample index) + a label byte gathered from the L2-resident
@@ -514,7 +543,7 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_groups_kernel(
             if (BVC_LDS_OK(0x501, at, words)) atomicAdd(&ghist[at], 1u);
         }
     };
-    for (int i = tid * 4; i < words; i += kCsrGroupThreads * 4) *reinterpret_cast<u32x4 *>(&ghist[i]) = u32x4{0u, 0u, 0u, 0u};
+    csr_groups_zero(ghist, words, tid);
     __syncthreads();
     for (int64_t site = blockIdx.x; site < n_sites; site += gridDim.x) {
         const int64_t o0 = offsets[site], o1 = offsets[site + 1];
@@ -544,12 +573,91 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_groups_kernel(
         }
         for (; i < o1; i += kCsrGroupThreads) one((uint8_t)bases[i], (uint8_t)quals[i], sample_of_obs[i]);
         __syncthreads();
-        uint32_t *dst = counts + site * (int64_t)classes;
-        for (int key = tid; key < classes; key += kCsrGroupThreads) {
-            uint32_t sum = 0;
-            for (int v = 0; v < (1 << log2c); ++v) { const int at = (key << log2c) + ((v + key) & ((1 << log2c) - 1)); sum += ghist[at]; ghist[at] = 0u; }
-            dst[key] = sum;
+        csr_groups_fold(ghist, counts + site * (int64_t)classes, classes, log2c, tid);
+        __syncthreads();
+    }
+}
+
+// The same histograms from ONE label byte per observation (bvc_lrt_csr_group_labels[_packed]): group_of_obs[i] is what
+// hist_csr_groups_kernel gathers as group_of_sample[sample_of_obs[i]], so 3 algorithmic bytes per observation (2 packed: obs = the
+// byte base << 6 | qual, quality bits 63 = skipped, and `quals` is not read) instead of 6, and no dependent load.  Same workgroup per
+// site, same LDS layout and copies, same fold: the counts are the same numbers.
+//
+// A site starts at any byte of the three arrays.  Where the arrays agree on that byte's alignment (always, for arrays allocated
+// alike: it is then o0 mod 4) a lane takes FOUR consecutive observations with one aligned 4-byte load per array, two such steps in
+// flight, in front of them the up to three observations before the first aligned one and behind them the up to three that fill no
+// word.  Where they disagree (device callers hand in arbitrary pointers) consecutive lanes take consecutive observations with byte
+// loads, four per lane in flight, as hist_csr_groups_kernel reads its bases and qualities.
+template <bool PACKED>
+__global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
+    int64_t n_sites, const int64_t *__restrict__ offsets, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ quals,
+    const uint8_t *__restrict__ group_of_obs, int n_groups, int log2c, uint32_t *__restrict__ counts)
+{
+    BVC_POISON_LDS();
+    extern __shared__ __attribute__((aligned(16))) uint32_t ghist[];        // [n_groups + 1][512][1 << log2c]
+    const int tid = threadIdx.x;
+    const int classes = (n_groups + 1) * BVC_NCLASS;
+    const int words = classes << log2c;
+    const uint32_t copy = (uint32_t)tid & ((1u << log2c) - 1u);
+    auto one = [&](uint32_t b, uint32_t q, uint32_t lab) {
+        if (PACKED) { q = b & 63u; b >>= 6; }
+        if (PACKED ? q != 63u : (b < 4u && q < 128u)) {
+            const uint32_t g = lab < (uint32_t)n_groups ? lab : (uint32_t)n_groups;
+            const uint32_t at = ((g * BVC_NCLASS + ((b << 7) | q)) << log2c) | copy;
+            if (BVC_LDS_OK(0x503, at, words)) atomicAdd(&ghist[at], 1u);
         }
+    };
+    auto four = [&](uint32_t wb, uint32_t wq, uint32_t wl) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) one((wb >> (8 * k)) & 0xFFu, (wq >> (8 * k)) & 0xFFu, (wl >> (8 * k)) & 0xFFu);
+    };
+    csr_groups_zero(ghist, words, tid);
+    __syncthreads();
+    for (int64_t site = blockIdx.x; site < n_sites; site += gridDim.x) {
+        const int64_t o0 = offsets[site], n = offsets[site + 1] - o0;
+        const uint8_t *__restrict__ pb = obs + o0, *__restrict__ pq = PACKED ? pb : quals + o0, *__restrict__ pl = group_of_obs + o0;
+        const uint32_t mis = (uint32_t)(uintptr_t)pb & 3u;
+        if (((uint32_t)(uintptr_t)pl & 3u) == mis && ((uint32_t)(uintptr_t)pq & 3u) == mis) {
+            constexpr int U = 2;
+            const int64_t to_word = (int64_t)((4u - mis) & 3u);
+            const int64_t head = to_word < n ? to_word : n;                  // observations in front of the first aligned word
+            const int64_t n4 = (n - head) >> 2, tail = head + 4 * n4;        // whole words; the first observation behind them
+            if (tid < 3) {
+                if (tid < head) one(pb[tid], pq[tid], pl[tid]);
+                if (tail + tid < n) one(pb[tail + tid], pq[tail + tid], pl[tail + tid]);
+            }
+            const uint32_t *__restrict__ wb = reinterpret_cast<const uint32_t *>(pb + head);
+            const uint32_t *__restrict__ wq = reinterpret_cast<const uint32_t *>(pq + head);
+            const uint32_t *__restrict__ wl = reinterpret_cast<const uint32_t *>(pl + head);
+            int64_t j = tid;
+            for (; j + (int64_t)(U - 1) * kCsrGroupThreads < n4; j += (int64_t)U * kCsrGroupThreads) {
+                uint32_t vb[U], vq[U], vl[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t at = j + (int64_t)u * kCsrGroupThreads;
+                    vb[u] = wb[at]; vq[u] = PACKED ? 0u : wq[at]; vl[u] = wl[at];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) four(vb[u], vq[u], vl[u]);
+            }
+            for (; j < n4; j += kCsrGroupThreads) four(wb[j], PACKED ? 0u : wq[j], wl[j]);
+        } else {
+            constexpr int U = 4;
+            int64_t i = tid;
+            for (; i + (int64_t)(U - 1) * kCsrGroupThreads < n; i += (int64_t)U * kCsrGroupThreads) {
+                uint32_t b[U], q[U], lab[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int64_t at = i + (int64_t)u * kCsrGroupThreads;
+                    b[u] = pb[at]; q[u] = PACKED ? 0u : pq[at]; lab[u] = pl[at];
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) one(b[u], q[u], lab[u]);
+            }
+            for (; i < n; i += kCsrGroupThreads) one(pb[i], PACKED ? 0u : pq[i], pl[i]);
+        }
+        __syncthreads();
+        csr_groups_fold(ghist, counts + site * (int64_t)classes, classes, log2c, tid);
         __syncthreads();
     }
 }
@@ -563,7 +671,8 @@ static ParseArgs parse_args_of(const PileupTile &P)
     A.n_batches = P.n_batches; A.n_pos = P.n_pos; A.line_stride = P.line_stride; A.n_pos_dev = P.n_pos_dev;
     A.line_entries = P.line_words; A.line_obs = P.line_words + P.n_lines_cap; A.line_last = P.line_words + 2 * P.n_lines_cap;
     A.line_need = P.line_words + 3 * P.n_lines_cap; A.status = P.status;
-    A.entries = P.entries; A.samples = P.samples; A.obs_base = P.obs_base; A.obs_qual = P.obs_qual; A.obs_sample = P.obs_sample;
+    A.entries = P.entries; A.samples = P.samples; A.obs_base = P.obs_base; A.obs_qual = P.obs_qual;
+    A.group_of_sample = P.group_of_sample; A.n_samples = P.n_samples; A.n_groups = P.n_groups; A.obs_label = P.obs_label;
     A.tally = P.tally; A.indels = P.indels; A.indel_cap = P.indel_cap;
     return A;
 }
@@ -798,21 +907,41 @@ hipError_t launch_indel_text(hipStream_t stream, const PileupTile &P, uint8_t *d
     return hipGetLastError();
 }
 
+// The LDS of the two ragged group kernels: as many copies of the (n_groups + 1) x 512 counters as fit 64 KiB, and the kernel's
+// dynamic-LDS limit raised where that is more than the 48 KiB a kernel gets unasked.
+static hipError_t csr_groups_lds(LaunchState &st, const void *kernel, int n_groups, int &log2c, size_t &lds)
+{
+    log2c = 0;
+    while (log2c < 5 && ((size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << (log2c + 1)) <= 64 * 1024) ++log2c;
+    lds = (size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << log2c;
+    return lds > 48 * 1024 ? raise_lds(st, kernel, (size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t)) : hipSuccess;
+}
+
 hipError_t launch_hist_csr_groups(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const int8_t *bases,
                                   const int8_t *quals, const int32_t *sample_of_obs, const uint8_t *group_of_sample, int64_t n_samples,
                                   int n_groups, uint32_t *counts)
 {
     if (n_sites <= 0) return hipSuccess;
-    int log2c = 0;                                               // copies: as many as fit 64 KiB
-    while (log2c < 5 && ((size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << (log2c + 1)) <= 64 * 1024) ++log2c;
-    const size_t lds = (size_t)(n_groups + 1) * BVC_NCLASS * sizeof(uint32_t) << log2c;
-    if (lds > 48 * 1024) {
-        const hipError_t e = raise_lds(st, reinterpret_cast<const void *>(hist_csr_groups_kernel),
-                                       (size_t)(BVC_MAX_GROUPS + 1) * BVC_NCLASS * sizeof(uint32_t));
-        if (e != hipSuccess) return e;
-    }
+    int log2c = 0;
+    size_t lds = 0;
+    const hipError_t e = csr_groups_lds(st, reinterpret_cast<const void *>(hist_csr_groups_kernel), n_groups, log2c, lds);
+    if (e != hipSuccess) return e;
     hipLaunchKernelGGL(hist_csr_groups_kernel, dim3((unsigned)(n_sites < 8192 ? n_sites : 8192)), dim3(kCsrGroupThreads), lds, stream, n_sites,
                        offsets, bases, quals, sample_of_obs, group_of_sample, n_samples, n_groups, log2c, counts);
+    return hipGetLastError();
+}
+
+hipError_t launch_hist_csr_labels(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
+                                  const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, uint32_t *counts)
+{
+    if (n_sites <= 0) return hipSuccess;
+    auto *kernel = quals ? hist_csr_labels_kernel<false> : hist_csr_labels_kernel<true>;
+    int log2c = 0;
+    size_t lds = 0;
+    const hipError_t e = csr_groups_lds(st, reinterpret_cast<const void *>(kernel), n_groups, log2c, lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_sites < 8192 ? n_sites : 8192)), dim3(kCsrGroupThreads), lds, stream, n_sites, offsets, obs,
+                       quals, group_of_obs, n_groups, log2c, counts);
     return hipGetLastError();
 }
 

@@ -52,7 +52,7 @@ EXPORTS = [
     "bvc_synchronize", "bvc_set_overlap", "bvc_join", "bvc_set_profiling", "bvc_get_profile", "bvc_lrt_dense", "bvc_lrt_dense_groups",
     "bvc_lrt_csr", "bvc_lrt_csr_comb", "bvc_hist_dense", "bvc_lrt_hist", "bvc_synth_dense", "bvc_stream_read_ms", "bvc_set_tuning",
     "bvc_lrt_dense_packed", "bvc_pack_dense", "bvc_hist_dense_packed", "bvc_lrt_dense_groups_packed",
-    "bvc_lrt_csr_packed", "bvc_lrt_csr_groups", "bvc_pileup_begin", "bvc_pileup_finish", "bvc_pileup_finish_called", "bvc_inflate_blocks", "bvc_pileup_begin_bgzf", "bvc_pileup_text",
+    "bvc_lrt_csr_packed", "bvc_lrt_csr_groups", "bvc_lrt_csr_group_labels", "bvc_lrt_csr_group_labels_packed", "bvc_pileup_begin", "bvc_pileup_finish", "bvc_pileup_finish_called", "bvc_inflate_blocks", "bvc_pileup_begin_bgzf", "bvc_pileup_text",
     "bvc_pileup_begin_bin",
     "bvc_host_alloc", "bvc_host_free",
 ]
@@ -118,6 +118,10 @@ def load_library():
     L.bvc_lrt_csr_packed.argtypes = [vp, i64, vp, vp, vp, dbl, vp, u32]
     L.bvc_lrt_csr_groups.restype = C.c_int
     L.bvc_lrt_csr_groups.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, vp, i64, i32, vp, vp, u32]
+    L.bvc_lrt_csr_group_labels.restype = C.c_int
+    L.bvc_lrt_csr_group_labels.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, i32, vp, vp, u32]
+    L.bvc_lrt_csr_group_labels_packed.restype = C.c_int
+    L.bvc_lrt_csr_group_labels_packed.argtypes = [vp, i64, vp, vp, vp, vp, dbl, i32, vp, vp, u32]
     L.bvc_pileup_begin.restype = C.c_int
     L.bvc_pileup_begin.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
     L.bvc_pileup_begin_bin.restype = C.c_int
@@ -285,6 +289,53 @@ class Context:
         self._check(self._L.bvc_lrt_csr_groups(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(bases_t), _dev_ptr(quals_t), _dev_ptr(samples_t),
                                                _dev_ptr(ref_t), float(min_af), _dev_ptr(group_t), group_t.numel(), int(n_groups),
                                                _dev_ptr(res), _dev_ptr(gres), BVC_PTR_DEVICE))
+        return res, gres
+
+    def lrt_csr_group_labels(self, offsets, bases, quals, group_of_obs, ref_base, min_af, n_groups):
+        """lrt_csr_groups for a caller who knows each observation's group: one label byte per observation (>= n_groups: no group)."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        b = np.ascontiguousarray(bases, dtype=np.int8)
+        q = np.ascontiguousarray(quals, dtype=np.int8)
+        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
+        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        n = len(o) - 1
+        out = np.zeros(n, dtype=SITE_DTYPE)
+        gout = np.zeros((n, n_groups), dtype=GROUP_DTYPE)
+        self._check(self._L.bvc_lrt_csr_group_labels(self._h, n, _np_ptr(o), _np_ptr(b), _np_ptr(q), _np_ptr(g), _np_ptr(r), float(min_af),
+                                                     int(n_groups), _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
+        return out, gout
+
+    def lrt_csr_group_labels_device(self, offsets_t, bases_t, quals_t, group_of_obs_t, ref_t, min_af, n_groups):
+        import torch
+        ns = offsets_t.numel() - 1
+        res = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        gres = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        self._check(self._L.bvc_lrt_csr_group_labels(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(bases_t), _dev_ptr(quals_t),
+                                                     _dev_ptr(group_of_obs_t), _dev_ptr(ref_t), float(min_af), int(n_groups),
+                                                     _dev_ptr(res), _dev_ptr(gres), BVC_PTR_DEVICE))
+        return res, gres
+
+    def lrt_csr_group_labels_packed(self, offsets, packed, group_of_obs, ref_base, min_af, n_groups):
+        """lrt_csr_group_labels at two bytes per observation: packed = base << 6 | qual (quality bits 63: skipped)."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        pk = np.ascontiguousarray(packed, dtype=np.uint8)
+        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
+        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        n = len(o) - 1
+        out = np.zeros(n, dtype=SITE_DTYPE)
+        gout = np.zeros((n, n_groups), dtype=GROUP_DTYPE)
+        self._check(self._L.bvc_lrt_csr_group_labels_packed(self._h, n, _np_ptr(o), _np_ptr(pk), _np_ptr(g), _np_ptr(r), float(min_af),
+                                                            int(n_groups), _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
+        return out, gout
+
+    def lrt_csr_group_labels_packed_device(self, offsets_t, packed_t, group_of_obs_t, ref_t, min_af, n_groups):
+        import torch
+        ns = offsets_t.numel() - 1
+        res = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        gres = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        self._check(self._L.bvc_lrt_csr_group_labels_packed(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(packed_t), _dev_ptr(group_of_obs_t),
+                                                            _dev_ptr(ref_t), float(min_af), int(n_groups), _dev_ptr(res), _dev_ptr(gres),
+                                                            BVC_PTR_DEVICE))
         return res, gres
 
     def pileup_tile(self, text, line_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,

@@ -225,6 +225,25 @@ int bvc_lrt_csr_groups(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, co
                        bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags);
 
 /*
+ * Additive: bvc_lrt_csr_groups for a caller who knows each entry's GROUP when it builds the vectors (src/BaseVarC.cpp:633-636 looks
+ * it up per entry): group_of_obs[i] is the group of observation i, one byte in place of the 4-byte sample index and the label
+ * vector.  Any value >= n_groups: in no group, as in bvc_lrt_dense_groups (the observation still counts in the overall record);
+ * no byte value is an error.  Skips what bvc_lrt_csr skips (a base outside 0..3, a quality byte outside 0..127).  Same records as
+ * bvc_lrt_csr_groups on the same observations with group_of_obs[i] = group_of_sample[sample_of_obs[i]] (an index outside the label
+ * vector: any byte >= n_groups), byte for byte.  3 bytes per observation instead of 6 over the host link and out of device memory,
+ * and no gather.  Host or device pointers (flags); device arrays may start at any byte.  n_groups outside 1..32, a null
+ * grp_results, null data or label pointers with observations present, offsets that do not start at 0 or that decrease:
+ * BVC_ERR_ARG.
+ */
+int bvc_lrt_csr_group_labels(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
+                             const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                             bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags);
+/* The same at TWO bytes per observation: packed[i] = base << 6 | qual as in bvc_lrt_csr_packed (quality bits 63: skipped). */
+int bvc_lrt_csr_group_labels_packed(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *packed,
+                                    const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                                    bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags);
+
+/*
  * Additive: BGZF blocks inflated on the device.  The reference reads its temp batches through htslib's bgzf_getline
  * (src/BaseVarC.cpp:406; written with bgzf_write, :509-527): one raw-deflate stream (RFC 1951) of at most 64 KiB of output per
  * block, blocks independent of each other.  blocks[i] names the deflate payload of a block inside `comp` (the bytes between the
