@@ -6,8 +6,8 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbvc.so")
-SOURCES = ["bvc_api.hip", "hist_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip"]
-DEPS = ["bvc_device.h", "bvc_internal.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h")]
+SOURCES = ["bvc_context.hip", "bvc_lrt.hip", "bvc_pileup.hip", "hist_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip"]
+DEPS = ["bvc_ctx.h", "bvc_device.h", "bvc_internal.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h")]
 
 
 def code_sha16(path=None):
@@ -98,7 +98,10 @@ def build(force=False, verbose=False):
         with open(STAMP + ".tmp", "w", encoding="utf-8") as f:
             f.write(_flag_stamp())
         os.replace(STAMP + ".tmp", STAMP)
-        for o, _ in procs:                                           # the objects of the library in place (tools/build_variants.sh links against them)
+        for f in os.listdir(os.path.join(CSRC, "_obj")):             # tools/build_variants.sh links every object here: none of a source that is gone
+            if f.endswith(".o"):
+                os.remove(os.path.join(CSRC, "_obj", f))
+        for o, _ in procs:                                           # the objects of the library in place
             os.replace(o, os.path.join(CSRC, "_obj", os.path.basename(o)))
     finally:
         shutil.rmtree(objdir, ignore_errors=True)

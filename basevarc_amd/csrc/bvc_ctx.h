@@ -1,0 +1,213 @@
+// bvc_ctx.h -- the context of libbvc and what every family of entry points needs of it (not installed).  The C ABI of include/bvc.h
+// is defined in bvc_context.hip (a context's life, streams, tuning, profile), bvc_lrt.hip (the two stages on tiles and ragged columns)
+// and bvc_pileup.hip (BGZF blocks and temp-batch tiles).  One context = one gfx950 device + one HIP stream + device scratch.  No CPU
+// fallback exists: every compute entry point launches the HIP kernels or fails with an error code.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <string>
+#include <vector>
+
+#include "bvc_internal.h"
+
+using namespace bvc;
+
+// the helpers below are shared by the library's translation units, not exported by it
+#pragma GCC visibility push(hidden)
+
+// Device scratch of a context: grown by ensure(), freed with the context.
+struct DevBuf {
+    char *p = nullptr;
+    size_t cap = 0;
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+};
+
+// bvc_pileup_begin / bvc_pileup_begin_bgzf / bvc_pileup_finish: their device buffers and the tile between the calls.
+struct PileupState {
+    DevBuf text, meta, out, called;    // the tile's text, its line tables and counts, its parsed columns and records, the called entries
+    // tiles inflated on the device (bvc_pileup_begin_bgzf): two text buffers (what a tile leaves of a batch is carried from one to the
+    // other), the compressed bytes, what the calls left of every batch
+    DevBuf pz_text[2], pz_comp;
+    int pz_cur = 0;                    // the buffer that holds the leftovers
+    std::vector<uint32_t> left_src, left_len;
+    struct Tile {                      // what a begin call leaves for the finish call; every begin starts from Tile{}
+        PileupTile P;
+        bool begun = false;
+        int64_t entries = 0, obs = 0, indels = 0;
+        int64_t text_bytes = 0, indel_bytes = 0;
+        bool on_device_text = false;
+    } tile;
+};
+
+struct bvc_ctx {
+    int device = -1;
+    hipStream_t stream = nullptr;      // the stream the entry points work on: own_stream until bvc_set_stream names another
+    hipStream_t own_stream = nullptr;  // created with the context.  A BLOCKING stream: ordered against the device's default stream as the
+                                       // default stream itself is (callers that prepare buffers there need no extra synchronisation), but the
+                                       // streams of different contexts run side by side -- sixteen threads of the host program, each with
+                                       // its context, were one queue when every context worked on the default stream
+    hipEvent_t ev_wait = nullptr;      // blocking-sync event: the long waits of the pileup calls SLEEP on it (wait_stream) where
+                                       // hipStreamSynchronize polls -- a host program with a thread per context on a CPU quota cannot afford that
+    QualLut *d_lut = nullptr;
+    // [sites][512] scratch between the two stages.  Overlap mode cycles through kRing buffers: with three, the
+    // histogram pass of call i+1 waits only for the EM of call i-2 (long finished), never for the one running
+    // beside it, so both streams run back to back.
+    static constexpr int kRing = 4;
+    DevBuf d_cnt[kRing];
+    // overlap mode: stage 2 of call i runs on `side` while stage 1 of call i+1 streams on `stream`
+    bool overlap = false;
+    hipStream_t side = nullptr;        // stage 2 of even calls
+    hipStream_t side_b = nullptr, side_c = nullptr;   // further stage-2 streams (two_em_streams below)
+    unsigned side_flip = 0;
+    int flip = 0;
+    hipEvent_t ev_hist_done[kRing] = {};
+    hipEvent_t ev_em_done[kRing] = {};
+    bool em_pending[kRing] = {};
+    DevBuf d_grp[kRing];               // [sites][groups + 1][512] in group mode
+    // item-engine scratch of stage 2 (em_items.hip), one per ring buffer (the stage 2 of consecutive calls may run
+    // side by side); the last one serves bvc_lrt_hist on the context's own stream
+    DevBuf d_em[kRing + 1];
+    DevBuf d_emg[kRing];               // the same for the (site, group) pseudo-sites of group calls
+    uint32_t *d_sink = nullptr;        // 256 bytes: sink of the streaming-read measurement kernel; bvc_pack_dense's counter at byte 64
+    DevBuf d_grp_labels;               // group mode: the call's group vector clamped to 0..n_groups (hist_kernel.hip)
+    int64_t *d_grp_scratch = nullptr;  // group mode: "samples ordered by group" flag + column bounds (hist_kernel.hip)
+    // staging for BVC_PTR_HOST calls: two sets, so that the upload of chunk i+1 (copy stream) runs under the kernels
+    // of chunk i
+    DevBuf d_stage[2];
+    hipStream_t copy = nullptr;
+    hipEvent_t ev_upload[2] = {nullptr, nullptr};
+    hipEvent_t ev_set_free[2] = {nullptr, nullptr};   // ragged host calls: the kernels that read staging set k have finished
+    PileupState pile;
+    // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
+    // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
+    char *h_up = nullptr, *h_down = nullptr;
+    size_t up_cap = 0, down_cap = 0;
+    LaunchState ls;                    // launch policy + one-time kernel setup of this context
+    bool profiling = false;
+    std::vector<hipEvent_t> ev_pool;   // free events
+    struct Triple { hipEvent_t a, b, c, d; int64_t sites; };   // hist = a..b, EM = c..d
+    std::vector<Triple> ev_pending;
+    bvc_profile prof{};
+    std::string err;
+};
+
+// The ring buffers of one call: [n_sites][512] counts, the [n_sites][n_groups + 1][512] group histograms (group calls)
+// and the item-engine scratch of both (null when stage 2 does not use the engine).
+struct RingSlot {
+    uint32_t *counts = nullptr, *grp = nullptr;
+    void *em = nullptr, *emg = nullptr;
+};
+
+inline int fail(bvc_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess)
+{
+    if (ctx) {
+        ctx->err = what;
+        if (e != hipSuccess) { ctx->err += ": "; ctx->err += hipGetErrorString(e); }
+    }
+    return code;
+}
+
+// Waits for the context's stream without spinning: the thread sleeps until the event behind everything enqueued so far fires.
+inline hipError_t wait_stream(bvc_ctx *ctx)
+{
+    hipError_t e = hipEventRecord(ctx->ev_wait, ctx->stream);
+    return e == hipSuccess ? hipEventSynchronize(ctx->ev_wait) : e;
+}
+
+#define BVC_HIP(ctx, call)                                                         \
+    do {                                                                           \
+        hipError_t e__ = (call);                                                   \
+        if (e__ != hipSuccess) return fail((ctx), BVC_ERR_DEVICE, #call, e__);     \
+    } while (0)
+
+// Every stream a context enqueues work on.
+inline std::array<hipStream_t, 5> streams_of(const bvc_ctx *ctx) { return {ctx->stream, ctx->copy, ctx->side, ctx->side_b, ctx->side_c}; }
+
+// Waits for every stream of the context (all of them, whatever one returns; the first error is the result): nothing of stage 2 is
+// pending afterwards.
+hipError_t sync_streams(bvc_ctx *ctx);
+
+// A failed call must not leave an upload or a kernel running on the context's buffers: the next call may free or refill
+// them, and stage 2 of what was already launched may still run on the side streams.  Returns `code`.
+int drain_on_error(bvc_ctx *ctx, int code);
+
+#define BVC_HIP_D(ctx, call)                                                                         \
+    do {                                                                                             \
+        hipError_t e__ = (call);                                                                     \
+        if (e__ != hipSuccess) return drain_on_error((ctx), fail((ctx), BVC_ERR_DEVICE, #call, e__)); \
+    } while (0)
+
+// Grows `buf` to `need` bytes (and a quarter more) after waiting for the context's stream and the copy stream; the new buffer is cleared.
+int ensure(bvc_ctx *ctx, DevBuf &buf, size_t need);
+
+// Grows `buf` to the slices of `list` (a function of a Layout &, bvc_internal.h) + `slack` bytes and carves it: the one list of take() calls runs
+// once to size the buffer and once to hand out the pointers, so the two cannot disagree.
+template <class List>
+int carve(bvc_ctx *ctx, DevBuf &buf, size_t slack, List list)
+{
+    Layout size;
+    list(size);
+    const int rc = ensure(ctx, buf, size.at + slack);
+    if (rc != BVC_OK) return rc;
+    Layout slices{reinterpret_cast<uintptr_t>(buf.p)};
+    list(slices);
+    return BVC_OK;
+}
+
+// The pool of timing events (profiling, bvc_stream_read_ms).
+hipEvent_t take_event(bvc_ctx *ctx);
+void give_back(bvc_ctx *ctx, hipEvent_t e);
+void give_back(bvc_ctx *ctx, bvc_ctx::Triple &t);
+// Four timing events for one call, or none at all (never a partial set).
+bool take_timing_events(bvc_ctx *ctx, bvc_ctx::Triple &t);
+// Drains finished timing records into the running totals so that ev_pending stays bounded when the caller never
+// asks for the profile.
+void reap_timing(bvc_ctx *ctx, bool all);
+
+// Make the context's stream wait for every stage-2 launch still running on the side stream.
+inline int join_side(bvc_ctx *ctx)
+{
+    for (int b = 0; b < bvc_ctx::kRing; ++b)
+        if (ctx->em_pending[b]) {
+            BVC_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_em_done[b], 0));
+            ctx->em_pending[b] = false;
+        }
+    return BVC_OK;
+}
+
+// Does [p, p + n) lie inside an allocation of bvc_host_alloc?  A transfer from / to it needs no bounce buffer.
+bool in_pinned(const void *p, size_t n);
+
+inline int check_common(bvc_ctx *ctx, int64_t n_sites, const void *a, const void *b, const void *c, const void *d)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (n_sites < 0) return fail(ctx, BVC_ERR_ARG, "n_sites < 0");
+    if (n_sites > 0 && (!a || !b || !c || !d)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n_sites > (int64_t)0x7FFFFFFF / 64) return fail(ctx, BVC_ERR_ARG, "too many sites in one call (split the tile)");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    return BVC_OK;
+}
+
+// check_common for rows of n_samples samples, row_stride bytes apart
+inline int check_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride, const void *a, const void *b, const void *c,
+                       const void *d)
+{
+    const int rc = check_common(ctx, n_sites, a, b, c, d);
+    if (rc != BVC_OK) return rc;
+    return n_samples >= 0 && row_stride >= n_samples ? BVC_OK : fail(ctx, BVC_ERR_ARG, "need 0 <= n_samples <= row_stride");
+}
+
+// The two stages on ragged columns in device memory (bvc_lrt.hip); bvc_pileup_finish runs them on the columns of its tile.
+int run_csr_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
+                   const int8_t *ref_base, double min_af, const int8_t *comb, const uint8_t *n_comb,
+                   bvc_site_result *results);
+// group records from one label byte per observation; obs = the bases, or with quals == nullptr the packed bytes
+int run_csr_labels_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *obs, const uint8_t *quals,
+                          const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
+                          bvc_site_result *results, bvc_group_result *grp_results);
+
+#pragma GCC visibility pop

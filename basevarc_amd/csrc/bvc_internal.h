@@ -16,7 +16,7 @@ struct LaunchState {
     int em_waves_per_cu = 0;   // 0 = default policy (em_kernel.hip); 1..32 resident EM wavefronts per CU
     int em_wpb = 4;            // waves per EM workgroup: 4, or 1 (A/B runs)
     int hist_split = 0;        // 0 = by tile shape; 1..64 workgroups sharing a site in the dense histogram pass
-    int64_t host_chunk_bytes = (int64_t)1 << 29;   // BVC_PTR_HOST calls: bytes per array and staging chunk
+    int host_chunk_kib = 1 << 19;  // BVC_PTR_HOST calls: KiB per array and staging chunk
     int em_streams = 0;        // overlap mode: side streams stage 2 alternates between: 0 = by call shape, 1..3
     int group_pipe = 1;        // any-order group histogram: issue the next chunk's loads before counting the current one
     int group_log2c = -1;      // any-order group histograms: -1 = as many LDS copies per histogram as fit 64 KiB; 0..5 = at most
@@ -45,7 +45,7 @@ inline size_t round256(size_t n) { return (n + 255) / 256 * 256; }
 
 // Slices of a device buffer, each starting on a 256-byte boundary: take<T>(count, pad) hands out count elements + pad bytes.
 // A list of take() calls written once as a function of a Layout & both sizes a buffer (base 0: `at` ends as the byte count)
-// and hands out its pointers, so the two cannot disagree (bvc_api.hip carve(); the stage-2 scratch of em_kernel.hip and
+// and hands out its pointers, so the two cannot disagree (bvc_ctx.h carve(); the stage-2 scratch of em_kernel.hip and
 // em_items.hip).
 struct Layout {
     uintptr_t base = 0;

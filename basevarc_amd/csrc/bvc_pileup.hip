@@ -1,0 +1,503 @@
+// bvc_pileup.hip -- the producer: BGZF blocks inflated on the device, and temp-batch tiles (text, binary records, or BGZF blocks of
+// text) -> columns -> records between a begin call and a finish call (pileup_kernel.hip, inflate_kernel.hip).
+#include <cstring>
+
+#include "bvc_ctx.h"
+
+namespace {
+
+// Transfers of one call through the context's pinned buffers: h2d copies the caller's bytes into pinned memory and enqueues the DMA,
+// d2h enqueues a DMA into pinned memory and deliver() -- after the stream has been waited for -- copies the bytes to the caller.
+struct PinIO {
+    bvc_ctx *ctx;
+    size_t up_used = 0, down_used = 0;
+    struct Out { void *dst; const char *src; size_t n; };
+    std::vector<Out> outs;
+    explicit PinIO(bvc_ctx *c) : ctx(c) {}
+    static size_t al(size_t n) { return (n + 63) & ~(size_t)63; }
+    int reserve(size_t up_bytes, size_t down_bytes)
+    {
+        auto grow = [&](char **buf, size_t *cap, size_t need) -> int {
+            if (need <= *cap) return BVC_OK;
+            if (*buf) {
+                if (wait_stream(ctx) != hipSuccess) return fail(ctx, BVC_ERR_DEVICE, "wait before growing a pinned buffer");
+                (void)hipHostFree(*buf);
+                *buf = nullptr; *cap = 0;
+            }
+            const size_t want = need + need / 4 + 4096;
+            if (hipHostMalloc(reinterpret_cast<void **>(buf), want, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, BVC_ERR_ALLOC, "pinned host allocation failed");
+            }
+            *cap = want;
+            return BVC_OK;
+        };
+        int rc = grow(&ctx->h_up, &ctx->up_cap, up_bytes);
+        return rc == BVC_OK ? grow(&ctx->h_down, &ctx->down_cap, down_bytes) : rc;
+    }
+    hipError_t h2d(void *dev, const void *host, size_t n)
+    {
+        if (n == 0) return hipSuccess;
+        if (in_pinned(host, n)) return hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, ctx->stream);
+        if (up_used + n > ctx->up_cap) return hipErrorOutOfMemory;
+        char *p = ctx->h_up + up_used;
+        std::memcpy(p, host, n);
+        up_used += al(n);
+        return hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, ctx->stream);
+    }
+    hipError_t d2h(void *host, const void *dev, size_t n)
+    {
+        if (n == 0) return hipSuccess;
+        if (down_used + n > ctx->down_cap) return hipErrorOutOfMemory;
+        char *p = ctx->h_down + down_used;
+        down_used += al(n);
+        outs.push_back(Out{host, p, n});
+        return hipMemcpyAsync(p, dev, n, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    void deliver() { for (auto const &o : outs) std::memcpy(o.dst, o.src, o.n); outs.clear(); }
+};
+
+}  // namespace
+
+extern "C" {
+
+// ---- BGZF blocks on the device (inflate_kernel.hip) ------------------------------------------------------------------------
+int bvc_inflate_blocks(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                       uint8_t *out, int64_t out_bytes, uint32_t *status, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (n_blocks < 0 || comp_bytes < 0 || out_bytes < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    if (n_blocks == 0) return BVC_OK;
+    if (!comp || !blocks || !status || (!out && out_bytes > 0)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    if (flags & BVC_PTR_DEVICE) {
+        BVC_HIP(ctx, launch_inflate(ctx->stream, comp, blocks, n_blocks, out, status));
+        return BVC_OK;
+    }
+    for (int64_t i = 0; i < n_blocks; ++i) {
+        const bvc_bgzf_block &b = blocks[i];
+        if (b.comp_off < 0 || b.comp_len < 0 || b.comp_off + b.comp_len > comp_bytes || b.isize < 0 || b.isize > 65536 || b.out_off < 0 ||
+            b.out_off + b.isize > out_bytes)
+            return fail(ctx, BVC_ERR_ARG, "block outside its buffer");
+    }
+    uint8_t *d_c, *d_o; bvc_bgzf_block *d_b; uint32_t *d_s;
+    int rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_c = L.take<uint8_t>((size_t)comp_bytes, 16);
+        d_b = L.take<bvc_bgzf_block>((size_t)n_blocks);
+        d_s = L.take<uint32_t>((size_t)n_blocks);
+        d_o = L.take<uint8_t>((size_t)out_bytes);
+    });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_c, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_b, blocks, (size_t)n_blocks * sizeof(bvc_bgzf_block), hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, launch_inflate(ctx->stream, d_c, d_b, n_blocks, d_o, d_s));
+    BVC_HIP_D(ctx, hipMemcpyAsync(status, d_s, (size_t)n_blocks * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (out_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(out, d_o, (size_t)out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
+    return BVC_OK;
+}
+
+// ---- temp-batch pileup text -> columns -> records (pileup_kernel.hip) -------------------------------------------------------
+// The slices of a tile's meta buffer that both begin calls lay out alike: the line table, the first sample and the size of every
+// batch (each slice batch_pad bytes longer), the per-line words, 256 bytes of status (the totals at +64), the two offset arrays
+// and the tallies.  Returns the bytes from the status to the end of the tallies: what a begin call clears.
+static size_t carve_tile(Layout &L, PileupTile &P, int32_t n_batches, int32_t n_pos, size_t batch_pad, uint32_t *&line_start,
+                         int32_t *&sample0, int32_t *&n_in_batch)
+{
+    const size_t T = (size_t)n_pos, nb = (size_t)n_batches;
+    P.n_batches = n_batches; P.n_pos = n_pos; P.line_stride = n_pos + 1;
+    P.n_lines_cap = (int64_t)n_batches * n_pos;
+    P.line_start = line_start = L.take<uint32_t>(nb * (T + 1));
+    P.sample0 = sample0 = L.take<int32_t>(nb, batch_pad);
+    P.n_in_batch = n_in_batch = L.take<int32_t>(nb, batch_pad);
+    P.line_words = L.take<uint32_t>((size_t)P.n_lines_cap * 4);
+    const size_t from = L.at;
+    char *st = L.take<char>(256);
+    P.status = reinterpret_cast<uint32_t *>(st);
+    P.totals = reinterpret_cast<int64_t *>(st + 64);
+    P.entry_off = L.take<int64_t>(T + 1);
+    P.obs_off = L.take<int64_t>(T + 1);
+    P.tally = L.take<int32_t>(T * 32);
+    return L.at - from;
+}
+
+// What a begin call checks of a batch's row of the host's table before a kernel indexes the tile with it.  Text: every line inside the text,
+// the lines of a batch in order.
+static int check_lines(bvc_ctx *ctx, const uint32_t *ls, int32_t n_positions, int64_t text_bytes)
+{
+    for (int32_t t = 0; t < n_positions; ++t)
+        if (ls[t + 1] <= ls[t]) return fail(ctx, BVC_ERR_ARG, "line_start: every line holds at least its newline, lines of a batch ascend");
+    if (n_positions > 0 && (int64_t)ls[n_positions] > text_bytes) return fail(ctx, BVC_ERR_ARG, "line_start points outside the text");
+    return BVC_OK;
+}
+
+// Binary records: every record inside the buffer, as long as its length word says (the kernel bounds every load with the table).
+static int check_records(bvc_ctx *ctx, const uint8_t *records, const uint32_t *rs, int32_t n_positions, int64_t records_bytes)
+{
+    for (int32_t t = 0; t < n_positions; ++t) {
+        const int64_t r0 = rs[t], r1 = rs[t + 1];
+        if (r1 < r0 + 4 || r1 > records_bytes) return fail(ctx, BVC_ERR_ARG, "rec_start: records of a batch ascend, each holds its length word, all lie inside records_bytes");
+        const uint8_t *q = records + r0;
+        const int64_t len = (int64_t)((uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24));
+        if (r1 - r0 != 4 + len) return fail(ctx, BVC_ERR_ARG, "rec_start disagrees with a record's length word");
+    }
+    return BVC_OK;
+}
+
+// bvc_pileup_begin (bin = false: `data` is the text, row_start its line table) and bvc_pileup_begin_bin (true: the binary records of the same
+// content (host/pileup.h) go where the text goes, rec_start where line_start goes, and the tile is marked so that the count and write passes
+// launch pileup_bin_kernel); bvc_pileup_finish[_called] serve both alike.  The forms differ in the check of the table, in P.bin and in what
+// a tile that does not parse means.
+static int pileup_begin_impl(bvc_ctx *ctx, bool bin, const uint8_t *data, int64_t data_bytes, const uint32_t *row_start,
+                             const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
+                             int64_t *n_entries, int64_t *n_indels)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    PileupState::Tile &tile = ctx->pile.tile;
+    tile = PileupState::Tile{};
+    if (n_batches < 0 || n_positions < 0 || data_bytes < 0 || !n_entries || !n_indels) return fail(ctx, BVC_ERR_ARG, "bad argument");
+    if (data_bytes > (int64_t)0xFFFFFF00)
+        return fail(ctx, BVC_ERR_ARG, bin ? "more than 4 GiB of records in one tile (use fewer positions)"
+                                          : "more than 4 GiB of text in one tile (use fewer positions)");
+    const int64_t n_rows = (int64_t)n_batches * n_positions;
+    if (n_rows > 0 && (!data || !row_start || !sample0 || !n_in_batch)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n_positions > (int32_t)(0x7FFFFFFF / 64)) return fail(ctx, BVC_ERR_ARG, "too many positions in one call (split the tile)");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    *n_entries = 0; *n_indels = 0;
+    for (int32_t b = 0; b < n_batches; ++b) {
+        const uint32_t *rows = row_start + (int64_t)b * (n_positions + 1);
+        if (n_in_batch[b] < 0) return fail(ctx, BVC_ERR_ARG, "negative batch size");
+        const int rcb = bin ? check_records(ctx, data, rows, n_positions, data_bytes) : check_lines(ctx, rows, n_positions, data_bytes);
+        if (rcb != BVC_OK) return rcb;
+    }
+    const size_t T = (size_t)n_positions, nb = (size_t)n_batches;
+    PileupTile &P = tile.P;
+    uint32_t *d_rows; int32_t *d_s0, *d_nib;
+    size_t clear = 0;
+    int rc = ensure(ctx, ctx->pile.text, (size_t)data_bytes + 64);
+    if (rc == BVC_OK)
+        rc = carve(ctx, ctx->pile.meta, 0, [&](Layout &L) { clear = carve_tile(L, P, n_batches, n_positions, 0, d_rows, d_s0, d_nib); });
+    if (rc != BVC_OK) return rc;
+    P.text = reinterpret_cast<const uint8_t *>(ctx->pile.text.p);
+    P.bin = bin;
+    BVC_HIP_D(ctx, hipMemsetAsync(P.status, 0, clear, ctx->stream));     // status, totals, offsets of an empty tile, tallies
+    if (n_rows > 0) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(ctx->pile.text.p, data, (size_t)data_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_rows, row_start, nb * (T + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_s0, sample0, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_nib, n_in_batch, nb * 4, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
+    }
+    uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t tot[2] = {0, 0};
+    BVC_HIP_D(ctx, hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    if (st[0] != 0) {
+        if (!bin) return BVC_PILEUP_IRREGULAR;                           // the caller parses such a tile on the host
+        const std::string what = std::to_string(st[0]) + " malformed record(s) in the tile (an entry or an indel text runs past its record's end, or a "
+                                 "sample index is not below the batch's size)";
+        return fail(ctx, BVC_ERR_DATA, what.c_str());
+    }
+    tile.entries = tot[0]; tile.obs = tot[1]; tile.indels = st[1];
+    // pileup_finish_impl gathers indel_bytes of indel text on the device: a text tile's caller has the text itself and its tile gathers none
+    tile.indel_bytes = bin ? st[4] : 0;
+    tile.begun = true;
+    *n_entries = tot[0]; *n_indels = st[1];
+    return BVC_OK;
+}
+
+int bvc_pileup_begin(bvc_ctx *ctx, const char *text, int64_t text_bytes, const uint32_t *line_start,
+                     const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
+                     int64_t *n_entries, int64_t *n_indels)
+{
+    return pileup_begin_impl(ctx, false, reinterpret_cast<const uint8_t *>(text), text_bytes, line_start, sample0, n_in_batch, n_batches,
+                             n_positions, n_entries, n_indels);
+}
+
+int bvc_pileup_begin_bin(bvc_ctx *ctx, const uint8_t *records, int64_t records_bytes, const uint32_t *rec_start,
+                         const int32_t *sample0, const int32_t *n_in_batch, int32_t n_batches, int32_t n_positions,
+                         int64_t *n_entries, int64_t *n_indels)
+{
+    return pileup_begin_impl(ctx, true, records, records_bytes, rec_start, sample0, n_in_batch, n_batches, n_positions, n_entries, n_indels);
+}
+
+int bvc_pileup_begin_bgzf(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks,
+                          const int32_t *blocks_of_batch, const int32_t *skip_bytes, const int32_t *sample0, const int32_t *n_in_batch,
+                          int32_t n_batches, int32_t max_positions, int32_t reset, int32_t *n_positions, int32_t *lines_of_batch,
+                          int64_t *n_entries, int64_t *n_indels, int64_t *indel_text_bytes)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    PileupState &pile = ctx->pile;
+    pile.tile = PileupState::Tile{};
+    if (n_batches < 0 || max_positions < 0 || comp_bytes < 0 || !n_positions || !n_entries || !n_indels || !indel_text_bytes)
+        return fail(ctx, BVC_ERR_ARG, "bad argument");
+    if (n_batches > 0 && (!blocks_of_batch || !sample0 || !n_in_batch || !lines_of_batch)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (max_positions > (int32_t)(0x7FFFFFFF / 64)) return fail(ctx, BVC_ERR_ARG, "too many positions in one call (split the tile)");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    *n_positions = 0; *n_entries = 0; *n_indels = 0; *indel_text_bytes = 0;
+    const size_t nb = (size_t)n_batches;
+    if (reset || pile.left_len.size() != nb) { pile.left_len.assign(nb, 0u); pile.left_src.assign(nb, 0u); }
+    int64_t n_blocks = 0;
+    for (size_t b = 0; b < nb; ++b) { if (blocks_of_batch[b] < 0 || n_in_batch[b] < 0) return fail(ctx, BVC_ERR_ARG, "negative count"); n_blocks += blocks_of_batch[b]; }
+    if (n_blocks > 0 && (!comp || !blocks)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    // layout of the new text buffer: per batch [left over | its new blocks' output], every region from a 16-byte boundary
+    std::vector<bvc_bgzf_block> blk((size_t)n_blocks);
+    std::vector<bvc_pileup_region> reg(nb);
+    std::vector<uint32_t> seg_base(nb + 1);
+    std::vector<uint32_t> region_end(nb);
+    uint64_t at = 0;
+    int64_t bi = 0;
+    uint32_t segs = 0;
+    for (size_t b = 0; b < nb; ++b) {
+        at = (at + 15) & ~(uint64_t)15;
+        const uint32_t left = pile.left_len[b];
+        uint64_t fresh = 0;
+        for (int32_t k = 0; k < blocks_of_batch[b]; ++k, ++bi) {
+            const bvc_bgzf_block &in = blocks[bi];
+            if (in.comp_off < 0 || in.comp_len < 0 || in.comp_off + in.comp_len > comp_bytes || in.isize < 0 || in.isize > 65536)
+                return fail(ctx, BVC_ERR_ARG, "block outside its buffer");
+            blk[(size_t)bi] = in;
+            blk[(size_t)bi].out_off = (int64_t)(at + left + fresh);
+            fresh += (uint64_t)in.isize;
+        }
+        uint32_t skip = 0;
+        if (skip_bytes && left == 0 && skip_bytes[b] > 0) skip = (uint32_t)skip_bytes[b];
+        if (skip > fresh) return fail(ctx, BVC_ERR_ARG, "skip_bytes beyond the batch's first blocks");
+        if (at + left + fresh > (uint64_t)0xFFFFFF00u) return fail(ctx, BVC_ERR_ARG, "more than 4 GiB of text in one tile (send fewer blocks)");
+        reg[b].start = (uint32_t)at + skip; reg[b].len = left + (uint32_t)fresh - skip; reg[b].left_src = pile.left_src[b]; reg[b].left_len = left;
+        region_end[b] = reg[b].start + reg[b].len;
+        seg_base[b] = segs;
+        segs += (reg[b].len + 1023u) / 1024u;
+        at += left + fresh;
+    }
+    seg_base[nb] = segs;
+    const uint64_t text_bytes = at;
+    const int nw = 1 - pile.pz_cur;
+    PileupTile &P = pile.tile.P;
+    int32_t *d_s0, *d_nib, *d_lines; uint32_t *d_ls, *d_bst, *d_sb, *d_sn, *d_ends; bvc_bgzf_block *d_blk; bvc_pileup_region *d_reg;
+    size_t clear = 0;
+    int rc = ensure(ctx, pile.pz_text[nw], (size_t)text_bytes + 64);
+    if (rc == BVC_OK) rc = ensure(ctx, pile.pz_comp, (size_t)comp_bytes + 64);
+    if (rc == BVC_OK)
+        rc = carve(ctx, pile.meta, 0, [&](Layout &L) {
+            clear = carve_tile(L, P, n_batches, max_positions, 4, d_ls, d_s0, d_nib);
+            d_blk = L.take<bvc_bgzf_block>((size_t)n_blocks);
+            d_bst = L.take<uint32_t>((size_t)n_blocks);
+            d_reg = L.take<bvc_pileup_region>(nb);
+            d_sb = L.take<uint32_t>(nb + 1);
+            d_sn = L.take<uint32_t>(segs, 4);
+            d_lines = L.take<int32_t>(nb, 4);
+            d_ends = L.take<uint32_t>(nb, 4);
+        });
+    if (rc != BVC_OK) return rc;
+    uint8_t *text_out = reinterpret_cast<uint8_t *>(pile.pz_text[nw].p);
+    P.text = text_out;
+    int32_t *d_T = reinterpret_cast<int32_t *>(reinterpret_cast<char *>(P.status) + 128);
+    P.n_pos_dev = d_T;
+    PinIO io(ctx);
+    rc = io.reserve((n_blocks > 0 && in_pinned(comp, (size_t)comp_bytes) ? 0 : (size_t)comp_bytes) + (size_t)n_blocks * sizeof(bvc_bgzf_block) +
+                        nb * (sizeof(bvc_pileup_region) + 12) + 1024,
+                    (size_t)n_blocks * 4 + nb * 8 + 1024);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemsetAsync(P.status, 0, clear, ctx->stream));
+    std::vector<uint32_t> bst((size_t)n_blocks);
+    std::vector<uint32_t> ends(nb);
+    uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t tot[2] = {0, 0};
+    int32_t Tgot = 0;
+    if (nb > 0) {
+        if (n_blocks > 0) {
+            BVC_HIP_D(ctx, io.h2d(pile.pz_comp.p, comp, (size_t)comp_bytes));
+            BVC_HIP_D(ctx, io.h2d(d_blk, blk.data(), (size_t)n_blocks * sizeof(bvc_bgzf_block)));
+        }
+        BVC_HIP_D(ctx, io.h2d(d_reg, reg.data(), nb * sizeof(bvc_pileup_region)));
+        BVC_HIP_D(ctx, io.h2d(d_sb, seg_base.data(), (nb + 1) * 4));
+        BVC_HIP_D(ctx, io.h2d(d_s0, sample0, nb * 4));
+        BVC_HIP_D(ctx, io.h2d(d_nib, n_in_batch, nb * 4));
+        BVC_HIP_D(ctx, launch_region_carry(ctx->stream, reinterpret_cast<const uint8_t *>(pile.pz_text[pile.pz_cur].p), text_out, d_reg,
+                                           n_batches));
+        if (n_blocks > 0)
+            BVC_HIP_D(ctx, launch_inflate(ctx->stream, reinterpret_cast<const uint8_t *>(pile.pz_comp.p), d_blk, n_blocks, text_out, d_bst));
+        BVC_HIP_D(ctx, launch_region_index(ctx->stream, P, d_reg, d_sb, (int64_t)segs, d_sn, d_lines, max_positions));
+        BVC_HIP_D(ctx, launch_region_ends(ctx->stream, P, d_ends));
+        BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
+        if (n_blocks > 0) BVC_HIP_D(ctx, io.d2h(bst.data(), d_bst, (size_t)n_blocks * 4));
+        BVC_HIP_D(ctx, io.d2h(lines_of_batch, d_lines, nb * 4));
+        BVC_HIP_D(ctx, io.d2h(ends.data(), d_ends, nb * 4));
+        BVC_HIP_D(ctx, io.d2h(&Tgot, d_T, 4));
+    }
+    BVC_HIP_D(ctx, io.d2h(st, P.status, sizeof st));
+    BVC_HIP_D(ctx, io.d2h(tot, P.totals, sizeof tot));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    for (int64_t i = 0; i < n_blocks; ++i)
+        if (bst[(size_t)i] != 0) {
+            pile.left_len.assign(nb, 0u);                        // the stream of this window is broken: nothing to carry on with
+            return fail(ctx, BVC_ERR_DATA, bst[(size_t)i] == 10 ? "a BGZF block of a temp batch fails its CRC32"
+                                                                : "a BGZF block of a temp batch is not valid deflate of its ISIZE bytes");
+        }
+    // what this tile leaves of every batch: from the end of its last line to the end of its region
+    for (size_t b = 0; b < nb; ++b) { pile.left_src[b] = ends[b]; pile.left_len[b] = region_end[b] - ends[b]; }
+    pile.pz_cur = nw;
+    P.n_pos = Tgot; P.n_pos_dev = nullptr;
+    pile.tile.text_bytes = (int64_t)text_bytes;
+    pile.tile.on_device_text = true;
+    *n_positions = Tgot;
+    if (Tgot == 0) return BVC_OK;
+    if (st[0] != 0) return BVC_PILEUP_IRREGULAR;
+    pile.tile.entries = tot[0]; pile.tile.obs = tot[1]; pile.tile.indels = st[1]; pile.tile.indel_bytes = st[4];
+    pile.tile.begun = true;
+    *n_entries = tot[0]; *n_indels = st[1]; *indel_text_bytes = st[4];
+    return BVC_OK;
+}
+
+int bvc_pileup_text(bvc_ctx *ctx, char *text, int64_t text_cap, int64_t *text_bytes_needed, uint32_t *line_start)
+{
+    if (!ctx || !text_bytes_needed) return BVC_ERR_ARG;
+    const PileupState::Tile &tile = ctx->pile.tile;
+    if (!tile.on_device_text) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_text without a tile from bvc_pileup_begin_bgzf");
+    *text_bytes_needed = tile.text_bytes;
+    if (!text) return BVC_OK;
+    if (text_cap < tile.text_bytes || !line_start) return fail(ctx, BVC_ERR_ARG, "text buffer too small / null line table");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const PileupTile &P = tile.P;
+    if (tile.text_bytes) BVC_HIP(ctx, hipMemcpyAsync(text, P.text, (size_t)tile.text_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (P.n_batches > 0)
+        BVC_HIP(ctx, hipMemcpy2DAsync(line_start, (size_t)(P.n_pos + 1) * 4, P.line_start, (size_t)P.line_stride * 4, (size_t)(P.n_pos + 1) * 4,
+                                      (size_t)P.n_batches, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+// bvc_pileup_finish (called_off = null: the entries of every position) and bvc_pileup_finish_called (the entries of the called
+// positions only, compacted on the device; called_cap = room in entries / samples)
+static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                              const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                              int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
+                              int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
+                              bvc_group_result *grp_results)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    PileupState &pile = ctx->pile;
+    PileupState::Tile &tile = pile.tile;
+    if (!tile.begun) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_finish without a bvc_pileup_begin that returned BVC_OK");
+    if (tile.on_device_text && tile.indels > 0 && !indel_text) return fail(ctx, BVC_ERR_ARG, "indel_text is needed: the tile's text is on the device only");
+    tile.begun = false;
+    PileupTile &P = tile.P;
+    const int64_t T = P.n_pos, n_e = tile.entries, n_o = tile.obs, n_i = tile.indels, n_it = tile.indel_bytes;
+    if (!carry_in || !carry_out || !entry_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if (T > 0 && (!ref_base || !tally || !results)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    const bool called_only = called_off != nullptr;
+    if ((n_e > 0 && !called_only && (!entries || !samples)) || (n_i > 0 && !indels)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if (called_only && (called_cap < 0 || (called_cap > 0 && (!entries || !samples)))) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
+    if (n_groups > 0 && (!grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    int8_t *d_ref; bvc_site_result *d_res; uint8_t *d_g, *d_itext; bvc_group_result *d_gres; int64_t *d_called_off;
+    int rc = carve(ctx, pile.out, 256, [&](Layout &L) {
+        P.entries = L.take<bvc_pileup_entry>((size_t)n_e, 16);
+        P.samples = L.take<int32_t>((size_t)n_e, 16);
+        P.obs_base = L.take<int8_t>((size_t)n_o, 16);
+        P.obs_qual = L.take<int8_t>((size_t)n_o, 16);
+        P.obs_label = L.take<uint8_t>((size_t)(n_groups ? n_o : 0), 16);
+        P.indels = L.take<bvc_pileup_indel>((size_t)n_i, 16);
+        d_ref = L.take<int8_t>((size_t)T, 16);
+        d_res = L.take<bvc_site_result>((size_t)T);
+        d_g = L.take<uint8_t>((size_t)(n_groups ? n_samples : 0), 16);
+        d_gres = L.take<bvc_group_result>((size_t)T * (size_t)n_groups);
+        d_itext = L.take<uint8_t>((size_t)(indel_text ? n_it : 0), 16);
+        d_called_off = L.take<int64_t>(called_only ? (size_t)(T + 1) : 0);
+    });
+    if (rc != BVC_OK) return rc;
+    P.indel_cap = (uint32_t)n_i;
+    P.group_of_sample = d_g; P.n_samples = n_groups ? n_samples : 0; P.n_groups = n_groups;
+    const uint32_t cin = (uint32_t)(carry_in[0] & 7u) | ((uint32_t)(carry_in[4] & 1u) << 3) | 0x80u | ((uint32_t)carry_in[1] << 8) |
+                         ((uint32_t)carry_in[2] << 16) | ((uint32_t)carry_in[3] << 24);
+    uint32_t cout = cin;
+    PinIO io(ctx);
+    rc = io.reserve((size_t)T + (size_t)(n_groups > 0 ? n_samples : 0) + 1024,
+                    (size_t)T * (sizeof(bvc_site_result) + 32 * 4 + 8 + (size_t)n_groups * sizeof(bvc_group_result)) +
+                        (size_t)(called_only ? 0 : n_e) * (sizeof(bvc_pileup_entry) + 4) + (called_only ? (size_t)(T + 1) * 8 : 0) +
+                        (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)n_it + 4096);
+    if (rc != BVC_OK) return rc;
+    if (T > 0) {
+        BVC_HIP_D(ctx, io.h2d(d_ref, ref_base, (size_t)T));
+        // the label vector goes up in front of the write pass: that pass turns it into one label byte per observation (obs_label)
+        if (n_groups > 0 && n_samples > 0) BVC_HIP_D(ctx, io.h2d(d_g, group_of_sample, (size_t)n_samples));
+        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, launch_pileup_write(ctx->stream, P, cin));
+        if (n_groups > 0)
+            rc = run_csr_labels_device(ctx, T, P.obs_off, reinterpret_cast<const uint8_t *>(P.obs_base),
+                                       reinterpret_cast<const uint8_t *>(P.obs_qual), P.obs_label, d_ref, min_af, n_groups, d_res, d_gres);
+        else
+            rc = run_csr_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, d_ref, min_af, nullptr, nullptr, d_res);
+        if (rc == BVC_OK) rc = join_side(ctx);
+        if (rc != BVC_OK) return drain_on_error(ctx, rc);
+        BVC_HIP_D(ctx, io.d2h(results, d_res, (size_t)T * sizeof(bvc_site_result)));
+        if (n_groups > 0)
+            BVC_HIP_D(ctx, io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
+        BVC_HIP_D(ctx, io.d2h(tally, P.tally, (size_t)T * 32 * 4));
+        if (n_e && !called_only) {
+            BVC_HIP_D(ctx, io.d2h(entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
+            BVC_HIP_D(ctx, io.d2h(samples, P.samples, (size_t)n_e * 4));
+        }
+        if (called_only) {
+            BVC_HIP_D(ctx, launch_called_scan(ctx->stream, P, d_res, d_called_off));
+            BVC_HIP_D(ctx, io.d2h(called_off, d_called_off, (size_t)(T + 1) * 8));
+        }
+        if (n_i && indel_text) {
+            BVC_HIP_D(ctx, launch_indel_text(ctx->stream, P, d_itext, (uint32_t)n_it, P.status + 5));
+            if (n_it) BVC_HIP_D(ctx, io.d2h(indel_text, d_itext, (size_t)n_it));
+        }
+        if (n_i) BVC_HIP_D(ctx, io.d2h(indels, P.indels, (size_t)n_i * sizeof(bvc_pileup_indel)));
+        if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, io.d2h(&cout, P.status + 3, 4));
+    }
+    BVC_HIP_D(ctx, io.d2h(entry_off, P.entry_off, (size_t)(T + 1) * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    if (called_only && T == 0) called_off[0] = 0;
+    if (called_only && T > 0 && called_off[T] > 0) {
+        // the second trip: the called positions' entries, gathered on the device (typically a few per cent of the tile's)
+        const int64_t n_c = called_off[T];
+        if (n_c > called_cap) return fail(ctx, BVC_ERR_ARG, "called_cap is smaller than the entries of the called positions (n_entries of the begin call always suffices)");
+        bvc_pileup_entry *d_ce; int32_t *d_cs;
+        rc = carve(ctx, pile.called, 0, [&](Layout &L) {
+            d_ce = L.take<bvc_pileup_entry>((size_t)n_c);
+            d_cs = L.take<int32_t>((size_t)n_c);
+        });
+        if (rc != BVC_OK) return rc;
+        io.down_used = 0;
+        rc = io.reserve(0, (size_t)n_c * (sizeof(bvc_pileup_entry) + 4) + 4096);
+        if (rc != BVC_OK) return rc;
+        BVC_HIP_D(ctx, launch_called_gather(ctx->stream, P, d_called_off, d_ce, d_cs));
+        BVC_HIP_D(ctx, io.d2h(entries, d_ce, (size_t)n_c * sizeof(bvc_pileup_entry)));
+        BVC_HIP_D(ctx, io.d2h(samples, d_cs, (size_t)n_c * 4));
+        BVC_HIP_D(ctx, wait_stream(ctx));
+        io.deliver();
+    }
+    carry_out[0] = (uint8_t)(cout & 7u); carry_out[1] = (uint8_t)(cout >> 8); carry_out[2] = (uint8_t)(cout >> 16);
+    carry_out[3] = (uint8_t)(cout >> 24); carry_out[4] = (uint8_t)((cout >> 3) & 1u);
+    return BVC_OK;
+}
+
+int bvc_pileup_finish(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                      const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                      int64_t *entry_off, int32_t *tally, bvc_pileup_entry *entries, int32_t *samples,
+                      bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results, bvc_group_result *grp_results)
+{
+    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, nullptr, 0,
+                              entries, samples, indels, indel_text, results, grp_results);
+}
+
+int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                             const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                             int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
+                             int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
+                             bvc_group_result *grp_results)
+{
+    if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
+                              called_cap, entries, samples, indels, indel_text, results, grp_results);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """PCIe-inclusive rate of the dense entry point when the boundary is handed HOST buffers (BVC_PTR_HOST): the tile is
-staged through device memory in chunks, the upload of chunk i+1 under the kernels of chunk i (bvc_api.hip, run_chunks).
+staged through device memory in chunks, the upload of chunk i+1 under the kernels of chunk i (bvc_lrt.hip, run_chunks).
 Pageable and pinned host memory.  usage: tools/host_pointer_rate.py [n_sites] [n_samples]   (needs a GPU)"""
 import json
 import os
