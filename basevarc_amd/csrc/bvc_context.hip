@@ -138,6 +138,7 @@ const Knob kKnobs[] = {
     {"em_engine", "BVC_EM_ENGINE", 0, 1, 1, 0, &LaunchState::em_engine},
     {"em_tiny_regions", "BVC_EM_TINY_REGIONS", 0, 1, 1, 0, &LaunchState::em_tiny_regions},
     {"em_prune", "BVC_EM_PRUNE", 0, 1, 1, 1, &LaunchState::em_prune},
+    {"csr_scatter_max", "BVC_CSR_SCATTER_MAX", 0, 1 << 30, 1, 64, &LaunchState::csr_scatter_max},
     {"host_chunk_kib", nullptr, 1, 1 << 21, 1, 1 << 19, &LaunchState::host_chunk_kib},
 };
 }  // namespace

@@ -73,6 +73,7 @@ struct bvc_ctx {
     DevBuf d_em[kRing + 1];
     DevBuf d_emg[kRing];               // the same for the (site, group) pseudo-sites of group calls
     uint32_t *d_sink = nullptr;        // 256 bytes: sink of the streaming-read measurement kernel; bvc_pack_dense's counter at byte 64
+    DevBuf d_acc;                      // bvc_counts_add_dense*: a chunk's histograms, before they are added to the caller's counts
     DevBuf d_grp_labels;               // group mode: the call's group vector clamped to 0..n_groups (hist_kernel.hip)
     int64_t *d_grp_scratch = nullptr;  // group mode: "samples ordered by group" flag + column bounds (hist_kernel.hip)
     // staging for BVC_PTR_HOST calls: two sets, so that the upload of chunk i+1 (copy stream) runs under the kernels
@@ -179,6 +180,17 @@ inline int join_side(bvc_ctx *ctx)
     return BVC_OK;
 }
 
+// Grows a buffer that a stage 2 on a side stream may still be reading: the context's stream waits for the side streams first (ensure
+// waits for the context's stream).
+inline int ensure_joined(bvc_ctx *ctx, DevBuf &buf, size_t need)
+{
+    if (need > buf.cap) {
+        const int rc = join_side(ctx);
+        if (rc != BVC_OK) return rc;
+    }
+    return ensure(ctx, buf, need);
+}
+
 // Does [p, p + n) lie inside an allocation of bvc_host_alloc?  A transfer from / to it needs no bounce buffer.
 bool in_pinned(const void *p, size_t n);
 
@@ -199,6 +211,19 @@ inline int check_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t
     const int rc = check_common(ctx, n_sites, a, b, c, d);
     if (rc != BVC_OK) return rc;
     return n_samples >= 0 && row_stride >= n_samples ? BVC_OK : fail(ctx, BVC_ERR_ARG, "need 0 <= n_samples <= row_stride");
+}
+
+// Host-pointer ragged calls: the chunking and the uploads index the observations with offsets[0..n_sites].
+inline int check_offsets_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets)
+{
+    bool ok = offsets[0] == 0;
+    for (int64_t s = 0; s < n_sites && ok; ++s) ok = offsets[s + 1] >= offsets[s];
+    return ok ? BVC_OK : fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
+}
+
+inline int check_n_groups(bvc_ctx *ctx, int32_t n_groups)
+{
+    return n_groups >= 1 && n_groups <= BVC_MAX_GROUPS ? BVC_OK : fail(ctx, BVC_ERR_ARG, "n_groups must be 1..32");
 }
 
 // The two stages on ragged columns in device memory (bvc_lrt.hip); bvc_pileup_finish runs them on the columns of its tile.

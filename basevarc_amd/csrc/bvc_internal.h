@@ -33,6 +33,8 @@ struct LaunchState {
     int em_tiny_regions = 0;       // 1: regions whose sites all have <= 8 quality values per allele take the one-lane-per-allele
                                // kernel (binned qualities: 0.23 -> 0.17 ms per 4000 sites).  Off by default: that kernel adds in a
                                // different order, so a site's last bits would depend on whether its five region neighbours are binned too
+    int csr_scatter_max = 64;      // bvc_counts_add_csr*: a site with at most this many observations in the call takes one atomic per
+                                   // observation (hist_csr_scatter_kernel, counts_kernel.hip) instead of a histogram in LDS; 0 = never
     int em_prune = 1;              // item engine: 1 = a level does not run the subset without the deepest candidate when a bound on its
                                    // log-likelihood shows that it cannot be the level's first minimum (em_items.hip, site_decide); 0 = it always runs
     int dbg_levels = 0;            // BVC_DBG_LEVELS (timing only, records wrong): cut region_kernel short after a phase; 0 = run all
@@ -204,6 +206,17 @@ hipError_t launch_hist_csr_groups(LaunchState &st, hipStream_t stream, int64_t n
 // packed byte base << 6 | qual.  Any byte alignment of the three arrays
 hipError_t launch_hist_csr_labels(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
                                   const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, uint32_t *counts);
+
+// ---- counts accumulated over chunks of a cohort's samples (counts_kernel.hip; hist_csr_add_kernel in pileup_kernel.hip) ------
+// dst[i] += src[i], i < n_words (mod 2^32): the fold of a chunk's scratch histograms into the caller's counts, and bvc_counts_merge
+hipError_t launch_counts_add(hipStream_t stream, int64_t n_words, uint32_t *dst, const uint32_t *src);
+// Ragged stage 1 ADDED to the caller's counts -- [site][512], or with group_of_obs [site][n_groups + 1][512]; quals == nullptr: obs is the
+// packed byte.  The two launches share a call's sites: the scatter kernel takes those of at most max_len observations (max_len <= 0:
+// none), the histogram kernel those of more than min_len.  Any byte alignment of the arrays.
+hipError_t launch_hist_csr_scatter(const LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
+                                   const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, int64_t max_len, uint32_t *counts);
+hipError_t launch_hist_csr_add(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
+                               const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, int64_t min_len, uint32_t *counts);
 
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);

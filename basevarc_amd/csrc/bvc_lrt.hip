@@ -21,17 +21,6 @@ hipStream_t em_stream(bvc_ctx *ctx, int by_default)
     return k == 0 ? ctx->side : (k == 1 ? ctx->side_b : ctx->side_c);
 }
 
-// Grows a buffer that a stage 2 on a side stream may still be reading: the context's stream waits for the side streams first (ensure
-// waits for the context's stream).
-int ensure_joined(bvc_ctx *ctx, DevBuf &buf, size_t need)
-{
-    if (need > buf.cap) {
-        const int rc = join_side(ctx);
-        if (rc != BVC_OK) return rc;
-    }
-    return ensure(ctx, buf, need);
-}
-
 // Device scratch of the item engine for a stage 2 of n_sites sites on ring buffer `slot` (null when the call will not
 // use the engine: launch_lrt's rule).  Growing it waits for whatever may still be using the old one.
 int em_scratch_for(bvc_ctx *ctx, int slot, int64_t n_sites, double min_af, void **out, int n_groups = 0)
@@ -49,22 +38,23 @@ int em_scratch_for(bvc_ctx *ctx, int slot, int64_t n_sites, double min_af, void 
 // The two stages of one call on device pointers.  `stage1(hist)` launches the histogram pass (dense, ragged, ...) on the
 // context's stream into a buffer of the ring -- the counts, or with n_groups > 0 the group histograms; `stage2(s2, slot)`
 // launches the EM/LRT on the same stream, or in overlap mode on a side stream (of em_stream(ctx, em_streams)) behind an event.
+// grp_in: the group histograms are the caller's (bvc_lrt_hist_groups): stage 1 has nothing to fill and stage 2 only reads them.
 template <class Stage1, class Stage2>
 int run_stages(bvc_ctx *ctx, int64_t n_sites, int n_groups, bool zero_counts, double min_af, int em_streams, Stage1 stage1,
-               Stage2 stage2)
+               Stage2 stage2, const uint32_t *grp_in = nullptr)
 {
     const size_t cbytes = (size_t)n_sites * BVC_NCLASS * sizeof(uint32_t), gbytes = cbytes * (size_t)(n_groups + 1);
     const int buf = ctx->overlap ? ctx->flip : 0;
     if (ctx->overlap) ctx->flip = (ctx->flip + 1) % bvc_ctx::kRing;
     DevBuf &cnt = ctx->d_cnt[buf], &grp = ctx->d_grp[buf];
     int rc = ensure_joined(ctx, cnt, cbytes);
-    if (rc == BVC_OK && n_groups > 0) rc = ensure_joined(ctx, grp, gbytes);
+    if (rc == BVC_OK && n_groups > 0 && !grp_in) rc = ensure_joined(ctx, grp, gbytes);
     RingSlot slot;
     if (rc == BVC_OK) rc = em_scratch_for(ctx, buf, n_sites, min_af, &slot.em);
     if (rc == BVC_OK && n_groups > 0) rc = em_scratch_for(ctx, buf, n_sites, min_af, &slot.emg, n_groups);
     if (rc != BVC_OK) return rc;
     slot.counts = reinterpret_cast<uint32_t *>(cnt.p);
-    if (n_groups > 0) slot.grp = reinterpret_cast<uint32_t *>(grp.p);
+    if (n_groups > 0) slot.grp = grp_in ? const_cast<uint32_t *>(grp_in) : reinterpret_cast<uint32_t *>(grp.p);
     bvc_ctx::Triple t{nullptr, nullptr, nullptr, nullptr, n_sites};
     const bool timed = ctx->profiling && take_timing_events(ctx, t);
     auto enqueue = [&]() -> int {
@@ -244,7 +234,7 @@ int run_dense_host(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row
 // overlap mode, on a side stream.  Dense tiles and ragged columns differ only in their stage 1.
 template <class Stage1>
 int run_group_stages(bvc_ctx *ctx, int64_t ns, int n_groups, bool long_rows, Stage1 stage1, const int8_t *r, double min_af,
-                     bvc_site_result *res, bvc_group_result *gres)
+                     bvc_site_result *res, bvc_group_result *gres, const uint32_t *grp_in = nullptr)
 {
     return run_stages(ctx, ns, n_groups, false, min_af, 2, stage1, [&](hipStream_t s2, const RingSlot &slot) -> int {
         BVC_HIP(ctx, launch_sum_groups(s2, ns, n_groups + 1, slot.grp, slot.counts));
@@ -254,7 +244,7 @@ int run_group_stages(bvc_ctx *ctx, int64_t ns, int n_groups, bool long_rows, Sta
                                 slot.em));
         BVC_HIP(ctx, launch_lrt_groups(ctx->ls, s2, ns, n_groups, slot.grp, r, min_af, ctx->d_lut, res, gres, shared, per_launch, slot.emg));
         return BVC_OK;
-    });
+    }, grp_in);
 }
 
 // The group calls on ragged columns with a sample index per observation.
@@ -483,6 +473,41 @@ int bvc_lrt_hist(bvc_ctx *ctx, int64_t n_sites, const uint32_t *counts, const in
     return BVC_OK;
 }
 
+// Stage 2 of the group calls on the caller's group histograms [n_sites][n_groups + 1][512] (slot n_groups: the samples in no group), as
+// bvc_counts_add_dense_groups / bvc_counts_add_csr_group_labels accumulate them: run_group_stages with no stage 1.  The overall counts are
+// summed into the context's ring; grp_counts is only read.
+int bvc_lrt_hist_groups(bvc_ctx *ctx, int64_t n_sites, const uint32_t *grp_counts, const int8_t *ref_base, double min_af, int32_t n_groups,
+                        bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags)
+{
+    int rc = check_common(ctx, n_sites, grp_counts, ref_base, results, results);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_n_groups(ctx, n_groups)) != BVC_OK) return rc;
+    if (!grp_results) return fail(ctx, BVC_ERR_ARG, "null group pointer");
+    if (n_sites == 0) return BVC_OK;
+    auto run_device = [&](const uint32_t *g, const int8_t *r, bvc_site_result *res, bvc_group_result *gres) {
+        return run_group_stages(ctx, n_sites, n_groups, false, [](uint32_t *) { return hipSuccess; }, r, min_af, res, gres, g);
+    };
+    if (flags & BVC_PTR_DEVICE) return run_device(grp_counts, ref_base, results, grp_results);
+    const size_t gwords = (size_t)n_sites * (size_t)(n_groups + 1) * BVC_NCLASS;
+    uint32_t *d_g; int8_t *d_r; bvc_site_result *d_res; bvc_group_result *d_gres;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_g = L.take<uint32_t>(gwords);
+        d_r = L.take<int8_t>((size_t)n_sites);
+        d_res = L.take<bvc_site_result>((size_t)n_sites);
+        d_gres = L.take<bvc_group_result>((size_t)n_sites * n_groups);
+    });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_g, grp_counts, gwords * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n_sites, hipMemcpyHostToDevice, ctx->stream));
+    rc = run_device(d_g, d_r, d_res, d_gres);
+    if (rc == BVC_OK) rc = join_side(ctx);
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(grp_results, d_gres, (size_t)n_sites * n_groups * sizeof(bvc_group_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
+    return BVC_OK;
+}
+
 // Ragged host-pointer calls (bvc_lrt_csr, bvc_lrt_csr_comb, bvc_lrt_csr_packed).  quals == nullptr: packed observations.
 // The per-site arrays (offsets, ref_base, candidate lists) go up once and the records come down once; the observations go
 // through two staging sets in chunks of sites, the upload of chunk i + 1 (copy stream) under the kernels of chunk i, the
@@ -569,14 +594,6 @@ static int run_csr_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, c
     BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n_sites * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipStreamSynchronize(ctx->stream));
     return BVC_OK;
-}
-
-// Host-pointer ragged calls: the chunking and the uploads index the observations with offsets[0..n_sites].
-static int check_offsets_host(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets)
-{
-    bool ok = offsets[0] == 0;
-    for (int64_t s = 0; s < n_sites && ok; ++s) ok = offsets[s + 1] >= offsets[s];
-    return ok ? BVC_OK : fail(ctx, BVC_ERR_ARG, "offsets must start at 0 and be non-decreasing");
 }
 
 int bvc_lrt_csr_comb(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets,

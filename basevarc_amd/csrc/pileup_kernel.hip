@@ -510,12 +510,16 @@ __device__ __forceinline__ void csr_groups_zero(uint32_t *ghist, int words, int 
     for (int i = tid * 4; i < words; i += kCsrGroupThreads * 4) *reinterpret_cast<u32x4 *>(&ghist[i]) = u32x4{0u, 0u, 0u, 0u};
 }
 
+// ADD: dst is the caller's running counts and the site's counters are added to them (the workgroup is the only writer of the site's
+// words; a class nobody was seen in is not touched).
+template <bool ADD = false>
 __device__ __forceinline__ void csr_groups_fold(uint32_t *ghist, uint32_t *__restrict__ dst, int classes, int log2c, int tid)
 {
     for (int key = tid; key < classes; key += kCsrGroupThreads) {
         uint32_t sum = 0;
         for (int v = 0; v < (1 << log2c); ++v) { const int at = (key << log2c) + ((v + key) & ((1 << log2c) - 1)); sum += ghist[at]; ghist[at] = 0u; }
-        dst[key] = sum;
+        if constexpr (ADD) { if (sum) dst[key] += sum; }
+        else dst[key] = sum;
     }
 }
 
@@ -588,21 +592,26 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_groups_kernel(
 // flight, in front of them the up to three observations before the first aligned one and behind them the up to three that fill no
 // word.  Where they disagree (device callers hand in arbitrary pointers) consecutive lanes take consecutive observations with byte
 // loads, four per lane in flight, as hist_csr_groups_kernel reads its bases and qualities.
-template <bool PACKED>
-__global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
+//
+// The body serves two kernels.  hist_csr_labels_kernel (LABELS, not ADD) is the stage 1 of the calls above.  hist_csr_add_kernel (ADD)
+// is the stage 1 of bvc_counts_add_csr[_packed] (LABELS = false: one histogram per site, no label array) and of
+// bvc_counts_add_csr_group_labels: it ADDS a site's counters to the caller's counts and leaves the sites of at most min_len
+// observations to hist_csr_scatter_kernel (counts_kernel.hip).
+template <bool PACKED, bool LABELS, bool ADD>
+__device__ __forceinline__ void hist_csr_labels_body(
     int64_t n_sites, const int64_t *__restrict__ offsets, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ quals,
-    const uint8_t *__restrict__ group_of_obs, int n_groups, int log2c, uint32_t *__restrict__ counts)
+    const uint8_t *__restrict__ group_of_obs, int n_groups, int log2c, int64_t min_len, uint32_t *__restrict__ counts)
 {
     BVC_POISON_LDS();
-    extern __shared__ __attribute__((aligned(16))) uint32_t ghist[];        // [n_groups + 1][512][1 << log2c]
+    extern __shared__ __attribute__((aligned(16))) uint32_t ghist[];        // [n_groups + 1 or 1][512][1 << log2c]
     const int tid = threadIdx.x;
-    const int classes = (n_groups + 1) * BVC_NCLASS;
+    const int classes = (LABELS ? n_groups + 1 : 1) * BVC_NCLASS;
     const int words = classes << log2c;
     const uint32_t copy = (uint32_t)tid & ((1u << log2c) - 1u);
     auto one = [&](uint32_t b, uint32_t q, uint32_t lab) {
         if (PACKED) { q = b & 63u; b >>= 6; }
         if (PACKED ? q != 63u : (b < 4u && q < 128u)) {
-            const uint32_t g = lab < (uint32_t)n_groups ? lab : (uint32_t)n_groups;
+            const uint32_t g = !LABELS ? 0u : (lab < (uint32_t)n_groups ? lab : (uint32_t)n_groups);
             const uint32_t at = ((g * BVC_NCLASS + ((b << 7) | q)) << log2c) | copy;
             if (BVC_LDS_OK(0x503, at, words)) atomicAdd(&ghist[at], 1u);
         }
@@ -615,7 +624,8 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
     __syncthreads();
     for (int64_t site = blockIdx.x; site < n_sites; site += gridDim.x) {
         const int64_t o0 = offsets[site], n = offsets[site + 1] - o0;
-        const uint8_t *__restrict__ pb = obs + o0, *__restrict__ pq = PACKED ? pb : quals + o0, *__restrict__ pl = group_of_obs + o0;
+        if constexpr (ADD) { if (n <= min_len) continue; }                   // (workgroup-uniform)
+        const uint8_t *__restrict__ pb = obs + o0, *__restrict__ pq = PACKED ? pb : quals + o0, *__restrict__ pl = LABELS ? group_of_obs + o0 : pb;
         const uint32_t mis = (uint32_t)(uintptr_t)pb & 3u;
         if (((uint32_t)(uintptr_t)pl & 3u) == mis && ((uint32_t)(uintptr_t)pq & 3u) == mis) {
             constexpr int U = 2;
@@ -623,8 +633,8 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
             const int64_t head = to_word < n ? to_word : n;                  // observations in front of the first aligned word
             const int64_t n4 = (n - head) >> 2, tail = head + 4 * n4;        // whole words; the first observation behind them
             if (tid < 3) {
-                if (tid < head) one(pb[tid], pq[tid], pl[tid]);
-                if (tail + tid < n) one(pb[tail + tid], pq[tail + tid], pl[tail + tid]);
+                if (tid < head) one(pb[tid], pq[tid], LABELS ? pl[tid] : 0u);
+                if (tail + tid < n) one(pb[tail + tid], pq[tail + tid], LABELS ? pl[tail + tid] : 0u);
             }
             const uint32_t *__restrict__ wb = reinterpret_cast<const uint32_t *>(pb + head);
             const uint32_t *__restrict__ wq = reinterpret_cast<const uint32_t *>(pq + head);
@@ -635,12 +645,12 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int64_t at = j + (int64_t)u * kCsrGroupThreads;
-                    vb[u] = wb[at]; vq[u] = PACKED ? 0u : wq[at]; vl[u] = wl[at];
+                    vb[u] = wb[at]; vq[u] = PACKED ? 0u : wq[at]; vl[u] = LABELS ? wl[at] : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) four(vb[u], vq[u], vl[u]);
             }
-            for (; j < n4; j += kCsrGroupThreads) four(wb[j], PACKED ? 0u : wq[j], wl[j]);
+            for (; j < n4; j += kCsrGroupThreads) four(wb[j], PACKED ? 0u : wq[j], LABELS ? wl[j] : 0u);
         } else {
             constexpr int U = 4;
             int64_t i = tid;
@@ -649,17 +659,33 @@ __global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
 #pragma unroll
                 for (int u = 0; u < U; ++u) {
                     const int64_t at = i + (int64_t)u * kCsrGroupThreads;
-                    b[u] = pb[at]; q[u] = PACKED ? 0u : pq[at]; lab[u] = pl[at];
+                    b[u] = pb[at]; q[u] = PACKED ? 0u : pq[at]; lab[u] = LABELS ? pl[at] : 0u;
                 }
 #pragma unroll
                 for (int u = 0; u < U; ++u) one(b[u], q[u], lab[u]);
             }
-            for (; i < n; i += kCsrGroupThreads) one(pb[i], PACKED ? 0u : pq[i], pl[i]);
+            for (; i < n; i += kCsrGroupThreads) one(pb[i], PACKED ? 0u : pq[i], LABELS ? pl[i] : 0u);
         }
         __syncthreads();
-        csr_groups_fold(ghist, counts + site * (int64_t)classes, classes, log2c, tid);
+        csr_groups_fold<ADD>(ghist, counts + site * (int64_t)classes, classes, log2c, tid);
         __syncthreads();
     }
+}
+
+template <bool PACKED>
+__global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_labels_kernel(
+    int64_t n_sites, const int64_t *__restrict__ offsets, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ quals,
+    const uint8_t *__restrict__ group_of_obs, int n_groups, int log2c, uint32_t *__restrict__ counts)
+{
+    hist_csr_labels_body<PACKED, true, false>(n_sites, offsets, obs, quals, group_of_obs, n_groups, log2c, 0, counts);
+}
+
+template <bool PACKED, bool LABELS>
+__global__ __launch_bounds__(kCsrGroupThreads) void hist_csr_add_kernel(
+    int64_t n_sites, const int64_t *__restrict__ offsets, const uint8_t *__restrict__ obs, const uint8_t *__restrict__ quals,
+    const uint8_t *__restrict__ group_of_obs, int n_groups, int log2c, int64_t min_len, uint32_t *__restrict__ counts)
+{
+    hist_csr_labels_body<PACKED, LABELS, true>(n_sites, offsets, obs, quals, group_of_obs, n_groups, log2c, min_len, counts);
 }
 
 }  // namespace
@@ -942,6 +968,24 @@ hipError_t launch_hist_csr_labels(LaunchState &st, hipStream_t stream, int64_t n
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kernel, dim3((unsigned)(n_sites < 8192 ? n_sites : 8192)), dim3(kCsrGroupThreads), lds, stream, n_sites, offsets, obs,
                        quals, group_of_obs, n_groups, log2c, counts);
+    return hipGetLastError();
+}
+
+// Sites of more than min_len observations ADDED to the caller's counts: [site][512] (group_of_obs == nullptr) or [site][n_groups + 1][512]
+hipError_t launch_hist_csr_add(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
+                               const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, int64_t min_len, uint32_t *counts)
+{
+    if (n_sites <= 0) return hipSuccess;
+    auto *kernel = group_of_obs ? (quals ? hist_csr_add_kernel<false, true> : hist_csr_add_kernel<true, true>)
+                                : (quals ? hist_csr_add_kernel<false, false> : hist_csr_add_kernel<true, false>);
+    int log2c = 0;
+    size_t lds = 0;
+    const hipError_t e = csr_groups_lds(st, reinterpret_cast<const void *>(kernel), group_of_obs ? n_groups : 0, log2c, lds);
+    if (e != hipSuccess) return e;
+    // one histogram per site: 8 copies (16 KiB) -- the 32 that fit would make the fold of a site of a few hundred observations 32 K words
+    if (!group_of_obs && log2c > 3) { log2c = 3; lds = (size_t)BVC_NCLASS * sizeof(uint32_t) << log2c; }
+    hipLaunchKernelGGL(kernel, dim3((unsigned)(n_sites < 8192 ? n_sites : 8192)), dim3(kCsrGroupThreads), lds, stream, n_sites, offsets, obs,
+                       quals, group_of_obs, n_groups, log2c, min_len, counts);
     return hipGetLastError();
 }
 

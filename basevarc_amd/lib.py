@@ -55,6 +55,8 @@ EXPORTS = [
     "bvc_lrt_csr_packed", "bvc_lrt_csr_groups", "bvc_lrt_csr_group_labels", "bvc_lrt_csr_group_labels_packed", "bvc_pileup_begin", "bvc_pileup_finish", "bvc_pileup_finish_called", "bvc_inflate_blocks", "bvc_pileup_begin_bgzf", "bvc_pileup_text",
     "bvc_pileup_begin_bin",
     "bvc_host_alloc", "bvc_host_free",
+    "bvc_counts_add_dense", "bvc_counts_add_dense_packed", "bvc_counts_add_csr", "bvc_counts_add_csr_packed",
+    "bvc_counts_add_dense_groups", "bvc_counts_add_csr_group_labels", "bvc_lrt_hist_groups", "bvc_counts_merge",
 ]
 
 _lib = None
@@ -137,6 +139,23 @@ def load_library():
     L.bvc_pileup_text.argtypes = [vp, vp, i64, C.POINTER(i64), vp]
     L.bvc_inflate_blocks.restype = C.c_int
     L.bvc_inflate_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, u32]
+    # counts accumulated over sample chunks
+    L.bvc_counts_add_dense.restype = C.c_int
+    L.bvc_counts_add_dense.argtypes = [vp, i64, i64, i64, vp, vp, vp, u32]
+    L.bvc_counts_add_dense_packed.restype = C.c_int
+    L.bvc_counts_add_dense_packed.argtypes = [vp, i64, i64, i64, vp, vp, u32]
+    L.bvc_counts_add_csr.restype = C.c_int
+    L.bvc_counts_add_csr.argtypes = [vp, i64, vp, vp, vp, vp, u32]
+    L.bvc_counts_add_csr_packed.restype = C.c_int
+    L.bvc_counts_add_csr_packed.argtypes = [vp, i64, vp, vp, vp, u32]
+    L.bvc_counts_add_dense_groups.restype = C.c_int
+    L.bvc_counts_add_dense_groups.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, vp, u32]
+    L.bvc_counts_add_csr_group_labels.restype = C.c_int
+    L.bvc_counts_add_csr_group_labels.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, u32]
+    L.bvc_lrt_hist_groups.restype = C.c_int
+    L.bvc_lrt_hist_groups.argtypes = [vp, i64, vp, vp, dbl, i32, vp, vp, u32]
+    L.bvc_counts_merge.restype = C.c_int
+    L.bvc_counts_merge.argtypes = [vp, i64, vp, vp, u32]
     _lib = L
     return L
 
@@ -651,6 +670,122 @@ class Context:
         self._check(self._L.bvc_hist_dense_packed(self._h, ns, n, packed_t.stride(0), _dev_ptr(packed_t),
                                                   _dev_ptr(counts_t), BVC_PTR_DEVICE))
         return counts_t
+
+    # ---- a cohort in sample chunks: counts that accumulate (include/bvc.h).  `counts` is added to IN PLACE: a uint32 / int32 array of
+    # [n_sites, 512] (plain) or [n_sites, n_groups + 1, 512] (groups; slot n_groups = in no group), numpy with the host calls, a tensor
+    # on this context's device with the *_device calls (asynchronous on the stream).
+    def _counts_call(self, fn, sizes, arrays, counts, device, n_groups=None):
+        """fn(ctx, *sizes, *arrays, [n_groups,] counts, flags): the argument order of every bvc_counts_add_* call."""
+        if device:
+            ok = counts.is_contiguous() and counts.element_size() == 4 and not counts.is_floating_point()
+        else:
+            ok = isinstance(counts, np.ndarray) and counts.flags.c_contiguous and counts.dtype.kind in "iu" and counts.dtype.itemsize == 4
+        if not ok:
+            raise ValueError("counts must be a contiguous array of 4-byte integers (it is added to in place)")
+        ptr = _dev_ptr if device else _np_ptr
+        groups = () if n_groups is None else (int(n_groups),)
+        self._check(fn(self._h, *sizes, *[ptr(a) for a in arrays], *groups, ptr(counts), BVC_PTR_DEVICE if device else BVC_PTR_HOST))
+        return counts
+
+    def counts_add_dense(self, bases, quals, counts):
+        b = np.ascontiguousarray(bases, dtype=np.int8)
+        q = np.ascontiguousarray(quals, dtype=np.int8)
+        return self._counts_call(self._L.bvc_counts_add_dense, (b.shape[0], b.shape[1], b.shape[1]), (b, q), counts, False)
+
+    def counts_add_dense_device(self, bases_t, quals_t, counts_t):
+        ns, n = bases_t.shape
+        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0)
+        return self._counts_call(self._L.bvc_counts_add_dense, (ns, n, bases_t.stride(0)), (bases_t, quals_t), counts_t, True)
+
+    def counts_add_dense_packed(self, packed, counts):
+        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        return self._counts_call(self._L.bvc_counts_add_dense_packed, (p.shape[0], p.shape[1], p.shape[1]), (p,), counts, False)
+
+    def counts_add_dense_packed_device(self, packed_t, counts_t):
+        ns, n = packed_t.shape
+        assert packed_t.stride(1) == 1
+        return self._counts_call(self._L.bvc_counts_add_dense_packed, (ns, n, packed_t.stride(0)), (packed_t,), counts_t, True)
+
+    def counts_add_csr(self, offsets, bases, quals, counts):
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        b = np.ascontiguousarray(bases, dtype=np.int8)
+        q = np.ascontiguousarray(quals, dtype=np.int8)
+        return self._counts_call(self._L.bvc_counts_add_csr, (len(o) - 1,), (o, b, q), counts, False)
+
+    def counts_add_csr_device(self, offsets_t, bases_t, quals_t, counts_t):
+        return self._counts_call(self._L.bvc_counts_add_csr, (offsets_t.numel() - 1,), (offsets_t, bases_t, quals_t), counts_t, True)
+
+    def counts_add_csr_packed(self, offsets, packed, counts):
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        return self._counts_call(self._L.bvc_counts_add_csr_packed, (len(o) - 1,), (o, p), counts, False)
+
+    def counts_add_csr_packed_device(self, offsets_t, packed_t, counts_t):
+        return self._counts_call(self._L.bvc_counts_add_csr_packed, (offsets_t.numel() - 1,), (offsets_t, packed_t), counts_t, True)
+
+    def counts_add_dense_groups(self, bases, quals, group_of_sample, n_groups, grp_counts):
+        b = np.ascontiguousarray(bases, dtype=np.int8)
+        q = np.ascontiguousarray(quals, dtype=np.int8)
+        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8)
+        if g.shape != (b.shape[1],):
+            raise ValueError("group_of_sample must have one label per column of the chunk")
+        return self._counts_call(self._L.bvc_counts_add_dense_groups, (b.shape[0], b.shape[1], b.shape[1]), (b, q, g), grp_counts, False, n_groups)
+
+    def counts_add_dense_groups_device(self, bases_t, quals_t, group_t, n_groups, grp_counts_t):
+        ns, n = bases_t.shape
+        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0) and group_t.numel() == n
+        return self._counts_call(self._L.bvc_counts_add_dense_groups, (ns, n, bases_t.stride(0)), (bases_t, quals_t, group_t), grp_counts_t, True,
+                                 n_groups)
+
+    def counts_add_csr_group_labels(self, offsets, bases, quals, group_of_obs, n_groups, grp_counts):
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        b = np.ascontiguousarray(bases, dtype=np.int8)
+        q = np.ascontiguousarray(quals, dtype=np.int8)
+        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
+        return self._counts_call(self._L.bvc_counts_add_csr_group_labels, (len(o) - 1,), (o, b, q, g), grp_counts, False, n_groups)
+
+    def counts_add_csr_group_labels_device(self, offsets_t, bases_t, quals_t, group_of_obs_t, n_groups, grp_counts_t):
+        return self._counts_call(self._L.bvc_counts_add_csr_group_labels, (offsets_t.numel() - 1,), (offsets_t, bases_t, quals_t, group_of_obs_t),
+                                 grp_counts_t, True, n_groups)
+
+    def counts_merge(self, dst, src):
+        """dst += src (mod 2^32), numpy arrays of equal size; dst in place."""
+        s_ = np.ascontiguousarray(src).view(np.uint32)
+        if s_.size != dst.size:
+            raise ValueError("dst and src differ in size")
+        return self._merge(dst, s_, False)
+
+    def counts_merge_device(self, dst_t, src_t):
+        assert dst_t.numel() == src_t.numel() and dst_t.is_contiguous() and src_t.is_contiguous()
+        return self._merge(dst_t, src_t, True)
+
+    def _merge(self, dst, src, device):
+        ptr = _dev_ptr if device else _np_ptr
+        n = dst.numel() if device else dst.size
+        self._check(self._L.bvc_counts_merge(self._h, int(n), ptr(dst), ptr(src), BVC_PTR_DEVICE if device else BVC_PTR_HOST))
+        return dst
+
+    def lrt_hist_groups(self, grp_counts, ref_base, min_af, n_groups):
+        """Stage 2 of the group calls on accumulated group histograms [n_sites, n_groups + 1, 512]: (site records, group records)."""
+        c = np.ascontiguousarray(grp_counts).view(np.uint32).reshape(-1, n_groups + 1, NCLASS)
+        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        out = np.zeros(c.shape[0], dtype=SITE_DTYPE)
+        gout = np.zeros((c.shape[0], n_groups), dtype=GROUP_DTYPE)
+        self._check(self._L.bvc_lrt_hist_groups(self._h, c.shape[0], _np_ptr(c), _np_ptr(r), float(min_af), int(n_groups), _np_ptr(out),
+                                                _np_ptr(gout), BVC_PTR_HOST))
+        return out, gout
+
+    def lrt_hist_groups_device(self, grp_counts_t, ref_t, min_af, n_groups, results_t=None, grp_results_t=None):
+        import torch
+        ns = ref_t.numel()
+        assert grp_counts_t.numel() == ns * (n_groups + 1) * NCLASS and grp_counts_t.is_contiguous()
+        if results_t is None:
+            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        if grp_results_t is None:
+            grp_results_t = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        self._check(self._L.bvc_lrt_hist_groups(self._h, ns, _dev_ptr(grp_counts_t), _dev_ptr(ref_t), float(min_af), int(n_groups),
+                                                _dev_ptr(results_t), _dev_ptr(grp_results_t), BVC_PTR_DEVICE))
+        return results_t, grp_results_t
 
     def synth_dense_device(self, seed, site0, bases_t, quals_t, ref_t, cov_thr16=65536):
         ns, n = bases_t.shape

@@ -6,6 +6,11 @@ its sites; the per-site reduction never crosses devices.  The only communication
 fixed-size result records to one rank, in position order -- the counterpart of the reference's merge of
 per-thread sub-files (src/BaseVarC.cpp:274-295).  torch.distributed supplies it (nccl = RCCL on GPUs,
 gloo in the CPU tests).
+
+By sample (UNMEASURED on hardware): class counts add over samples, so rank r may instead own a contiguous range of the cohort's
+SAMPLES for all sites (sample_ranges), accumulate its partial counts with the bvc_counts_add_* calls, and the ranks sum them
+(allreduce_counts: [n_sites, 512] or [n_sites, k + 1, 512] words per tile) before any one of them runs stage 2 on the sum.  That is
+2 KB per site and rank on the wire where sharding by site moves nothing but records: it is for callers whose DATA is split by sample.
 """
 import numpy as np
 
@@ -17,6 +22,35 @@ def shard_range(n_sites, rank, world):
     base, extra = divmod(int(n_sites), int(world))
     lo = rank * base + min(rank, extra)
     return lo, lo + base + (1 if rank < extra else 0)
+
+
+def sample_ranges(n_samples, world):
+    """Contiguous, balanced split of the cohort's samples: [(lo, hi)] for ranks 0..world-1 (empty ranges when n_samples < world)."""
+    if world < 1:
+        raise ValueError("bad world")
+    return [shard_range(n_samples, r, world) for r in range(int(world))]
+
+
+def allreduce_counts(counts, group=None):
+    """Sum of every rank's partial class counts, exact modulo 2^32 (the arithmetic of bvc_counts_merge).  counts: a numpy array or a
+    CPU / device tensor of 4-byte integers, the same shape on every rank; returns the same kind, on every rank.  torch has no unsigned
+    reduction: the words are summed as int32, which wraps to the same bits."""
+    import torch
+    import torch.distributed as dist
+    if isinstance(counts, np.ndarray):
+        words = np.ascontiguousarray(counts)
+        if words.dtype.itemsize != 4:
+            raise ValueError("counts must be 4-byte integers")
+        t = torch.from_numpy(words.view(np.int32).copy())
+        if dist.get_backend(group) == "nccl":
+            t = t.to(torch.device("cuda", torch.cuda.current_device()))
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        return t.cpu().numpy().view(words.dtype).reshape(counts.shape)
+    if counts.element_size() != 4 or counts.is_floating_point():
+        raise ValueError("counts must be 4-byte integers")
+    t = counts.contiguous().view(torch.int32).clone()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t.view(counts.dtype).reshape(counts.shape)
 
 
 def call_sizes(n_sites, sites_per_call, min_calls=1):

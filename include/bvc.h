@@ -395,6 +395,55 @@ int bvc_lrt_hist(bvc_ctx *ctx, int64_t n_sites, const uint32_t *counts, const in
                  double min_af, const int8_t *base_comb, const uint8_t *n_comb,
                  bvc_site_result *results, uint32_t flags);
 
+/* ---- a cohort in SAMPLE chunks: counts that accumulate (additive) ------------------------------------------------------------ */
+/*
+ * A site's record depends on its samples only through its 512 class counts, and counts add over samples.  So a cohort need not arrive
+ * site by site with all its samples: zero counts[n_sites][512] once, ADD every chunk of samples to it (a temp batch of 500 samples, a
+ * node's share of the cohort) with the calls below, then run stage 2 on the sum -- bvc_lrt_hist, or with groups bvc_lrt_hist_groups.
+ * The records are those of the one-piece call on all samples, byte for byte (the counts are the same integers).
+ *
+ *   counts[s * 512 + c] += the chunk's covered observations of class c = base * 128 + qual at site s        (exact)
+ * in unsigned 32-bit arithmetic: a class of more than 2^32 - 1 observations wraps, which is NOT checked.  `counts` follows `flags` like
+ * every other pointer.  BVC_PTR_DEVICE: asynchronous on the context's stream (in overlap mode too: these calls are ordered like
+ * bvc_hist_dense).  BVC_PTR_HOST: the convenience form -- the inputs AND the counts are staged up, added to on the device and brought
+ * back, in one piece and synchronously; a caller with many chunks keeps the counts on the device.
+ * What counts as a covered observation is what the bvc_lrt_* call of the same layout says.  BVC_ERR_ARG: null pointers with work
+ * present, negative sizes, n_groups outside 1..32, host offsets that do not start at 0 or that decrease.
+ */
+/* Dense chunk: the tile of bvc_hist_dense[_packed], its n_samples columns a chunk of the cohort's. */
+int bvc_counts_add_dense(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride,
+                         const int8_t *bases, const int8_t *quals, uint32_t *counts, uint32_t flags);
+int bvc_counts_add_dense_packed(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride,
+                                const uint8_t *packed, uint32_t *counts, uint32_t flags);
+/* Ragged chunk: offsets and columns as bvc_lrt_csr[_packed] take them; site s of the chunk adds into row s.  A site without an
+ * observation in the chunk (offsets[s] == offsets[s + 1]) is legal and costs nothing.  Device arrays may start at any byte. */
+int bvc_counts_add_csr(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
+                       uint32_t *counts, uint32_t flags);
+int bvc_counts_add_csr_packed(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *packed,
+                              uint32_t *counts, uint32_t flags);
+/*
+ * With groups: grp_counts[n_sites][n_groups + 1][512], the layout the group calls use between their stages.  Slot g < n_groups holds
+ * the observations of group g; the LAST slot, n_groups, holds those in no group (a label >= n_groups).  The overall counts of a site
+ * are the sum of its n_groups + 1 slots.
+ *   bvc_counts_add_dense_groups       two-byte tile; group_of_sample[n_samples] are the labels of the CHUNK's columns
+ *   bvc_counts_add_csr_group_labels   two-byte ragged columns with one label byte per observation (bvc_lrt_csr_group_labels)
+ */
+int bvc_counts_add_dense_groups(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int64_t row_stride,
+                                const int8_t *bases, const int8_t *quals, const uint8_t *group_of_sample, int32_t n_groups,
+                                uint32_t *grp_counts, uint32_t flags);
+int bvc_counts_add_csr_group_labels(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const int8_t *bases, const int8_t *quals,
+                                    const uint8_t *group_of_obs, int32_t n_groups, uint32_t *grp_counts, uint32_t flags);
+/*
+ * Stage 2 of the group calls on accumulated group histograms: the site records and the [n_sites][n_groups] group records of
+ * bvc_lrt_dense_groups / bvc_lrt_csr_group_labels on the same observations, byte for byte.  The overall counts are summed into the
+ * context's own scratch; grp_counts is only read.  In overlap mode stage 2 runs on a side stream like that of every bvc_lrt_* call:
+ * grp_counts, ref_base and the record buffers stay untouched until bvc_join.
+ */
+int bvc_lrt_hist_groups(bvc_ctx *ctx, int64_t n_sites, const uint32_t *grp_counts, const int8_t *ref_base, double min_af,
+                        int32_t n_groups, bvc_site_result *results, bvc_group_result *grp_results, uint32_t flags);
+/* dst[i] += src[i] for i < n_words (mod 2^32): partial counts of another context, device or rank (either layout) added to this one's. */
+int bvc_counts_merge(bvc_ctx *ctx, int64_t n_words, uint32_t *dst, const uint32_t *src, uint32_t flags);
+
 /* ---- synthetic pileup generator (benchmark / test input); device pointers only ------ */
 /* Fills sites site0 .. site0+n_sites-1.  cov_thr16 = 65536 gives dense coverage; smaller values leave
  * a sample uncovered (base = -1) with probability 1 - cov_thr16/65536.  Integer arithmetic only. */
@@ -422,6 +471,10 @@ int bvc_synth_dense(bvc_ctx *ctx, uint64_t seed, int64_t site0, int64_t n_sites,
  *                      workgroups of 64 KiB
  *   "group_h16"        any-order group histograms on packed rows: 0 (default) = 16 LDS copies of 32-bit counters, 1 = 32
  *                      conflict-free copies of 16-bit counter pairs (A/B runs)
+ *   "csr_scatter_max"  bvc_counts_add_csr*: a site with at most this many observations IN THE CALL is counted with one global atomic per
+ *                      observation, lanes running over the observations across site boundaries; a longer one through a histogram in
+ *                      LDS that one workgroup adds to the counts.  0 = never scatter, up to 1 << 30 (= always: the scatter kernel alone, sites of any length).  Default 64
+ *                      (measured: DESIGN.md section 3.10).  Environment: BVC_CSR_SCATTER_MAX
  *   "host_chunk_kib"   BVC_PTR_HOST calls stage the tile through device memory in chunks of sites of at most this
  *                      many KiB per array (default 524288 = 512 MiB); the upload of chunk i+1 runs under the kernels
  *                      of chunk i
