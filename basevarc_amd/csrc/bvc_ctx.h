@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <cstring>
 #include <string>
 #include <vector>
 
@@ -193,6 +194,57 @@ inline int ensure_joined(bvc_ctx *ctx, DevBuf &buf, size_t need)
 
 // Does [p, p + n) lie inside an allocation of bvc_host_alloc?  A transfer from / to it needs no bounce buffer.
 bool in_pinned(const void *p, size_t n);
+
+// Transfers of one call through the context's pinned buffers: h2d copies the caller's bytes into pinned memory and enqueues the DMA,
+// d2h enqueues a DMA into pinned memory and deliver() -- after the stream has been waited for -- copies the bytes to the caller.
+struct PinIO {
+    bvc_ctx *ctx;
+    size_t up_used = 0, down_used = 0;
+    struct Out { void *dst; const char *src; size_t n; };
+    std::vector<Out> outs;
+    explicit PinIO(bvc_ctx *c) : ctx(c) {}
+    static size_t al(size_t n) { return (n + 63) & ~(size_t)63; }
+    int reserve(size_t up_bytes, size_t down_bytes)
+    {
+        auto grow = [&](char **buf, size_t *cap, size_t need) -> int {
+            if (need <= *cap) return BVC_OK;
+            if (*buf) {
+                if (wait_stream(ctx) != hipSuccess) return fail(ctx, BVC_ERR_DEVICE, "wait before growing a pinned buffer");
+                (void)hipHostFree(*buf);
+                *buf = nullptr; *cap = 0;
+            }
+            const size_t want = need + need / 4 + 4096;
+            if (hipHostMalloc(reinterpret_cast<void **>(buf), want, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(ctx, BVC_ERR_ALLOC, "pinned host allocation failed");
+            }
+            *cap = want;
+            return BVC_OK;
+        };
+        int rc = grow(&ctx->h_up, &ctx->up_cap, up_bytes);
+        return rc == BVC_OK ? grow(&ctx->h_down, &ctx->down_cap, down_bytes) : rc;
+    }
+    hipError_t h2d(void *dev, const void *host, size_t n)
+    {
+        if (n == 0) return hipSuccess;
+        if (in_pinned(host, n)) return hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, ctx->stream);
+        if (up_used + n > ctx->up_cap) return hipErrorOutOfMemory;
+        char *p = ctx->h_up + up_used;
+        std::memcpy(p, host, n);
+        up_used += al(n);
+        return hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, ctx->stream);
+    }
+    hipError_t d2h(void *host, const void *dev, size_t n)
+    {
+        if (n == 0) return hipSuccess;
+        if (down_used + n > ctx->down_cap) return hipErrorOutOfMemory;
+        char *p = ctx->h_down + down_used;
+        down_used += al(n);
+        outs.push_back(Out{host, p, n});
+        return hipMemcpyAsync(p, dev, n, hipMemcpyDeviceToHost, ctx->stream);
+    }
+    void deliver() { for (auto const &o : outs) std::memcpy(o.dst, o.src, o.n); outs.clear(); }
+};
 
 inline int check_common(bvc_ctx *ctx, int64_t n_sites, const void *a, const void *b, const void *c, const void *d)
 {

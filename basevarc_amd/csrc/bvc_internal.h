@@ -37,6 +37,8 @@ struct LaunchState {
                                    // observation (hist_csr_scatter_kernel, counts_kernel.hip) instead of a histogram in LDS; 0 = never
     int em_prune = 1;              // item engine: 1 = a level does not run the subset without the deepest candidate when a bound on its
                                    // log-likelihood shows that it cannot be the level's first minimum (em_items.hip, site_decide); 0 = it always runs
+    int stats_log2c = 2;           // site_stats_kernel: 2^n LDS copies of its 1536 counters (0..4; 2 = 30 KiB with the folded counters: four
+                                   // 512-thread workgroups a CU, as many as its 32 wavefronts hold; measured, profiles/site_stats/README.txt)
     int dbg_levels = 0;            // BVC_DBG_LEVELS (timing only, records wrong): cut region_kernel short after a phase; 0 = run all
     mutable uint32_t em_epoch = 0; // stage-2 launches of this context so far (em_items.hip: the narrow launch tells the wide one)
     struct RaisedLds { const void *kernel; size_t bytes; };
@@ -218,12 +220,20 @@ hipError_t launch_hist_csr_scatter(const LaunchState &st, hipStream_t stream, in
 hipError_t launch_hist_csr_add(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const uint8_t *obs,
                                const uint8_t *quals, const uint8_t *group_of_obs, int n_groups, int64_t min_len, uint32_t *counts);
 
+// site_stats_kernel.hip: the rank sums and strand counts of the called sites' entries (include/bvc.h, bvc_site_stats); a site that is not
+// called gets a zeroed record.  A workgroup takes one site at a time, called or not; st.stats_log2c LDS copies of the counters.
+constexpr int kStatsMaxLog2c = 4;
+constexpr int kSiteStatsTrip = 4096;     // entries a workgroup takes per trip of its streaming loop (the sizes the tests straddle)
+hipError_t launch_site_stats(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const bvc_pileup_entry *entries,
+                             const int8_t *ref_base, const bvc_site_result *results, bvc_site_stats *stats);
+
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);
 
 #ifdef BVC_CHECK_LDS
 hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);
+hipError_t debug_read_site_stats(uint32_t *out8, bool reset);
 // diagnostic builds: each translation unit's violation record (bvc_device.h)
 hipError_t debug_read_hist(uint32_t *out8, bool reset);
 hipError_t debug_read_wave_engine(uint32_t *out8, bool reset);

@@ -1,63 +1,6 @@
 // bvc_pileup.hip -- the producer: BGZF blocks inflated on the device, and temp-batch tiles (text, binary records, or BGZF blocks of
 // text) -> columns -> records between a begin call and a finish call (pileup_kernel.hip, inflate_kernel.hip).
-#include <cstring>
-
 #include "bvc_ctx.h"
-
-namespace {
-
-// Transfers of one call through the context's pinned buffers: h2d copies the caller's bytes into pinned memory and enqueues the DMA,
-// d2h enqueues a DMA into pinned memory and deliver() -- after the stream has been waited for -- copies the bytes to the caller.
-struct PinIO {
-    bvc_ctx *ctx;
-    size_t up_used = 0, down_used = 0;
-    struct Out { void *dst; const char *src; size_t n; };
-    std::vector<Out> outs;
-    explicit PinIO(bvc_ctx *c) : ctx(c) {}
-    static size_t al(size_t n) { return (n + 63) & ~(size_t)63; }
-    int reserve(size_t up_bytes, size_t down_bytes)
-    {
-        auto grow = [&](char **buf, size_t *cap, size_t need) -> int {
-            if (need <= *cap) return BVC_OK;
-            if (*buf) {
-                if (wait_stream(ctx) != hipSuccess) return fail(ctx, BVC_ERR_DEVICE, "wait before growing a pinned buffer");
-                (void)hipHostFree(*buf);
-                *buf = nullptr; *cap = 0;
-            }
-            const size_t want = need + need / 4 + 4096;
-            if (hipHostMalloc(reinterpret_cast<void **>(buf), want, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(ctx, BVC_ERR_ALLOC, "pinned host allocation failed");
-            }
-            *cap = want;
-            return BVC_OK;
-        };
-        int rc = grow(&ctx->h_up, &ctx->up_cap, up_bytes);
-        return rc == BVC_OK ? grow(&ctx->h_down, &ctx->down_cap, down_bytes) : rc;
-    }
-    hipError_t h2d(void *dev, const void *host, size_t n)
-    {
-        if (n == 0) return hipSuccess;
-        if (in_pinned(host, n)) return hipMemcpyAsync(dev, host, n, hipMemcpyHostToDevice, ctx->stream);
-        if (up_used + n > ctx->up_cap) return hipErrorOutOfMemory;
-        char *p = ctx->h_up + up_used;
-        std::memcpy(p, host, n);
-        up_used += al(n);
-        return hipMemcpyAsync(dev, p, n, hipMemcpyHostToDevice, ctx->stream);
-    }
-    hipError_t d2h(void *host, const void *dev, size_t n)
-    {
-        if (n == 0) return hipSuccess;
-        if (down_used + n > ctx->down_cap) return hipErrorOutOfMemory;
-        char *p = ctx->h_down + down_used;
-        down_used += al(n);
-        outs.push_back(Out{host, p, n});
-        return hipMemcpyAsync(p, dev, n, hipMemcpyDeviceToHost, ctx->stream);
-    }
-    void deliver() { for (auto const &o : outs) std::memcpy(o.dst, o.src, o.n); outs.clear(); }
-};
-
-}  // namespace
 
 extern "C" {
 
@@ -371,12 +314,13 @@ int bvc_pileup_text(bvc_ctx *ctx, char *text, int64_t text_cap, int64_t *text_by
 }
 
 // bvc_pileup_finish (called_off = null: the entries of every position) and bvc_pileup_finish_called (the entries of the called
-// positions only, compacted on the device; called_cap = room in entries / samples)
+// positions only, compacted on the device; called_cap = room in entries / samples); stats (called_off given): the called positions'
+// rank sums and strand counts too (bvc_pileup_finish_called_stats), computed where the entries lie and delivered with the records
 static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
                               const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
                               int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
                               int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
-                              bvc_group_result *grp_results)
+                              bvc_group_result *grp_results, bvc_site_stats *stats)
 {
     if (!ctx) return BVC_ERR_ARG;
     PileupState &pile = ctx->pile;
@@ -394,7 +338,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
     if (n_groups > 0 && (!grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    int8_t *d_ref; bvc_site_result *d_res; uint8_t *d_g, *d_itext; bvc_group_result *d_gres; int64_t *d_called_off;
+    int8_t *d_ref; bvc_site_result *d_res; uint8_t *d_g, *d_itext; bvc_group_result *d_gres; int64_t *d_called_off; bvc_site_stats *d_stats;
     int rc = carve(ctx, pile.out, 256, [&](Layout &L) {
         P.entries = L.take<bvc_pileup_entry>((size_t)n_e, 16);
         P.samples = L.take<int32_t>((size_t)n_e, 16);
@@ -408,6 +352,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         d_gres = L.take<bvc_group_result>((size_t)T * (size_t)n_groups);
         d_itext = L.take<uint8_t>((size_t)(indel_text ? n_it : 0), 16);
         d_called_off = L.take<int64_t>(called_only ? (size_t)(T + 1) : 0);
+        d_stats = L.take<bvc_site_stats>(stats ? (size_t)T : 0);
     });
     if (rc != BVC_OK) return rc;
     P.indel_cap = (uint32_t)n_i;
@@ -419,7 +364,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     rc = io.reserve((size_t)T + (size_t)(n_groups > 0 ? n_samples : 0) + 1024,
                     (size_t)T * (sizeof(bvc_site_result) + 32 * 4 + 8 + (size_t)n_groups * sizeof(bvc_group_result)) +
                         (size_t)(called_only ? 0 : n_e) * (sizeof(bvc_pileup_entry) + 4) + (called_only ? (size_t)(T + 1) * 8 : 0) +
-                        (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)n_it + 4096);
+                        (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)n_it + (stats ? (size_t)T * sizeof(bvc_site_stats) : 0) + 4096);
     if (rc != BVC_OK) return rc;
     if (T > 0) {
         BVC_HIP_D(ctx, io.h2d(d_ref, ref_base, (size_t)T));
@@ -433,7 +378,9 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
             rc = run_csr_device(ctx, T, P.obs_off, P.obs_base, P.obs_qual, d_ref, min_af, nullptr, nullptr, d_res);
         if (rc == BVC_OK) rc = join_side(ctx);
         if (rc != BVC_OK) return drain_on_error(ctx, rc);
+        if (stats) BVC_HIP_D(ctx, launch_site_stats(ctx->ls, ctx->stream, T, P.entry_off, P.entries, d_ref, d_res, d_stats));
         BVC_HIP_D(ctx, io.d2h(results, d_res, (size_t)T * sizeof(bvc_site_result)));
+        if (stats) BVC_HIP_D(ctx, io.d2h(stats, d_stats, (size_t)T * sizeof(bvc_site_stats)));
         if (n_groups > 0)
             BVC_HIP_D(ctx, io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
         BVC_HIP_D(ctx, io.d2h(tally, P.tally, (size_t)T * 32 * 4));
@@ -486,7 +433,7 @@ int bvc_pileup_finish(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const
                       bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results, bvc_group_result *grp_results)
 {
     return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, nullptr, 0,
-                              entries, samples, indels, indel_text, results, grp_results);
+                              entries, samples, indels, indel_text, results, grp_results, nullptr);
 }
 
 int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
@@ -497,7 +444,18 @@ int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af
 {
     if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
     return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
-                              called_cap, entries, samples, indels, indel_text, results, grp_results);
+                              called_cap, entries, samples, indels, indel_text, results, grp_results, nullptr);
+}
+
+int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                                   const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                                   int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
+                                   int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
+                                   bvc_group_result *grp_results, bvc_site_stats *stats)
+{
+    if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
+                              called_cap, entries, samples, indels, indel_text, results, grp_results, stats);
 }
 
 }  // extern "C"

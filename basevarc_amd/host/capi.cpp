@@ -35,6 +35,8 @@ double bvchost_ranksum(const double *x, int n1, const double *y, int n2)
     std::vector<double> a(x, x + n1), b(y, y + n2);
     return RankSumTest(a, b);
 }
+// the same from what bvc_site_stats carries: rank2 = 2 x the rank sum of the first sample (an integer), n1, n2 = the samples' sizes
+double bvchost_ranksum_from_rank2(int64_t rank2, int64_t n1, int64_t n2) { return RankSumFromR1((double)rank2 / 2.0, (size_t)n1, (size_t)n2); }
 
 // Parses the concatenated batch lines of ONE position (lines separated by '\n') and formats the CVG line and, when
 // `bt` says called, the VCF line.  Returns the number of bytes needed; output is truncated to cap.

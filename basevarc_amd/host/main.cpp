@@ -183,6 +183,9 @@ static bool device_inflate() { return env_int("BVC_HOST_DEVICE_INFLATE", 1) != 0
 // 0: a device-parsed tile's entries come back for every position, not for the called ones only (WriteVcf is their one reader,
 // src/BaseVarC.cpp:664; as up to round 5's first form of this feed)
 static bool called_only() { return env_int("BVC_HOST_CALLED_ONLY", 1) != 0; }
+// 1: the rank sums and strand counts of a called position's VCF line are computed on the device, where the tile's entries lie
+// (bvc_pileup_finish_called_stats), not from its entries on this CPU (three sorts per called position); needs called_only
+static bool device_stats() { return env_int("BVC_HOST_DEVICE_STATS", 0) != 0; }
 static bool two_byte_tiles() { return env_set("BVC_HOST_TWO_BYTE_TILES"); }            // set: never one byte per observation in the CPU parser's tiles
 static bool no_crc() { return env_set("BVC_HOST_NO_CRC"); }                            // set: the device does not check the CRC32 of the blocks it inflates
 // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
@@ -319,8 +322,9 @@ struct Tile {
     std::vector<int32_t> tally, samples;
     std::vector<bvc_pileup_entry> ent;
     std::vector<bvc_pileup_indel> indels;
+    std::vector<bvc_site_stats> stats;   // per position, where the device computed them (empty: vcf_line tallies the entries itself)
     bool handed_back = false;            // a line was not regular: the tile went through the CPU parser and its columns are in `sites`
-    void reset() { form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); }
+    void reset() { form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); stats.clear(); }
     bool empty() const { return form == TileForm::Sites ? n_used == 0 : n_pos == 0; }     // nothing for stage 2 to do
     bool device_parsed() const { return form != TileForm::Sites && !handed_back; }        // (once stage 2 is through with it)
     // the tile is the T positions from w.pv[ip] on: their coordinates and reference bases
@@ -338,6 +342,7 @@ struct Tile {
         v.aiv = reinterpret_cast<const Entry *>(&ent[(size_t)a0]);
         v.sample = &samples[(size_t)a0];
         v.n = (size_t)(entry_off[t + 1] - entry_off[t]);
+        v.stats = stats.empty() ? nullptr : &stats[t];
         return v;
     }
 };
@@ -387,6 +392,7 @@ struct TileRunner {
     std::string err;                     // first failure of stage 2 or 3
     bool started = false;
     int64_t tiles_one_byte = 0, tiles_two_byte = 0;   // library calls by tile form (stage 2's thread; read after finish())
+    int64_t tiles_dev_stats = 0;                      // of the tiles parsed on the device: those whose called positions' statistics the device computed
     int64_t tiles_dev_parsed = 0, tiles_cpu_parsed = 0;   // tiles of text or records: parsed on the device / handed back (a line was not regular)
     std::vector<int32_t> sample0, n_in_batch;         // per temp batch: its first sample and its samples (device-parsed tiles)
     uint8_t carry[5] = {0, 0, 0, 0, 0};               // the parser's long-lived AlleleInfo between tiles (stage 2's thread)
@@ -494,12 +500,15 @@ struct TileRunner {
         if (text_on_device) T.text.resize((size_t)ind_bytes + 1);
         uint8_t carry_out[5];
         int rc;
+        T.stats.clear();
         if (knob::called_only()) {
             T.called_off.resize(T.n_pos + 1);
-            rc = bvc_pileup_finish_called(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
-                                          ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(), T.called_off.data(),
-                                          n_ent, T.ent.data(), T.samples.data(), T.indels.data(), text_on_device ? T.text.data() : nullptr,
-                                          T.res.data(), ng ? T.gres.data() : nullptr);
+            if (knob::device_stats()) T.stats.resize(T.n_pos);
+            rc = bvc_pileup_finish_called_stats(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
+                                                ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(),
+                                                T.called_off.data(), n_ent, T.ent.data(), T.samples.data(), T.indels.data(),
+                                                text_on_device ? T.text.data() : nullptr, T.res.data(), ng ? T.gres.data() : nullptr,
+                                                T.stats.empty() ? nullptr : T.stats.data());
         } else {
             T.called_off.clear();
             rc = bvc_pileup_finish(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
@@ -512,6 +521,7 @@ struct TileRunner {
         T.indels.resize((size_t)n_ind);
         std::sort(T.indels.begin(), T.indels.end(), [](const bvc_pileup_indel &a, const bvc_pileup_indel &b) { return a.entry < b.entry; });
         tiles_dev_parsed += 1;
+        if (!T.stats.empty()) tiles_dev_stats += 1;
     }
 
     // stage 2 of a tile of TEXT or of binary RECORDS: parse and LRT on the device.  Text goes to the CPU parser when a line is not what
@@ -1235,7 +1245,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     if (knob::profile()) {
         std::cerr << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
                   << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
-                  << tr.tiles_cpu_parsed << std::endl;
+                  << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats << std::endl;
         const StageClock &c = tr.clk, &d = tr.clk_dev, &o = tr.clk_out;
         std::cerr << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "
                   << d.pack << " s, libbvc " << d.gpu << " s | stage 3 cvg lines " << o.cvg << " s, vcf lines " << o.vcf

@@ -415,7 +415,7 @@ std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t r
         samgt += ':';
         samgt += kStrand[a.strand & 1];
         samgt += bp_field(a.qual);                          // ":<1 - 10^(-qual/10) as {:.6f}>\t"
-        if (a.is_indel == 1 || a.base == 4) continue;
+        if (site.stats || a.is_indel == 1 || a.base == 4) continue;
         const bool alt = is_alt(a.base);
         if (a.base == ref_base) { ref_quals.push_back(a.qual); ref_mapqs.push_back(a.mapq); ref_rprs.push_back(a.rpr); }
         else if (alt) { alt_quals.push_back(a.qual); alt_mapqs.push_back(a.mapq); alt_rprs.push_back(a.rpr); }
@@ -423,9 +423,19 @@ std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t r
         else { if (a.base == ref_base) ref_rev += 1; else if (alt) alt_rev += 1; }
     }
     no_calls(samgt, n_samples - next);
-    const double phred_mapq = RankSumTest(ref_mapqs, alt_mapqs);
-    const double phred_qual = RankSumTest(ref_quals, alt_quals);
-    const double phred_rpr = RankSumTest(ref_rprs, alt_rprs);
+    double phred_mapq, phred_qual, phred_rpr;
+    if (const bvc_site_stats *st = site.stats) {
+        // counted on the device from the same entries: rank2 / 2.0 is the double rank_r1 makes of them (include/bvc.h)
+        const size_t n1 = (size_t)st->n_ref, n2 = (size_t)st->n_alt;
+        phred_mapq = RankSumFromR1((double)st->rank2[0] / 2.0, n1, n2);
+        phred_qual = RankSumFromR1((double)st->rank2[1] / 2.0, n1, n2);
+        phred_rpr = RankSumFromR1((double)st->rank2[2] / 2.0, n1, n2);
+        ref_fwd = st->ref_fwd; ref_rev = st->ref_rev; alt_fwd = st->alt_fwd; alt_rev = st->alt_rev;
+    } else {
+        phred_mapq = RankSumTest(ref_mapqs, alt_mapqs);
+        phred_qual = RankSumTest(ref_quals, alt_quals);
+        phred_rpr = RankSumTest(ref_rprs, alt_rprs);
+    }
     const double fs = bt_fisher_exact(ref_fwd, ref_rev, alt_fwd, alt_rev);
     const double sor = (alt_fwd * ref_rev > 0) ? (double)(ref_fwd * alt_rev) / (ref_rev * alt_fwd) : 10000.0;
     double ad_sum = 0;

@@ -91,6 +91,9 @@ struct SiteView {
     const int32_t *cnt = nullptr, *fwd = nullptr, *rev = nullptr;   // [4], [8], [8]
     const std::string *indels = nullptr;    // indel text of the entries with is_indel = 1, in entry order
     size_t n_indels = 0;
+    // the position's rank sums and strand counts where the device computed them (bvc_pileup_finish_called_stats): vcf_line then takes
+    // them from the record and walks the entries for the sample columns alone.  nullptr: it tallies them itself
+    const bvc_site_stats *stats = nullptr;
 };
 inline SiteView view_of(const SiteColumn &c)
 {

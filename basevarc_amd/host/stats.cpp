@@ -155,7 +155,11 @@ double RankSumTest(std::vector<double> &x, std::vector<double> &y)
 {
     const size_t n1 = x.size(), n2 = y.size();
     x.insert(x.end(), y.begin(), y.end());
-    const double r1 = rank_r1(x, n1);
+    return RankSumFromR1(rank_r1(x, n1), n1, n2);
+}
+
+double RankSumFromR1(double r1, size_t n1, size_t n2)
+{
     const double expected = (double)(n1 * (n1 + n2 + 1)) / 2.0;
     const double z = (r1 - expected) / std::sqrt((double)(n1 * n2 * (n1 + n2 + 1)) / 12.0);
     double p = -10 * std::log10(2 * normsf(std::abs(z)));

@@ -5,6 +5,7 @@
 #ifndef BVC_HOST_STATS_H
 #define BVC_HOST_STATS_H
 
+#include <cstddef>
 #include <vector>
 
 namespace bvchost {
@@ -15,6 +16,10 @@ double kt_fisher_exact(int n11, int n12, int n21, int n22, double *left, double 
 double normsf(double x);                                      // src/Algorithm.cpp:9-14
 double bt_fisher_exact(int n11, int n12, int n21, int n22);   // src/Algorithm.cpp:16-25: phred of the two-sided p
 double RankSumTest(std::vector<double> &x, std::vector<double> &y);   // src/Algorithm.cpp:55-67 (x is extended by y)
+// The tail of RankSumTest (src/Algorithm.cpp:59-66): the phred-scaled two-sided p of the rank sum r1 of a first sample of n1 values
+// among n1 + n2.  r1 may come from elsewhere: bvc_site_stats (include/bvc.h) carries 2 * r1 as an integer, and rank2 / 2.0 is the
+// double rank_r1 returns.
+double RankSumFromR1(double r1, size_t n1, size_t n2);
 
 }  // namespace bvchost
 #endif

@@ -44,7 +44,13 @@ SITE_DTYPE = np.dtype([
     ("n_alt", "u1"), ("called", "u1"), ("n_kept", "u1"), ("kept", "i1", (4,)), ("status", "u1"), ("n_fits", "u1"),
 ])
 GROUP_DTYPE = np.dtype([("af", "<f8", (3,)), ("depth", "<i4", (4,)), ("ran", "u1"), ("present", "u1"), ("pad", "u1", (6,))])
+# bvc_site_stats, 64 bytes: the called sites' rank sums (rank2 = 2 x rankR1 of the REF observations: mapq, qual, rpr) and strand counts
+STATS_DTYPE = np.dtype([("rank2", "<i8", (3,)), ("n_ref", "<i4"), ("n_alt", "<i4"), ("ref_fwd", "<i4"), ("ref_rev", "<i4"),
+                        ("alt_fwd", "<i4"), ("alt_rev", "<i4"), ("valid", "u1"), ("pad", "u1", (15,))])
+ENTRY_DTYPE = np.dtype([("base", "u1"), ("mapq", "u1"), ("qual", "u1"), ("rpr", "u1"), ("strand", "u1"), ("is_indel", "u1"), ("pad", "<u2")])
+SITE_STATS_TRIP = 4096      # entries a workgroup of site_stats_kernel takes per trip of its loop (csrc/bvc_internal.h, kSiteStatsTrip)
 assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 120
+assert STATS_DTYPE.itemsize == 64 and ENTRY_DTYPE.itemsize == 8
 assert GROUP_DTYPE.itemsize == C.sizeof(GroupResult) == 48
 
 EXPORTS = [
@@ -57,6 +63,7 @@ EXPORTS = [
     "bvc_host_alloc", "bvc_host_free",
     "bvc_counts_add_dense", "bvc_counts_add_dense_packed", "bvc_counts_add_csr", "bvc_counts_add_csr_packed",
     "bvc_counts_add_dense_groups", "bvc_counts_add_csr_group_labels", "bvc_lrt_hist_groups", "bvc_counts_merge",
+    "bvc_site_stats_csr", "bvc_pileup_finish_called_stats",
 ]
 
 _lib = None
@@ -156,6 +163,10 @@ def load_library():
     L.bvc_lrt_hist_groups.argtypes = [vp, i64, vp, vp, dbl, i32, vp, vp, u32]
     L.bvc_counts_merge.restype = C.c_int
     L.bvc_counts_merge.argtypes = [vp, i64, vp, vp, u32]
+    L.bvc_site_stats_csr.restype = C.c_int
+    L.bvc_site_stats_csr.argtypes = [vp, i64, vp, vp, vp, vp, vp, u32]
+    L.bvc_pileup_finish_called_stats.restype = C.c_int
+    L.bvc_pileup_finish_called_stats.argtypes = L.bvc_pileup_finish_called.argtypes + [vp]
     _lib = L
     return L
 
@@ -357,11 +368,37 @@ class Context:
                                                             BVC_PTR_DEVICE))
         return res, gres
 
+    def site_stats_csr(self, offsets, entries, ref_base, results):
+        """bvc_site_stats_csr on host arrays: entries (ENTRY_DTYPE) of site s at offsets[s] .. offsets[s + 1], results (SITE_DTYPE: called,
+        n_alt and alt_base are read).  Returns STATS_DTYPE [n_sites]; a site that is not called has an all-zero record."""
+        o = np.ascontiguousarray(offsets, dtype=np.int64)
+        e = np.ascontiguousarray(entries, dtype=ENTRY_DTYPE)
+        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        res = np.ascontiguousarray(results, dtype=SITE_DTYPE)
+        n = len(o) - 1
+        assert r.shape == (n,) and res.shape == (n,)
+        out = np.zeros(n, dtype=STATS_DTYPE)
+        self._check(self._L.bvc_site_stats_csr(self._h, n, _np_ptr(o), _np_ptr(e) if len(e) else None, _np_ptr(r), _np_ptr(res), _np_ptr(out),
+                                               BVC_PTR_HOST))
+        return out
+
+    def site_stats_csr_device(self, offsets_t, entries_t, ref_t, results_t, stats_t=None):
+        """The same on device tensors (entries_t / results_t / the returned tensor: uint8 views of the records); asynchronous on the
+        context's stream.  In overlap mode call join() first: the records must be complete."""
+        import torch
+        ns = offsets_t.numel() - 1
+        if stats_t is None:
+            stats_t = torch.empty(ns * STATS_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
+        self._check(self._L.bvc_site_stats_csr(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(entries_t), _dev_ptr(ref_t), _dev_ptr(results_t),
+                                               _dev_ptr(stats_t), BVC_PTR_DEVICE))
+        return stats_t
+
     def pileup_tile(self, text, line_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
-                    n_groups=0, called_only=False):
+                    n_groups=0, called_only=False, stats=False):
         """bvc_pileup_begin + bvc_pileup_finish on one tile of temp-batch pileup text (include/bvc.h).  text: bytes;
         line_start: uint32 [n_batches, n_positions + 1].  Returns None when a line is not regular (BVC_PILEUP_IRREGULAR), else a
-        dict: entry_off, tally [T, 32], entries (structured), samples, indels (sorted by entry), results, grp_results, carry_out."""
+        dict: entry_off, tally [T, 32], entries (structured), samples, indels (sorted by entry), results, grp_results, carry_out.
+        stats=True (needs called_only=True): bvc_pileup_finish_called_stats -- key "stats", STATS_DTYPE [T]."""
         ls = np.ascontiguousarray(line_start, dtype=np.uint32)
         nb, T = ls.shape[0], ls.shape[1] - 1
         s0 = np.ascontiguousarray(sample0, dtype=np.int32)
@@ -373,10 +410,10 @@ class Context:
         if rc == 1:
             return None
         self._check(rc)
-        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only)
+        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
 
     def pileup_tile_bin(self, records, rec_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
-                        n_groups=0, called_only=False):
+                        n_groups=0, called_only=False, stats=False):
         """bvc_pileup_begin_bin + bvc_pileup_finish on one tile of binary temp-batch records (include/bvc.h).  records: bytes;
         rec_start: uint32 [n_batches, n_positions + 1].  Returns the dict of pileup_tile (indels' text_off are offsets into records);
         raises BvcError (status BVC_ERR_DATA = -5: a malformed record, BVC_ERR_ARG = -1: a rec_start that does not fit)."""
@@ -392,13 +429,15 @@ class Context:
         ne, ni = C.c_int64(0), C.c_int64(0)
         self._check(self._L.bvc_pileup_begin_bin(self._h, _np_ptr(buf) if len(buf) else None, len(buf), _np_ptr(rs), _np_ptr(s0), _np_ptr(nib),
                                                  nb, T, C.byref(ne), C.byref(ni)))
-        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only)
+        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
 
     def _pileup_finish(self, T, n_entries, n_indels, indel_text_bytes, ref_base, min_af, carry_in, group_of_sample, n_groups,
-                       called_only=False, called_cap=None):
+                       called_only=False, called_cap=None, stats=False):
         """called_only: bvc_pileup_finish_called -- `entries` / `samples` hold the called positions' entries only, position t's at
-        called_off[t] .. called_off[t + 1] (key "called_off")."""
-        ENTRY = np.dtype([("base", "u1"), ("mapq", "u1"), ("qual", "u1"), ("rpr", "u1"), ("strand", "u1"), ("is_indel", "u1"), ("pad", "<u2")])
+        called_off[t] .. called_off[t + 1] (key "called_off").  stats (with called_only): bvc_pileup_finish_called_stats, key "stats"."""
+        if stats and not called_only:
+            raise ValueError("stats=True needs called_only=True (bvc_pileup_finish_called_stats)")
+        ENTRY = ENTRY_DTYPE
         INDEL = np.dtype([("entry", "<i8"), ("text_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])
         r = np.ascontiguousarray(ref_base, dtype=np.int8)
         assert r.shape == (T,)
@@ -416,17 +455,24 @@ class Context:
         if called_only:
             called_off = np.zeros(T + 1, dtype=np.int64)
             cap = n_entries if called_cap is None else int(called_cap)
-            self._check(self._L.bvc_pileup_finish_called(self._h, _np_ptr(r), float(min_af), _np_ptr(cin), _np_ptr(cout),
-                                                         _np_ptr(g) if n_groups else None, len(g), int(n_groups), _np_ptr(entry_off), _np_ptr(tally),
-                                                         _np_ptr(called_off), cap, _np_ptr(entries), _np_ptr(samples), _np_ptr(indels),
-                                                         _np_ptr(itext) if indel_text_bytes else None, _np_ptr(res),
-                                                         _np_ptr(gres) if n_groups else None))
+            args = [self._h, _np_ptr(r), float(min_af), _np_ptr(cin), _np_ptr(cout),
+                    _np_ptr(g) if n_groups else None, len(g), int(n_groups), _np_ptr(entry_off), _np_ptr(tally),
+                    _np_ptr(called_off), cap, _np_ptr(entries), _np_ptr(samples), _np_ptr(indels),
+                    _np_ptr(itext) if indel_text_bytes else None, _np_ptr(res), _np_ptr(gres) if n_groups else None]
+            if stats:
+                st = np.zeros(max(1, T), dtype=STATS_DTYPE)
+                self._check(self._L.bvc_pileup_finish_called_stats(*args, _np_ptr(st)))
+            else:
+                self._check(self._L.bvc_pileup_finish_called(*args))
             n_c = int(called_off[T])
             ind = indels[:n_indels]
             ind = ind[np.argsort(ind["entry"], kind="stable")]
-            return dict(entry_off=entry_off, called_off=called_off, tally=tally, entries=entries[:n_c], samples=samples[:n_c], indels=ind,
-                        results=res, grp_results=gres if n_groups else None, carry_out=[int(x) for x in cout],
-                        indel_text=itext[:indel_text_bytes].tobytes())
+            out = dict(entry_off=entry_off, called_off=called_off, tally=tally, entries=entries[:n_c], samples=samples[:n_c], indels=ind,
+                       results=res, grp_results=gres if n_groups else None, carry_out=[int(x) for x in cout],
+                       indel_text=itext[:indel_text_bytes].tobytes())
+            if stats:
+                out["stats"] = st[:T]
+            return out
         self._check(self._L.bvc_pileup_finish(self._h, _np_ptr(r), float(min_af), _np_ptr(cin), _np_ptr(cout), _np_ptr(g) if n_groups else None,
                                               len(g), int(n_groups), _np_ptr(entry_off), _np_ptr(tally), _np_ptr(entries), _np_ptr(samples),
                                               _np_ptr(indels), _np_ptr(itext) if indel_text_bytes else None, _np_ptr(res),

@@ -353,6 +353,52 @@ int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af
                              int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
                              bvc_group_result *grp_results);
 /*
+ * Additive: what WriteVcf (src/BaseType.cpp:141-234) computes from a CALLED position's entries besides the sample columns -- the
+ * inputs of MQRankSum / BaseQRankSum / ReadPosRankSum (RankSumTest, src/Algorithm.cpp:55-67) and of FS / SOR / SB_REF / SB_ALT (Stat,
+ * src/BaseType.cpp:174-186) -- as integers, computed on the device from the entries.
+ *
+ * An entry counts iff is_indel != 1 and base <= 3.  It is a REF observation iff base == ref_base[s] (a ref_base outside 0..3 matches
+ * nothing), otherwise an ALT observation iff base is one of results[s].alt_base[0 .. n_alt) (n_alt > 3 is read as 3), otherwise it is
+ * ignored; forward iff strand == 1 (WriteVcf:164-186).
+ *
+ * rankR1 (src/Algorithm.cpp:27-53) ranks the pooled ref + alt values in DESCENDING order, a run of equal values sharing the mean of its
+ * ranks, and sums the ranks of the ref observations.  All three fields are bytes (src/BamProcess.h:32-37), so with r[v] / a[v] the
+ * ref / alt observations of value v and lo the pooled observations of a value larger than v, the run of v occupies the ranks
+ * lo + 1 .. lo + r[v] + a[v] and
+ *     rank2 = 2 * r1 = sum over v of r[v] * (2 * lo + r[v] + a[v] + 1)
+ * an integer; rank2 / 2.0 is exact (below 2^53) and is the double the host's rank_r1 returns (host/stats.cpp), so z, the phred value and
+ * the printed text follow from (rank2, n_ref, n_alt) unchanged: bvchost_ranksum_from_rank2 / RankSumFromR1 (host/stats.h).  The
+ * reference's rankR1 itself keeps a run's rank sum in an int32_t, which overflows once a run of equal values is longer than about 65,536
+ * observations; this statistic is the host program's, which does not (host/stats.cpp).
+ */
+typedef struct bvc_site_stats {          /* 64 bytes */
+    int64_t rank2[3];                    /* 2 x rankR1 of the REF observations in the pooled ref + alt values: [0] mapq, [1] qual, [2] rpr */
+    int32_t n_ref, n_alt;                /* sizes of the two samples (RankSumTest's n1, n2) */
+    int32_t ref_fwd, ref_rev, alt_fwd, alt_rev;   /* Stat, src/BaseType.cpp:174-186 */
+    uint8_t valid;                       /* 1 where results[s].called != 0, else the whole record is 0 */
+    uint8_t pad[15];
+} bvc_site_stats;
+/*
+ * stats[s] for site s < n_sites from its entries[offsets[s] .. offsets[s + 1]); a site with results[s].called == 0 gets a zeroed record and
+ * its entries are not read.  Host or device pointers (flags); device `entries` may start at any entry; device `stats` must start on a
+ * 16-byte boundary (the records are written with 16-byte stores).  With host pointers the small arrays are staged through the context's page-locked buffer; the entries, the bulk, are copied
+ * from the caller's memory as it is -- a DMA the call sleeps behind when they lie in bvc_host_alloc memory, a pageable copy otherwise.  Of `results`
+ * only called, n_alt and alt_base are read, and they must be COMPLETE: in overlap mode call bvc_join after the bvc_lrt_* call that
+ * writes them -- this call is ordered on the context's stream behind that join, it does not join by itself.  BVC_ERR_ARG: null pointers
+ * with work present, a negative n_sites, host offsets that do not start at 0 or that decrease.
+ */
+int bvc_site_stats_csr(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const bvc_pileup_entry *entries,
+                       const int8_t *ref_base, const bvc_site_result *results, bvc_site_stats *stats, uint32_t flags);
+/*
+ * bvc_pileup_finish_called with the statistics of every position of the tile: stats [n_positions], computed on the tile's entries where
+ * they lie on the device and delivered with the records (no further transfer or wait).  stats == NULL: bvc_pileup_finish_called itself.
+ */
+int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                                   const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                                   int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
+                                   int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
+                                   bvc_group_result *grp_results, bvc_site_stats *stats);
+/*
  * The same from the COMPRESSED temp batches: the BGZF blocks go to the device as they are in the files (a fifth of the bytes of
  * their text), are inflated there (bvc_inflate_blocks) and the text never exists on the host.  The caller no longer knows where the
  * lines are, so the call decides the tile's positions itself: every batch's text so far = what the previous call left of it (kept
@@ -475,6 +521,8 @@ int bvc_synth_dense(bvc_ctx *ctx, uint64_t seed, int64_t site0, int64_t n_sites,
  *                      observation, lanes running over the observations across site boundaries; a longer one through a histogram in
  *                      LDS that one workgroup adds to the counts.  0 = never scatter, up to 1 << 30 (= always: the scatter kernel alone, sites of any length).  Default 64
  *                      (measured: DESIGN.md section 3.10).  Environment: BVC_CSR_SCATTER_MAX
+ *   "stats_copies_log2"  bvc_site_stats_csr / bvc_pileup_finish_called_stats: 2^n copies (0..4, default 2) of the 1536 counters a
+ *                      workgroup keeps in LDS, copy = lane mod 2^n (A/B runs).  Environment: BVC_STATS_LOG2C
  *   "host_chunk_kib"   BVC_PTR_HOST calls stage the tile through device memory in chunks of sites of at most this
  *                      many KiB per array (default 524288 = 512 MiB); the upload of chunk i+1 runs under the kernels
  *                      of chunk i
