@@ -1,6 +1,7 @@
 """ctypes binding of libbvc.so (include/bvc.h).  Device memory, streams and multi-process plumbing come
 from torch; the arithmetic is all inside the library's HIP kernels."""
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -38,39 +39,95 @@ class Profile(C.Structure):
                 ("em_launches", C.c_int64), ("sites", C.c_int64)]
 
 
-SITE_DTYPE = np.dtype([
-    ("var_qual", "<f8"), ("chi", "<f8"), ("depth_total", "<f8"), ("af", "<f8", (3,)), ("lr_alt", "<f8"),
-    ("base_frq", "<f8", (4,)), ("depth", "<i4", (4,)), ("n_passes", "<i4"), ("alt_base", "i1", (3,)),
-    ("n_alt", "u1"), ("called", "u1"), ("n_kept", "u1"), ("kept", "i1", (4,)), ("status", "u1"), ("n_fits", "u1"),
-])
-GROUP_DTYPE = np.dtype([("af", "<f8", (3,)), ("depth", "<i4", (4,)), ("ran", "u1"), ("present", "u1"), ("pad", "u1", (6,))])
+SITE_DTYPE = np.dtype(SiteResult)
+GROUP_DTYPE = np.dtype(GroupResult)
 # bvc_site_stats, 64 bytes: the called sites' rank sums (rank2 = 2 x rankR1 of the REF observations: mapq, qual, rpr) and strand counts
 STATS_DTYPE = np.dtype([("rank2", "<i8", (3,)), ("n_ref", "<i4"), ("n_alt", "<i4"), ("ref_fwd", "<i4"), ("ref_rev", "<i4"),
                         ("alt_fwd", "<i4"), ("alt_rev", "<i4"), ("valid", "u1"), ("pad", "u1", (15,))])
 ENTRY_DTYPE = np.dtype([("base", "u1"), ("mapq", "u1"), ("qual", "u1"), ("rpr", "u1"), ("strand", "u1"), ("is_indel", "u1"), ("pad", "<u2")])
+INDEL_DTYPE = np.dtype([("entry", "<i8"), ("text_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])                 # bvc_pileup_indel
+BLOCK_DTYPE = np.dtype([("comp_off", "<i8"), ("out_off", "<i8"), ("comp_len", "<i4"), ("isize", "<i4"), ("crc32", "<u4"),
+                        ("check_crc", "<u4")])                                                                   # bvc_bgzf_block
 SITE_STATS_TRIP = 4096      # entries a workgroup of site_stats_kernel takes per trip of its loop (csrc/bvc_internal.h, kSiteStatsTrip)
 assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 120
 assert STATS_DTYPE.itemsize == 64 and ENTRY_DTYPE.itemsize == 8
 assert GROUP_DTYPE.itemsize == C.sizeof(GroupResult) == 48
 
-EXPORTS = [
-    "bvc_version", "bvc_device_count", "bvc_create", "bvc_destroy", "bvc_last_error", "bvc_set_stream",
-    "bvc_synchronize", "bvc_set_overlap", "bvc_join", "bvc_set_profiling", "bvc_get_profile", "bvc_lrt_dense", "bvc_lrt_dense_groups",
-    "bvc_lrt_csr", "bvc_lrt_csr_comb", "bvc_hist_dense", "bvc_lrt_hist", "bvc_synth_dense", "bvc_stream_read_ms", "bvc_set_tuning",
-    "bvc_lrt_dense_packed", "bvc_pack_dense", "bvc_hist_dense_packed", "bvc_lrt_dense_groups_packed",
-    "bvc_lrt_csr_packed", "bvc_lrt_csr_groups", "bvc_lrt_csr_group_labels", "bvc_lrt_csr_group_labels_packed", "bvc_pileup_begin", "bvc_pileup_finish", "bvc_pileup_finish_called", "bvc_inflate_blocks", "bvc_pileup_begin_bgzf", "bvc_pileup_text",
-    "bvc_pileup_begin_bin",
-    "bvc_host_alloc", "bvc_host_free",
-    "bvc_counts_add_dense", "bvc_counts_add_dense_packed", "bvc_counts_add_csr", "bvc_counts_add_csr_packed",
-    "bvc_counts_add_dense_groups", "bvc_counts_add_csr_group_labels", "bvc_lrt_hist_groups", "bvc_counts_merge",
-    "bvc_site_stats_csr", "bvc_pileup_finish_called_stats",
-]
+# The C ABI, one row per function: name -> (restype, argtypes), in the order of include/bvc.h (tests/test_binding_abi.py compares
+# the two).  A new entry point takes a row here and a Context method below.
+_vp, _i64, _i32, _u32, _dbl, _int = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_double, C.c_int
+_pi64 = C.POINTER(C.c_int64)
+PROTOTYPES = {
+    "bvc_version": (C.c_char_p, []),
+    "bvc_device_count": (_int, []),
+    "bvc_create": (_int, [C.POINTER(_vp), _int]),
+    "bvc_destroy": (None, [_vp]),
+    "bvc_host_alloc": (_vp, [C.c_size_t]),
+    "bvc_host_free": (None, [_vp]),
+    "bvc_last_error": (C.c_char_p, [_vp]),
+    "bvc_set_stream": (_int, [_vp, _vp]),
+    "bvc_synchronize": (_int, [_vp]),
+    "bvc_set_overlap": (_int, [_vp, _int]),
+    "bvc_join": (_int, [_vp]),
+    "bvc_set_profiling": (_int, [_vp, _int]),
+    "bvc_get_profile": (_int, [_vp, C.POINTER(Profile), _int]),
+    "bvc_lrt_dense": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _dbl, _vp, _u32]),
+    "bvc_lrt_dense_groups": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _dbl, _vp, _i32, _vp, _vp, _u32]),
+    "bvc_lrt_csr": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _u32]),
+    "bvc_lrt_csr_comb": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _dbl, _vp, _vp, _vp, _u32]),
+    "bvc_lrt_csr_packed": (_int, [_vp, _i64, _vp, _vp, _vp, _dbl, _vp, _u32]),
+    "bvc_lrt_dense_packed": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dbl, _vp, _u32]),
+    "bvc_lrt_dense_groups_packed": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _dbl, _vp, _i32, _vp, _vp, _u32]),
+    "bvc_pack_dense": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _pi64, _u32]),
+    "bvc_lrt_csr_groups": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _vp, _i64, _i32, _vp, _vp, _u32]),
+    "bvc_lrt_csr_group_labels": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _u32]),
+    "bvc_lrt_csr_group_labels_packed": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _dbl, _i32, _vp, _vp, _u32]),
+    "bvc_inflate_blocks": (_int, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _u32]),
+    "bvc_pileup_begin": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _pi64, _pi64]),
+    "bvc_pileup_finish": (_int, [_vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bvc_pileup_begin_bin": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _i32, _i32, _pi64, _pi64]),
+    "bvc_pileup_finish_called": (_int, [_vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bvc_site_stats_csr": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _u32]),
+    "bvc_pileup_finish_called_stats": (_int, [_vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp,
+                                              _vp, _vp]),
+    "bvc_pileup_begin_bgzf": (_int, [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, C.POINTER(_i32), _vp, _pi64, _pi64, _pi64]),
+    "bvc_pileup_text": (_int, [_vp, _vp, _i64, _pi64, _vp]),
+    "bvc_hist_dense": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _u32]),
+    "bvc_hist_dense_packed": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _u32]),
+    "bvc_lrt_hist": (_int, [_vp, _i64, _vp, _vp, _dbl, _vp, _vp, _vp, _u32]),
+    "bvc_counts_add_dense": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _u32]),
+    "bvc_counts_add_dense_packed": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _u32]),
+    "bvc_counts_add_csr": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _u32]),
+    "bvc_counts_add_csr_packed": (_int, [_vp, _i64, _vp, _vp, _vp, _u32]),
+    "bvc_counts_add_dense_groups": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _u32]),
+    "bvc_counts_add_csr_group_labels": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _u32]),
+    "bvc_lrt_hist_groups": (_int, [_vp, _i64, _vp, _vp, _dbl, _i32, _vp, _vp, _u32]),
+    "bvc_counts_merge": (_int, [_vp, _i64, _vp, _vp, _u32]),
+    "bvc_synth_dense": (_int, [_vp, C.c_uint64, _i64, _i64, _i64, _i64, _u32, _vp, _vp, _vp]),
+    "bvc_set_tuning": (_int, [_vp, C.c_char_p, _int]),
+    "bvc_stream_read_ms": (_int, [_vp, _vp, _i64, _int, C.POINTER(_dbl)]),
+    # not in the header: diagnostic builds of the library only export it (-DBVC_CHECK_LDS, csrc/bvc_device.h)
+    "bvc_debug_report": (_int, [_vp, C.POINTER(_u32), _int]),
+}
+OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
+EXPORTS = [name for name in PROTOTYPES if name not in OPTIONAL]   # what every build of the library exports
 
 _lib = None
 
 
 def library_path():
     return _LIB
+
+
+def bind(cdll):
+    """Gives every function of PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
+    symbol that the library lacks is an AttributeError."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        if name in OPTIONAL and not hasattr(cdll, name):
+            continue
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll
 
 
 def load_library():
@@ -85,90 +142,8 @@ def load_library():
     if not os.path.exists(_LIB):
         raise BvcError(f"{_LIB} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                        "(hipcc --offload-arch=gfx950); basevarc_amd has no CPU fallback")
-    L = C.CDLL(_LIB)
-    vp, i64, u32, i32, dbl = C.c_void_p, C.c_int64, C.c_uint32, C.c_int32, C.c_double
-    L.bvc_version.restype = C.c_char_p
-    L.bvc_device_count.restype = C.c_int
-    L.bvc_create.restype = C.c_int; L.bvc_create.argtypes = [C.POINTER(vp), C.c_int]
-    L.bvc_destroy.restype = None; L.bvc_destroy.argtypes = [vp]
-    L.bvc_last_error.restype = C.c_char_p; L.bvc_last_error.argtypes = [vp]
-    L.bvc_set_stream.restype = C.c_int; L.bvc_set_stream.argtypes = [vp, vp]
-    L.bvc_synchronize.restype = C.c_int; L.bvc_synchronize.argtypes = [vp]
-    L.bvc_set_overlap.restype = C.c_int; L.bvc_set_overlap.argtypes = [vp, C.c_int]
-    L.bvc_join.restype = C.c_int; L.bvc_join.argtypes = [vp]
-    L.bvc_set_profiling.restype = C.c_int; L.bvc_set_profiling.argtypes = [vp, C.c_int]
-    L.bvc_get_profile.restype = C.c_int; L.bvc_get_profile.argtypes = [vp, C.POINTER(Profile), C.c_int]
-    L.bvc_lrt_dense.restype = C.c_int
-    L.bvc_lrt_dense.argtypes = [vp, i64, i64, i64, vp, vp, vp, dbl, vp, u32]
-    L.bvc_lrt_dense_groups.restype = C.c_int
-    L.bvc_lrt_dense_groups.argtypes = [vp, i64, i64, i64, vp, vp, vp, dbl, vp, i32, vp, vp, u32]
-    L.bvc_lrt_csr.restype = C.c_int
-    L.bvc_lrt_csr.argtypes = [vp, i64, vp, vp, vp, vp, dbl, vp, u32]
-    L.bvc_hist_dense.restype = C.c_int
-    L.bvc_hist_dense.argtypes = [vp, i64, i64, i64, vp, vp, vp, u32]
-    L.bvc_lrt_hist.restype = C.c_int
-    L.bvc_lrt_hist.argtypes = [vp, i64, vp, vp, dbl, vp, vp, vp, u32]
-    L.bvc_synth_dense.restype = C.c_int
-    L.bvc_synth_dense.argtypes = [vp, C.c_uint64, i64, i64, i64, i64, u32, vp, vp, vp]
-    L.bvc_lrt_csr_comb.restype = C.c_int
-    L.bvc_lrt_csr_comb.argtypes = [vp, i64, vp, vp, vp, vp, dbl, vp, vp, vp, u32]
-    L.bvc_set_tuning.restype = C.c_int; L.bvc_set_tuning.argtypes = [vp, C.c_char_p, C.c_int]
-    L.bvc_stream_read_ms.restype = C.c_int
-    L.bvc_stream_read_ms.argtypes = [vp, vp, i64, C.c_int, C.POINTER(C.c_double)]
-    L.bvc_lrt_dense_packed.restype = C.c_int
-    L.bvc_lrt_dense_packed.argtypes = [vp, i64, i64, i64, vp, vp, dbl, vp, u32]
-    L.bvc_pack_dense.restype = C.c_int
-    L.bvc_pack_dense.argtypes = [vp, i64, i64, i64, vp, vp, i64, vp, C.POINTER(i64), u32]
-    L.bvc_lrt_dense_groups_packed.restype = C.c_int
-    L.bvc_lrt_dense_groups_packed.argtypes = [vp, i64, i64, i64, vp, vp, dbl, vp, i32, vp, vp, u32]
-    L.bvc_hist_dense_packed.restype = C.c_int
-    L.bvc_hist_dense_packed.argtypes = [vp, i64, i64, i64, vp, vp, u32]
-    L.bvc_lrt_csr_packed.restype = C.c_int
-    L.bvc_lrt_csr_packed.argtypes = [vp, i64, vp, vp, vp, dbl, vp, u32]
-    L.bvc_lrt_csr_groups.restype = C.c_int
-    L.bvc_lrt_csr_groups.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, vp, i64, i32, vp, vp, u32]
-    L.bvc_lrt_csr_group_labels.restype = C.c_int
-    L.bvc_lrt_csr_group_labels.argtypes = [vp, i64, vp, vp, vp, vp, vp, dbl, i32, vp, vp, u32]
-    L.bvc_lrt_csr_group_labels_packed.restype = C.c_int
-    L.bvc_lrt_csr_group_labels_packed.argtypes = [vp, i64, vp, vp, vp, vp, dbl, i32, vp, vp, u32]
-    L.bvc_pileup_begin.restype = C.c_int
-    L.bvc_pileup_begin.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
-    L.bvc_pileup_begin_bin.restype = C.c_int
-    L.bvc_pileup_begin_bin.argtypes = [vp, vp, i64, vp, vp, vp, i32, i32, C.POINTER(i64), C.POINTER(i64)]
-    L.bvc_pileup_finish.restype = C.c_int
-    L.bvc_pileup_finish.argtypes = [vp, vp, dbl, vp, vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.bvc_pileup_finish_called.restype = C.c_int
-    L.bvc_pileup_finish_called.argtypes = [vp, vp, dbl, vp, vp, vp, i64, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp]
-    L.bvc_pileup_begin_bgzf.restype = C.c_int
-    L.bvc_pileup_begin_bgzf.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, i32, i32, i32, C.POINTER(i32), vp, C.POINTER(i64), C.POINTER(i64),
-                                        C.POINTER(i64)]
-    L.bvc_pileup_text.restype = C.c_int
-    L.bvc_pileup_text.argtypes = [vp, vp, i64, C.POINTER(i64), vp]
-    L.bvc_inflate_blocks.restype = C.c_int
-    L.bvc_inflate_blocks.argtypes = [vp, vp, i64, vp, i64, vp, i64, vp, u32]
-    # counts accumulated over sample chunks
-    L.bvc_counts_add_dense.restype = C.c_int
-    L.bvc_counts_add_dense.argtypes = [vp, i64, i64, i64, vp, vp, vp, u32]
-    L.bvc_counts_add_dense_packed.restype = C.c_int
-    L.bvc_counts_add_dense_packed.argtypes = [vp, i64, i64, i64, vp, vp, u32]
-    L.bvc_counts_add_csr.restype = C.c_int
-    L.bvc_counts_add_csr.argtypes = [vp, i64, vp, vp, vp, vp, u32]
-    L.bvc_counts_add_csr_packed.restype = C.c_int
-    L.bvc_counts_add_csr_packed.argtypes = [vp, i64, vp, vp, vp, u32]
-    L.bvc_counts_add_dense_groups.restype = C.c_int
-    L.bvc_counts_add_dense_groups.argtypes = [vp, i64, i64, i64, vp, vp, vp, i32, vp, u32]
-    L.bvc_counts_add_csr_group_labels.restype = C.c_int
-    L.bvc_counts_add_csr_group_labels.argtypes = [vp, i64, vp, vp, vp, vp, i32, vp, u32]
-    L.bvc_lrt_hist_groups.restype = C.c_int
-    L.bvc_lrt_hist_groups.argtypes = [vp, i64, vp, vp, dbl, i32, vp, vp, u32]
-    L.bvc_counts_merge.restype = C.c_int
-    L.bvc_counts_merge.argtypes = [vp, i64, vp, vp, u32]
-    L.bvc_site_stats_csr.restype = C.c_int
-    L.bvc_site_stats_csr.argtypes = [vp, i64, vp, vp, vp, vp, vp, u32]
-    L.bvc_pileup_finish_called_stats.restype = C.c_int
-    L.bvc_pileup_finish_called_stats.argtypes = L.bvc_pileup_finish_called.argtypes + [vp]
-    _lib = L
-    return L
+    _lib = bind(C.CDLL(_LIB))
+    return _lib
 
 
 def _np_ptr(a):
@@ -177,6 +152,33 @@ def _np_ptr(a):
 
 def _dev_ptr(t):
     return C.c_void_p(t.data_ptr())
+
+
+def _pointers(args, ptr):
+    """A call's arguments in the header's order: arrays and tensors become pointers; None (NULL), numbers and ctypes objects pass as they are."""
+    return [ptr(a) if isinstance(a, np.ndarray) or hasattr(a, "data_ptr") else a for a in args]
+
+
+def _as(a, dtype):
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def _tile(bases_t, quals_t=None):
+    """(n_sites, n_samples, row_stride) of a device tile: rows contiguous, and with two tensors both of one stride."""
+    assert bases_t.stride(1) == 1 and (quals_t is None or (quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0)))
+    return (*bases_t.shape, bases_t.stride(0))
+
+
+def _block_table(blocks, consecutive):
+    """blocks: [(comp_off, comp_len, isize[, crc32])]; with a CRC it is compared.  consecutive: the outputs lie one after the other
+    (out_off), else out_off stays 0.  Returns (BLOCK_DTYPE table of at least one row, the sum of isize)."""
+    tab = np.zeros(max(1, len(blocks)), dtype=BLOCK_DTYPE)
+    at = 0
+    for i, blk in enumerate(blocks):
+        co, cl, isz = blk[:3]
+        tab[i] = (co, at if consecutive else 0, cl, isz, blk[3] if len(blk) > 3 else 0, 1 if len(blk) > 3 else 0)
+        at += isz
+    return tab, at
 
 
 class Context:
@@ -217,6 +219,23 @@ class Context:
             err.status = rc
             raise err
 
+    def _call(self, fn, device, args, records=()):
+        """fn(ctx, *args, *records, flags), the shape of every compute entry point: `device` picks host (numpy, synchronous) or device
+        (torch tensors, asynchronous on the stream) pointers and the flag.  args: the sizes, input arrays and scalars in the header's
+        order.  records: (buffer or None, shape, dtype) per result array; a missing one is np.zeros of the dtype on the host, uint8
+        bytes on the device of the first input tensor.  Returns the list of record buffers."""
+        bufs = []
+        for buf, shape, dtype in records:
+            if buf is None and device:
+                import torch
+                on = next(a for a in args if hasattr(a, "data_ptr")).device
+                buf = torch.empty(math.prod(shape) * dtype.itemsize, dtype=torch.uint8, device=on)
+            elif buf is None:
+                buf = np.zeros(shape, dtype=dtype)
+            bufs.append(buf)
+        self._check(fn(self._h, *_pointers((*args, *bufs), _dev_ptr if device else _np_ptr), BVC_PTR_DEVICE if device else BVC_PTR_HOST))
+        return bufs
+
     # ---- plumbing
     def set_stream(self, stream):
         """stream: a torch.cuda.Stream, a raw hipStream_t integer, or None for the default stream."""
@@ -248,188 +267,259 @@ class Context:
         if not hasattr(self._L, "bvc_debug_report"):
             return None
         out = (C.c_uint32 * 24)()
-        self._L.bvc_debug_report.restype = C.c_int
-        self._L.bvc_debug_report.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.c_int]
         self._check(self._L.bvc_debug_report(self._h, out, int(bool(reset))))
         return {tu: [int(x) for x in out[8 * i:8 * i + 6]] for i, tu in enumerate(("hist_kernel", "em_kernel", "em_items"))}
 
-    # ---- host-pointer calls (numpy in, numpy structured array out)
+    def set_tuning(self, key, value):
+        """Launch policy of this context (include/bvc.h); results never depend on it."""
+        self._check(self._L.bvc_set_tuning(self._h, key.encode(), int(value)))
+
+    def host_alloc(self, nbytes):
+        """bvc_host_alloc: (address, uint8 view of the page-locked bytes); free with host_free(address)."""
+        addr = self._L.bvc_host_alloc(int(nbytes))
+        if not addr:
+            raise BvcError("bvc_host_alloc failed")
+        return addr, np.ctypeslib.as_array((C.c_uint8 * int(nbytes)).from_address(addr))
+
+    def host_free(self, addr):
+        self._L.bvc_host_free(addr)
+
+    def stream_read_gbs(self, tensor, repeats=5):
+        """Empirical HBM read bandwidth (GB/s): a plain 16 B/lane streaming read of `tensor` (device, contiguous)."""
+        ms = C.c_double()
+        nbytes = tensor.numel() * tensor.element_size()
+        self._check(self._L.bvc_stream_read_ms(self._h, _dev_ptr(tensor), nbytes, int(repeats), C.byref(ms)))
+        return nbytes / (ms.value * 1e-3) / 1e9
+
+    def synth_dense_device(self, seed, site0, bases_t, quals_t, ref_t, cov_thr16=65536):
+        ns, n = bases_t.shape
+        self._check(self._L.bvc_synth_dense(self._h, int(seed), int(site0), ns, n, bases_t.stride(0), int(cov_thr16),
+                                            _dev_ptr(bases_t), _dev_ptr(quals_t), _dev_ptr(ref_t)))
+
+    # ---- the compute entry points.  Each has one private body (device, sizes, arrays, scalars[, result buffers]) that holds the
+    # call's argument list, and two public forms on it: host (numpy in, numpy structured arrays out, synchronous) and *_device
+    # (torch tensors on this context's device in, uint8 tensors of the records out, asynchronous on the stream).
+    def _lrt_dense(self, device, ns, n, stride, b, q, r, min_af, res=None):
+        return self._call(self._L.bvc_lrt_dense, device, (ns, n, stride, b, q, r, float(min_af)), [(res, (ns,), SITE_DTYPE)])[0]
+
     def lrt_dense(self, bases, quals, ref_base, min_af):
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        b, q, r = _as(bases, np.int8), _as(quals, np.int8), _as(ref_base, np.int8)
         if b.ndim != 2 or b.shape != q.shape or r.shape != (b.shape[0],):
             raise ValueError("bases/quals must be [n_sites, n_samples] and ref_base [n_sites]")
-        out = np.zeros(b.shape[0], dtype=SITE_DTYPE)
-        self._check(self._L.bvc_lrt_dense(self._h, b.shape[0], b.shape[1], b.shape[1], _np_ptr(b), _np_ptr(q),
-                                          _np_ptr(r), float(min_af), _np_ptr(out), BVC_PTR_HOST))
-        return out
+        return self._lrt_dense(False, b.shape[0], b.shape[1], b.shape[1], b, q, r, min_af)
+
+    def lrt_dense_device(self, bases_t, quals_t, ref_t, min_af, results_t=None):
+        """bases_t/quals_t: int8 [n_sites, row_stride]-strided CUDA tensors; results_t: uint8 [n_sites*120]."""
+        return self._lrt_dense(True, *_tile(bases_t, quals_t), bases_t, quals_t, ref_t, min_af, results_t)
+
+    def _lrt_dense_groups(self, device, ns, n, stride, b, q, r, min_af, g, n_groups, res=None, gres=None):
+        return tuple(self._call(self._L.bvc_lrt_dense_groups, device, (ns, n, stride, b, q, r, float(min_af), g, int(n_groups)),
+                                [(res, (ns,), SITE_DTYPE), (gres, (ns, n_groups), GROUP_DTYPE)]))
 
     def lrt_dense_groups(self, bases, quals, ref_base, min_af, group_of_sample, n_groups):
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8)
+        b, q, r, g = _as(bases, np.int8), _as(quals, np.int8), _as(ref_base, np.int8), _as(group_of_sample, np.uint8)
         if b.ndim != 2 or b.shape != q.shape or r.shape != (b.shape[0],) or g.shape != (b.shape[1],):
             raise ValueError("shape mismatch")
-        out = np.zeros(b.shape[0], dtype=SITE_DTYPE)
-        gout = np.zeros((b.shape[0], n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_dense_groups(self._h, b.shape[0], b.shape[1], b.shape[1], _np_ptr(b),
-                                                 _np_ptr(q), _np_ptr(r), float(min_af), _np_ptr(g), int(n_groups),
-                                                 _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
-        return out, gout
+        return self._lrt_dense_groups(False, b.shape[0], b.shape[1], b.shape[1], b, q, r, min_af, g, n_groups)
+
+    def lrt_dense_groups_device(self, bases_t, quals_t, ref_t, min_af, group_t, n_groups, results_t=None,
+                                grp_results_t=None):
+        """Group mode on device tensors; group_t: uint8 [n_samples].  Returns (results_t, grp_results_t)."""
+        return self._lrt_dense_groups(True, *_tile(bases_t, quals_t), bases_t, quals_t, ref_t, min_af, group_t, n_groups, results_t, grp_results_t)
 
     def lrt_csr(self, offsets, bases, quals, ref_base, min_af, base_comb=None, n_comb=None):
         """Ragged sites (the vectors bt_f builds); base_comb/n_comb: optional per-site SetBase lists."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        o, b, q, r = _as(offsets, np.int64), _as(bases, np.int8), _as(quals, np.int8), _as(ref_base, np.int8)
         n = len(o) - 1
-        out = np.zeros(n, dtype=SITE_DTYPE)
         cb = nc = None
         if base_comb is not None:
-            cb = np.ascontiguousarray(base_comb, dtype=np.int8).reshape(-1, 4)
-            nc = np.ascontiguousarray(n_comb, dtype=np.uint8)
-        self._check(self._L.bvc_lrt_csr_comb(self._h, n, _np_ptr(o), _np_ptr(b), _np_ptr(q), _np_ptr(r), float(min_af),
-                                             _np_ptr(cb) if cb is not None else None,
-                                             _np_ptr(nc) if nc is not None else None, _np_ptr(out), BVC_PTR_HOST))
-        return out
+            cb = _as(base_comb, np.int8).reshape(-1, 4)
+            nc = _as(n_comb, np.uint8)
+        return self._call(self._L.bvc_lrt_csr_comb, False, (n, o, b, q, r, float(min_af), cb, nc), [(None, (n,), SITE_DTYPE)])[0]
+
+    def lrt_csr_device(self, offsets_t, bases_t, quals_t, ref_t, min_af, results_t=None):
+        """offsets_t: int64 [n_sites + 1]; bases_t/quals_t: int8 [total] CUDA tensors (asynchronous on the stream)."""
+        ns = offsets_t.numel() - 1
+        return self._call(self._L.bvc_lrt_csr, True, (ns, offsets_t, bases_t, quals_t, ref_t, float(min_af)),
+                          [(results_t, (ns,), SITE_DTYPE)])[0]
+
+    def _lrt_csr_packed(self, device, ns, o, pk, r, min_af, res=None):
+        return self._call(self._L.bvc_lrt_csr_packed, device, (ns, o, pk, r, float(min_af)), [(res, (ns,), SITE_DTYPE)])[0]
+
+    def lrt_csr_packed(self, offsets, packed, ref_base, min_af):
+        """Ragged sites at one byte per observation (base << 6 | qual); host arrays, synchronous."""
+        o = _as(offsets, np.int64)
+        return self._lrt_csr_packed(False, len(o) - 1, o, _as(packed, np.uint8), _as(ref_base, np.int8), min_af)
+
+    def lrt_csr_packed_device(self, offsets_t, packed_t, ref_t, min_af, results_t=None):
+        return self._lrt_csr_packed(True, offsets_t.numel() - 1, offsets_t, packed_t, ref_t, min_af, results_t)
+
+    def _lrt_csr_groups(self, device, ns, o, b, q, sm, r, min_af, g, n_samples, n_groups):
+        return tuple(self._call(self._L.bvc_lrt_csr_groups, device, (ns, o, b, q, sm, r, float(min_af), g, n_samples, int(n_groups)),
+                                [(None, (ns,), SITE_DTYPE), (None, (ns, n_groups), GROUP_DTYPE)]))
 
     def lrt_csr_groups(self, offsets, bases, quals, sample_of_obs, ref_base, min_af, group_of_sample, n_groups):
         """The --group loop on ragged sites: per observation its sample index; group_of_sample[n_samples] (>= n_groups: no group)."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        sm = np.ascontiguousarray(sample_of_obs, dtype=np.int32)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8)
-        n = len(o) - 1
-        out = np.zeros(n, dtype=SITE_DTYPE)
-        gout = np.zeros((n, n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_csr_groups(self._h, n, _np_ptr(o), _np_ptr(b), _np_ptr(q), _np_ptr(sm), _np_ptr(r), float(min_af),
-                                               _np_ptr(g), len(g), int(n_groups), _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
-        return out, gout
+        o, g = _as(offsets, np.int64), _as(group_of_sample, np.uint8)
+        return self._lrt_csr_groups(False, len(o) - 1, o, _as(bases, np.int8), _as(quals, np.int8), _as(sample_of_obs, np.int32),
+                                    _as(ref_base, np.int8), min_af, g, len(g), n_groups)
 
     def lrt_csr_groups_device(self, offsets_t, bases_t, quals_t, samples_t, ref_t, min_af, group_t, n_groups):
-        import torch
-        ns = offsets_t.numel() - 1
-        res = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        gres = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        self._check(self._L.bvc_lrt_csr_groups(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(bases_t), _dev_ptr(quals_t), _dev_ptr(samples_t),
-                                               _dev_ptr(ref_t), float(min_af), _dev_ptr(group_t), group_t.numel(), int(n_groups),
-                                               _dev_ptr(res), _dev_ptr(gres), BVC_PTR_DEVICE))
-        return res, gres
+        return self._lrt_csr_groups(True, offsets_t.numel() - 1, offsets_t, bases_t, quals_t, samples_t, ref_t, min_af, group_t,
+                                    group_t.numel(), n_groups)
+
+    def _lrt_csr_group_labels(self, fn, device, ns, columns, g, r, min_af, n_groups):
+        """bvc_lrt_csr_group_labels (columns: offsets, bases, quals) and its packed form (offsets, packed)."""
+        return tuple(self._call(fn, device, (ns, *columns, g, r, float(min_af), int(n_groups)),
+                                [(None, (ns,), SITE_DTYPE), (None, (ns, n_groups), GROUP_DTYPE)]))
 
     def lrt_csr_group_labels(self, offsets, bases, quals, group_of_obs, ref_base, min_af, n_groups):
         """lrt_csr_groups for a caller who knows each observation's group: one label byte per observation (>= n_groups: no group)."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        n = len(o) - 1
-        out = np.zeros(n, dtype=SITE_DTYPE)
-        gout = np.zeros((n, n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_csr_group_labels(self._h, n, _np_ptr(o), _np_ptr(b), _np_ptr(q), _np_ptr(g), _np_ptr(r), float(min_af),
-                                                     int(n_groups), _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
-        return out, gout
+        o = _as(offsets, np.int64)
+        return self._lrt_csr_group_labels(self._L.bvc_lrt_csr_group_labels, False, len(o) - 1, (o, _as(bases, np.int8), _as(quals, np.int8)),
+                                          _as(group_of_obs, np.uint8), _as(ref_base, np.int8), min_af, n_groups)
 
     def lrt_csr_group_labels_device(self, offsets_t, bases_t, quals_t, group_of_obs_t, ref_t, min_af, n_groups):
-        import torch
-        ns = offsets_t.numel() - 1
-        res = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        gres = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        self._check(self._L.bvc_lrt_csr_group_labels(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                                     _dev_ptr(group_of_obs_t), _dev_ptr(ref_t), float(min_af), int(n_groups),
-                                                     _dev_ptr(res), _dev_ptr(gres), BVC_PTR_DEVICE))
-        return res, gres
+        return self._lrt_csr_group_labels(self._L.bvc_lrt_csr_group_labels, True, offsets_t.numel() - 1, (offsets_t, bases_t, quals_t),
+                                          group_of_obs_t, ref_t, min_af, n_groups)
 
     def lrt_csr_group_labels_packed(self, offsets, packed, group_of_obs, ref_base, min_af, n_groups):
         """lrt_csr_group_labels at two bytes per observation: packed = base << 6 | qual (quality bits 63: skipped)."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        pk = np.ascontiguousarray(packed, dtype=np.uint8)
-        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        n = len(o) - 1
-        out = np.zeros(n, dtype=SITE_DTYPE)
-        gout = np.zeros((n, n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_csr_group_labels_packed(self._h, n, _np_ptr(o), _np_ptr(pk), _np_ptr(g), _np_ptr(r), float(min_af),
-                                                            int(n_groups), _np_ptr(out), _np_ptr(gout), BVC_PTR_HOST))
-        return out, gout
+        o = _as(offsets, np.int64)
+        return self._lrt_csr_group_labels(self._L.bvc_lrt_csr_group_labels_packed, False, len(o) - 1, (o, _as(packed, np.uint8)),
+                                          _as(group_of_obs, np.uint8), _as(ref_base, np.int8), min_af, n_groups)
 
     def lrt_csr_group_labels_packed_device(self, offsets_t, packed_t, group_of_obs_t, ref_t, min_af, n_groups):
-        import torch
-        ns = offsets_t.numel() - 1
-        res = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        gres = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        self._check(self._L.bvc_lrt_csr_group_labels_packed(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(packed_t), _dev_ptr(group_of_obs_t),
-                                                            _dev_ptr(ref_t), float(min_af), int(n_groups), _dev_ptr(res), _dev_ptr(gres),
-                                                            BVC_PTR_DEVICE))
-        return res, gres
+        return self._lrt_csr_group_labels(self._L.bvc_lrt_csr_group_labels_packed, True, offsets_t.numel() - 1, (offsets_t, packed_t),
+                                          group_of_obs_t, ref_t, min_af, n_groups)
+
+    def _site_stats_csr(self, device, ns, o, e, r, res, stats=None):
+        return self._call(self._L.bvc_site_stats_csr, device, (ns, o, e, r, res), [(stats, (ns,), STATS_DTYPE)])[0]
 
     def site_stats_csr(self, offsets, entries, ref_base, results):
         """bvc_site_stats_csr on host arrays: entries (ENTRY_DTYPE) of site s at offsets[s] .. offsets[s + 1], results (SITE_DTYPE: called,
         n_alt and alt_base are read).  Returns STATS_DTYPE [n_sites]; a site that is not called has an all-zero record."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        e = np.ascontiguousarray(entries, dtype=ENTRY_DTYPE)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        res = np.ascontiguousarray(results, dtype=SITE_DTYPE)
+        o, e, r, res = _as(offsets, np.int64), _as(entries, ENTRY_DTYPE), _as(ref_base, np.int8), _as(results, SITE_DTYPE)
         n = len(o) - 1
         assert r.shape == (n,) and res.shape == (n,)
-        out = np.zeros(n, dtype=STATS_DTYPE)
-        self._check(self._L.bvc_site_stats_csr(self._h, n, _np_ptr(o), _np_ptr(e) if len(e) else None, _np_ptr(r), _np_ptr(res), _np_ptr(out),
-                                               BVC_PTR_HOST))
-        return out
+        return self._site_stats_csr(False, n, o, e if len(e) else None, r, res)
 
     def site_stats_csr_device(self, offsets_t, entries_t, ref_t, results_t, stats_t=None):
         """The same on device tensors (entries_t / results_t / the returned tensor: uint8 views of the records); asynchronous on the
         context's stream.  In overlap mode call join() first: the records must be complete."""
-        import torch
-        ns = offsets_t.numel() - 1
-        if stats_t is None:
-            stats_t = torch.empty(ns * STATS_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        self._check(self._L.bvc_site_stats_csr(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(entries_t), _dev_ptr(ref_t), _dev_ptr(results_t),
-                                               _dev_ptr(stats_t), BVC_PTR_DEVICE))
-        return stats_t
+        return self._site_stats_csr(True, offsets_t.numel() - 1, offsets_t, entries_t, ref_t, results_t, stats_t)
 
+    # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
+    def pack_dense_device(self, bases_t, quals_t, packed_t=None):
+        """Two-byte device tile -> packed device tile.  Returns (packed_t, n_unrepresentable)."""
+        import torch
+        ns, n, stride_in = _tile(bases_t, quals_t)
+        if packed_t is None:
+            stride = (n + 127) // 128 * 128
+            packed_t = torch.empty((ns, stride), dtype=torch.uint8, device=bases_t.device)[:, :n]
+        bad = C.c_int64(0)
+        self._call(self._L.bvc_pack_dense, True, (ns, n, stride_in, bases_t, quals_t, packed_t.stride(0), packed_t, C.byref(bad)))
+        return packed_t, int(bad.value)
+
+    def _lrt_dense_packed(self, device, ns, n, stride, p, r, min_af, res=None):
+        return self._call(self._L.bvc_lrt_dense_packed, device, (ns, n, stride, p, r, float(min_af)), [(res, (ns,), SITE_DTYPE)])[0]
+
+    def lrt_dense_packed(self, packed, ref_base, min_af):
+        """Host (numpy) packed tile [n_sites, n_samples] uint8."""
+        p = _as(packed, np.uint8)
+        ns, n = p.shape
+        return self._lrt_dense_packed(False, ns, n, n, p, _as(ref_base, np.int8), min_af)
+
+    def lrt_dense_packed_device(self, packed_t, ref_t, min_af, results_t=None):
+        return self._lrt_dense_packed(True, *_tile(packed_t), packed_t, ref_t, min_af, results_t)
+
+    def _lrt_dense_groups_packed(self, device, ns, n, stride, p, r, min_af, g, n_groups, res=None, gres=None):
+        return tuple(self._call(self._L.bvc_lrt_dense_groups_packed, device, (ns, n, stride, p, r, float(min_af), g, int(n_groups)),
+                                [(res, (ns,), SITE_DTYPE), (gres, (ns, n_groups), GROUP_DTYPE)]))
+
+    def lrt_dense_groups_packed(self, packed, ref_base, min_af, group_of_sample, n_groups):
+        p = _as(packed, np.uint8)
+        return self._lrt_dense_groups_packed(False, p.shape[0], p.shape[1], p.shape[1], p, _as(ref_base, np.int8), min_af,
+                                             _as(group_of_sample, np.uint8), n_groups)
+
+    def lrt_dense_groups_packed_device(self, packed_t, ref_t, min_af, group_t, n_groups, results_t=None, grp_results_t=None):
+        return self._lrt_dense_groups_packed(True, *_tile(packed_t), packed_t, ref_t, min_af, group_t, n_groups, results_t,
+                                             grp_results_t)
+
+    # ---- the two stages on their own
+    def hist_dense(self, bases, quals):
+        b, q = _as(bases, np.int8), _as(quals, np.int8)
+        out = np.zeros((b.shape[0], NCLASS), dtype=np.uint32)
+        self._call(self._L.bvc_hist_dense, False, (b.shape[0], b.shape[1], b.shape[1], b, q, out))
+        return out
+
+    def hist_dense_device(self, bases_t, quals_t, counts_t=None):
+        import torch
+        ns, n = bases_t.shape
+        if counts_t is None:
+            counts_t = torch.empty((ns, NCLASS), dtype=torch.int32, device=bases_t.device)
+        self._call(self._L.bvc_hist_dense, True, (ns, n, bases_t.stride(0), bases_t, quals_t, counts_t))
+        return counts_t
+
+    def hist_dense_packed_device(self, packed_t, counts_t=None):
+        import torch
+        ns, n = packed_t.shape
+        if counts_t is None:
+            counts_t = torch.empty((ns, NCLASS), dtype=torch.int32, device=packed_t.device)
+        self._call(self._L.bvc_hist_dense_packed, True, (ns, n, packed_t.stride(0), packed_t, counts_t))
+        return counts_t
+
+    def _lrt_hist(self, device, ns, c, r, min_af, cb=None, nc=None, res=None):
+        return self._call(self._L.bvc_lrt_hist, device, (ns, c, r, float(min_af), cb, nc), [(res, (ns,), SITE_DTYPE)])[0]
+
+    def lrt_hist(self, counts, ref_base, min_af, base_comb=None, n_comb=None):
+        c = _as(counts, np.uint32).reshape(-1, NCLASS)
+        cb = nc = None
+        if base_comb is not None:
+            cb = _as(base_comb, np.int8).reshape(-1, 4)
+            nc = _as(n_comb, np.uint8)
+        return self._lrt_hist(False, c.shape[0], c, _as(ref_base, np.int8), min_af, cb, nc)
+
+    def lrt_hist_device(self, counts_t, ref_t, min_af, results_t=None):
+        """Stage 2 alone on device tensors: counts_t int32/uint32 [n_sites, 512]; asynchronous on the stream."""
+        return self._lrt_hist(True, counts_t.shape[0], counts_t, ref_t, min_af, res=results_t)
+
+    # ---- the producer: temp batches parsed on the device (host pointers only)
     def pileup_tile(self, text, line_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
                     n_groups=0, called_only=False, stats=False):
         """bvc_pileup_begin + bvc_pileup_finish on one tile of temp-batch pileup text (include/bvc.h).  text: bytes;
         line_start: uint32 [n_batches, n_positions + 1].  Returns None when a line is not regular (BVC_PILEUP_IRREGULAR), else a
         dict: entry_off, tally [T, 32], entries (structured), samples, indels (sorted by entry), results, grp_results, carry_out.
         stats=True (needs called_only=True): bvc_pileup_finish_called_stats -- key "stats", STATS_DTYPE [T]."""
-        ls = np.ascontiguousarray(line_start, dtype=np.uint32)
-        nb, T = ls.shape[0], ls.shape[1] - 1
-        s0 = np.ascontiguousarray(sample0, dtype=np.int32)
-        nib = np.ascontiguousarray(n_in_batch, dtype=np.int32)
-        buf = np.frombuffer(bytes(text), dtype=np.uint8)
-        ne, ni = C.c_int64(0), C.c_int64(0)
-        rc = self._L.bvc_pileup_begin(self._h, _np_ptr(buf) if len(buf) else None, len(buf), _np_ptr(ls), _np_ptr(s0), _np_ptr(nib), nb, T,
-                                      C.byref(ne), C.byref(ni))
+        ls = _as(line_start, np.uint32)
+        rc, T, ne, ni = self._pileup_begin(self._L.bvc_pileup_begin, text, ls, _as(sample0, np.int32), _as(n_in_batch, np.int32))
         if rc == 1:
             return None
         self._check(rc)
-        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
+        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
 
     def pileup_tile_bin(self, records, rec_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
                         n_groups=0, called_only=False, stats=False):
         """bvc_pileup_begin_bin + bvc_pileup_finish on one tile of binary temp-batch records (include/bvc.h).  records: bytes;
         rec_start: uint32 [n_batches, n_positions + 1].  Returns the dict of pileup_tile (indels' text_off are offsets into records);
         raises BvcError (status BVC_ERR_DATA = -5: a malformed record, BVC_ERR_ARG = -1: a rec_start that does not fit)."""
-        rs = np.ascontiguousarray(rec_start, dtype=np.uint32)
+        rs = _as(rec_start, np.uint32)
         if rs.ndim != 2 or rs.shape[1] < 1:
             raise ValueError("rec_start must be [n_batches, n_positions + 1]")
-        nb, T = rs.shape[0], rs.shape[1] - 1
-        s0 = np.ascontiguousarray(sample0, dtype=np.int32)
-        nib = np.ascontiguousarray(n_in_batch, dtype=np.int32)
-        if s0.shape != (nb,) or nib.shape != (nb,):
+        s0, nib = _as(sample0, np.int32), _as(n_in_batch, np.int32)
+        if s0.shape != (rs.shape[0],) or nib.shape != (rs.shape[0],):
             raise ValueError("sample0 / n_in_batch must be [n_batches]")
-        buf = np.frombuffer(bytes(records), dtype=np.uint8)
+        rc, T, ne, ni = self._pileup_begin(self._L.bvc_pileup_begin_bin, records, rs, s0, nib)
+        self._check(rc)
+        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
+
+    def _pileup_begin(self, fn, data, start, s0, nib):
+        """bvc_pileup_begin (text, line_start) / bvc_pileup_begin_bin (records, rec_start): (rc, n_positions, n_entries, n_indels)."""
+        nb, T = start.shape[0], start.shape[1] - 1
+        buf = np.frombuffer(bytes(data), dtype=np.uint8)
         ne, ni = C.c_int64(0), C.c_int64(0)
-        self._check(self._L.bvc_pileup_begin_bin(self._h, _np_ptr(buf) if len(buf) else None, len(buf), _np_ptr(rs), _np_ptr(s0), _np_ptr(nib),
-                                                 nb, T, C.byref(ne), C.byref(ni)))
-        return self._pileup_finish(T, ne.value, ni.value, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
+        rc = fn(self._h, *_pointers((buf if len(buf) else None, len(buf), start, s0, nib, nb, T, C.byref(ne), C.byref(ni)), _np_ptr))
+        return rc, T, ne.value, ni.value
 
     def _pileup_finish(self, T, n_entries, n_indels, indel_text_bytes, ref_base, min_af, carry_in, group_of_sample, n_groups,
                        called_only=False, called_cap=None, stats=False):
@@ -437,91 +527,61 @@ class Context:
         called_off[t] .. called_off[t + 1] (key "called_off").  stats (with called_only): bvc_pileup_finish_called_stats, key "stats"."""
         if stats and not called_only:
             raise ValueError("stats=True needs called_only=True (bvc_pileup_finish_called_stats)")
-        ENTRY = ENTRY_DTYPE
-        INDEL = np.dtype([("entry", "<i8"), ("text_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
+        r = _as(ref_base, np.int8)
         assert r.shape == (T,)
         entry_off = np.zeros(T + 1, dtype=np.int64)
         tally = np.zeros((T, 32), dtype=np.int32)
-        entries = np.zeros(max(1, n_entries), dtype=ENTRY)
+        entries = np.zeros(max(1, n_entries), dtype=ENTRY_DTYPE)
         samples = np.zeros(max(1, n_entries), dtype=np.int32)
-        indels = np.zeros(max(1, n_indels), dtype=INDEL)
+        indels = np.zeros(max(1, n_indels), dtype=INDEL_DTYPE)
         itext = np.zeros(max(1, indel_text_bytes), dtype=np.uint8)
         res = np.zeros(T, dtype=SITE_DTYPE)
         gres = np.zeros((T, max(1, n_groups)), dtype=GROUP_DTYPE)
-        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8) if n_groups else np.zeros(0, dtype=np.uint8)
+        g = _as(group_of_sample, np.uint8) if n_groups else np.zeros(0, dtype=np.uint8)
         cin = np.asarray(carry_in, dtype=np.uint8)
         cout = np.zeros(5, dtype=np.uint8)
+        fn = self._L.bvc_pileup_finish
+        args = [r, float(min_af), cin, cout, g if n_groups else None, len(g), int(n_groups), entry_off, tally]
         if called_only:
+            fn = self._L.bvc_pileup_finish_called_stats if stats else self._L.bvc_pileup_finish_called
             called_off = np.zeros(T + 1, dtype=np.int64)
-            cap = n_entries if called_cap is None else int(called_cap)
-            args = [self._h, _np_ptr(r), float(min_af), _np_ptr(cin), _np_ptr(cout),
-                    _np_ptr(g) if n_groups else None, len(g), int(n_groups), _np_ptr(entry_off), _np_ptr(tally),
-                    _np_ptr(called_off), cap, _np_ptr(entries), _np_ptr(samples), _np_ptr(indels),
-                    _np_ptr(itext) if indel_text_bytes else None, _np_ptr(res), _np_ptr(gres) if n_groups else None]
-            if stats:
-                st = np.zeros(max(1, T), dtype=STATS_DTYPE)
-                self._check(self._L.bvc_pileup_finish_called_stats(*args, _np_ptr(st)))
-            else:
-                self._check(self._L.bvc_pileup_finish_called(*args))
-            n_c = int(called_off[T])
-            ind = indels[:n_indels]
-            ind = ind[np.argsort(ind["entry"], kind="stable")]
-            out = dict(entry_off=entry_off, called_off=called_off, tally=tally, entries=entries[:n_c], samples=samples[:n_c], indels=ind,
-                       results=res, grp_results=gres if n_groups else None, carry_out=[int(x) for x in cout],
-                       indel_text=itext[:indel_text_bytes].tobytes())
-            if stats:
-                out["stats"] = st[:T]
-            return out
-        self._check(self._L.bvc_pileup_finish(self._h, _np_ptr(r), float(min_af), _np_ptr(cin), _np_ptr(cout), _np_ptr(g) if n_groups else None,
-                                              len(g), int(n_groups), _np_ptr(entry_off), _np_ptr(tally), _np_ptr(entries), _np_ptr(samples),
-                                              _np_ptr(indels), _np_ptr(itext) if indel_text_bytes else None, _np_ptr(res),
-                                              _np_ptr(gres) if n_groups else None))
+            args += [called_off, n_entries if called_cap is None else int(called_cap)]
+        args += [entries, samples, indels, itext if indel_text_bytes else None, res, gres if n_groups else None]
+        if stats:
+            st = np.zeros(max(1, T), dtype=STATS_DTYPE)
+            args.append(st)
+        self._check(fn(self._h, *_pointers(args, _np_ptr)))
+        n_kept = int(called_off[T]) if called_only else n_entries
         ind = indels[:n_indels]
         ind = ind[np.argsort(ind["entry"], kind="stable")]
-        return dict(entry_off=entry_off, tally=tally, entries=entries[:n_entries], samples=samples[:n_entries], indels=ind, results=res,
-                    grp_results=gres if n_groups else None, carry_out=[int(x) for x in cout], indel_text=itext[:indel_text_bytes].tobytes())
+        out = dict(entry_off=entry_off, tally=tally, entries=entries[:n_kept], samples=samples[:n_kept], indels=ind, results=res,
+                   grp_results=gres if n_groups else None, carry_out=[int(x) for x in cout], indel_text=itext[:indel_text_bytes].tobytes())
+        if called_only:
+            out["called_off"] = called_off
+        if stats:
+            out["stats"] = st[:T]
+        return out
 
     def pileup_begin_bgzf(self, comp, blocks, blocks_of_batch, skip_bytes, sample0, n_in_batch, max_positions, reset):
         """bvc_pileup_begin_bgzf.  comp: bytes; blocks: [(comp_off, comp_len, isize)] batch after batch.  Returns a dict with rc
         (0, 1 = irregular, negative = error), T, lines (per batch) and the sizes bvc_pileup_finish needs."""
-        BLOCK = np.dtype([("comp_off", "<i8"), ("out_off", "<i8"), ("comp_len", "<i4"), ("isize", "<i4"), ("crc32", "<u4"), ("check_crc", "<u4")])
-        tab = np.zeros(max(1, len(blocks)), dtype=BLOCK)
-        for i, blk in enumerate(blocks):
-            co, cl, isz = blk[:3]
-            tab[i] = (co, 0, cl, isz, blk[3] if len(blk) > 3 else 0, 1 if len(blk) > 3 else 0)
+        tab, _ = _block_table(blocks, consecutive=False)
         if isinstance(comp, np.ndarray):                         # e.g. a view of page-locked memory (host_alloc): used where it lies
             buf = comp
             comp_len = len(buf)
         else:
             buf = np.frombuffer(bytes(comp) + b"\0" * 8, dtype=np.uint8)
             comp_len = len(buf) - 8
-        bob = np.ascontiguousarray(blocks_of_batch, dtype=np.int32)
+        bob = _as(blocks_of_batch, np.int32)
         nb = len(bob)
-        sk = np.ascontiguousarray(skip_bytes, dtype=np.int32) if skip_bytes is not None else None
-        s0 = np.ascontiguousarray(sample0, dtype=np.int32)
-        nib = np.ascontiguousarray(n_in_batch, dtype=np.int32)
+        sk = _as(skip_bytes, np.int32) if skip_bytes is not None else None
         lines = np.zeros(max(1, nb), dtype=np.int32)
         T, ne, ni, nt = C.c_int32(0), C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        rc = self._L.bvc_pileup_begin_bgzf(self._h, _np_ptr(buf), comp_len, _np_ptr(tab), _np_ptr(bob), _np_ptr(sk) if sk is not None else None,
-                                           _np_ptr(s0), _np_ptr(nib), nb, int(max_positions), int(bool(reset)), C.byref(T), _np_ptr(lines),
-                                           C.byref(ne), C.byref(ni), C.byref(nt))
+        rc = self._L.bvc_pileup_begin_bgzf(self._h, *_pointers(
+            (buf, comp_len, tab, bob, sk, _as(sample0, np.int32), _as(n_in_batch, np.int32), nb, int(max_positions), int(bool(reset)),
+             C.byref(T), lines, C.byref(ne), C.byref(ni), C.byref(nt)), _np_ptr))
         return dict(rc=rc, T=T.value, lines=lines[:nb].copy(), n_entries=ne.value, n_indels=ni.value, indel_text_bytes=nt.value,
                     error=self._L.bvc_last_error(self._h).decode() if rc < 0 else "")
-
-    def host_alloc(self, nbytes):
-        """bvc_host_alloc: (address, uint8 view of the page-locked bytes); free with host_free(address)."""
-        self._L.bvc_host_alloc.restype = C.c_void_p
-        self._L.bvc_host_alloc.argtypes = [C.c_size_t]
-        addr = self._L.bvc_host_alloc(int(nbytes))
-        if not addr:
-            raise BvcError("bvc_host_alloc failed")
-        return addr, np.ctypeslib.as_array((C.c_uint8 * int(nbytes)).from_address(addr))
-
-    def host_free(self, addr):
-        self._L.bvc_host_free.restype = None
-        self._L.bvc_host_free.argtypes = [C.c_void_p]
-        self._L.bvc_host_free(addr)
 
     def pileup_text(self, n_batches, T):
         need = C.c_int64(0)
@@ -534,188 +594,12 @@ class Context:
     def inflate_blocks(self, comp, blocks):
         """Raw-deflate streams inflated on the device.  comp: bytes; blocks: [(comp_off, comp_len, isize)] -- outputs are laid out one
         after the other.  Returns (list of bytes, status array)."""
-        BLOCK = np.dtype([("comp_off", "<i8"), ("out_off", "<i8"), ("comp_len", "<i4"), ("isize", "<i4"), ("crc32", "<u4"), ("check_crc", "<u4")])
-        tab = np.zeros(len(blocks), dtype=BLOCK)
-        at = 0
-        for i, blk in enumerate(blocks):                        # (comp_off, comp_len, isize[, crc32]): with a CRC it is compared
-            co, cl, isz = blk[:3]
-            tab[i] = (co, at, cl, isz, blk[3] if len(blk) > 3 else 0, 1 if len(blk) > 3 else 0)
-            at += isz
+        tab, at = _block_table(blocks, consecutive=True)
         buf = np.frombuffer(bytes(comp) + b"\0" * 8, dtype=np.uint8)
         out = np.zeros(max(1, at), dtype=np.uint8)
         status = np.zeros(max(1, len(blocks)), dtype=np.uint32)
-        self._check(self._L.bvc_inflate_blocks(self._h, _np_ptr(buf), len(buf), _np_ptr(tab), len(blocks), _np_ptr(out), at, _np_ptr(status),
-                                               BVC_PTR_HOST))
-        return [out[int(t["out_off"]):int(t["out_off"]) + int(t["isize"])].tobytes() for t in tab], status[:len(blocks)]
-
-    def lrt_csr_packed(self, offsets, packed, ref_base, min_af):
-        """Ragged sites at one byte per observation (base << 6 | qual); host arrays, synchronous."""
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        pk = np.ascontiguousarray(packed, dtype=np.uint8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        out = np.zeros(len(o) - 1, dtype=SITE_DTYPE)
-        self._check(self._L.bvc_lrt_csr_packed(self._h, len(o) - 1, _np_ptr(o), _np_ptr(pk), _np_ptr(r), float(min_af),
-                                               _np_ptr(out), BVC_PTR_HOST))
-        return out
-
-    def lrt_csr_packed_device(self, offsets_t, packed_t, ref_t, min_af, results_t=None):
-        import torch
-        ns = offsets_t.numel() - 1
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=packed_t.device)
-        self._check(self._L.bvc_lrt_csr_packed(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(packed_t), _dev_ptr(ref_t),
-                                               float(min_af), _dev_ptr(results_t), BVC_PTR_DEVICE))
-        return results_t
-
-    def lrt_csr_device(self, offsets_t, bases_t, quals_t, ref_t, min_af, results_t=None):
-        """offsets_t: int64 [n_sites + 1]; bases_t/quals_t: int8 [total] CUDA tensors (asynchronous on the stream)."""
-        import torch
-        ns = offsets_t.numel() - 1
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        self._check(self._L.bvc_lrt_csr(self._h, ns, _dev_ptr(offsets_t), _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                        _dev_ptr(ref_t), float(min_af), _dev_ptr(results_t), BVC_PTR_DEVICE))
-        return results_t
-
-    def set_tuning(self, key, value):
-        """Launch policy of this context (include/bvc.h); results never depend on it."""
-        self._check(self._L.bvc_set_tuning(self._h, key.encode(), int(value)))
-
-    def hist_dense(self, bases, quals):
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        out = np.zeros((b.shape[0], NCLASS), dtype=np.uint32)
-        self._check(self._L.bvc_hist_dense(self._h, b.shape[0], b.shape[1], b.shape[1], _np_ptr(b), _np_ptr(q),
-                                           _np_ptr(out), BVC_PTR_HOST))
-        return out
-
-    def lrt_hist(self, counts, ref_base, min_af, base_comb=None, n_comb=None):
-        c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1, NCLASS)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        out = np.zeros(c.shape[0], dtype=SITE_DTYPE)
-        cb = nc = None
-        if base_comb is not None:
-            cb = np.ascontiguousarray(base_comb, dtype=np.int8).reshape(-1, 4)
-            nc = np.ascontiguousarray(n_comb, dtype=np.uint8)
-        self._check(self._L.bvc_lrt_hist(self._h, c.shape[0], _np_ptr(c), _np_ptr(r), float(min_af),
-                                         _np_ptr(cb) if cb is not None else None,
-                                         _np_ptr(nc) if nc is not None else None, _np_ptr(out), BVC_PTR_HOST))
-        return out
-
-    # ---- device-pointer calls (torch tensors on this context's device; asynchronous on the stream)
-    def lrt_dense_device(self, bases_t, quals_t, ref_t, min_af, results_t=None):
-        """bases_t/quals_t: int8 [n_sites, row_stride]-strided CUDA tensors; results_t: uint8 [n_sites*120]."""
-        import torch
-        ns, n = bases_t.shape
-        stride = bases_t.stride(0)
-        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == stride
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        self._check(self._L.bvc_lrt_dense(self._h, ns, n, stride, _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                          _dev_ptr(ref_t), float(min_af), _dev_ptr(results_t), BVC_PTR_DEVICE))
-        return results_t
-
-    def lrt_dense_groups_device(self, bases_t, quals_t, ref_t, min_af, group_t, n_groups, results_t=None,
-                                grp_results_t=None):
-        """Group mode on device tensors; group_t: uint8 [n_samples].  Returns (results_t, grp_results_t)."""
-        import torch
-        ns, n = bases_t.shape
-        stride = bases_t.stride(0)
-        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == stride
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        if grp_results_t is None:
-            grp_results_t = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=bases_t.device)
-        self._check(self._L.bvc_lrt_dense_groups(self._h, ns, n, stride, _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                                 _dev_ptr(ref_t), float(min_af), _dev_ptr(group_t), int(n_groups),
-                                                 _dev_ptr(results_t), _dev_ptr(grp_results_t), BVC_PTR_DEVICE))
-        return results_t, grp_results_t
-
-    def lrt_hist_device(self, counts_t, ref_t, min_af, results_t=None):
-        """Stage 2 alone on device tensors: counts_t int32/uint32 [n_sites, 512]; asynchronous on the stream."""
-        import torch
-        ns = counts_t.shape[0]
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=counts_t.device)
-        self._check(self._L.bvc_lrt_hist(self._h, ns, _dev_ptr(counts_t), _dev_ptr(ref_t), float(min_af), None, None,
-                                         _dev_ptr(results_t), BVC_PTR_DEVICE))
-        return results_t
-
-    def hist_dense_device(self, bases_t, quals_t, counts_t=None):
-        import torch
-        ns, n = bases_t.shape
-        if counts_t is None:
-            counts_t = torch.empty((ns, NCLASS), dtype=torch.int32, device=bases_t.device)
-        self._check(self._L.bvc_hist_dense(self._h, ns, n, bases_t.stride(0), _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                           _dev_ptr(counts_t), BVC_PTR_DEVICE))
-        return counts_t
-
-    # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
-    def pack_dense_device(self, bases_t, quals_t, packed_t=None):
-        """Two-byte device tile -> packed device tile.  Returns (packed_t, n_unrepresentable)."""
-        import torch
-        ns, n = bases_t.shape
-        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0)
-        if packed_t is None:
-            stride = (n + 127) // 128 * 128
-            packed_t = torch.empty((ns, stride), dtype=torch.uint8, device=bases_t.device)[:, :n]
-        bad = C.c_int64(0)
-        self._check(self._L.bvc_pack_dense(self._h, ns, n, bases_t.stride(0), _dev_ptr(bases_t), _dev_ptr(quals_t),
-                                           packed_t.stride(0), _dev_ptr(packed_t), C.byref(bad), BVC_PTR_DEVICE))
-        return packed_t, int(bad.value)
-
-    def lrt_dense_packed_device(self, packed_t, ref_t, min_af, results_t=None):
-        import torch
-        ns, n = packed_t.shape
-        assert packed_t.stride(1) == 1
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=packed_t.device)
-        self._check(self._L.bvc_lrt_dense_packed(self._h, ns, n, packed_t.stride(0), _dev_ptr(packed_t), _dev_ptr(ref_t),
-                                                 float(min_af), _dev_ptr(results_t), BVC_PTR_DEVICE))
-        return results_t
-
-    def lrt_dense_groups_packed_device(self, packed_t, ref_t, min_af, group_t, n_groups, results_t=None, grp_results_t=None):
-        import torch
-        ns, n = packed_t.shape
-        assert packed_t.stride(1) == 1
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=packed_t.device)
-        if grp_results_t is None:
-            grp_results_t = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=packed_t.device)
-        self._check(self._L.bvc_lrt_dense_groups_packed(self._h, ns, n, packed_t.stride(0), _dev_ptr(packed_t), _dev_ptr(ref_t),
-                                                        float(min_af), _dev_ptr(group_t), int(n_groups),
-                                                        _dev_ptr(results_t), _dev_ptr(grp_results_t), BVC_PTR_DEVICE))
-        return results_t, grp_results_t
-
-    def lrt_dense_groups_packed(self, packed, ref_base, min_af, group_of_sample, n_groups):
-        p = np.ascontiguousarray(packed, dtype=np.uint8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8)
-        out = np.zeros(p.shape[0], dtype=SITE_DTYPE)
-        gout = np.zeros((p.shape[0], n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_dense_groups_packed(self._h, p.shape[0], p.shape[1], p.shape[1], _np_ptr(p), _np_ptr(r),
-                                                        float(min_af), _np_ptr(g), int(n_groups), _np_ptr(out), _np_ptr(gout),
-                                                        BVC_PTR_HOST))
-        return out, gout
-
-    def lrt_dense_packed(self, packed, ref_base, min_af):
-        """Host (numpy) packed tile [n_sites, n_samples] uint8."""
-        p = np.ascontiguousarray(packed, dtype=np.uint8)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        ns, n = p.shape
-        out = np.zeros(ns, dtype=SITE_DTYPE)
-        self._check(self._L.bvc_lrt_dense_packed(self._h, ns, n, n, _np_ptr(p), _np_ptr(r), float(min_af), _np_ptr(out),
-                                                 BVC_PTR_HOST))
-        return out
-
-    def hist_dense_packed_device(self, packed_t, counts_t=None):
-        import torch
-        ns, n = packed_t.shape
-        if counts_t is None:
-            counts_t = torch.empty((ns, NCLASS), dtype=torch.int32, device=packed_t.device)
-        self._check(self._L.bvc_hist_dense_packed(self._h, ns, n, packed_t.stride(0), _dev_ptr(packed_t),
-                                                  _dev_ptr(counts_t), BVC_PTR_DEVICE))
-        return counts_t
+        self._call(self._L.bvc_inflate_blocks, False, (buf, len(buf), tab, len(blocks), out, at, status))
+        return [out[int(t["out_off"]):int(t["out_off"]) + int(t["isize"])].tobytes() for t in tab[:len(blocks)]], status[:len(blocks)]
 
     # ---- a cohort in sample chunks: counts that accumulate (include/bvc.h).  `counts` is added to IN PLACE: a uint32 / int32 array of
     # [n_sites, 512] (plain) or [n_sites, n_groups + 1, 512] (groups; slot n_groups = in no group), numpy with the host calls, a tensor
@@ -728,66 +612,52 @@ class Context:
             ok = isinstance(counts, np.ndarray) and counts.flags.c_contiguous and counts.dtype.kind in "iu" and counts.dtype.itemsize == 4
         if not ok:
             raise ValueError("counts must be a contiguous array of 4-byte integers (it is added to in place)")
-        ptr = _dev_ptr if device else _np_ptr
         groups = () if n_groups is None else (int(n_groups),)
-        self._check(fn(self._h, *sizes, *[ptr(a) for a in arrays], *groups, ptr(counts), BVC_PTR_DEVICE if device else BVC_PTR_HOST))
+        self._call(fn, device, (*sizes, *arrays, *groups, counts))
         return counts
 
     def counts_add_dense(self, bases, quals, counts):
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
+        b, q = _as(bases, np.int8), _as(quals, np.int8)
         return self._counts_call(self._L.bvc_counts_add_dense, (b.shape[0], b.shape[1], b.shape[1]), (b, q), counts, False)
 
     def counts_add_dense_device(self, bases_t, quals_t, counts_t):
-        ns, n = bases_t.shape
-        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0)
-        return self._counts_call(self._L.bvc_counts_add_dense, (ns, n, bases_t.stride(0)), (bases_t, quals_t), counts_t, True)
+        return self._counts_call(self._L.bvc_counts_add_dense, _tile(bases_t, quals_t), (bases_t, quals_t), counts_t, True)
 
     def counts_add_dense_packed(self, packed, counts):
-        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        p = _as(packed, np.uint8)
         return self._counts_call(self._L.bvc_counts_add_dense_packed, (p.shape[0], p.shape[1], p.shape[1]), (p,), counts, False)
 
     def counts_add_dense_packed_device(self, packed_t, counts_t):
-        ns, n = packed_t.shape
-        assert packed_t.stride(1) == 1
-        return self._counts_call(self._L.bvc_counts_add_dense_packed, (ns, n, packed_t.stride(0)), (packed_t,), counts_t, True)
+        return self._counts_call(self._L.bvc_counts_add_dense_packed, _tile(packed_t), (packed_t,), counts_t, True)
 
     def counts_add_csr(self, offsets, bases, quals, counts):
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
+        o, b, q = _as(offsets, np.int64), _as(bases, np.int8), _as(quals, np.int8)
         return self._counts_call(self._L.bvc_counts_add_csr, (len(o) - 1,), (o, b, q), counts, False)
 
     def counts_add_csr_device(self, offsets_t, bases_t, quals_t, counts_t):
         return self._counts_call(self._L.bvc_counts_add_csr, (offsets_t.numel() - 1,), (offsets_t, bases_t, quals_t), counts_t, True)
 
     def counts_add_csr_packed(self, offsets, packed, counts):
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        p = np.ascontiguousarray(packed, dtype=np.uint8)
+        o, p = _as(offsets, np.int64), _as(packed, np.uint8)
         return self._counts_call(self._L.bvc_counts_add_csr_packed, (len(o) - 1,), (o, p), counts, False)
 
     def counts_add_csr_packed_device(self, offsets_t, packed_t, counts_t):
         return self._counts_call(self._L.bvc_counts_add_csr_packed, (offsets_t.numel() - 1,), (offsets_t, packed_t), counts_t, True)
 
     def counts_add_dense_groups(self, bases, quals, group_of_sample, n_groups, grp_counts):
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_sample, dtype=np.uint8)
+        b, q, g = _as(bases, np.int8), _as(quals, np.int8), _as(group_of_sample, np.uint8)
         if g.shape != (b.shape[1],):
             raise ValueError("group_of_sample must have one label per column of the chunk")
         return self._counts_call(self._L.bvc_counts_add_dense_groups, (b.shape[0], b.shape[1], b.shape[1]), (b, q, g), grp_counts, False, n_groups)
 
     def counts_add_dense_groups_device(self, bases_t, quals_t, group_t, n_groups, grp_counts_t):
-        ns, n = bases_t.shape
-        assert bases_t.stride(1) == 1 and quals_t.stride(1) == 1 and quals_t.stride(0) == bases_t.stride(0) and group_t.numel() == n
-        return self._counts_call(self._L.bvc_counts_add_dense_groups, (ns, n, bases_t.stride(0)), (bases_t, quals_t, group_t), grp_counts_t, True,
+        sizes = _tile(bases_t, quals_t)
+        assert group_t.numel() == sizes[1]
+        return self._counts_call(self._L.bvc_counts_add_dense_groups, sizes, (bases_t, quals_t, group_t), grp_counts_t, True,
                                  n_groups)
 
     def counts_add_csr_group_labels(self, offsets, bases, quals, group_of_obs, n_groups, grp_counts):
-        o = np.ascontiguousarray(offsets, dtype=np.int64)
-        b = np.ascontiguousarray(bases, dtype=np.int8)
-        q = np.ascontiguousarray(quals, dtype=np.int8)
-        g = np.ascontiguousarray(group_of_obs, dtype=np.uint8)
+        o, b, q, g = _as(offsets, np.int64), _as(bases, np.int8), _as(quals, np.int8), _as(group_of_obs, np.uint8)
         return self._counts_call(self._L.bvc_counts_add_csr_group_labels, (len(o) - 1,), (o, b, q, g), grp_counts, False, n_groups)
 
     def counts_add_csr_group_labels_device(self, offsets_t, bases_t, quals_t, group_of_obs_t, n_groups, grp_counts_t):
@@ -806,48 +676,22 @@ class Context:
         return self._merge(dst_t, src_t, True)
 
     def _merge(self, dst, src, device):
-        ptr = _dev_ptr if device else _np_ptr
-        n = dst.numel() if device else dst.size
-        self._check(self._L.bvc_counts_merge(self._h, int(n), ptr(dst), ptr(src), BVC_PTR_DEVICE if device else BVC_PTR_HOST))
+        self._call(self._L.bvc_counts_merge, device, (int(dst.numel() if device else dst.size), dst, src))
         return dst
+
+    def _lrt_hist_groups(self, device, ns, c, r, min_af, n_groups, res=None, gres=None):
+        return tuple(self._call(self._L.bvc_lrt_hist_groups, device, (ns, c, r, float(min_af), int(n_groups)),
+                                [(res, (ns,), SITE_DTYPE), (gres, (ns, n_groups), GROUP_DTYPE)]))
 
     def lrt_hist_groups(self, grp_counts, ref_base, min_af, n_groups):
         """Stage 2 of the group calls on accumulated group histograms [n_sites, n_groups + 1, 512]: (site records, group records)."""
         c = np.ascontiguousarray(grp_counts).view(np.uint32).reshape(-1, n_groups + 1, NCLASS)
-        r = np.ascontiguousarray(ref_base, dtype=np.int8)
-        out = np.zeros(c.shape[0], dtype=SITE_DTYPE)
-        gout = np.zeros((c.shape[0], n_groups), dtype=GROUP_DTYPE)
-        self._check(self._L.bvc_lrt_hist_groups(self._h, c.shape[0], _np_ptr(c), _np_ptr(r), float(min_af), int(n_groups), _np_ptr(out),
-                                                _np_ptr(gout), BVC_PTR_HOST))
-        return out, gout
+        return self._lrt_hist_groups(False, c.shape[0], c, _as(ref_base, np.int8), min_af, n_groups)
 
     def lrt_hist_groups_device(self, grp_counts_t, ref_t, min_af, n_groups, results_t=None, grp_results_t=None):
-        import torch
         ns = ref_t.numel()
         assert grp_counts_t.numel() == ns * (n_groups + 1) * NCLASS and grp_counts_t.is_contiguous()
-        if results_t is None:
-            results_t = torch.empty(ns * SITE_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        if grp_results_t is None:
-            grp_results_t = torch.empty(ns * n_groups * GROUP_DTYPE.itemsize, dtype=torch.uint8, device=ref_t.device)
-        self._check(self._L.bvc_lrt_hist_groups(self._h, ns, _dev_ptr(grp_counts_t), _dev_ptr(ref_t), float(min_af), int(n_groups),
-                                                _dev_ptr(results_t), _dev_ptr(grp_results_t), BVC_PTR_DEVICE))
-        return results_t, grp_results_t
-
-    def synth_dense_device(self, seed, site0, bases_t, quals_t, ref_t, cov_thr16=65536):
-        ns, n = bases_t.shape
-        self._check(self._L.bvc_synth_dense(self._h, int(seed), int(site0), ns, n, bases_t.stride(0), int(cov_thr16),
-                                            _dev_ptr(bases_t), _dev_ptr(quals_t), _dev_ptr(ref_t)))
-
-
-def _stream_read_gbs(self, tensor, repeats=5):
-    """Empirical HBM read bandwidth (GB/s): a plain 16 B/lane streaming read of `tensor` (device, contiguous)."""
-    ms = C.c_double()
-    nbytes = tensor.numel() * tensor.element_size()
-    self._check(self._L.bvc_stream_read_ms(self._h, _dev_ptr(tensor), nbytes, int(repeats), C.byref(ms)))
-    return nbytes / (ms.value * 1e-3) / 1e9
-
-
-Context.stream_read_gbs = _stream_read_gbs
+        return self._lrt_hist_groups(True, ns, grp_counts_t, ref_t, min_af, n_groups, results_t, grp_results_t)
 
 
 def results_from_tensor(results_t):

@@ -33,21 +33,19 @@ def header_parameters(name):
 
 def test_the_header_declares_them_and_the_binding_matches():
     from basevarc_amd import lib as bl
-    argtypes = {}
-    src = open(os.path.join(ROOT, "basevarc_amd", "lib.py")).read()
     for s in SYMBOLS:
         params = header_parameters(s)
         assert params[0] == "bvc_ctx *ctx" and params[-1] == "uint32_t flags", s
         assert s in bl.EXPORTS, s
-        m = re.search(r"L\." + s + r"\.argtypes = \[([^\]]*)\]", src)
-        assert m, f"basevarc_amd.lib does not bind {s}"
-        argtypes[s] = [a.strip() for a in m.group(1).split(",")]
-        assert len(argtypes[s]) == len(params), (s, argtypes[s], params)
+        assert s in bl.PROTOTYPES, f"basevarc_amd.lib does not bind {s}"
+        restype, argtypes = bl.PROTOTYPES[s]
+        assert restype is C.c_int, (s, restype)
+        assert len(argtypes) == len(params), (s, argtypes, params)
         # pointers are bound as pointers, sizes as 64-bit integers
-        for a, prm in zip(argtypes[s], params):
-            assert (a == "vp") == ("*" in prm), (s, a, prm)
+        for a, prm in zip(argtypes, params):
+            assert (a is C.c_void_p) == ("*" in prm), (s, a, prm)
             if prm.startswith("int64_t"):
-                assert a == "i64", (s, a, prm)
+                assert a is C.c_int64, (s, a, prm)
     for m in ("counts_add_dense", "counts_add_dense_device", "counts_add_dense_packed", "counts_add_dense_packed_device", "counts_add_csr",
               "counts_add_csr_device", "counts_add_csr_packed", "counts_add_csr_packed_device", "counts_add_dense_groups",
               "counts_add_dense_groups_device", "counts_add_csr_group_labels", "counts_add_csr_group_labels_device", "lrt_hist_groups",

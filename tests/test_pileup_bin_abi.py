@@ -23,8 +23,7 @@ def test_the_entry_point_is_declared_and_exported():
     for name in lib.EXPORTS:
         assert hasattr(L, name), name
     # a null context is refused before anything else is looked at (BVC_ERR_ARG)
-    L.bvc_pileup_begin_bin.restype = C.c_int
-    L.bvc_pileup_begin_bin.argtypes = [C.c_void_p] * 2 + [C.c_int64] + [C.c_void_p] * 3 + [C.c_int32] * 2 + [C.c_void_p] * 2
+    lib.bind(L)
     assert L.bvc_pileup_begin_bin(None, None, 0, None, None, None, 0, 0, None, None) == -1
 
 

@@ -9,7 +9,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 from basevarc_amd import Context
-from basevarc_amd.lib import BVC_PTR_DEVICE
+from basevarc_amd.lib import BVC_PTR_DEVICE, bind
 
 variant = sys.argv[1]
 pairs = int(sys.argv[2]) if len(sys.argv) > 2 else 10
@@ -17,13 +17,8 @@ S, N = 4000, 1_000_000
 stride = (N + 127) // 128 * 128
 dev = torch.device("cuda:0")
 ctx = Context(0)
-L2 = C.CDLL(os.path.join(ROOT, "basevarc_amd", "_variants", f"libbvc_{variant}.so"))
-vp, i64 = C.c_void_p, C.c_int64
-L2.bvc_create.restype = C.c_int; L2.bvc_create.argtypes = [C.POINTER(vp), C.c_int]
-L2.bvc_hist_dense.restype = C.c_int
-L2.bvc_hist_dense.argtypes = [vp, i64, i64, i64, vp, vp, vp, C.c_int]
-L2.bvc_synchronize.restype = C.c_int; L2.bvc_synchronize.argtypes = [vp]
-h2 = vp()
+L2 = bind(C.CDLL(os.path.join(ROOT, "basevarc_amd", "_variants", f"libbvc_{variant}.so")))
+h2 = C.c_void_p()
 assert L2.bvc_create(C.byref(h2), 0) == 0
 counts = torch.empty((S, 512), dtype=torch.int32, device=dev)
 counts2 = torch.empty((S, 512), dtype=torch.int32, device=dev)
