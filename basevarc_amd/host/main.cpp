@@ -1243,15 +1243,19 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     tr.finish();
     const double loop_s = StageClock::now() - t_loop, setup_s = t_loop - t_start;
     if (knob::profile()) {
-        std::cerr << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
-                  << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
-                  << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats << std::endl;
+        // (each line composed first and written at once: the threads end side by side, and a line written piece by piece ends up inside
+        // another thread's)
+        std::ostringstream os;
+        os << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
+           << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
+           << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats << "\n";
         const StageClock &c = tr.clk, &d = tr.clk_dev, &o = tr.clk_out;
-        std::cerr << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "
-                  << d.pack << " s, libbvc " << d.gpu << " s | stage 3 cvg lines " << o.cvg << " s, vcf lines " << o.vcf
-                  << " s, compress+write " << o.write << " s; setup (open batches " << t_opened - t_start << " s, names + header "
-                  << t_header - t_opened << " s, bvc_create " << create_s << " s) " << setup_s << " s, position loop " << loop_s << " s, thread total "
-                  << StageClock::now() - t_start << " s" << std::endl;
+        os << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "
+           << d.pack << " s, libbvc " << d.gpu << " s | stage 3 cvg lines " << o.cvg << " s, vcf lines " << o.vcf
+           << " s, compress+write " << o.write << " s; setup (open batches " << t_opened - t_start << " s, names + header "
+           << t_header - t_opened << " s, bvc_create " << create_s << " s) " << setup_s << " s, position loop " << loop_s << " s, thread total "
+           << StageClock::now() - t_start << " s\n";
+        std::cerr << os.str() << std::flush;
     }
     bvc_destroy(tr.ctx);
     if (!fpv.close()) std::cerr << "warning: file cannot be closed" << std::endl;
