@@ -58,18 +58,23 @@ __device__ __forceinline__ uint8_t label_of_sample(const uint8_t *__restrict__ g
 }
 
 // "b,m,q,r,s " at text[p..] (p < e): five fields of one to three decimal digits, four commas, a space.  Returns the packed token,
-// 0 for any other shape.  Three aligned 8-byte loads cover the 20 bytes of the longest such token wherever p falls (the text
-// buffer is allocated 32 bytes longer than the text).
+// 0 for any other shape.  The 20 bytes of the longest such token (19 and the space) reach byte (p & 7) + 19 <= 26 of the aligned
+// words at p & ~7: FOUR aligned 8-byte loads, 32 bytes (the text buffer is allocated 64 bytes longer than the text and p < e lies
+// inside the text, so the last load ends at most 31 bytes behind it).  They are shifted into the token's own bytes 0..7, 8..15,
+// 16..19 once, by 8 (p & 7) = 0..56 bits ((x << 1) << (63 - s) is x << (64 - s) without a shift by 64 at s = 0), so that every
+// byte of the walk is taken with a shift count known at compile time.
 __device__ __forceinline__ uint32_t parse_base_token(const uint8_t *__restrict__ text, uint32_t p, uint32_t e)
 {
     const uint64_t *w = reinterpret_cast<const uint64_t *>(text + (p & ~7u));
-    const uint64_t w0 = w[0], w1 = w[1], w2 = w[2];
-    const uint32_t sh = p & 7u;
+    const uint64_t w0 = w[0], w1 = w[1], w2 = w[2], w3 = w[3];
+    const uint32_t s8 = 8u * (p & 7u);
+    const uint64_t t0 = (w0 >> s8) | ((w1 << 1) << (63u - s8));
+    const uint64_t t1 = (w1 >> s8) | ((w2 << 1) << (63u - s8));
+    const uint32_t t2 = (uint32_t)((w2 >> s8) | ((w3 << 1) << (63u - s8)));
     uint32_t f = 0, nd = 0, acc = 0, v0 = 0, v1 = 0, v2 = 0, v3 = 0;
 #pragma unroll
     for (int i = 0; i < 20; ++i) {
-        const uint32_t k = sh + (uint32_t)i;
-        uint32_t c = (uint32_t)((k < 8u ? w0 >> (8u * k) : (k < 16u ? w1 >> (8u * (k - 8u)) : w2 >> (8u * (k - 16u)))) & 0xFFu);
+        uint32_t c = (i < 8 ? (uint32_t)(t0 >> (8 * i)) : (i < 16 ? (uint32_t)(t1 >> (8 * (i - 8))) : t2 >> (8 * (i - 16)))) & 0xFFu;
         if (p + (uint32_t)i >= e) c = 0x20u;
         if (c == 0x20u) {
             if (nd == 0u || f != 4u) return 0u;

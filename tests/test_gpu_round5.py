@@ -118,8 +118,10 @@ def random_token(rng, p_data, p_indel, wide=False):
 @pytest.mark.parametrize("shape", ["sparse", "dense", "indel_heavy", "wide_fields", "tiny_batches"])
 def test_device_parse_of_fuzzed_regular_lines_equals_the_restated_parser(ctx, shape):
     """Regular lines of every kind the writer can produce, at every alignment: tokens crossing the 16-byte lanes and the 1 KiB steps,
-    indel tokens first in a line / after an N base / in runs, fields of three digits (bit-field wrap: base & 7, strand & 1, the
-    others mod 256), batches of one sample, empty positions; three consecutive tiles share one parser state (the carry)."""
+    indel tokens first in a line / after an N base / in runs, mapq, qual and rpr of up to three digits (wide_fields; bit-field wrap:
+    the others mod 256, base & 7 and strand & 1 from ONE digit each, so its longest token is 16 bytes -- base and strand of two and
+    three digits and every token length at every alignment are tests/test_gpu_pileup_lines.py's), batches of one sample, empty
+    positions; three consecutive tiles share one parser state (the carry)."""
     rng = np.random.default_rng({"sparse": 1, "dense": 2, "indel_heavy": 3, "wide_fields": 4, "tiny_batches": 5}[shape])
     p_data, p_indel, wide = {"sparse": (0.08, 0.004, False), "dense": (0.9, 0.02, False), "indel_heavy": (0.2, 0.3, False),
                              "wide_fields": (0.5, 0.05, True), "tiny_batches": (0.3, 0.05, False)}[shape]
