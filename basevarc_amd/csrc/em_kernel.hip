@@ -141,9 +141,14 @@ __device__ __forceinline__ PassOut em_pass(Slots<NS> &S, const Freq f, double in
 // EM (src/Algorithm.cpp:115-130) followed by UpdateF's log-likelihood sum (src/BaseType.cpp:58-62).
 // f0 = the lane's initial frequency.  Returns the log-likelihood of the last pass; ex = expect_allele_prob
 // of that pass (one M step ahead of the frequencies the log-likelihood belongs to, as in the reference).
+// first_stop: the stop rule may end the fit after its second pass.  Not so when the subset repeats a base (a SetBase list
+// with a duplicate): SetAlleleFreq divides by a depth sum that counts the base twice (src/BaseType.cpp:27-37), the starting
+// frequencies sum to S < 1, and pass 0's marginals are S times those of the normalised start f0 that runs here.  Posteriors do
+// not see the factor, so every later pass is the same; only the first delta has -log S in every term, and with
+// sum_c n_c log(m'_c / m_c) >= 0 (an EM step) it is at least N log(1 + 1 / N) >= log 2: never below 1e-3.
 template <int NS, int NA = NS>
 __device__ __forceinline__ double em_fit(Slots<NS> &S, int lane, double f0, double inv_n,
-                                         double (&ex)[4], int &passes)
+                                         double (&ex)[4], int &passes, bool first_stop)
 {
     Freq f{f0};
     PassOut o;
@@ -161,7 +166,7 @@ __device__ __forceinline__ double em_fit(Slots<NS> &S, int lane, double f0, doub
         f.fb = o.ex_own;
         o = em_pass<NS, NA>(S, f, inv_n, lane);
         passes += 1;
-        if (o.converged) break;
+        if (o.converged && (it > 0 || first_stop)) break;
         if (it + 1 == kEmIters) break;
         f.fb = o.ex_own;
     }
@@ -279,7 +284,8 @@ __device__ bool lrt_site(const uint32_t *__restrict__ hist, int ref, double min_
     int status = 0;
 
     // fit of one subset given as a mask over base codes; returns false when UpdateF skips it (:54)
-    auto fit_set = [&](uint32_t setmask, double &loglik, double (&ex)[4]) __attribute__((always_inline)) -> bool {
+    // `repeats`: the subset holds a base twice (see em_fit)
+    auto fit_set = [&](uint32_t setmask, bool repeats, double &loglik, double (&ex)[4]) __attribute__((always_inline)) -> bool {
         int depth_sum = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) depth_sum += ((setmask >> j) & 1u) ? depth[j] : 0;
@@ -291,8 +297,8 @@ __device__ bool lrt_site(const uint32_t *__restrict__ hist, int ref, double min_
         if (freq_sum == 0) return false;
         // (wave-uniform) the variant's narrower form when the site leaves its last slots empty
         constexpr int kNarrow = NS == 2 ? 1 : (NS == 4 ? 3 : 6);   // <= 16 values (binned qualities), <= 48, <= 96
-        if (kNarrow < NS && nslots <= kNarrow) loglik = em_fit<NS, kNarrow>(S, lane, pick4(f, row), inv_n, ex, passes);
-        else loglik = em_fit<NS>(S, lane, pick4(f, row), inv_n, ex, passes);
+        if (kNarrow < NS && nslots <= kNarrow) loglik = em_fit<NS, kNarrow>(S, lane, pick4(f, row), inv_n, ex, passes, !repeats);
+        else loglik = em_fit<NS>(S, lane, pick4(f, row), inv_n, ex, passes, !repeats);
         fits += 1;
         return true;
     };
@@ -309,8 +315,14 @@ __device__ bool lrt_site(const uint32_t *__restrict__ hist, int ref, double min_
             uint32_t setmask = 0;
             for (int p = 0; p < 4; ++p)
                 if ((pm >> p) & 1u) setmask |= 1u << ((blist >> (4 * p)) & 3u);
+            // a repeated base with observations: the reference's depth sum counts them twice
+            int depth_set = 0;
+            for (int j = 0; j < 4; ++j) depth_set += ((setmask >> j) & 1u) ? depth[j] : 0;
+            int depth_listed = 0;
+            for (int p = 0; p < 4; ++p)
+                if ((pm >> p) & 1u) depth_listed += pick4(depth, (int)((blist >> (4 * p)) & 3u));
             double ex[4], ll;
-            if (!fit_set(setmask, ll, ex)) continue;
+            if (!fit_set(setmask, depth_listed != depth_set, ll, ex)) continue;
             const double chi_c = 2.0 * (lr_alt - ll);
             if (n_fit == 0 || chi_c < best_chi) {                // std::min_element: first minimum, '<'
                 best_chi = chi_c; best_lr = ll; i_min = n_fit;

@@ -436,7 +436,11 @@ int bvc_hist_dense_packed(bvc_ctx *ctx, int64_t n_sites, int64_t n_samples, int6
  * rejected with BVC_ERR_ARG before anything runs.  With BVC_PTR_DEVICE the library cannot look at the arrays without
  * a round trip, so the kernels apply the reference's own rule instead: a candidate that is not A, C, G or T has
  * depth 0 in BaseType (src/BaseType.cpp:79 reads depth[b]) and falls to the min_af filter, i.e. the entry is
- * ignored (the record equals the one for the list without it), and n_comb[s] > 4 is read as 4. */
+ * ignored (the record equals the one for the list without it), and n_comb[s] > 4 is read as 4.
+ * A list may repeat a base (the reference then divides the starting frequencies by a depth sum that counts it twice,
+ * src/BaseType.cpp:27-37; the record is the reference's).
+ * Counts: a site's observations must sum to at most 2^31 - 1 (depth[] is int32_t, as BaseType::depth is); larger sums are not
+ * checked and wrap the depths. */
 int bvc_lrt_hist(bvc_ctx *ctx, int64_t n_sites, const uint32_t *counts, const int8_t *ref_base,
                  double min_af, const int8_t *base_comb, const uint8_t *n_comb,
                  bvc_site_result *results, uint32_t flags);
