@@ -41,7 +41,15 @@ struct PileupState {
         int64_t entries = 0, obs = 0, indels = 0;
         int64_t text_bytes = 0, indel_bytes = 0;
         bool on_device_text = false;
+        // after bvc_pileup_finish_called_text: the tile's columns stay where they are for bvc_pileup_sample_text -- the reference bases
+        // and records on the device, and on the host what sizes the text (every position's entries, which positions are called)
+        bool text_ready = false;
+        const int8_t *d_ref = nullptr;
+        const bvc_site_result *d_res = nullptr;
+        std::vector<int64_t> h_entry_off;
+        std::vector<uint8_t> h_called;
     } tile;
+    DevBuf vtext;                      // bvc_pileup_sample_text: the text, its offsets and lengths
 };
 
 struct bvc_ctx {
@@ -84,6 +92,7 @@ struct bvc_ctx {
     hipEvent_t ev_upload[2] = {nullptr, nullptr};
     hipEvent_t ev_set_free[2] = {nullptr, nullptr};   // ragged host calls: the kernels that read staging set k have finished
     PileupState pile;
+    DevBuf d_vcf, d_vcf_lut;           // vcf_samples_kernel.hip: the plan's scratch (device-pointer calls); the 256 x 8 bytes of bvc_vcf_bp_lut
     // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
     // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
     char *h_up = nullptr, *h_down = nullptr;
@@ -286,5 +295,8 @@ int run_csr_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const 
 int run_csr_labels_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *obs, const uint8_t *quals,
                           const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
                           bvc_site_result *results, bvc_group_result *grp_results);
+
+// bvc_vcf.hip: the device copy of bvc_vcf_bp_lut in ctx->d_vcf_lut, made at the context's first use of it
+int vcf_lut_device(bvc_ctx *ctx);
 
 #pragma GCC visibility pop

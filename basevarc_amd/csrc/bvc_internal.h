@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/bvc.h"
+#include "../../include/bvc_vcf.h"
 
 namespace bvc {
 
@@ -227,6 +228,21 @@ constexpr int kSiteStatsTrip = 4096;     // entries a workgroup takes per trip o
 hipError_t launch_site_stats(LaunchState &st, hipStream_t stream, int64_t n_sites, const int64_t *offsets, const bvc_pileup_entry *entries,
                              const int8_t *ref_base, const bvc_site_result *results, bvc_site_stats *stats);
 
+// vcf_samples_kernel.hip: the sample columns of the called sites' VCF lines (include/bvc.h, bvc_vcf_samples_csr).  The plan launches fill
+// text_off [n_sites + 1], text_len [n_sites] and the scratch (vcf_samples_scratch_bytes of device memory: head[0] = called sites, head[1] =
+// the sum of the slots, the called sites' list, every site's valid prefix); launch_vcf_samples then formats into `text` (16-byte aligned) and
+// writes nothing when head[1] > text_cap.  bp_lut: the 2048 bytes of bvc_vcf_bp_lut in device memory.
+constexpr int kVcfSamplesTile = 508;     // samples a workgroup formats per trip of its loop (the sizes the tests straddle)
+struct VcfSamplesScratch { int64_t *head; int32_t *called_list; uint32_t *n_valid; };
+size_t vcf_samples_scratch_bytes(int64_t n_sites);
+VcfSamplesScratch vcf_samples_scratch(void *buf, int64_t n_sites);
+hipError_t launch_vcf_samples_plan(hipStream_t stream, int64_t n_sites, const int64_t *offsets, const int32_t *samples,
+                                   const bvc_site_result *results, int64_t n_samples, int64_t *text_off, int64_t *text_len,
+                                   const VcfSamplesScratch &s);
+hipError_t launch_vcf_samples(hipStream_t stream, int64_t n_sites, const int64_t *offsets, const bvc_pileup_entry *entries,
+                              const int32_t *samples, const int8_t *ref_base, const bvc_site_result *results, int64_t n_samples,
+                              const int64_t *text_off, const VcfSamplesScratch &s, const char *bp_lut, char *text, int64_t text_cap);
+
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);
 
@@ -234,6 +250,7 @@ hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgz
 hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);
 hipError_t debug_read_site_stats(uint32_t *out8, bool reset);
+hipError_t debug_read_vcf_samples(uint32_t *out8, bool reset);
 // diagnostic builds: each translation unit's violation record (bvc_device.h)
 hipError_t debug_read_hist(uint32_t *out8, bool reset);
 hipError_t debug_read_wave_engine(uint32_t *out8, bool reset);

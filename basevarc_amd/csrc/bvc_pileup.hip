@@ -1,5 +1,7 @@
 // bvc_pileup.hip -- the producer: BGZF blocks inflated on the device, and temp-batch tiles (text, binary records, or BGZF blocks of
 // text) -> columns -> records between a begin call and a finish call (pileup_kernel.hip, inflate_kernel.hip).
+#include <cstdio>
+
 #include "bvc_ctx.h"
 
 extern "C" {
@@ -315,12 +317,14 @@ int bvc_pileup_text(bvc_ctx *ctx, char *text, int64_t text_cap, int64_t *text_by
 
 // bvc_pileup_finish (called_off = null: the entries of every position) and bvc_pileup_finish_called (the entries of the called
 // positions only, compacted on the device; called_cap = room in entries / samples); stats (called_off given): the called positions'
-// rank sums and strand counts too (bvc_pileup_finish_called_stats), computed where the entries lie and delivered with the records
+// rank sums and strand counts too (bvc_pileup_finish_called_stats), computed where the entries lie and delivered with the records;
+// for_text (called_off null, stats given): no entries or samples come down at all (bvc_pileup_finish_called_text) -- the tile's columns
+// and records stay on the device for bvc_pileup_sample_text
 static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
                               const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
                               int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
                               int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
-                              bvc_group_result *grp_results, bvc_site_stats *stats)
+                              bvc_group_result *grp_results, bvc_site_stats *stats, bool for_text = false)
 {
     if (!ctx) return BVC_ERR_ARG;
     PileupState &pile = ctx->pile;
@@ -333,7 +337,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     if (!carry_in || !carry_out || !entry_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
     if (T > 0 && (!ref_base || !tally || !results)) return fail(ctx, BVC_ERR_ARG, "null pointer");
     const bool called_only = called_off != nullptr;
-    if ((n_e > 0 && !called_only && (!entries || !samples)) || (n_i > 0 && !indels)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if ((n_e > 0 && !called_only && !for_text && (!entries || !samples)) || (n_i > 0 && !indels)) return fail(ctx, BVC_ERR_ARG, "null pointer");
     if (called_only && (called_cap < 0 || (called_cap > 0 && (!entries || !samples)))) return fail(ctx, BVC_ERR_ARG, "null pointer");
     if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
     if (n_groups > 0 && (!grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
@@ -363,7 +367,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     PinIO io(ctx);
     rc = io.reserve((size_t)T + (size_t)(n_groups > 0 ? n_samples : 0) + 1024,
                     (size_t)T * (sizeof(bvc_site_result) + 32 * 4 + 8 + (size_t)n_groups * sizeof(bvc_group_result)) +
-                        (size_t)(called_only ? 0 : n_e) * (sizeof(bvc_pileup_entry) + 4) + (called_only ? (size_t)(T + 1) * 8 : 0) +
+                        (size_t)(called_only || for_text ? 0 : n_e) * (sizeof(bvc_pileup_entry) + 4) + (called_only ? (size_t)(T + 1) * 8 : 0) +
                         (size_t)n_i * sizeof(bvc_pileup_indel) + (size_t)n_it + (stats ? (size_t)T * sizeof(bvc_site_stats) : 0) + 4096);
     if (rc != BVC_OK) return rc;
     if (T > 0) {
@@ -384,7 +388,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         if (n_groups > 0)
             BVC_HIP_D(ctx, io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
         BVC_HIP_D(ctx, io.d2h(tally, P.tally, (size_t)T * 32 * 4));
-        if (n_e && !called_only) {
+        if (n_e && !called_only && !for_text) {
             BVC_HIP_D(ctx, io.d2h(entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
             BVC_HIP_D(ctx, io.d2h(samples, P.samples, (size_t)n_e * 4));
         }
@@ -424,6 +428,13 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
     }
     carry_out[0] = (uint8_t)(cout & 7u); carry_out[1] = (uint8_t)(cout >> 8); carry_out[2] = (uint8_t)(cout >> 16);
     carry_out[3] = (uint8_t)(cout >> 24); carry_out[4] = (uint8_t)((cout >> 3) & 1u);
+    if (for_text) {
+        tile.d_ref = d_ref; tile.d_res = d_res;
+        tile.h_entry_off.assign(entry_off, entry_off + T + 1);
+        tile.h_called.resize((size_t)T);
+        for (int64_t t = 0; t < T; ++t) tile.h_called[(size_t)t] = results[t].called;
+        tile.text_ready = true;
+    }
     return BVC_OK;
 }
 
@@ -456,6 +467,63 @@ int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double 
     if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
     return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
                               called_cap, entries, samples, indels, indel_text, results, grp_results, stats);
+}
+
+int bvc_pileup_finish_called_text(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                                  const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                                  int64_t *entry_off, int32_t *tally, bvc_pileup_indel *indels, char *indel_text,
+                                  bvc_site_result *results, bvc_group_result *grp_results, bvc_site_stats *stats)
+{
+    if (ctx && !stats) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, nullptr, 0,
+                              nullptr, nullptr, indels, indel_text, results, grp_results, stats, true);
+}
+
+int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    PileupState &pile = ctx->pile;
+    const PileupState::Tile &tile = pile.tile;
+    if (!tile.text_ready) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_sample_text without the tile of a bvc_pileup_finish_called_text");
+    const PileupTile &P = tile.P;
+    const int64_t T = P.n_pos;
+    if (n_samples < 0 || text_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0");
+    if (!text_off || (T > 0 && !text_len) || (text_cap > 0 && !text)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    // the sum of the slots from what the finish call delivered: a buffer that is too small costs no launch and leaves the tile as it is
+    int64_t need = 0;
+    for (int64_t t = 0; t < T; ++t)
+        if (tile.h_called[(size_t)t]) need += bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]);
+    if (need > text_cap) {
+        char msg[160];
+        std::snprintf(msg, sizeof msg, "text_cap is %lld bytes, the called positions' slots need %lld", (long long)text_cap, (long long)need);
+        return fail(ctx, BVC_ERR_ARG, msg);
+    }
+    if (T == 0) { text_off[0] = 0; return BVC_OK; }
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = vcf_lut_device(ctx);
+    if (rc != BVC_OK) return rc;
+    int64_t *d_toff, *d_tlen; char *d_text, *d_scr;
+    rc = carve(ctx, pile.vtext, 256, [&](Layout &L) {
+        d_toff = L.take<int64_t>((size_t)T + 1);
+        d_tlen = L.take<int64_t>((size_t)T);
+        d_text = L.take<char>((size_t)need, 16);
+        d_scr = L.take<char>(vcf_samples_scratch_bytes(T));
+    });
+    if (rc != BVC_OK) return rc;
+    const VcfSamplesScratch scr = vcf_samples_scratch(d_scr, T);
+    PinIO io(ctx);
+    rc = io.reserve(0, (2 * (size_t)T + 1) * 8 + 1024);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, launch_vcf_samples_plan(ctx->stream, T, P.entry_off, P.samples, tile.d_res, n_samples, d_toff, d_tlen, scr));
+    BVC_HIP_D(ctx, launch_vcf_samples(ctx->stream, T, P.entry_off, P.entries, P.samples, tile.d_ref, tile.d_res, n_samples, d_toff, scr,
+                                      ctx->d_vcf_lut.p, d_text, need));
+    // (straight into the caller's memory: a DMA where that is bvc_host_alloc memory)
+    if (need) BVC_HIP_D(ctx, hipMemcpyAsync(text, d_text, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, io.d2h(text_off, d_toff, ((size_t)T + 1) * 8));
+    BVC_HIP_D(ctx, io.d2h(text_len, d_tlen, (size_t)T * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    return BVC_OK;
 }
 
 }  // extern "C"

@@ -195,11 +195,11 @@ size_t bvchost_cvg_line(const bvchost_site *s, const char *chr, int8_t ref_base,
 {
     return copy_out(cvg_line(chr, s->col.pos, ref_base, s->col, grp, n_groups), out, cap);
 }
-size_t bvchost_vcf_line(const bvchost_site *s, const bvc_site_result *bt, const char *chr, int8_t ref_base, int32_t n_samples,
-                        const char *extra_info_keys, const char *extra_info_vals, char *out, size_t cap)
+// ';'-separated parallel lists of extra INFO keys and values (the "<group>_AF" entries)
+static std::map<std::string, std::string> extra_info(const char *extra_info_keys, const char *extra_info_vals)
 {
     std::map<std::string, std::string> info;
-    if (extra_info_keys && extra_info_vals) {                    // ';'-separated parallel lists
+    if (extra_info_keys && extra_info_vals) {
         std::string k(extra_info_keys), v(extra_info_vals);
         size_t a = 0, b = 0;
         while (a < k.size()) {
@@ -209,7 +209,40 @@ size_t bvchost_vcf_line(const bvchost_site *s, const bvc_site_result *bt, const 
             a = ea + 1; b = eb + 1;
         }
     }
+    return info;
+}
+size_t bvchost_vcf_line(const bvchost_site *s, const bvc_site_result *bt, const char *chr, int8_t ref_base, int32_t n_samples,
+                        const char *extra_info_keys, const char *extra_info_vals, char *out, size_t cap)
+{
+    std::map<std::string, std::string> info = extra_info(extra_info_keys, extra_info_vals);
     return copy_out(vcf_line(*bt, chr, s->col.pos, ref_base, s->col, info, n_samples), out, cap);
+}
+// A site from arrays (n entries in bvc_pileup_entry layout and the sample each belongs to), as they are: nothing is dropped or checked.
+bvchost_site *bvchost_site_from_arrays(const bvc_pileup_entry *entries, const int32_t *samples, int64_t n, int32_t pos)
+{
+    bvchost_site *s = new bvchost_site();
+    s->col.pos = pos;
+    for (int64_t k = 0; k < n; ++k) {
+        AlleleInfo a;
+        a.base = entries[k].base; a.mapq = entries[k].mapq; a.qual = entries[k].qual; a.rpr = entries[k].rpr;
+        a.strand = entries[k].strand; a.is_indel = entries[k].is_indel;
+        s->col.add(a, samples[k]);
+    }
+    return s;
+}
+// The sample columns of bvchost_vcf_line alone (what libbvc's bvc_vcf_samples_csr formats on the device): bytes needed with the
+// terminating NUL; the output is truncated to cap.
+size_t bvchost_vcf_samples(const bvchost_site *s, const bvc_site_result *bt, int8_t ref_base, int32_t n_samples, char *out, size_t cap)
+{
+    return copy_out(vcf_samples(*bt, ref_base, view_of(s->col), n_samples), out, cap);
+}
+// The VCF line from sample columns that exist already and the device's statistics (vcf_line's overload that reads no entries).
+size_t bvchost_vcf_line_from_text(const bvc_site_result *bt, const char *chr, int32_t pos, int8_t ref_base, const bvc_site_stats *stats,
+                                  const char *extra_info_keys, const char *extra_info_vals, const char *samples_text, size_t samples_len,
+                                  char *out, size_t cap)
+{
+    std::map<std::string, std::string> info = extra_info(extra_info_keys, extra_info_vals);
+    return copy_out(vcf_line(*bt, chr, pos, ref_base, *stats, info, samples_text, samples_len), out, cap);
 }
 size_t bvchost_format_token(int base, int mapq, int qual, int rpr, int strand, const char *indel, char *out, size_t cap)
 {

@@ -40,6 +40,7 @@
 #include "bam.h"
 #include "bgzf.h"
 #include "pileup.h"
+#include "../../include/bvc_vcf.h"
 
 using namespace bvchost;
 
@@ -184,8 +185,14 @@ static bool device_inflate() { return env_int("BVC_HOST_DEVICE_INFLATE", 1) != 0
 // src/BaseVarC.cpp:664; as up to round 5's first form of this feed)
 static bool called_only() { return env_int("BVC_HOST_CALLED_ONLY", 1) != 0; }
 // 1: the rank sums and strand counts of a called position's VCF line are computed on the device, where the tile's entries lie
-// (bvc_pileup_finish_called_stats), not from its entries on this CPU (three sorts per called position); needs called_only
-static bool device_stats() { return env_int("BVC_HOST_DEVICE_STATS", 0) != 0; }
+// (bvc_pileup_finish_called_stats), not from its entries on this CPU (three sorts per called position); needs called_only.  On since the
+// eight-thread comparison of profiles/site_stats/README.txt item 3; 0: the CPU's own tallies (A/B runs)
+static bool device_stats() { return env_int("BVC_HOST_DEVICE_STATS", 1) != 0; }
+// 1: the sample columns of a called position's VCF line -- one GT:AB:SO:BP field per sample -- are formatted on the device too
+// (bvc_pileup_finish_called_text + bvc_pileup_sample_text) and no entry of a device-parsed tile comes to this CPU at all; implies the
+// device's statistics for those tiles -- BVC_HOST_DEVICE_STATS=0 therefore turns this off as well; needs called_only.  On since the
+// eight-thread comparison of profiles/vcf_samples/README.txt; 0: vcf_line's sample loop on the CPU (A/B runs)
+static bool device_samples() { return env_int("BVC_HOST_DEVICE_SAMPLES", 1) != 0 && device_stats(); }
 static bool two_byte_tiles() { return env_set("BVC_HOST_TWO_BYTE_TILES"); }            // set: never one byte per observation in the CPU parser's tiles
 static bool no_crc() { return env_set("BVC_HOST_NO_CRC"); }                            // set: the device does not check the CRC32 of the blocks it inflates
 // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
@@ -323,8 +330,21 @@ struct Tile {
     std::vector<bvc_pileup_entry> ent;
     std::vector<bvc_pileup_indel> indels;
     std::vector<bvc_site_stats> stats;   // per position, where the device computed them (empty: vcf_line tallies the entries itself)
+    // the called positions' sample columns where the device formatted them (BVC_HOST_DEVICE_SAMPLES): position t's are vtext_len[t] bytes
+    // at vtext + vtext_off[t]; page-locked memory that grows on demand and lives as long as the tile.  vtext_len empty: vcf_line formats
+    char *vtext = nullptr;
+    size_t vtext_cap = 0;
+    std::vector<int64_t> vtext_off, vtext_len;
+    Tile() = default;
+    Tile(const Tile &) = delete;
+    Tile &operator=(const Tile &) = delete;
+    ~Tile() { bvc_host_free(vtext); }
     bool handed_back = false;            // a line was not regular: the tile went through the CPU parser and its columns are in `sites`
-    void reset() { form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); stats.clear(); }
+    void reset()
+    {
+        form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); stats.clear();
+        vtext_off.clear(); vtext_len.clear();
+    }
     bool empty() const { return form == TileForm::Sites ? n_used == 0 : n_pos == 0; }     // nothing for stage 2 to do
     bool device_parsed() const { return form != TileForm::Sites && !handed_back; }        // (once stage 2 is through with it)
     // the tile is the T positions from w.pv[ip] on: their coordinates and reference bases
@@ -393,6 +413,7 @@ struct TileRunner {
     bool started = false;
     int64_t tiles_one_byte = 0, tiles_two_byte = 0;   // library calls by tile form (stage 2's thread; read after finish())
     int64_t tiles_dev_stats = 0;                      // of the tiles parsed on the device: those whose called positions' statistics the device computed
+    int64_t tiles_dev_samples = 0;                    // ... and whose called positions' sample columns the device formatted
     int64_t tiles_dev_parsed = 0, tiles_cpu_parsed = 0;   // tiles of text or records: parsed on the device / handed back (a line was not regular)
     std::vector<int32_t> sample0, n_in_batch;         // per temp batch: its first sample and its samples (device-parsed tiles)
     uint8_t carry[5] = {0, 0, 0, 0, 0};               // the parser's long-lived AlleleInfo between tiles (stage 2's thread)
@@ -501,7 +522,33 @@ struct TileRunner {
         uint8_t carry_out[5];
         int rc;
         T.stats.clear();
-        if (knob::called_only()) {
+        T.vtext_off.clear(); T.vtext_len.clear();
+        if (knob::called_only() && knob::device_samples()) {
+            // no entry comes back: the statistics with the records, then the called positions' sample columns as text
+            T.called_off.assign(T.n_pos + 1, 0);
+            T.stats.resize(T.n_pos);
+            rc = bvc_pileup_finish_called_text(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
+                                               ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(),
+                                               T.indels.data(), text_on_device ? T.text.data() : nullptr, T.res.data(),
+                                               ng ? T.gres.data() : nullptr, T.stats.data());
+            bvc_check(ctx, rc);
+            int64_t need = 0;
+            for (size_t t = 0; t < T.n_pos; ++t)
+                if (T.res[t].called) need += bvc_vcf_samples_slot(n_samples, T.entry_off[t + 1] - T.entry_off[t]);
+            if ((size_t)need > T.vtext_cap) {
+                bvc_host_free(T.vtext);
+                T.vtext = nullptr; T.vtext_cap = 0;
+                const size_t want = (size_t)need + (size_t)need / 4 + 4096;
+                T.vtext = static_cast<char *>(bvc_host_alloc(want));
+                if (!T.vtext) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
+                T.vtext_cap = want;
+            }
+            T.vtext_off.resize(T.n_pos + 1);
+            T.vtext_len.resize(T.n_pos + 1);
+            rc = bvc_pileup_sample_text(ctx, n_samples, T.vtext, (int64_t)T.vtext_cap, T.vtext_off.data(), T.vtext_len.data());
+            T.vtext_len.resize(T.n_pos);
+            tiles_dev_samples += 1;
+        } else if (knob::called_only()) {
             T.called_off.resize(T.n_pos + 1);
             if (knob::device_stats()) T.stats.resize(T.n_pos);
             rc = bvc_pileup_finish_called_stats(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
@@ -652,7 +699,10 @@ struct TileRunner {
                     const size_t t = called_t[k];
                     std::map<std::string, std::string> info;
                     if (ng) group_af_info(T.res[t], &T.gres[t * (size_t)ng], *groups, info);
-                    vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], T.view(t), info, n_samples);
+                    if (!T.vtext_off.empty())
+                        vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, T.vtext + T.vtext_off[t], (size_t)T.vtext_len[t]);
+                    else
+                        vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], T.view(t), info, n_samples);
                 }
             };
             {
@@ -1248,7 +1298,8 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
         std::ostringstream os;
         os << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
            << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
-           << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats << "\n";
+           << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats
+           << ", with their sample columns from the device " << tr.tiles_dev_samples << "\n";
         const StageClock &c = tr.clk, &d = tr.clk_dev, &o = tr.clk_out;
         os << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "
            << d.pack << " s, libbvc " << d.gpu << " s | stage 3 cvg lines " << o.cvg << " s, vcf lines " << o.vcf

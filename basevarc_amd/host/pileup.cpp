@@ -379,23 +379,28 @@ static const std::string &bp_field(uint8_t qual)
 }
 
 // ---- VCF line: WriteVcf, src/BaseType.cpp:141-234 ---------------------------------------------------------
-std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t ref_base, const SiteView &site,
-                     std::map<std::string, std::string> &info, int32_t n_samples)
+namespace {
+
+// What the sample loop tallies besides the text where the device has not (site.stats == nullptr): the inputs of the rank sums and the
+// strand counts.
+struct SampleTally {
+    int ref_fwd = 0, ref_rev = 0, alt_fwd = 0, alt_rev = 0;
+    std::vector<double> ref_quals, ref_mapqs, ref_rprs, alt_quals, alt_mapqs, alt_rprs;
+};
+
+// The sample columns, one field per sample, each followed by a tab (the caller drops the last); tally == nullptr: the text alone.
+void sample_columns(const bvc_site_result &bt, int8_t ref_base, const SiteView &site, int32_t n_samples, std::string &samgt, SampleTally *tally)
 {
-    const int32_t pos = site.pos;
     std::string alt_gt[8];                                        // genotype string per base code 0..7
     bool has_gt[8] = {false, false, false, false, false, false, false, false};
     auto is_alt = [&bt](int b) { for (int i = 0; i < bt.n_alt; ++i) if (bt.alt_base[i] == b) return true; return false; };
     for (int i = 0; i < bt.n_alt; ++i) { alt_gt[bt.alt_base[i] & 7] = "./" + std::to_string(i + 1); has_gt[bt.alt_base[i] & 7] = true; }
-    int ref_fwd = 0, ref_rev = 0, alt_fwd = 0, alt_rev = 0;
-    std::vector<double> ref_quals, ref_mapqs, ref_rprs, alt_quals, alt_mapqs, alt_rprs;
     // one field per SAMPLE: "./.\t" for a sample without an entry -- nine in ten at the coverage this tool is for, so the runs between
     // the covered samples are appended whole from a block of the pattern (the sample loop below visits the covered ones only)
     static const std::string kNoCall = [] { std::string p; for (int i = 0; i < 4096; ++i) p += "./.\t"; return p; }();
     auto no_calls = [](std::string &s, int64_t n) {
         for (; n > 0; n -= 4096) s.append(kNoCall, 0, (size_t)(n < 4096 ? n : 4096) * 4);
     };
-    std::string samgt;
     samgt.reserve((size_t)n_samples * 4 + site.n * 16 + 16);
     int32_t next = 0;                                              // first sample not written yet
     for (size_t k = 0; k < site.n; ++k) {
@@ -415,27 +420,21 @@ std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t r
         samgt += ':';
         samgt += kStrand[a.strand & 1];
         samgt += bp_field(a.qual);                          // ":<1 - 10^(-qual/10) as {:.6f}>\t"
-        if (site.stats || a.is_indel == 1 || a.base == 4) continue;
+        if (!tally || a.is_indel == 1 || a.base == 4) continue;
         const bool alt = is_alt(a.base);
-        if (a.base == ref_base) { ref_quals.push_back(a.qual); ref_mapqs.push_back(a.mapq); ref_rprs.push_back(a.rpr); }
-        else if (alt) { alt_quals.push_back(a.qual); alt_mapqs.push_back(a.mapq); alt_rprs.push_back(a.rpr); }
-        if (a.strand == 1) { if (a.base == ref_base) ref_fwd += 1; else if (alt) alt_fwd += 1; }
-        else { if (a.base == ref_base) ref_rev += 1; else if (alt) alt_rev += 1; }
+        if (a.base == ref_base) { tally->ref_quals.push_back(a.qual); tally->ref_mapqs.push_back(a.mapq); tally->ref_rprs.push_back(a.rpr); }
+        else if (alt) { tally->alt_quals.push_back(a.qual); tally->alt_mapqs.push_back(a.mapq); tally->alt_rprs.push_back(a.rpr); }
+        if (a.strand == 1) { if (a.base == ref_base) tally->ref_fwd += 1; else if (alt) tally->alt_fwd += 1; }
+        else { if (a.base == ref_base) tally->ref_rev += 1; else if (alt) tally->alt_rev += 1; }
     }
     no_calls(samgt, n_samples - next);
-    double phred_mapq, phred_qual, phred_rpr;
-    if (const bvc_site_stats *st = site.stats) {
-        // counted on the device from the same entries: rank2 / 2.0 is the double rank_r1 makes of them (include/bvc.h)
-        const size_t n1 = (size_t)st->n_ref, n2 = (size_t)st->n_alt;
-        phred_mapq = RankSumFromR1((double)st->rank2[0] / 2.0, n1, n2);
-        phred_qual = RankSumFromR1((double)st->rank2[1] / 2.0, n1, n2);
-        phred_rpr = RankSumFromR1((double)st->rank2[2] / 2.0, n1, n2);
-        ref_fwd = st->ref_fwd; ref_rev = st->ref_rev; alt_fwd = st->alt_fwd; alt_rev = st->alt_rev;
-    } else {
-        phred_mapq = RankSumTest(ref_mapqs, alt_mapqs);
-        phred_qual = RankSumTest(ref_quals, alt_quals);
-        phred_rpr = RankSumTest(ref_rprs, alt_rprs);
-    }
+}
+
+// Everything of the line but the sample columns, then the columns (samples_len bytes, no tab behind the last field).
+std::string line_around(const bvc_site_result &bt, const std::string &chr, int32_t pos, int8_t ref_base, std::map<std::string, std::string> &info,
+                        double phred_mapq, double phred_qual, double phred_rpr, int ref_fwd, int ref_rev, int alt_fwd, int alt_rev,
+                        const char *samples_text, size_t samples_len)
+{
     const double fs = bt_fisher_exact(ref_fwd, ref_rev, alt_fwd, alt_rev);
     const double sor = (alt_fwd * ref_rev > 0) ? (double)(ref_fwd * alt_rev) / (ref_rev * alt_fwd) : 10000.0;
     double ad_sum = 0;
@@ -449,7 +448,6 @@ std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t r
         caf += fmt_fixed(bt.depth[b] / bt.depth_total, 6) + ",";
     }
     alt.pop_back();
-    if (!samgt.empty()) samgt.pop_back();
     ac.pop_back(); info.insert({"CM_AC", ac});
     af.pop_back(); info.insert({"CM_AF", af});
     caf.pop_back(); info.insert({"CM_CAF", caf});
@@ -467,8 +465,53 @@ std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t r
                       fmt_fixed(bt.var_qual, 2) + "\t" + qt + "\t";
     for (auto const &kv : info) out += kv.first + "=" + kv.second + ";";
     out.pop_back();
-    out += "\tGT:AB:SO:BP\t" + samgt + "\n";
+    out.reserve(out.size() + 16 + samples_len);
+    out += "\tGT:AB:SO:BP\t";
+    out.append(samples_text, samples_len);
+    out += "\n";
     return out;
+}
+
+// the statistics the device counted from the same entries: rank2 / 2.0 is the double rank_r1 makes of them (include/bvc.h)
+std::string line_from_stats(const bvc_site_result &bt, const std::string &chr, int32_t pos, int8_t ref_base, const bvc_site_stats &st,
+                            std::map<std::string, std::string> &info, const char *samples_text, size_t samples_len)
+{
+    const size_t n1 = (size_t)st.n_ref, n2 = (size_t)st.n_alt;
+    return line_around(bt, chr, pos, ref_base, info, RankSumFromR1((double)st.rank2[0] / 2.0, n1, n2),
+                       RankSumFromR1((double)st.rank2[1] / 2.0, n1, n2), RankSumFromR1((double)st.rank2[2] / 2.0, n1, n2), st.ref_fwd,
+                       st.ref_rev, st.alt_fwd, st.alt_rev, samples_text, samples_len);
+}
+
+}  // namespace
+
+std::string vcf_samples(const bvc_site_result &bt, int8_t ref_base, const SiteView &site, int32_t n_samples)
+{
+    std::string samgt;
+    sample_columns(bt, ref_base, site, n_samples, samgt, nullptr);
+    if (!samgt.empty()) samgt.pop_back();
+    return samgt;
+}
+
+std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int8_t ref_base, const SiteView &site,
+                     std::map<std::string, std::string> &info, int32_t n_samples)
+{
+    std::string samgt;
+    if (site.stats) {
+        sample_columns(bt, ref_base, site, n_samples, samgt, nullptr);
+        if (!samgt.empty()) samgt.pop_back();
+        return line_from_stats(bt, chr, site.pos, ref_base, *site.stats, info, samgt.data(), samgt.size());
+    }
+    SampleTally t;
+    sample_columns(bt, ref_base, site, n_samples, samgt, &t);
+    if (!samgt.empty()) samgt.pop_back();
+    return line_around(bt, chr, site.pos, ref_base, info, RankSumTest(t.ref_mapqs, t.alt_mapqs), RankSumTest(t.ref_quals, t.alt_quals),
+                       RankSumTest(t.ref_rprs, t.alt_rprs), t.ref_fwd, t.ref_rev, t.alt_fwd, t.alt_rev, samgt.data(), samgt.size());
+}
+
+std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int32_t pos, int8_t ref_base, const bvc_site_stats &stats,
+                     std::map<std::string, std::string> &info, const char *samples_text, size_t samples_len)
+{
+    return line_from_stats(bt, chr, pos, ref_base, stats, info, samples_text, samples_len);
 }
 
 // ---- orchestration ---------------------------------------------------------------------------------------

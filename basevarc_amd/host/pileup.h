@@ -177,6 +177,13 @@ inline std::string vcf_line(const bvc_site_result &bt, const std::string &chr, i
     v.pos = pos;
     return vcf_line(bt, chr, ref_base, v, info, n_samples);
 }
+// The sample columns of that line alone: one GT:AB:SO:BP field per sample, tab separated (what libbvc's bvc_vcf_samples_csr formats
+// on the device, byte for byte).
+std::string vcf_samples(const bvc_site_result &bt, int8_t ref_base, const SiteView &site, int32_t n_samples);
+// The VCF line around sample columns that exist already (samples_len bytes, no tab behind the last field) and the statistics the
+// device computed: reads no entries.
+std::string vcf_line(const bvc_site_result &bt, const std::string &chr, int32_t pos, int8_t ref_base, const bvc_site_stats &stats,
+                     std::map<std::string, std::string> &info, const char *samples_text, size_t samples_len);
 // "<group>_AF" values from the group records (src/BaseVarC.cpp:646-658).
 void group_af_info(const bvc_site_result &bt, const bvc_group_result *grp, const Groups &g,
                    std::map<std::string, std::string> &info);

@@ -49,6 +49,7 @@ INDEL_DTYPE = np.dtype([("entry", "<i8"), ("text_off", "<i8"), ("len", "<i4"), (
 BLOCK_DTYPE = np.dtype([("comp_off", "<i8"), ("out_off", "<i8"), ("comp_len", "<i4"), ("isize", "<i4"), ("crc32", "<u4"),
                         ("check_crc", "<u4")])                                                                   # bvc_bgzf_block
 SITE_STATS_TRIP = 4096      # entries a workgroup of site_stats_kernel takes per trip of its loop (csrc/bvc_internal.h, kSiteStatsTrip)
+VCF_SAMPLES_TILE = 508      # samples a workgroup of vcf_samples_kernel formats per trip of its loop (csrc/bvc_internal.h, kVcfSamplesTile)
 assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 120
 assert STATS_DTYPE.itemsize == 64 and ENTRY_DTYPE.itemsize == 8
 assert GROUP_DTYPE.itemsize == C.sizeof(GroupResult) == 48
@@ -109,6 +110,15 @@ PROTOTYPES = {
     # not in the header: diagnostic builds of the library only export it (-DBVC_CHECK_LDS, csrc/bvc_device.h)
     "bvc_debug_report": (_int, [_vp, C.POINTER(_u32), _int]),
 }
+# The second header, include/bvc_vcf.h (the VCF sample columns): the same kind of table, in that header's order
+# (tests/test_vcf_samples_abi.py compares the two), bound by bind() with the first.
+VCF_PROTOTYPES = {
+    "bvc_vcf_bp_lut": (None, [_vp]),
+    "bvc_vcf_samples_csr": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _u32]),
+    "bvc_pileup_finish_called_text": (_int, [_vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bvc_pileup_sample_text": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+}
+VCF_EXPORTS = list(VCF_PROTOTYPES)
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
 EXPORTS = [name for name in PROTOTYPES if name not in OPTIONAL]   # what every build of the library exports
 
@@ -122,7 +132,7 @@ def library_path():
 def bind(cdll):
     """Gives every function of PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
     symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(VCF_PROTOTYPES.items()):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -144,6 +154,25 @@ def load_library():
                        "(hipcc --offload-arch=gfx950); basevarc_amd has no CPU fallback")
     _lib = bind(C.CDLL(_LIB))
     return _lib
+
+
+def vcf_samples_slot(n_samples, n_entries):
+    """bvc_vcf_samples_slot (include/bvc_vcf.h): bytes of a called site's slot in the text of vcf_samples_csr / pileup_sample_text."""
+    return (4 * int(n_samples) + 13 * int(n_entries) + 15) // 16 * 16
+
+
+def vcf_samples_need(n_samples, offsets, results):
+    """The sum of the slots: the text buffer vcf_samples_csr / pileup_sample_text need for these sites."""
+    o = np.asarray(offsets, dtype=np.int64)
+    called = np.asarray(results["called"]) != 0
+    return int(sum(vcf_samples_slot(n_samples, n) for n in (o[1:] - o[:-1])[called]))
+
+
+def vcf_bp_lut():
+    """bvc_vcf_bp_lut: the 256 x 8 characters d.dddddd of the BP sub-field, as bytes (no device needed)."""
+    out = C.create_string_buffer(2048)
+    load_library().bvc_vcf_bp_lut(out)
+    return out.raw
 
 
 def _np_ptr(a):
@@ -409,6 +438,48 @@ class Context:
         context's stream.  In overlap mode call join() first: the records must be complete."""
         return self._site_stats_csr(True, offsets_t.numel() - 1, offsets_t, entries_t, ref_t, results_t, stats_t)
 
+    def vcf_samples_csr(self, offsets, entries, samples, ref_base, results, n_samples, text=None, text_cap=None):
+        """bvc_vcf_samples_csr on host arrays: the sample columns of the called sites' VCF lines.  entries (ENTRY_DTYPE) and samples
+        (int32) of site s at offsets[s] .. offsets[s + 1].  text: a uint8 array to format into (e.g. a host_alloc view; default: a new one
+        of the size needed); text_cap: what to tell the library instead of its size.  Returns (text, text_off [n_sites + 1], text_len
+        [n_sites]): site s's columns are text[text_off[s] : text_off[s] + text_len[s]]."""
+        o, e, sm = _as(offsets, np.int64), _as(entries, ENTRY_DTYPE), _as(samples, np.int32)
+        r, res = _as(ref_base, np.int8), _as(results, SITE_DTYPE)
+        n = len(o) - 1
+        assert r.shape == (n,) and res.shape == (n,) and len(e) == len(sm)
+        if text is None:
+            text = np.zeros(max(1, vcf_samples_need(n_samples, o, res)), dtype=np.uint8)
+        cap = len(text) if text_cap is None else int(text_cap)
+        off, ln = self._call(self._L.bvc_vcf_samples_csr, False,
+                             (n, o, e if len(e) else None, sm if len(sm) else None, r, res, int(n_samples), text, cap),
+                             [(None, (n + 1,), np.dtype(np.int64)), (None, (n,), np.dtype(np.int64))])
+        return text, off, ln
+
+    def vcf_samples_csr_device(self, offsets_t, entries_t, samples_t, ref_t, results_t, n_samples, text_t, text_off_t=None,
+                               text_len_t=None, text_cap=None):
+        """The same on device tensors (entries_t / results_t: uint8 views of the records; text_t: uint8, 16-byte aligned; text_off_t /
+        text_len_t: int64).  The call waits once for the sum of the slots (BvcError when text_t is too small); the formatting is
+        asynchronous on the context's stream.  In overlap mode call join() first."""
+        import torch
+        ns = offsets_t.numel() - 1
+        if text_off_t is None:
+            text_off_t = torch.empty(ns + 1, dtype=torch.int64, device=offsets_t.device)
+        if text_len_t is None:
+            text_len_t = torch.empty(max(1, ns), dtype=torch.int64, device=offsets_t.device)
+        cap = text_t.numel() if text_cap is None else int(text_cap)
+        self._call(self._L.bvc_vcf_samples_csr, True, (ns, offsets_t, entries_t, samples_t, ref_t, results_t, int(n_samples), text_t, cap,
+                                                       text_off_t, text_len_t))
+        return text_t, text_off_t, text_len_t
+
+    def pileup_sample_text(self, n_positions, n_samples, text, text_cap=None):
+        """bvc_pileup_sample_text after a tile finished with sample_text=True: the called positions' sample columns into text (uint8 array).
+        Returns (text, text_off [T + 1], text_len [T])."""
+        off = np.zeros(n_positions + 1, dtype=np.int64)
+        ln = np.zeros(max(1, n_positions), dtype=np.int64)
+        cap = len(text) if text_cap is None else int(text_cap)
+        self._check(self._L.bvc_pileup_sample_text(self._h, int(n_samples), _np_ptr(text) if len(text) else None, cap, _np_ptr(off), _np_ptr(ln)))
+        return text, off, ln[:n_positions]
+
     # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
     def pack_dense_device(self, bases_t, quals_t, packed_t=None):
         """Two-byte device tile -> packed device tile.  Returns (packed_t, n_unrepresentable)."""
@@ -486,20 +557,21 @@ class Context:
 
     # ---- the producer: temp batches parsed on the device (host pointers only)
     def pileup_tile(self, text, line_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
-                    n_groups=0, called_only=False, stats=False):
+                    n_groups=0, called_only=False, stats=False, sample_text=False):
         """bvc_pileup_begin + bvc_pileup_finish on one tile of temp-batch pileup text (include/bvc.h).  text: bytes;
         line_start: uint32 [n_batches, n_positions + 1].  Returns None when a line is not regular (BVC_PILEUP_IRREGULAR), else a
         dict: entry_off, tally [T, 32], entries (structured), samples, indels (sorted by entry), results, grp_results, carry_out.
-        stats=True (needs called_only=True): bvc_pileup_finish_called_stats -- key "stats", STATS_DTYPE [T]."""
+        stats=True (needs called_only=True): bvc_pileup_finish_called_stats -- key "stats", STATS_DTYPE [T].
+        sample_text=True: bvc_pileup_finish_called_text -- "stats" too, no entries / samples; pileup_sample_text() then formats the columns."""
         ls = _as(line_start, np.uint32)
         rc, T, ne, ni = self._pileup_begin(self._L.bvc_pileup_begin, text, ls, _as(sample0, np.int32), _as(n_in_batch, np.int32))
         if rc == 1:
             return None
         self._check(rc)
-        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
+        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats, sample_text=sample_text)
 
     def pileup_tile_bin(self, records, rec_start, sample0, n_in_batch, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None,
-                        n_groups=0, called_only=False, stats=False):
+                        n_groups=0, called_only=False, stats=False, sample_text=False):
         """bvc_pileup_begin_bin + bvc_pileup_finish on one tile of binary temp-batch records (include/bvc.h).  records: bytes;
         rec_start: uint32 [n_batches, n_positions + 1].  Returns the dict of pileup_tile (indels' text_off are offsets into records);
         raises BvcError (status BVC_ERR_DATA = -5: a malformed record, BVC_ERR_ARG = -1: a rec_start that does not fit)."""
@@ -511,7 +583,7 @@ class Context:
             raise ValueError("sample0 / n_in_batch must be [n_batches]")
         rc, T, ne, ni = self._pileup_begin(self._L.bvc_pileup_begin_bin, records, rs, s0, nib)
         self._check(rc)
-        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats)
+        return self._pileup_finish(T, ne, ni, 0, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats, sample_text=sample_text)
 
     def _pileup_begin(self, fn, data, start, s0, nib):
         """bvc_pileup_begin (text, line_start) / bvc_pileup_begin_bin (records, rec_start): (rc, n_positions, n_entries, n_indels)."""
@@ -522,9 +594,12 @@ class Context:
         return rc, T, ne.value, ni.value
 
     def _pileup_finish(self, T, n_entries, n_indels, indel_text_bytes, ref_base, min_af, carry_in, group_of_sample, n_groups,
-                       called_only=False, called_cap=None, stats=False):
+                       called_only=False, called_cap=None, stats=False, sample_text=False):
         """called_only: bvc_pileup_finish_called -- `entries` / `samples` hold the called positions' entries only, position t's at
-        called_off[t] .. called_off[t + 1] (key "called_off").  stats (with called_only): bvc_pileup_finish_called_stats, key "stats"."""
+        called_off[t] .. called_off[t + 1] (key "called_off").  stats (with called_only): bvc_pileup_finish_called_stats, key "stats".
+        sample_text (alone): bvc_pileup_finish_called_text -- key "stats", and "entries" / "samples" stay empty: the columns stay on the device."""
+        if sample_text and (called_only or stats):
+            raise ValueError("sample_text=True stands alone (bvc_pileup_finish_called_text delivers the statistics itself)")
         if stats and not called_only:
             raise ValueError("stats=True needs called_only=True (bvc_pileup_finish_called_stats)")
         r = _as(ref_base, np.int8)
@@ -546,12 +621,17 @@ class Context:
             fn = self._L.bvc_pileup_finish_called_stats if stats else self._L.bvc_pileup_finish_called
             called_off = np.zeros(T + 1, dtype=np.int64)
             args += [called_off, n_entries if called_cap is None else int(called_cap)]
-        args += [entries, samples, indels, itext if indel_text_bytes else None, res, gres if n_groups else None]
+        if sample_text:
+            fn = self._L.bvc_pileup_finish_called_text
+            stats = True
+        else:
+            args += [entries, samples]
+        args += [indels, itext if indel_text_bytes else None, res, gres if n_groups else None]
         if stats:
             st = np.zeros(max(1, T), dtype=STATS_DTYPE)
             args.append(st)
         self._check(fn(self._h, *_pointers(args, _np_ptr)))
-        n_kept = int(called_off[T]) if called_only else n_entries
+        n_kept = int(called_off[T]) if called_only else (0 if sample_text else n_entries)
         ind = indels[:n_indels]
         ind = ind[np.argsort(ind["entry"], kind="stable")]
         out = dict(entry_off=entry_off, tally=tally, entries=entries[:n_kept], samples=samples[:n_kept], indels=ind, results=res,

@@ -398,6 +398,8 @@ int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double 
                                    int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
                                    int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
                                    bvc_group_result *grp_results, bvc_site_stats *stats);
+/* The called positions' VCF sample columns formatted on the device -- bvc_vcf_samples_csr, bvc_pileup_finish_called_text,
+ * bvc_pileup_sample_text -- are declared in bvc_vcf.h beside this header. */
 /*
  * The same from the COMPRESSED temp batches: the BGZF blocks go to the device as they are in the files (a fifth of the bytes of
  * their text), are inflated there (bvc_inflate_blocks) and the text never exists on the host.  The caller no longer knows where the

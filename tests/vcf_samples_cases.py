@@ -1,0 +1,199 @@
+"""The sample columns of a called site's VCF line: a plain Python model of the text (include/bvc_vcf.h, bvc_vcf_samples_csr), the host
+program's own columns through libbvchost.so (bvchost_vcf_samples, the reference), and the hand-built catalogue of sites both the CPU and
+the GPU tests walk.  Nothing here needs a device."""
+import ctypes as C
+import itertools
+import math
+
+import numpy as np
+
+T = 508                                                            # the kernel's sample tile (csrc/bvc_internal.h, kVcfSamplesTile)
+SIZES = (1, 2, 3, 4, 5, T - 1, T, T + 1, 2 * T, 2 * T + 1)
+BP = [("%.6f" % (1 - math.exp(-0.23025850929940458 * q))).encode() for q in range(256)]
+INT_MAX = 2 ** 31 - 1
+
+
+# ------------------------------------------------------------------------------------------------------------------ the model
+def valid_prefix(n_samples, samples):
+    nxt, k = 0, 0
+    for k, s in enumerate(int(x) for x in samples):
+        if s < nxt or s >= n_samples:
+            return k
+        nxt = s + 1
+    return len(samples)
+
+
+def model_columns(n_samples, samples, entries, ref_base, n_alt, alt_base):
+    """The text of one called site: 4 bytes for a sample without an entry, 17 for one with, the last tab dropped."""
+    nv = valid_prefix(n_samples, samples)
+    fields = [b"./."] * n_samples
+    for k in range(nv):
+        base, qual, strand = int(entries["base"][k]) & 7, int(entries["qual"][k]), int(entries["strand"][k])
+        if base == int(ref_base):
+            g = b"0/."
+        else:
+            g = b"./."
+            for i in range(min(int(n_alt), 3)):
+                if (int(alt_base[i]) & 7) == base:
+                    g = b"./%d" % (i + 1)                          # (the last one wins)
+        fields[int(samples[k])] = g + b":" + b"ACGTNN"[min(base, 5):min(base, 5) + 1] + b":" + b"-+"[strand & 1:(strand & 1) + 1] + b":" + BP[qual]
+    text = b"\t".join(fields)
+    assert len(text) == max(0, 4 * n_samples + 13 * nv - 1)
+    return text
+
+
+# ------------------------------------------------------------------------------------------------------------------ the host program's columns
+def host_library():
+    from basevarc_amd import build as b
+    _, hostlib = b.build_host()
+    H = C.CDLL(hostlib)
+    H.bvchost_site_from_arrays.restype = C.c_void_p
+    H.bvchost_site_from_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    H.bvchost_site_free.argtypes = [C.c_void_p]
+    H.bvchost_vcf_samples.restype = C.c_size_t
+    H.bvchost_vcf_samples.argtypes = [C.c_void_p, C.c_void_p, C.c_int8, C.c_int32, C.c_char_p, C.c_size_t]
+    H.bvchost_vcf_line.restype = C.c_size_t
+    H.bvchost_vcf_line.argtypes = [C.c_void_p, C.c_void_p, C.c_char_p, C.c_int8, C.c_int32, C.c_char_p, C.c_char_p, C.c_char_p, C.c_size_t]
+    H.bvchost_vcf_line_from_text.restype = C.c_size_t
+    H.bvchost_vcf_line_from_text.argtypes = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int8, C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p,
+                                             C.c_size_t, C.c_char_p, C.c_size_t]
+    return H
+
+
+class HostSite:
+    """A bvchost_site made of arrays (entries in ENTRY_DTYPE, samples int32), freed with the object."""
+
+    def __init__(self, H, entries, samples, pos=1):
+        self.H = H
+        e, s = np.ascontiguousarray(entries), np.ascontiguousarray(samples, dtype=np.int32)
+        self.h = H.bvchost_site_from_arrays(e.ctypes.data if len(e) else None, s.ctypes.data if len(s) else None, len(e), pos)
+
+    def __del__(self):
+        self.H.bvchost_site_free(self.h)
+
+
+def host_defined(result):
+    """The host program loops over n_alt alleles of a three-element array: a record with n_alt > 3 (the LRT writes none) is the device's
+    and the model's to define -- they read it as 3."""
+    return int(result["n_alt"]) <= 3
+
+
+def host_columns(H, n_samples, samples, entries, ref_base, result):
+    site = HostSite(H, entries, samples)
+    res = np.ascontiguousarray(result)
+    cap = 4 * n_samples + 17 * len(samples) + 64
+    buf = C.create_string_buffer(cap)
+    need = H.bvchost_vcf_samples(site.h, res.ctypes.data, int(ref_base), n_samples, buf, cap)
+    assert need <= cap
+    return buf.raw[:need - 1]
+
+
+# ------------------------------------------------------------------------------------------------------------------ the catalogue
+def make_entries(n, rng=None, **fields):
+    from basevarc_amd.lib import ENTRY_DTYPE
+    e = np.zeros(n, dtype=ENTRY_DTYPE)
+    if rng is not None:
+        e["base"] = rng.integers(0, 8, n); e["qual"] = rng.integers(0, 256, n); e["strand"] = rng.integers(0, 4, n)
+        e["mapq"] = rng.integers(0, 256, n); e["rpr"] = rng.integers(0, 256, n); e["is_indel"] = rng.integers(0, 2, n)
+        e["pad"] = rng.integers(0, 65536, n)                       # (nobody reads it)
+    for k, v in fields.items():
+        e[k] = v
+    return e
+
+
+def make_result(called=1, n_alt=1, alt_base=(1, -1, -1)):
+    from basevarc_amd.lib import SITE_DTYPE
+    r = np.zeros((), dtype=SITE_DTYPE)
+    r["called"] = called; r["n_alt"] = n_alt; r["alt_base"] = alt_base
+    return r
+
+
+def coverage_patterns(n):
+    """name -> ascending sample indices, for n samples."""
+    pats = {"none": [], "all": list(range(n)), "first": [0], "last": [n - 1], "alternating": list(range(0, n, 2)),
+            "odd": list(range(1, n, 2))}
+    edges = sorted({i for t0 in range(0, n, T) for i in (t0, min(n, t0 + T) - 1)})
+    pats["tile_ends"] = edges                                      # the first and the last sample of every tile
+    runs = sorted({i for t0 in range(T, n + T, T) for i in range(t0 - 5, t0 + 6) if 0 <= i < n})
+    pats["runs_across_edges"] = runs                               # covered samples either side of every tile edge (and of the end)
+    return {k: np.array(v, dtype=np.int32) for k, v in pats.items()}
+
+
+def sites_of(n):
+    """The catalogue at n samples: [(name, samples, entries, ref_base, result)], called sites and uncalled ones whose entries are poison."""
+    rng = np.random.default_rng(20261019 + n)
+    out = []
+
+    def add(name, samples, entries=None, ref=None, result=None):
+        samples = np.asarray(samples, dtype=np.int32)
+        if entries is None:
+            entries = make_entries(len(samples), rng)
+        if result is None:
+            na = int(rng.integers(0, 4))
+            result = make_result(1 + len(out) % 3, na, tuple(int(x) for x in rng.integers(0, 4, 3)))
+        out.append((name, samples, entries, int(rng.integers(-1, 6)) if ref is None else ref, result))
+
+    for name, s in coverage_patterns(n).items():
+        add(f"coverage {name}", s)
+        # an uncalled site between the called ones: its samples are out of order and out of range, its entries all 0xFF
+        bad = np.full(7, -5, dtype=np.int32)
+        add(f"uncalled behind {name}", bad, np.frombuffer(b"\xff" * 56, dtype=make_entries(0).dtype).copy(), result=make_result(0, 3, (0, 1, 2)))
+    # every base against every reference base, every alt assignment of 0..3 alleles from A, C, G, T (duplicates: the last one wins)
+    m = min(n, 8)
+    bases = np.arange(8, dtype=np.uint8)[:m] if n >= 8 else None
+    alts = [()] + [a for k in (1, 2, 3) for a in itertools.product(range(4), repeat=k)]
+    alts += [(-1,), (4, 4), (7, 5, 4), (1, 1, 1)]
+    if n not in (5, T + 1):
+        alts = alts[::7] + alts[-4:]                               # (the whole list at one size below eight samples and at one above a tile)
+    for ref in range(-1, 6):
+        for a in alts:
+            for chunk in ([bases] if bases is not None else [np.arange(c, min(8, c + m), dtype=np.uint8) for c in range(0, 8, m)]):
+                k = len(chunk)
+                e = make_entries(k, rng, base=chunk)
+                at = np.sort(rng.choice(n, k, replace=False)).astype(np.int32)
+                add(f"ref {ref} alts {a}", at, e, ref, make_result(1, len(a), tuple(a) + (-1,) * (3 - len(a))))
+    add("n_alt 5 is read as 3", np.arange(min(n, 4)), make_entries(min(n, 4), rng, base=np.arange(min(n, 4))), 0, make_result(1, 5, (1, 2, 3)))
+    # every quality, strand bytes 0..3, indel flag 0 / 1
+    for q0 in range(0, 256, min(n, 256)):
+        k = min(n, 256, 256 - q0)
+        at = np.sort(rng.choice(n, k, replace=False)).astype(np.int32)
+        add(f"qualities from {q0}", at, make_entries(k, rng, qual=np.arange(q0, q0 + k), strand=np.arange(k) % 4, is_indel=(np.arange(k) // 4) % 2))
+    # validity: where the entries stop counting
+    full = np.arange(n, dtype=np.int32)
+    add("n = 0 on a called site", [])
+    add("first entry negative", np.concatenate([[-1], full]))
+    add("first entry = n", np.concatenate([[n], full]))
+    add("first entry 2^31 - 1", np.concatenate([[INT_MAX], full]))
+    add("last entry = n", np.concatenate([full, [n]]))
+    add("last entry 2^31 - 1", np.concatenate([full, [INT_MAX], [0]]))
+    add("everything repeated", np.repeat(full, 2))
+    if n >= 2:
+        add("descending at k = 1", np.array([n - 1, 0], dtype=np.int32))
+        add("repeated at k = 1", np.concatenate([[0, 0], full[1:]]))
+        add("negative in the middle", np.concatenate([full[:n // 2], [-7], full[n // 2:]]))
+    if n >= 5:
+        for where in sorted({n // 3, min(n - 2, T // 2), min(n - 2, T - 1), min(n - 2, T), min(n - 2, T + 1)}):
+            s = full.copy()
+            s[where + 1] = s[where] - (where % 2)                  # a repeat (even) or a step back (odd) in front of / at / behind a tile's first sample
+            add(f"breaks behind entry {where}", s)
+            sparse = full[::3].copy()
+            if where // 3 + 1 < len(sparse):
+                sparse[where // 3 + 1] = sparse[where // 3]
+                add(f"sparse, repeats behind entry {where // 3}", sparse)
+    return out
+
+
+def pack(sites):
+    """The catalogue's sites as the arrays of one call: offsets, entries, samples, ref_base, results."""
+    from basevarc_amd.lib import SITE_DTYPE
+    lens = [len(s[1]) for s in sites]
+    offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+    entries = np.concatenate([s[2] for s in sites]) if sites else make_entries(0)
+    samples = np.concatenate([s[1] for s in sites]).astype(np.int32) if sites else np.zeros(0, np.int32)
+    refs = np.array([s[3] for s in sites], dtype=np.int8)
+    results = np.array([s[4] for s in sites], dtype=SITE_DTYPE)
+    return offsets, entries, samples, refs, results
+
+
+def model_of(n, sites):
+    return [model_columns(n, s[1], s[2], s[3], s[4]["n_alt"], s[4]["alt_base"]) if int(s[4]["called"]) else b"" for s in sites]
