@@ -1,0 +1,162 @@
+// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip), and
+// bvc_pileup_sample_bgzf, which hands a tile's sample columns (vcf_samples_kernel.hip) to the same kernels where they are made.
+#include <cstdio>
+
+#include "bvc_ctx.h"
+
+int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_data, const int64_t *d_off, const int64_t *d_len,
+                        const int64_t *upper, uint8_t *d_comp, int64_t comp_cap, int64_t *d_comp_off, bool wait_for_upload)
+{
+    std::vector<int64_t> first((size_t)n_pieces + 1);
+    int64_t n_blocks = 0;
+    for (int64_t i = 0; i < n_pieces; ++i) { first[(size_t)i] = n_blocks; n_blocks += bvc_bgzf_blocks(upper[i]); }
+    first[(size_t)n_pieces] = n_blocks;
+    const int rc = ensure(ctx, ctx->d_bgzf, bgzf_deflate_scratch_bytes(n_pieces, n_blocks));
+    if (rc != BVC_OK) return rc;
+    const BgzfDeflateScratch scr = bgzf_deflate_scratch(ctx->d_bgzf.p, n_pieces, n_blocks);
+    BVC_HIP_D(ctx, io.h2d(scr.first_block, first.data(), first.size() * 8));
+    // a call that returns with its launches in flight must not leave a transfer out of the page-locked buffer in flight too: the next
+    // call on the context fills that buffer at once.  (The stream holds nothing but this copy here: its caller has just waited.)
+    if (wait_for_upload) BVC_HIP_D(ctx, wait_stream(ctx));
+    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off));
+    return BVC_OK;
+}
+
+static int fail_comp_cap(bvc_ctx *ctx, int64_t need, int64_t comp_cap)
+{
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "comp_cap is %lld bytes, the bounds of the pieces need %lld", (long long)comp_cap, (long long)need);
+    return fail(ctx, BVC_ERR_ARG, msg);
+}
+
+// The sum of the pieces' lengths and of their bounds; false where an offset or a length is negative.
+static bool sum_pieces(int64_t n_pieces, const int64_t *off, const int64_t *len, int64_t *total, int64_t *need)
+{
+    *total = 0; *need = 0;
+    for (int64_t i = 0; i < n_pieces; ++i) {
+        if (off[i] < 0 || len[i] < 0) return false;
+        *total += len[i];
+        *need += bvc_bgzf_bound(len[i]);
+    }
+    return true;
+}
+
+extern "C" {
+
+int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
+                     uint8_t *comp, int64_t comp_cap, int64_t *comp_off, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (n_pieces < 0 || comp_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_pieces < 0 or comp_cap < 0");
+    if (!comp_off || (n_pieces > 0 && (!piece_off || !piece_len))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n_pieces > (int64_t)0x7FFFFFFF / 64) return fail(ctx, BVC_ERR_ARG, "too many pieces in one call");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t np = (size_t)n_pieces;
+    PinIO io(ctx);
+    int64_t total = 0, need = 0;
+    if (flags & BVC_PTR_DEVICE) {
+        if (n_pieces == 0) { BVC_HIP(ctx, hipMemsetAsync(comp_off, 0, 8, ctx->stream)); return BVC_OK; }
+        // the wait of the device form: the launches and the scratch are sized from the pieces' lengths
+        int rc = io.reserve((np + 1) * 8 + 64, 2 * np * 8 + 128);
+        if (rc != BVC_OK) return rc;
+        std::vector<int64_t> off(np), len(np);
+        BVC_HIP_D(ctx, io.d2h(off.data(), piece_off, np * 8));
+        BVC_HIP_D(ctx, io.d2h(len.data(), piece_len, np * 8));
+        BVC_HIP_D(ctx, wait_stream(ctx));
+        io.deliver();
+        if (!sum_pieces(n_pieces, off.data(), len.data(), &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
+        if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+        if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
+        return bgzf_deflate_device(ctx, io, n_pieces, data, piece_off, piece_len, len.data(), comp, comp_cap, comp_off, true);
+    }
+    if (!sum_pieces(n_pieces, piece_off, piece_len, &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
+    if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
+    if (n_pieces == 0) { comp_off[0] = 0; return BVC_OK; }
+    uint8_t *d_data, *d_comp; int64_t *d_off, *d_len, *d_coff;
+    int rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
+        d_data = L.take<uint8_t>((size_t)total, 16);
+        d_off = L.take<int64_t>(np);
+        d_len = L.take<int64_t>(np);
+        d_comp = L.take<uint8_t>((size_t)need);
+        d_coff = L.take<int64_t>(np + 1);
+    });
+    if (rc != BVC_OK) return rc;
+    rc = io.reserve((size_t)total + (3 * np + 1) * 8 + 512, (np + 1) * 8 + 64);
+    if (rc != BVC_OK) return rc;
+    // the pieces one after the other (wherever they lie in the caller's memory) through the page-locked buffer: one transfer
+    std::vector<int64_t> off(np);
+    {
+        char *const stage = ctx->h_up + io.up_used;
+        int64_t at = 0;
+        for (size_t i = 0; i < np; ++i) {
+            off[i] = at;
+            if (piece_len[i]) std::memcpy(stage + at, data + piece_off[i], (size_t)piece_len[i]);
+            at += piece_len[i];
+        }
+        io.up_used += PinIO::al((size_t)total);
+        if (total) BVC_HIP_D(ctx, hipMemcpyAsync(d_data, stage, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+    }
+    BVC_HIP_D(ctx, io.h2d(d_off, off.data(), np * 8));
+    BVC_HIP_D(ctx, io.h2d(d_len, piece_len, np * 8));
+    rc = bgzf_deflate_device(ctx, io, n_pieces, d_data, d_off, d_len, piece_len, d_comp, need, d_coff, false);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, io.d2h(comp_off, d_coff, (np + 1) * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    // the second wait: only the packed bytes come down, and how many they are was not known before
+    const int64_t packed = comp_off[n_pieces];
+    if (packed > 0) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
+        BVC_HIP_D(ctx, wait_stream(ctx));
+    }
+    return BVC_OK;
+}
+
+int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    const int64_t need_text = pileup_sample_text_need(ctx, n_samples, "bvc_pileup_sample_bgzf");
+    if (need_text < 0) return BVC_ERR_ARG;
+    const PileupState::Tile &tile = ctx->pile.tile;
+    const int64_t T = tile.P.n_pos;
+    if (comp_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or comp_cap < 0");
+    if (!comp_off || (T > 0 && !text_len) || (comp_cap > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    // a position's text is at most its slot: the blocks' bound from what the finish call delivered, before anything is launched
+    std::vector<int64_t> upper((size_t)T);
+    int64_t need = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        upper[(size_t)t] = tile.h_called[(size_t)t] ? bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]) : 0;
+        need += bvc_bgzf_bound(upper[(size_t)t]);
+    }
+    if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
+    if (T == 0) { comp_off[0] = 0; return BVC_OK; }
+    int64_t *d_toff, *d_tlen; char *d_text;
+    int rc = pileup_sample_text_device(ctx, n_samples, need_text, &d_toff, &d_tlen, &d_text);
+    if (rc != BVC_OK) return rc;
+    uint8_t *d_comp; int64_t *d_coff;
+    rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
+        d_comp = L.take<uint8_t>((size_t)need);
+        d_coff = L.take<int64_t>((size_t)T + 1);
+    });
+    if (rc != BVC_OK) return rc;
+    PinIO io(ctx);
+    rc = io.reserve(((size_t)T + 1) * 8 + 64, (2 * (size_t)T + 1) * 8 + 1024);
+    if (rc != BVC_OK) return rc;
+    // position t's piece: its text_len bytes at text_off[t] of the text
+    rc = bgzf_deflate_device(ctx, io, T, reinterpret_cast<const uint8_t *>(d_text), d_toff, d_tlen, upper.data(), d_comp, need, d_coff, false);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, io.d2h(comp_off, d_coff, ((size_t)T + 1) * 8));
+    BVC_HIP_D(ctx, io.d2h(text_len, d_tlen, (size_t)T * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    // the wait its twin does not have: the packed bytes, straight into the caller's memory (a DMA where that is bvc_host_alloc memory)
+    const int64_t packed = comp_off[T];
+    if (packed > 0) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
+        BVC_HIP_D(ctx, wait_stream(ctx));
+    }
+    return BVC_OK;
+}
+
+}  // extern "C"

@@ -380,6 +380,8 @@ int bvc_debug_report(bvc_ctx *ctx, uint32_t *out24, int reset)
     if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
     BVC_HIP(ctx, debug_read_vcf_samples(pl, reset != 0));
     if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
+    BVC_HIP(ctx, debug_read_bgzf_deflate(pl, reset != 0));
+    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
     return BVC_OK;
 }
 #endif

@@ -93,6 +93,7 @@ struct bvc_ctx {
     hipEvent_t ev_set_free[2] = {nullptr, nullptr};   // ragged host calls: the kernels that read staging set k have finished
     PileupState pile;
     DevBuf d_vcf, d_vcf_lut;           // vcf_samples_kernel.hip: the plan's scratch (device-pointer calls); the 256 x 8 bytes of bvc_vcf_bp_lut
+    DevBuf d_bgzf, d_bgzf_io;          // bgzf_deflate_kernel.hip: block tables, match rows, staged blocks; a call's staged pieces (host pointers), its packed blocks and comp_off
     // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
     // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
     char *h_up = nullptr, *h_down = nullptr;
@@ -295,6 +296,18 @@ int run_csr_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const 
 int run_csr_labels_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const uint8_t *obs, const uint8_t *quals,
                           const uint8_t *group_of_obs, const int8_t *ref_base, double min_af, int32_t n_groups,
                           bvc_site_result *results, bvc_group_result *grp_results);
+
+// bvc_bgzf.hip: pieces in device memory -> BGZF blocks in d_comp (device), comp_off [n_pieces + 1] in d_comp_off (device), all on the
+// stream.  upper[i] >= piece i's length, on the host (the lengths themselves where it knows them): it sizes the launches and the scratch
+// (ctx->d_bgzf).  io: the call's transfers, with (n_pieces + 1) * 8 + 64 bytes reserved going up.  wait_for_upload: for a caller that
+// returns without a wait of its own behind this -- the block table has left the page-locked buffer before the kernels are launched.
+int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_data, const int64_t *d_off, const int64_t *d_len,
+                        const int64_t *upper, uint8_t *d_comp, int64_t comp_cap, int64_t *d_comp_off, bool wait_for_upload);
+// bvc_pileup.hip: what bvc_pileup_sample_text and bvc_pileup_sample_bgzf share.  The sum of the called positions' slots of the tile that
+// bvc_pileup_finish_called_text left (-1 with the error set: there is none), and the text formatted into the context's device memory, on
+// the stream: d_toff [T + 1], d_tlen [T], d_text [need].
+int64_t pileup_sample_text_need(bvc_ctx *ctx, int64_t n_samples, const char *caller);
+int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int64_t **d_toff, int64_t **d_tlen, char **d_text);
 
 // bvc_vcf.hip: the device copy of bvc_vcf_bp_lut in ctx->d_vcf_lut, made at the context's first use of it
 int vcf_lut_device(bvc_ctx *ctx);

@@ -7,6 +7,7 @@
 
 #include "../../include/bvc.h"
 #include "../../include/bvc_vcf.h"
+#include "../../include/bvc_bgzf.h"
 
 namespace bvc {
 
@@ -243,6 +244,17 @@ hipError_t launch_vcf_samples(hipStream_t stream, int64_t n_sites, const int64_t
                               const int32_t *samples, const int8_t *ref_base, const bvc_site_result *results, int64_t n_samples,
                               const int64_t *text_off, const VcfSamplesScratch &s, const char *bp_lut, char *text, int64_t text_cap);
 
+// bgzf_deflate_kernel.hip: pieces of device memory deflated into BGZF blocks (include/bvc_bgzf.h, bvc_bgzf_deflate).  Piece i holds the
+// blocks first_block[i] .. first_block[i + 1] of the call (first_block [n_pieces + 1] in the scratch, filled by the caller: from the
+// pieces' lengths or from upper bounds of them -- a block behind a piece's real length is empty and takes no byte); comp_off
+// [n_pieces + 1] and the packed blocks are written on the stream.  Nothing is packed when the blocks do not fit comp_cap.
+constexpr int kBgzfDeflateGrid = 256;    // workgroups of bgzf_deflate_kernel: a call of more blocks sends each round its loop again
+struct BgzfDeflateScratch { int64_t *first_block, *block_off; char *desc; uint32_t *bsize, *match_rows; uint8_t *staging; };
+size_t bgzf_deflate_scratch_bytes(int64_t n_pieces, int64_t n_blocks);
+BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_blocks, Layout *sized = nullptr);
+hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off);
+
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);
 
@@ -251,6 +263,7 @@ hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);
 hipError_t debug_read_site_stats(uint32_t *out8, bool reset);
 hipError_t debug_read_vcf_samples(uint32_t *out8, bool reset);
+hipError_t debug_read_bgzf_deflate(uint32_t *out8, bool reset);
 // diagnostic builds: each translation unit's violation record (bvc_device.h)
 hipError_t debug_read_hist(uint32_t *out8, bool reset);
 hipError_t debug_read_wave_engine(uint32_t *out8, bool reset);

@@ -482,41 +482,24 @@ int bvc_pileup_finish_called_text(bvc_ctx *ctx, const int8_t *ref_base, double m
 int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len)
 {
     if (!ctx) return BVC_ERR_ARG;
-    PileupState &pile = ctx->pile;
-    const PileupState::Tile &tile = pile.tile;
-    if (!tile.text_ready) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_sample_text without the tile of a bvc_pileup_finish_called_text");
-    const PileupTile &P = tile.P;
-    const int64_t T = P.n_pos;
-    if (n_samples < 0 || text_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0");
+    const int64_t need = pileup_sample_text_need(ctx, n_samples, "bvc_pileup_sample_text");
+    if (need < 0) return BVC_ERR_ARG;
+    const int64_t T = ctx->pile.tile.P.n_pos;
+    if (text_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0");
     if (!text_off || (T > 0 && !text_len) || (text_cap > 0 && !text)) return fail(ctx, BVC_ERR_ARG, "null pointer");
     // the sum of the slots from what the finish call delivered: a buffer that is too small costs no launch and leaves the tile as it is
-    int64_t need = 0;
-    for (int64_t t = 0; t < T; ++t)
-        if (tile.h_called[(size_t)t]) need += bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]);
     if (need > text_cap) {
         char msg[160];
         std::snprintf(msg, sizeof msg, "text_cap is %lld bytes, the called positions' slots need %lld", (long long)text_cap, (long long)need);
         return fail(ctx, BVC_ERR_ARG, msg);
     }
     if (T == 0) { text_off[0] = 0; return BVC_OK; }
-    BVC_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = vcf_lut_device(ctx);
+    int64_t *d_toff, *d_tlen; char *d_text;
+    int rc = pileup_sample_text_device(ctx, n_samples, need, &d_toff, &d_tlen, &d_text);
     if (rc != BVC_OK) return rc;
-    int64_t *d_toff, *d_tlen; char *d_text, *d_scr;
-    rc = carve(ctx, pile.vtext, 256, [&](Layout &L) {
-        d_toff = L.take<int64_t>((size_t)T + 1);
-        d_tlen = L.take<int64_t>((size_t)T);
-        d_text = L.take<char>((size_t)need, 16);
-        d_scr = L.take<char>(vcf_samples_scratch_bytes(T));
-    });
-    if (rc != BVC_OK) return rc;
-    const VcfSamplesScratch scr = vcf_samples_scratch(d_scr, T);
     PinIO io(ctx);
     rc = io.reserve(0, (2 * (size_t)T + 1) * 8 + 1024);
     if (rc != BVC_OK) return rc;
-    BVC_HIP_D(ctx, launch_vcf_samples_plan(ctx->stream, T, P.entry_off, P.samples, tile.d_res, n_samples, d_toff, d_tlen, scr));
-    BVC_HIP_D(ctx, launch_vcf_samples(ctx->stream, T, P.entry_off, P.entries, P.samples, tile.d_ref, tile.d_res, n_samples, d_toff, scr,
-                                      ctx->d_vcf_lut.p, d_text, need));
     // (straight into the caller's memory: a DMA where that is bvc_host_alloc memory)
     if (need) BVC_HIP_D(ctx, hipMemcpyAsync(text, d_text, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, io.d2h(text_off, d_toff, ((size_t)T + 1) * 8));
@@ -527,3 +510,41 @@ int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t 
 }
 
 }  // extern "C"
+
+int64_t pileup_sample_text_need(bvc_ctx *ctx, int64_t n_samples, const char *caller)
+{
+    const PileupState::Tile &tile = ctx->pile.tile;
+    if (!tile.text_ready) {
+        ctx->err = std::string(caller) + " without the tile of a bvc_pileup_finish_called_text";
+        return -1;
+    }
+    if (n_samples < 0) { (void)fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0"); return -1; }
+    int64_t need = 0;
+    for (int64_t t = 0; t < tile.P.n_pos; ++t)
+        if (tile.h_called[(size_t)t]) need += bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]);
+    return need;
+}
+
+int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int64_t **d_toff, int64_t **d_tlen, char **d_text)
+{
+    PileupState &pile = ctx->pile;
+    const PileupState::Tile &tile = pile.tile;
+    const PileupTile &P = tile.P;
+    const int64_t T = P.n_pos;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = vcf_lut_device(ctx);
+    if (rc != BVC_OK) return rc;
+    char *d_scr;
+    rc = carve(ctx, pile.vtext, 256, [&](Layout &L) {
+        *d_toff = L.take<int64_t>((size_t)T + 1);
+        *d_tlen = L.take<int64_t>((size_t)T);
+        *d_text = L.take<char>((size_t)need, 16);
+        d_scr = L.take<char>(vcf_samples_scratch_bytes(T));
+    });
+    if (rc != BVC_OK) return rc;
+    const VcfSamplesScratch scr = vcf_samples_scratch(d_scr, T);
+    BVC_HIP_D(ctx, launch_vcf_samples_plan(ctx->stream, T, P.entry_off, P.samples, tile.d_res, n_samples, *d_toff, *d_tlen, scr));
+    BVC_HIP_D(ctx, launch_vcf_samples(ctx->stream, T, P.entry_off, P.entries, P.samples, tile.d_ref, tile.d_res, n_samples, *d_toff, scr,
+                                      ctx->d_vcf_lut.p, *d_text, need));
+    return BVC_OK;
+}

@@ -104,17 +104,19 @@ BgzfWriter::BgzfWriter(const std::string &path, int level, bool background, int 
                 std::vector<unsigned char> blk, out;
                 for (;;) {
                     uint64_t seq;
+                    bool ready;
                     {
                         std::unique_lock<std::mutex> g(mu_);
                         cv_.wait(g, [&] { return !pending_.empty() || closing_; });
                         if (pending_.empty()) return;
-                        blk.swap(pending_.front());
+                        blk.swap(pending_.front().bytes);
+                        ready = pending_.front().ready;
                         pending_.pop_front();
                         seq = taken_++;
                     }
                     cv_.notify_all();               // room for the producer
                     out.clear();
-                    deflate_block(blk, out);
+                    if (ready) out.swap(blk); else deflate_block(blk, out);
                     {
                         std::unique_lock<std::mutex> g(mu_);
                         cv_.wait(g, [&] { return written_ == seq; });     // in the order the blocks were handed over
@@ -176,11 +178,28 @@ void BgzfWriter::flush_block(size_t n)
     std::vector<unsigned char> blk(buf_.begin(), buf_.begin() + n);
     buf_.erase(buf_.begin(), buf_.begin() + n);
     if (!background_) { deflate_and_write(blk); return; }
+    hand_over(std::move(blk), false);
+}
+
+// Background mode: an item into the in-order queue.
+void BgzfWriter::hand_over(std::vector<unsigned char> &&bytes, bool ready)
+{
     std::unique_lock<std::mutex> g(mu_);
-    cv_.wait(g, [&] { return pending_.size() < 256; });          // at most 16 MB waiting for the deflater
-    pending_.push_back(std::move(blk));
+    cv_.wait(g, [&] { return pending_.size() < 256; });          // at most 16 MB of text waiting for the deflater
+    pending_.push_back(Item{std::move(bytes), ready});
     g.unlock();
     cv_.notify_all();
+}
+
+void BgzfWriter::write_blocks(const unsigned char *blocks, size_t n)
+{
+    flush_block(buf_.size());
+    if (!fp_ || n == 0) return;
+    if (!background_) {
+        if (std::fwrite(blocks, 1, n, fp_) != n) failed_ = true;
+        return;
+    }
+    hand_over(std::vector<unsigned char>(blocks, blocks + n), true);
 }
 
 // Background mode: every block handed over so far has reached the file.

@@ -29,12 +29,17 @@ class BgzfWriter {
     bool ok() const { return fp_ != nullptr && !failed_; }
     void write(const char *data, size_t n);
     void write(const std::string &s) { write(s.data(), s.size()); }
+    // Finished BGZF blocks (n bytes of whole blocks, e.g. deflated on the device) into the file after everything written before and
+    // before everything written after.  Ends the block being filled (a short block is legal).  In background mode the blocks join
+    // the in-order queue as an item that needs no deflate.
+    void write_blocks(const unsigned char *blocks, size_t n);
     bool close();                               // flushes and appends the EOF marker block
     // Appends a finished BGZF file block for block (its EOF marker dropped): BGZF blocks are independent gzip
     // members, so concatenating files is concatenating their blocks -- no inflate/deflate round trip.
     bool append_file(const std::string &path);
  private:
     void flush_block(size_t n);
+    void hand_over(std::vector<unsigned char> &&bytes, bool ready);
     void deflate_block(const std::vector<unsigned char> &in, std::vector<unsigned char> &out);
     void deflate_and_write(std::vector<unsigned char> &in);
     void drain();
@@ -47,7 +52,8 @@ class BgzfWriter {
     std::vector<std::thread> workers_;
     std::mutex mu_;
     std::condition_variable cv_;
-    std::deque<std::vector<unsigned char>> pending_;
+    struct Item { std::vector<unsigned char> bytes; bool ready; };   // ready: finished blocks, written as they are
+    std::deque<Item> pending_;
     uint64_t taken_ = 0, written_ = 0;          // blocks handed to a worker / whose bytes are in the file
     bool closing_ = false;
 };

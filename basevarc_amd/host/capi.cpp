@@ -311,6 +311,19 @@ int bvchost_bgzf_write(const char *path, const char *data, int64_t n, int64_t pi
     return w.close() ? 1 : 0;
 }
 
+// Test hook: one BGZF file from parts in order -- kind 0: text, through BgzfWriter::write; kind 1: finished blocks, through write_blocks.
+int bvchost_bgzf_splice(const char *path, const char *const *parts, const int64_t *lens, const int32_t *kinds, int32_t n_parts, int level,
+                        int background)
+{
+    BgzfWriter w(path, level, background != 0, background);
+    if (!w.ok()) return 0;
+    for (int32_t i = 0; i < n_parts; ++i) {
+        if (kinds[i] == 1) w.write_blocks(reinterpret_cast<const unsigned char *>(parts[i]), (size_t)lens[i]);
+        else w.write(parts[i], (size_t)lens[i]);
+    }
+    return w.close() ? 1 : 0;
+}
+
 // Test hook: reads `n_files` BGZF files the way the position loop does -- round robin, one line (by_line) or `piece` bytes
 // of each per turn -- through readers attached to an InflatePool of `threads` threads (0: no pool), a seek back to the
 // start of file 0 after `seek_after` turns, and returns a 64-bit FNV-1a hash over everything read (order included).

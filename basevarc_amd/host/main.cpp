@@ -40,7 +40,7 @@
 #include "bam.h"
 #include "bgzf.h"
 #include "pileup.h"
-#include "../../include/bvc_vcf.h"
+#include "../../include/bvc_bgzf.h"
 
 using namespace bvchost;
 
@@ -193,6 +193,11 @@ static bool device_stats() { return env_int("BVC_HOST_DEVICE_STATS", 1) != 0; }
 // device's statistics for those tiles -- BVC_HOST_DEVICE_STATS=0 therefore turns this off as well; needs called_only.  On since the
 // eight-thread comparison of profiles/vcf_samples/README.txt; 0: vcf_line's sample loop on the CPU (A/B runs)
 static bool device_samples() { return env_int("BVC_HOST_DEVICE_SAMPLES", 1) != 0 && device_stats(); }
+// 1: those sample columns are also deflated on the device (bvc_pileup_sample_bgzf): their text never comes to this CPU, and a called
+// position's line is written as the text in front of the columns, the columns' finished BGZF blocks (BgzfWriter::write_blocks) and the
+// newline.  The .vcf.gz inflates to the same bytes; it is larger than zlib's level 6 makes it (profiles/vcf_deflate/README.txt).  Needs
+// device_samples; acts on device-parsed tiles only.  Off by default
+static bool device_deflate() { return env_int("BVC_HOST_DEVICE_DEFLATE", 0) != 0 && device_samples(); }
 static bool two_byte_tiles() { return env_set("BVC_HOST_TWO_BYTE_TILES"); }            // set: never one byte per observation in the CPU parser's tiles
 static bool no_crc() { return env_set("BVC_HOST_NO_CRC"); }                            // set: the device does not check the CRC32 of the blocks it inflates
 // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
@@ -335,15 +340,20 @@ struct Tile {
     char *vtext = nullptr;
     size_t vtext_cap = 0;
     std::vector<int64_t> vtext_off, vtext_len;
+    // ... or deflated them too (BVC_HOST_DEVICE_DEFLATE): position t's BGZF blocks are vcomp[vcomp_off[t] .. vcomp_off[t + 1]), page-locked
+    // as vtext; vtext_len then says how long the text would have been and vtext_off stays empty
+    unsigned char *vcomp = nullptr;
+    size_t vcomp_cap = 0;
+    std::vector<int64_t> vcomp_off;
     Tile() = default;
     Tile(const Tile &) = delete;
     Tile &operator=(const Tile &) = delete;
-    ~Tile() { bvc_host_free(vtext); }
+    ~Tile() { bvc_host_free(vtext); bvc_host_free(vcomp); }
     bool handed_back = false;            // a line was not regular: the tile went through the CPU parser and its columns are in `sites`
     void reset()
     {
         form = TileForm::Sites; handed_back = false; n_used = 0; entries = 0; refs.clear(); n_pos = 0; pos.clear(); stats.clear();
-        vtext_off.clear(); vtext_len.clear();
+        vtext_off.clear(); vtext_len.clear(); vcomp_off.clear();
     }
     bool empty() const { return form == TileForm::Sites ? n_used == 0 : n_pos == 0; }     // nothing for stage 2 to do
     bool device_parsed() const { return form != TileForm::Sites && !handed_back; }        // (once stage 2 is through with it)
@@ -414,6 +424,7 @@ struct TileRunner {
     int64_t tiles_one_byte = 0, tiles_two_byte = 0;   // library calls by tile form (stage 2's thread; read after finish())
     int64_t tiles_dev_stats = 0;                      // of the tiles parsed on the device: those whose called positions' statistics the device computed
     int64_t tiles_dev_samples = 0;                    // ... and whose called positions' sample columns the device formatted
+    int64_t tiles_dev_deflate = 0;                    // ... and deflated
     int64_t tiles_dev_parsed = 0, tiles_cpu_parsed = 0;   // tiles of text or records: parsed on the device / handed back (a line was not regular)
     std::vector<int32_t> sample0, n_in_batch;         // per temp batch: its first sample and its samples (device-parsed tiles)
     uint8_t carry[5] = {0, 0, 0, 0, 0};               // the parser's long-lived AlleleInfo between tiles (stage 2's thread)
@@ -522,7 +533,7 @@ struct TileRunner {
         uint8_t carry_out[5];
         int rc;
         T.stats.clear();
-        T.vtext_off.clear(); T.vtext_len.clear();
+        T.vtext_off.clear(); T.vtext_len.clear(); T.vcomp_off.clear();
         if (knob::called_only() && knob::device_samples()) {
             // no entry comes back: the statistics with the records, then the called positions' sample columns as text
             T.called_off.assign(T.n_pos + 1, 0);
@@ -532,20 +543,34 @@ struct TileRunner {
                                                T.indels.data(), text_on_device ? T.text.data() : nullptr, T.res.data(),
                                                ng ? T.gres.data() : nullptr, T.stats.data());
             bvc_check(ctx, rc);
+            const bool deflate = knob::device_deflate();
             int64_t need = 0;
             for (size_t t = 0; t < T.n_pos; ++t)
-                if (T.res[t].called) need += bvc_vcf_samples_slot(n_samples, T.entry_off[t + 1] - T.entry_off[t]);
-            if ((size_t)need > T.vtext_cap) {
-                bvc_host_free(T.vtext);
-                T.vtext = nullptr; T.vtext_cap = 0;
+                if (T.res[t].called) {
+                    const int64_t slot = bvc_vcf_samples_slot(n_samples, T.entry_off[t + 1] - T.entry_off[t]);
+                    need += deflate ? bvc_bgzf_bound(slot) : slot;
+                }
+            // (page-locked memory of the tile's, grown on demand: the text, or its blocks)
+            auto grow = [&](void **buf, size_t *cap) {
+                if ((size_t)need <= *cap) return;
+                bvc_host_free(*buf);
+                *buf = nullptr; *cap = 0;
                 const size_t want = (size_t)need + (size_t)need / 4 + 4096;
-                T.vtext = static_cast<char *>(bvc_host_alloc(want));
-                if (!T.vtext) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
-                T.vtext_cap = want;
-            }
-            T.vtext_off.resize(T.n_pos + 1);
+                *buf = bvc_host_alloc(want);
+                if (!*buf) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
+                *cap = want;
+            };
             T.vtext_len.resize(T.n_pos + 1);
-            rc = bvc_pileup_sample_text(ctx, n_samples, T.vtext, (int64_t)T.vtext_cap, T.vtext_off.data(), T.vtext_len.data());
+            if (deflate) {
+                grow(reinterpret_cast<void **>(&T.vcomp), &T.vcomp_cap);
+                T.vcomp_off.resize(T.n_pos + 1);
+                rc = bvc_pileup_sample_bgzf(ctx, n_samples, T.vcomp, (int64_t)T.vcomp_cap, T.vcomp_off.data(), T.vtext_len.data());
+                tiles_dev_deflate += 1;
+            } else {
+                grow(reinterpret_cast<void **>(&T.vtext), &T.vtext_cap);
+                T.vtext_off.resize(T.n_pos + 1);
+                rc = bvc_pileup_sample_text(ctx, n_samples, T.vtext, (int64_t)T.vtext_cap, T.vtext_off.data(), T.vtext_len.data());
+            }
             T.vtext_len.resize(T.n_pos);
             tiles_dev_samples += 1;
         } else if (knob::called_only()) {
@@ -699,7 +724,11 @@ struct TileRunner {
                     const size_t t = called_t[k];
                     std::map<std::string, std::string> info;
                     if (ng) group_af_info(T.res[t], &T.gres[t * (size_t)ng], *groups, info);
-                    if (!T.vtext_off.empty())
+                    if (!T.vcomp_off.empty()) {
+                        // the line around columns that are not here: everything in front of them; their blocks and the newline follow below
+                        vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, "", 0);
+                        vcf_pre[k].pop_back();
+                    } else if (!T.vtext_off.empty())
                         vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, T.vtext + T.vtext_off[t], (size_t)T.vtext_len[t]);
                     else
                         vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], T.view(t), info, n_samples);
@@ -736,6 +765,10 @@ struct TileRunner {
                 t1 = StageClock::now(); c.write += t1 - t0; t0 = t1;
                 if (T.res[t].called) {
                     fvcf->write(vcf_pre[next_called++]);
+                    if (!T.vcomp_off.empty()) {
+                        fvcf->write_blocks(T.vcomp + T.vcomp_off[t], (size_t)(T.vcomp_off[t + 1] - T.vcomp_off[t]));
+                        fvcf->write("\n", 1);
+                    }
                     t1 = StageClock::now(); c.write += t1 - t0; t0 = t1;
                 }
                 const int64_t done = ++sites_done;
@@ -1299,7 +1332,8 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
         os << "[profile] thread " << ithread << ": library calls on one-byte tiles " << tr.tiles_one_byte << ", on two-byte tiles "
            << tr.tiles_two_byte << "; tiles of text or records parsed on the device " << tr.tiles_dev_parsed << ", handed back to the CPU parser "
            << tr.tiles_cpu_parsed << "; with the called positions' statistics from the device " << tr.tiles_dev_stats
-           << ", with their sample columns from the device " << tr.tiles_dev_samples << "\n";
+           << ", with their sample columns from the device " << tr.tiles_dev_samples << ", with those columns deflated on the device "
+           << tr.tiles_dev_deflate << "\n";
         const StageClock &c = tr.clk, &d = tr.clk_dev, &o = tr.clk_out;
         os << "[profile] thread " << ithread << ": stage 1 read+inflate " << c.read << " s, parse " << c.parse << " s | stage 2 pack "
            << d.pack << " s, libbvc " << d.gpu << " s | stage 3 cvg lines " << o.cvg << " s, vcf lines " << o.vcf

@@ -119,6 +119,15 @@ VCF_PROTOTYPES = {
     "bvc_pileup_sample_text": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
 }
 VCF_EXPORTS = list(VCF_PROTOTYPES)
+# The third header, include/bvc_bgzf.h (byte ranges deflated into BGZF blocks on the device): the same again
+# (tests/test_bgzf_deflate_abi.py compares the two).
+BGZF_PROTOTYPES = {
+    "bvc_bgzf_deflate": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _u32]),
+    "bvc_pileup_sample_bgzf": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+}
+BGZF_EXPORTS = list(BGZF_PROTOTYPES)
+BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc_bgzf.h, BVC_BGZF_BLOCK_INPUT)
+BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
 EXPORTS = [name for name in PROTOTYPES if name not in OPTIONAL]   # what every build of the library exports
 
@@ -132,7 +141,7 @@ def library_path():
 def bind(cdll):
     """Gives every function of PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
     symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(VCF_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(VCF_PROTOTYPES.items()) + list(BGZF_PROTOTYPES.items()):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -166,6 +175,16 @@ def vcf_samples_need(n_samples, offsets, results):
     o = np.asarray(offsets, dtype=np.int64)
     called = np.asarray(results["called"]) != 0
     return int(sum(vcf_samples_slot(n_samples, n) for n in (o[1:] - o[:-1])[called]))
+
+
+def bgzf_blocks(length):
+    """bvc_bgzf_blocks (include/bvc_bgzf.h): the BGZF blocks a piece of `length` bytes becomes."""
+    return 0 if length <= 0 else (int(length) + BGZF_BLOCK_INPUT - 1) // BGZF_BLOCK_INPUT
+
+
+def bgzf_bound(length):
+    """bvc_bgzf_bound (include/bvc_bgzf.h): the most bytes the blocks of a piece of `length` bytes take."""
+    return 0 if length <= 0 else int(length) + 31 * bgzf_blocks(length)
 
 
 def vcf_bp_lut():
@@ -479,6 +498,41 @@ class Context:
         cap = len(text) if text_cap is None else int(text_cap)
         self._check(self._L.bvc_pileup_sample_text(self._h, int(n_samples), _np_ptr(text) if len(text) else None, cap, _np_ptr(off), _np_ptr(ln)))
         return text, off, ln[:n_positions]
+
+    def bgzf_deflate(self, data, piece_off, piece_len, comp=None, comp_cap=None):
+        """bvc_bgzf_deflate on host arrays: piece i = data[piece_off[i] : piece_off[i] + piece_len[i]] (uint8) as BGZF blocks.  comp: a uint8
+        array to write into (default: a new one of the bound); comp_cap: what to tell the library instead of its size.  Returns (comp,
+        comp_off [n + 1]): piece i's blocks are comp[comp_off[i] : comp_off[i + 1]]."""
+        d, o, ln = _as(data, np.uint8), _as(piece_off, np.int64), _as(piece_len, np.int64)
+        n = len(o)
+        assert ln.shape == (n,)
+        if comp is None:
+            comp = np.zeros(max(1, sum(bgzf_bound(x) for x in ln)), dtype=np.uint8)
+        cap = len(comp) if comp_cap is None else int(comp_cap)
+        off, = self._call(self._L.bvc_bgzf_deflate, False, (n, d if len(d) else None, o if n else None, ln if n else None, comp, cap),
+                          [(None, (n + 1,), np.dtype(np.int64))])
+        return comp, off
+
+    def bgzf_deflate_device(self, data_t, piece_off_t, piece_len_t, comp_t, comp_off_t=None, comp_cap=None):
+        """The same on device tensors (data_t / comp_t: uint8, any alignment; piece_off_t / piece_len_t / comp_off_t: int64).  The call
+        waits for the pieces' lengths (BvcError when comp_t is smaller than the sum of their bounds) and for its small block table to
+        have gone up; the blocks and comp_off are written asynchronously on the context's stream."""
+        import torch
+        n = piece_off_t.numel()
+        if comp_off_t is None:
+            comp_off_t = torch.empty(n + 1, dtype=torch.int64, device=comp_t.device)
+        cap = comp_t.numel() if comp_cap is None else int(comp_cap)
+        self._call(self._L.bvc_bgzf_deflate, True, (n, data_t, piece_off_t, piece_len_t, comp_t, cap, comp_off_t))
+        return comp_t, comp_off_t
+
+    def pileup_sample_bgzf(self, n_positions, n_samples, comp, comp_cap=None):
+        """bvc_pileup_sample_bgzf after a tile finished with sample_text=True: the called positions' sample columns as BGZF blocks into comp
+        (uint8 array).  Returns (comp, comp_off [T + 1], text_len [T])."""
+        off = np.zeros(n_positions + 1, dtype=np.int64)
+        ln = np.zeros(max(1, n_positions), dtype=np.int64)
+        cap = len(comp) if comp_cap is None else int(comp_cap)
+        self._check(self._L.bvc_pileup_sample_bgzf(self._h, int(n_samples), _np_ptr(comp) if len(comp) else None, cap, _np_ptr(off), _np_ptr(ln)))
+        return comp, off, ln[:n_positions]
 
     # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
     def pack_dense_device(self, bases_t, quals_t, packed_t=None):

@@ -103,6 +103,7 @@ def main():
                 n_vcf = sum(1 for l in gzip.decompress(open(out + ".vcf.gz", "rb").read()).split(b"\n") if l and not l.startswith(b"#"))
                 import re
                 loops = [float(m.group(1)) for m in (re.search(r"position loop ([0-9.e+-]+) s", l) for l in prof) if m]
+                cpu = [float(m.group(1)) for m in (re.search(r"process CPU time ([0-9.e+-]+) s", l) for l in prof) if m]
                 body = [gzip.decompress(open(out + k, "rb").read()) for k in (".cvg.gz", ".vcf.gz")]
                 variant_outputs.setdefault(fmt, body)
                 assert variant_outputs[fmt] == body, f"variant {var} writes other outputs than the first run"
@@ -110,6 +111,7 @@ def main():
                                   "entries": entries, "batch_files_MB": round(size / 1e6, 1), "generate_s": round(gen_s, 2),
                                   "seconds": round(dt, 3), "positions_per_s": round(npos / dt, 1),
                                   "entries_per_s": round(entries / dt), "cvg_lines": n_cvg, "vcf_lines": n_vcf,
+                                  "process_cpu_s": cpu[-1] if cpu else None, "vcf_gz_bytes": os.path.getsize(out + ".vcf.gz"),
                                   "profile": prof if thread <= 4 else prof[-1:] + prof[:2]}), flush=True)
             for k in (".cvg.gz", ".vcf.gz"):
                 os.replace(out + k, os.path.join(d, f"{fmt}{k}"))
