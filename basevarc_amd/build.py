@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbvc.so")
 SOURCES = ["bvc_context.hip", "bvc_lrt.hip", "bvc_pileup.hip", "bvc_counts.hip", "bvc_stats.hip", "bvc_vcf.hip", "bvc_bgzf.hip", "hist_kernel.hip", "counts_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip", "site_stats_kernel.hip", "vcf_samples_kernel.hip", "bgzf_deflate_kernel.hip"]
-DEPS = ["bvc_ctx.h", "bvc_device.h", "bvc_internal.h", "crc32_device.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h"), os.path.join("..", "..", "include", "bvc_vcf.h"), os.path.join("..", "..", "include", "bvc_bgzf.h")]
+DEPS = ["bvc_ctx.h", "bvc_device.h", "bvc_internal.h", "crc32_device.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h")]
 
 
 def code_sha16(path=None):

@@ -1,4 +1,4 @@
-// bgzf_deflate_kernel.hip -- DEFLATE (RFC 1951) of byte ranges in device memory into finished BGZF blocks (include/bvc_bgzf.h): what
+// bgzf_deflate_kernel.hip -- DEFLATE (RFC 1951) of byte ranges in device memory into finished BGZF blocks (include/bvc.h): what
 // the host program's BgzfWriter does with zlib, done where the VCF sample columns are made (vcf_samples_kernel.hip).
 //
 // A block is at most 65280 input bytes and static: every position can look for its match at once.  One WORKGROUP of 1024 threads per

@@ -1,7 +1,5 @@
-// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip), and
-// bvc_pileup_sample_bgzf, which hands a tile's sample columns (vcf_samples_kernel.hip) to the same kernels where they are made.
-#include <cstdio>
-
+// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip).
+// bvc_pileup_sample_bgzf (bvc_pileup.hip) hands a tile's sample columns to the same kernels where they are made.
 #include "bvc_ctx.h"
 
 int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_data, const int64_t *d_off, const int64_t *d_len,
@@ -22,11 +20,19 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
     return BVC_OK;
 }
 
-static int fail_comp_cap(bvc_ctx *ctx, int64_t need, int64_t comp_cap)
+int bgzf_blocks_down(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_comp, const int64_t *d_comp_off, uint8_t *comp,
+                     int64_t *comp_off)
 {
-    char msg[160];
-    std::snprintf(msg, sizeof msg, "comp_cap is %lld bytes, the bounds of the pieces need %lld", (long long)comp_cap, (long long)need);
-    return fail(ctx, BVC_ERR_ARG, msg);
+    BVC_HIP_D(ctx, io.d2h(comp_off, d_comp_off, ((size_t)n_pieces + 1) * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    // the second wait: only the packed bytes come down, and how many they are was not known before
+    const int64_t packed = comp_off[n_pieces];
+    if (packed > 0) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
+        BVC_HIP_D(ctx, wait_stream(ctx));
+    }
+    return BVC_OK;
 }
 
 // The sum of the pieces' lengths and of their bounds; false where an offset or a length is negative.
@@ -66,12 +72,12 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
         io.deliver();
         if (!sum_pieces(n_pieces, off.data(), len.data(), &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
         if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
-        if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
+        if (need > comp_cap) return fail_cap(ctx, "comp_cap", comp_cap, "the bounds of the pieces", need);
         return bgzf_deflate_device(ctx, io, n_pieces, data, piece_off, piece_len, len.data(), comp, comp_cap, comp_off, true);
     }
     if (!sum_pieces(n_pieces, piece_off, piece_len, &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
     if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
-    if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
+    if (need > comp_cap) return fail_cap(ctx, "comp_cap", comp_cap, "the bounds of the pieces", need);
     if (n_pieces == 0) { comp_off[0] = 0; return BVC_OK; }
     uint8_t *d_data, *d_comp; int64_t *d_off, *d_len, *d_coff;
     int rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
@@ -101,62 +107,7 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
     BVC_HIP_D(ctx, io.h2d(d_len, piece_len, np * 8));
     rc = bgzf_deflate_device(ctx, io, n_pieces, d_data, d_off, d_len, piece_len, d_comp, need, d_coff, false);
     if (rc != BVC_OK) return rc;
-    BVC_HIP_D(ctx, io.d2h(comp_off, d_coff, (np + 1) * 8));
-    BVC_HIP_D(ctx, wait_stream(ctx));
-    io.deliver();
-    // the second wait: only the packed bytes come down, and how many they are was not known before
-    const int64_t packed = comp_off[n_pieces];
-    if (packed > 0) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
-        BVC_HIP_D(ctx, wait_stream(ctx));
-    }
-    return BVC_OK;
-}
-
-int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len)
-{
-    if (!ctx) return BVC_ERR_ARG;
-    const int64_t need_text = pileup_sample_text_need(ctx, n_samples, "bvc_pileup_sample_bgzf");
-    if (need_text < 0) return BVC_ERR_ARG;
-    const PileupState::Tile &tile = ctx->pile.tile;
-    const int64_t T = tile.P.n_pos;
-    if (comp_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or comp_cap < 0");
-    if (!comp_off || (T > 0 && !text_len) || (comp_cap > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    // a position's text is at most its slot: the blocks' bound from what the finish call delivered, before anything is launched
-    std::vector<int64_t> upper((size_t)T);
-    int64_t need = 0;
-    for (int64_t t = 0; t < T; ++t) {
-        upper[(size_t)t] = tile.h_called[(size_t)t] ? bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]) : 0;
-        need += bvc_bgzf_bound(upper[(size_t)t]);
-    }
-    if (need > comp_cap) return fail_comp_cap(ctx, need, comp_cap);
-    if (T == 0) { comp_off[0] = 0; return BVC_OK; }
-    int64_t *d_toff, *d_tlen; char *d_text;
-    int rc = pileup_sample_text_device(ctx, n_samples, need_text, &d_toff, &d_tlen, &d_text);
-    if (rc != BVC_OK) return rc;
-    uint8_t *d_comp; int64_t *d_coff;
-    rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
-        d_comp = L.take<uint8_t>((size_t)need);
-        d_coff = L.take<int64_t>((size_t)T + 1);
-    });
-    if (rc != BVC_OK) return rc;
-    PinIO io(ctx);
-    rc = io.reserve(((size_t)T + 1) * 8 + 64, (2 * (size_t)T + 1) * 8 + 1024);
-    if (rc != BVC_OK) return rc;
-    // position t's piece: its text_len bytes at text_off[t] of the text
-    rc = bgzf_deflate_device(ctx, io, T, reinterpret_cast<const uint8_t *>(d_text), d_toff, d_tlen, upper.data(), d_comp, need, d_coff, false);
-    if (rc != BVC_OK) return rc;
-    BVC_HIP_D(ctx, io.d2h(comp_off, d_coff, ((size_t)T + 1) * 8));
-    BVC_HIP_D(ctx, io.d2h(text_len, d_tlen, (size_t)T * 8));
-    BVC_HIP_D(ctx, wait_stream(ctx));
-    io.deliver();
-    // the wait its twin does not have: the packed bytes, straight into the caller's memory (a DMA where that is bvc_host_alloc memory)
-    const int64_t packed = comp_off[T];
-    if (packed > 0) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
-        BVC_HIP_D(ctx, wait_stream(ctx));
-    }
-    return BVC_OK;
+    return bgzf_blocks_down(ctx, io, n_pieces, d_comp, d_coff, comp, comp_off);
 }
 
 }  // extern "C"

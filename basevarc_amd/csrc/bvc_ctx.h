@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include <array>
+#include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -121,6 +122,14 @@ inline int fail(bvc_ctx *ctx, int code, const char *what, hipError_t e = hipSucc
         if (e != hipSuccess) { ctx->err += ": "; ctx->err += hipGetErrorString(e); }
     }
     return code;
+}
+
+// BVC_ERR_ARG for an output buffer that is too small: "<name> is <cap> bytes, <what> need <need>".
+inline int fail_cap(bvc_ctx *ctx, const char *name, int64_t cap, const char *what, int64_t need)
+{
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "%s is %lld bytes, %s need %lld", name, (long long)cap, what, (long long)need);
+    return fail(ctx, BVC_ERR_ARG, msg);
 }
 
 // Waits for the context's stream without spinning: the thread sleeps until the event behind everything enqueued so far fires.
@@ -303,11 +312,11 @@ int run_csr_labels_device(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets,
 // returns without a wait of its own behind this -- the block table has left the page-locked buffer before the kernels are launched.
 int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_data, const int64_t *d_off, const int64_t *d_len,
                         const int64_t *upper, uint8_t *d_comp, int64_t comp_cap, int64_t *d_comp_off, bool wait_for_upload);
-// bvc_pileup.hip: what bvc_pileup_sample_text and bvc_pileup_sample_bgzf share.  The sum of the called positions' slots of the tile that
-// bvc_pileup_finish_called_text left (-1 with the error set: there is none), and the text formatted into the context's device memory, on
-// the stream: d_toff [T + 1], d_tlen [T], d_text [need].
-int64_t pileup_sample_text_need(bvc_ctx *ctx, int64_t n_samples, const char *caller);
-int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int64_t **d_toff, int64_t **d_tlen, char **d_text);
+// The tail of a call that delivers blocks to the host: comp_off [n_pieces + 1] comes down through io and is waited for and delivered (with
+// whatever else io has coming down), then only the comp_off[n_pieces] packed bytes come straight into the caller's memory (a DMA where
+// that is bvc_host_alloc memory), with a second wait.  io: (n_pieces + 1) * 8 + 64 bytes reserved coming down.
+int bgzf_blocks_down(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_comp, const int64_t *d_comp_off, uint8_t *comp,
+                     int64_t *comp_off);
 
 // bvc_vcf.hip: the device copy of bvc_vcf_bp_lut in ctx->d_vcf_lut, made at the context's first use of it
 int vcf_lut_device(bvc_ctx *ctx);

@@ -6,8 +6,6 @@
 #include <vector>
 
 #include "../../include/bvc.h"
-#include "../../include/bvc_vcf.h"
-#include "../../include/bvc_bgzf.h"
 
 namespace bvc {
 
@@ -244,7 +242,7 @@ hipError_t launch_vcf_samples(hipStream_t stream, int64_t n_sites, const int64_t
                               const int32_t *samples, const int8_t *ref_base, const bvc_site_result *results, int64_t n_samples,
                               const int64_t *text_off, const VcfSamplesScratch &s, const char *bp_lut, char *text, int64_t text_cap);
 
-// bgzf_deflate_kernel.hip: pieces of device memory deflated into BGZF blocks (include/bvc_bgzf.h, bvc_bgzf_deflate).  Piece i holds the
+// bgzf_deflate_kernel.hip: pieces of device memory deflated into BGZF blocks (include/bvc.h, bvc_bgzf_deflate).  Piece i holds the
 // blocks first_block[i] .. first_block[i + 1] of the call (first_block [n_pieces + 1] in the scratch, filled by the caller: from the
 // pieces' lengths or from upper bounds of them -- a block behind a piece's real length is empty and takes no byte); comp_off
 // [n_pieces + 1] and the packed blocks are written on the stream.  Nothing is packed when the blocks do not fit comp_cap.

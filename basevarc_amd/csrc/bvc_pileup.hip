@@ -1,7 +1,5 @@
 // bvc_pileup.hip -- the producer: BGZF blocks inflated on the device, and temp-batch tiles (text, binary records, or BGZF blocks of
 // text) -> columns -> records between a begin call and a finish call (pileup_kernel.hip, inflate_kernel.hip).
-#include <cstdio>
-
 #include "bvc_ctx.h"
 
 extern "C" {
@@ -315,32 +313,44 @@ int bvc_pileup_text(bvc_ctx *ctx, char *text, int64_t text_cap, int64_t *text_by
     return BVC_OK;
 }
 
-// bvc_pileup_finish (called_off = null: the entries of every position) and bvc_pileup_finish_called (the entries of the called
-// positions only, compacted on the device; called_cap = room in entries / samples); stats (called_off given): the called positions'
-// rank sums and strand counts too (bvc_pileup_finish_called_stats), computed where the entries lie and delivered with the records;
-// for_text (called_off null, stats given): no entries or samples come down at all (bvc_pileup_finish_called_text) -- the tile's columns
-// and records stay on the device for bvc_pileup_sample_text
-static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
-                              const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
-                              int64_t *entry_off, int32_t *tally, int64_t *called_off, int64_t called_cap, bvc_pileup_entry *entries,
-                              int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
-                              bvc_group_result *grp_results, bvc_site_stats *stats, bool for_text = false)
+// What a finish call delivers besides entry_off and tally, and which of the forms it is.  All (bvc_pileup_finish): the entries of every
+// position.  Called (bvc_pileup_finish_called[_stats]): the entries of the called positions only, compacted on the device into called_off
+// / entries / samples (called_cap = room in the two).  CalledText (bvc_pileup_finish_called_text): no entries or samples come down at all
+// -- the tile's columns and records stay on the device for bvc_pileup_sample_text / _bgzf.  stats (Called: optional, CalledText:
+// required): the called positions' rank sums and strand counts too, computed where the entries lie and delivered with the records.
+enum class Finish { All, Called, CalledText };
+struct FinishOut {
+    int64_t *called_off = nullptr;
+    int64_t called_cap = 0;
+    bvc_pileup_entry *entries = nullptr;
+    int32_t *samples = nullptr;
+    bvc_pileup_indel *indels = nullptr;
+    char *indel_text = nullptr;
+    bvc_site_result *results = nullptr;
+    bvc_group_result *grp_results = nullptr;
+    bvc_site_stats *stats = nullptr;
+};
+
+static int pileup_finish_impl(bvc_ctx *ctx, Finish mode, const int8_t *ref_base, double min_af, const uint8_t carry_in[5],
+                              uint8_t carry_out[5], const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                              int64_t *entry_off, int32_t *tally, const FinishOut &out)
 {
     if (!ctx) return BVC_ERR_ARG;
     PileupState &pile = ctx->pile;
     PileupState::Tile &tile = pile.tile;
+    const bool called_only = mode == Finish::Called, for_text = mode == Finish::CalledText;
+    const bvc_site_stats *const stats = out.stats;
     if (!tile.begun) return fail(ctx, BVC_ERR_ARG, "bvc_pileup_finish without a bvc_pileup_begin that returned BVC_OK");
-    if (tile.on_device_text && tile.indels > 0 && !indel_text) return fail(ctx, BVC_ERR_ARG, "indel_text is needed: the tile's text is on the device only");
+    if (tile.on_device_text && tile.indels > 0 && !out.indel_text) return fail(ctx, BVC_ERR_ARG, "indel_text is needed: the tile's text is on the device only");
     tile.begun = false;
     PileupTile &P = tile.P;
     const int64_t T = P.n_pos, n_e = tile.entries, n_o = tile.obs, n_i = tile.indels, n_it = tile.indel_bytes;
     if (!carry_in || !carry_out || !entry_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    if (T > 0 && (!ref_base || !tally || !results)) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    const bool called_only = called_off != nullptr;
-    if ((n_e > 0 && !called_only && !for_text && (!entries || !samples)) || (n_i > 0 && !indels)) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    if (called_only && (called_cap < 0 || (called_cap > 0 && (!entries || !samples)))) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if (T > 0 && (!ref_base || !tally || !out.results)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if ((n_e > 0 && !called_only && !for_text && (!out.entries || !out.samples)) || (n_i > 0 && !out.indels)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    if (called_only && (out.called_cap < 0 || (out.called_cap > 0 && (!out.entries || !out.samples)))) return fail(ctx, BVC_ERR_ARG, "null pointer");
     if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
-    if (n_groups > 0 && (!grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
+    if (n_groups > 0 && (!out.grp_results || n_samples < 0 || (n_samples > 0 && !group_of_sample))) return fail(ctx, BVC_ERR_ARG, "null group pointer");
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     int8_t *d_ref; bvc_site_result *d_res; uint8_t *d_g, *d_itext; bvc_group_result *d_gres; int64_t *d_called_off; bvc_site_stats *d_stats;
     int rc = carve(ctx, pile.out, 256, [&](Layout &L) {
@@ -354,7 +364,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         d_res = L.take<bvc_site_result>((size_t)T);
         d_g = L.take<uint8_t>((size_t)(n_groups ? n_samples : 0), 16);
         d_gres = L.take<bvc_group_result>((size_t)T * (size_t)n_groups);
-        d_itext = L.take<uint8_t>((size_t)(indel_text ? n_it : 0), 16);
+        d_itext = L.take<uint8_t>((size_t)(out.indel_text ? n_it : 0), 16);
         d_called_off = L.take<int64_t>(called_only ? (size_t)(T + 1) : 0);
         d_stats = L.take<bvc_site_stats>(stats ? (size_t)T : 0);
     });
@@ -383,34 +393,34 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         if (rc == BVC_OK) rc = join_side(ctx);
         if (rc != BVC_OK) return drain_on_error(ctx, rc);
         if (stats) BVC_HIP_D(ctx, launch_site_stats(ctx->ls, ctx->stream, T, P.entry_off, P.entries, d_ref, d_res, d_stats));
-        BVC_HIP_D(ctx, io.d2h(results, d_res, (size_t)T * sizeof(bvc_site_result)));
-        if (stats) BVC_HIP_D(ctx, io.d2h(stats, d_stats, (size_t)T * sizeof(bvc_site_stats)));
+        BVC_HIP_D(ctx, io.d2h(out.results, d_res, (size_t)T * sizeof(bvc_site_result)));
+        if (stats) BVC_HIP_D(ctx, io.d2h(out.stats, d_stats, (size_t)T * sizeof(bvc_site_stats)));
         if (n_groups > 0)
-            BVC_HIP_D(ctx, io.d2h(grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
+            BVC_HIP_D(ctx, io.d2h(out.grp_results, d_gres, (size_t)T * (size_t)n_groups * sizeof(bvc_group_result)));
         BVC_HIP_D(ctx, io.d2h(tally, P.tally, (size_t)T * 32 * 4));
         if (n_e && !called_only && !for_text) {
-            BVC_HIP_D(ctx, io.d2h(entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
-            BVC_HIP_D(ctx, io.d2h(samples, P.samples, (size_t)n_e * 4));
+            BVC_HIP_D(ctx, io.d2h(out.entries, P.entries, (size_t)n_e * sizeof(bvc_pileup_entry)));
+            BVC_HIP_D(ctx, io.d2h(out.samples, P.samples, (size_t)n_e * 4));
         }
         if (called_only) {
             BVC_HIP_D(ctx, launch_called_scan(ctx->stream, P, d_res, d_called_off));
-            BVC_HIP_D(ctx, io.d2h(called_off, d_called_off, (size_t)(T + 1) * 8));
+            BVC_HIP_D(ctx, io.d2h(out.called_off, d_called_off, (size_t)(T + 1) * 8));
         }
-        if (n_i && indel_text) {
+        if (n_i && out.indel_text) {
             BVC_HIP_D(ctx, launch_indel_text(ctx->stream, P, d_itext, (uint32_t)n_it, P.status + 5));
-            if (n_it) BVC_HIP_D(ctx, io.d2h(indel_text, d_itext, (size_t)n_it));
+            if (n_it) BVC_HIP_D(ctx, io.d2h(out.indel_text, d_itext, (size_t)n_it));
         }
-        if (n_i) BVC_HIP_D(ctx, io.d2h(indels, P.indels, (size_t)n_i * sizeof(bvc_pileup_indel)));
+        if (n_i) BVC_HIP_D(ctx, io.d2h(out.indels, P.indels, (size_t)n_i * sizeof(bvc_pileup_indel)));
         if ((int64_t)P.n_pos * P.n_batches > 0) BVC_HIP_D(ctx, io.d2h(&cout, P.status + 3, 4));
     }
     BVC_HIP_D(ctx, io.d2h(entry_off, P.entry_off, (size_t)(T + 1) * 8));
     BVC_HIP_D(ctx, wait_stream(ctx));
     io.deliver();
-    if (called_only && T == 0) called_off[0] = 0;
-    if (called_only && T > 0 && called_off[T] > 0) {
+    if (called_only && T == 0) out.called_off[0] = 0;
+    if (called_only && T > 0 && out.called_off[T] > 0) {
         // the second trip: the called positions' entries, gathered on the device (typically a few per cent of the tile's)
-        const int64_t n_c = called_off[T];
-        if (n_c > called_cap) return fail(ctx, BVC_ERR_ARG, "called_cap is smaller than the entries of the called positions (n_entries of the begin call always suffices)");
+        const int64_t n_c = out.called_off[T];
+        if (n_c > out.called_cap) return fail(ctx, BVC_ERR_ARG, "called_cap is smaller than the entries of the called positions (n_entries of the begin call always suffices)");
         bvc_pileup_entry *d_ce; int32_t *d_cs;
         rc = carve(ctx, pile.called, 0, [&](Layout &L) {
             d_ce = L.take<bvc_pileup_entry>((size_t)n_c);
@@ -421,8 +431,8 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         rc = io.reserve(0, (size_t)n_c * (sizeof(bvc_pileup_entry) + 4) + 4096);
         if (rc != BVC_OK) return rc;
         BVC_HIP_D(ctx, launch_called_gather(ctx->stream, P, d_called_off, d_ce, d_cs));
-        BVC_HIP_D(ctx, io.d2h(entries, d_ce, (size_t)n_c * sizeof(bvc_pileup_entry)));
-        BVC_HIP_D(ctx, io.d2h(samples, d_cs, (size_t)n_c * 4));
+        BVC_HIP_D(ctx, io.d2h(out.entries, d_ce, (size_t)n_c * sizeof(bvc_pileup_entry)));
+        BVC_HIP_D(ctx, io.d2h(out.samples, d_cs, (size_t)n_c * 4));
         BVC_HIP_D(ctx, wait_stream(ctx));
         io.deliver();
     }
@@ -432,7 +442,7 @@ static int pileup_finish_impl(bvc_ctx *ctx, const int8_t *ref_base, double min_a
         tile.d_ref = d_ref; tile.d_res = d_res;
         tile.h_entry_off.assign(entry_off, entry_off + T + 1);
         tile.h_called.resize((size_t)T);
-        for (int64_t t = 0; t < T; ++t) tile.h_called[(size_t)t] = results[t].called;
+        for (int64_t t = 0; t < T; ++t) tile.h_called[(size_t)t] = out.results[t].called;
         tile.text_ready = true;
     }
     return BVC_OK;
@@ -443,8 +453,10 @@ int bvc_pileup_finish(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const
                       int64_t *entry_off, int32_t *tally, bvc_pileup_entry *entries, int32_t *samples,
                       bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results, bvc_group_result *grp_results)
 {
-    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, nullptr, 0,
-                              entries, samples, indels, indel_text, results, grp_results, nullptr);
+    FinishOut out;
+    out.entries = entries; out.samples = samples; out.indels = indels; out.indel_text = indel_text;
+    out.results = results; out.grp_results = grp_results;
+    return pileup_finish_impl(ctx, Finish::All, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, out);
 }
 
 int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
@@ -454,8 +466,10 @@ int bvc_pileup_finish_called(bvc_ctx *ctx, const int8_t *ref_base, double min_af
                              bvc_group_result *grp_results)
 {
     if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
-                              called_cap, entries, samples, indels, indel_text, results, grp_results, nullptr);
+    FinishOut out;
+    out.called_off = called_off; out.called_cap = called_cap; out.entries = entries; out.samples = samples;
+    out.indels = indels; out.indel_text = indel_text; out.results = results; out.grp_results = grp_results;
+    return pileup_finish_impl(ctx, Finish::Called, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, out);
 }
 
 int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
@@ -465,8 +479,10 @@ int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double 
                                    bvc_group_result *grp_results, bvc_site_stats *stats)
 {
     if (ctx && !called_off) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, called_off,
-                              called_cap, entries, samples, indels, indel_text, results, grp_results, stats);
+    FinishOut out;
+    out.called_off = called_off; out.called_cap = called_cap; out.entries = entries; out.samples = samples;
+    out.indels = indels; out.indel_text = indel_text; out.results = results; out.grp_results = grp_results; out.stats = stats;
+    return pileup_finish_impl(ctx, Finish::Called, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, out);
 }
 
 int bvc_pileup_finish_called_text(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
@@ -475,57 +491,14 @@ int bvc_pileup_finish_called_text(bvc_ctx *ctx, const int8_t *ref_base, double m
                                   bvc_site_result *results, bvc_group_result *grp_results, bvc_site_stats *stats)
 {
     if (ctx && !stats) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    return pileup_finish_impl(ctx, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, nullptr, 0,
-                              nullptr, nullptr, indels, indel_text, results, grp_results, stats, true);
+    FinishOut out;
+    out.indels = indels; out.indel_text = indel_text; out.results = results; out.grp_results = grp_results; out.stats = stats;
+    return pileup_finish_impl(ctx, Finish::CalledText, ref_base, min_af, carry_in, carry_out, group_of_sample, n_samples, n_groups, entry_off, tally, out);
 }
 
-int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len)
-{
-    if (!ctx) return BVC_ERR_ARG;
-    const int64_t need = pileup_sample_text_need(ctx, n_samples, "bvc_pileup_sample_text");
-    if (need < 0) return BVC_ERR_ARG;
-    const int64_t T = ctx->pile.tile.P.n_pos;
-    if (text_cap < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0");
-    if (!text_off || (T > 0 && !text_len) || (text_cap > 0 && !text)) return fail(ctx, BVC_ERR_ARG, "null pointer");
-    // the sum of the slots from what the finish call delivered: a buffer that is too small costs no launch and leaves the tile as it is
-    if (need > text_cap) {
-        char msg[160];
-        std::snprintf(msg, sizeof msg, "text_cap is %lld bytes, the called positions' slots need %lld", (long long)text_cap, (long long)need);
-        return fail(ctx, BVC_ERR_ARG, msg);
-    }
-    if (T == 0) { text_off[0] = 0; return BVC_OK; }
-    int64_t *d_toff, *d_tlen; char *d_text;
-    int rc = pileup_sample_text_device(ctx, n_samples, need, &d_toff, &d_tlen, &d_text);
-    if (rc != BVC_OK) return rc;
-    PinIO io(ctx);
-    rc = io.reserve(0, (2 * (size_t)T + 1) * 8 + 1024);
-    if (rc != BVC_OK) return rc;
-    // (straight into the caller's memory: a DMA where that is bvc_host_alloc memory)
-    if (need) BVC_HIP_D(ctx, hipMemcpyAsync(text, d_text, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(ctx, io.d2h(text_off, d_toff, ((size_t)T + 1) * 8));
-    BVC_HIP_D(ctx, io.d2h(text_len, d_tlen, (size_t)T * 8));
-    BVC_HIP_D(ctx, wait_stream(ctx));
-    io.deliver();
-    return BVC_OK;
-}
-
-}  // extern "C"
-
-int64_t pileup_sample_text_need(bvc_ctx *ctx, int64_t n_samples, const char *caller)
-{
-    const PileupState::Tile &tile = ctx->pile.tile;
-    if (!tile.text_ready) {
-        ctx->err = std::string(caller) + " without the tile of a bvc_pileup_finish_called_text";
-        return -1;
-    }
-    if (n_samples < 0) { (void)fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0"); return -1; }
-    int64_t need = 0;
-    for (int64_t t = 0; t < tile.P.n_pos; ++t)
-        if (tile.h_called[(size_t)t]) need += bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]);
-    return need;
-}
-
-int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int64_t **d_toff, int64_t **d_tlen, char **d_text)
+// The called positions' sample columns of the tile that bvc_pileup_finish_called_text left, formatted into the context's device memory
+// on the stream: d_toff [T + 1], d_tlen [T], d_text [need] (need = the sum of their slots).
+static int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int64_t **d_toff, int64_t **d_tlen, char **d_text)
 {
     PileupState &pile = ctx->pile;
     const PileupState::Tile &tile = pile.tile;
@@ -548,3 +521,69 @@ int pileup_sample_text_device(bvc_ctx *ctx, int64_t n_samples, int64_t need, int
                                       ctx->d_vcf_lut.p, *d_text, need));
     return BVC_OK;
 }
+
+// bvc_pileup_sample_text (deflate = false: out / cap / off are text / text_cap / text_off) and bvc_pileup_sample_bgzf (deflate = true:
+// comp / comp_cap / comp_off).  Both format the text on the device; the first brings it down with its offsets and lengths (one wait),
+// the second deflates it there and brings down the offsets and lengths, then the packed blocks (two waits).
+static int pileup_sample_impl(bvc_ctx *ctx, bool deflate, int64_t n_samples, void *out, int64_t cap, int64_t *off, int64_t *text_len)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    const PileupState::Tile &tile = ctx->pile.tile;
+    if (!tile.text_ready)
+        return fail(ctx, BVC_ERR_ARG, deflate ? "bvc_pileup_sample_bgzf without the tile of a bvc_pileup_finish_called_text"
+                                              : "bvc_pileup_sample_text without the tile of a bvc_pileup_finish_called_text");
+    if (n_samples < 0) return fail(ctx, BVC_ERR_ARG, "n_samples < 0 or text_cap < 0");
+    if (cap < 0) return fail(ctx, BVC_ERR_ARG, deflate ? "n_samples < 0 or comp_cap < 0" : "n_samples < 0 or text_cap < 0");
+    const int64_t T = tile.P.n_pos;
+    if (!off || (T > 0 && !text_len) || (cap > 0 && !out)) return fail(ctx, BVC_ERR_ARG, "null pointer");
+    // the needs from what the finish call delivered -- the sum of the called positions' slots, and of the bounds of their blocks (a
+    // position's text is at most its slot): a buffer that is too small costs no launch and leaves the tile as it is
+    std::vector<int64_t> slot((size_t)T);
+    int64_t need_text = 0, need_comp = 0;
+    for (int64_t t = 0; t < T; ++t) {
+        slot[(size_t)t] = tile.h_called[(size_t)t] ? bvc_vcf_samples_slot(n_samples, tile.h_entry_off[(size_t)t + 1] - tile.h_entry_off[(size_t)t]) : 0;
+        need_text += slot[(size_t)t];
+        need_comp += bvc_bgzf_bound(slot[(size_t)t]);
+    }
+    if (deflate && need_comp > cap) return fail_cap(ctx, "comp_cap", cap, "the bounds of the pieces", need_comp);
+    if (!deflate && need_text > cap) return fail_cap(ctx, "text_cap", cap, "the called positions' slots", need_text);
+    if (T == 0) { off[0] = 0; return BVC_OK; }
+    int64_t *d_toff, *d_tlen; char *d_text;
+    int rc = pileup_sample_text_device(ctx, n_samples, need_text, &d_toff, &d_tlen, &d_text);
+    if (rc != BVC_OK) return rc;
+    uint8_t *d_comp = nullptr; int64_t *d_coff = nullptr;
+    if (deflate) {
+        rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
+            d_comp = L.take<uint8_t>((size_t)need_comp);
+            d_coff = L.take<int64_t>((size_t)T + 1);
+        });
+        if (rc != BVC_OK) return rc;
+    }
+    PinIO io(ctx);
+    rc = io.reserve(deflate ? ((size_t)T + 1) * 8 + 64 : 0, (2 * (size_t)T + 1) * 8 + 1024);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, io.d2h(text_len, d_tlen, (size_t)T * 8));
+    if (deflate) {
+        // position t's piece: its text_len bytes at text_off[t] of the text
+        rc = bgzf_deflate_device(ctx, io, T, reinterpret_cast<const uint8_t *>(d_text), d_toff, d_tlen, slot.data(), d_comp, need_comp, d_coff, false);
+        return rc == BVC_OK ? bgzf_blocks_down(ctx, io, T, d_comp, d_coff, static_cast<uint8_t *>(out), off) : rc;
+    }
+    // (straight into the caller's memory: a DMA where that is bvc_host_alloc memory)
+    if (need_text) BVC_HIP_D(ctx, hipMemcpyAsync(out, d_text, (size_t)need_text, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, io.d2h(off, d_toff, ((size_t)T + 1) * 8));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    return BVC_OK;
+}
+
+int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len)
+{
+    return pileup_sample_impl(ctx, false, n_samples, text, text_cap, text_off, text_len);
+}
+
+int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len)
+{
+    return pileup_sample_impl(ctx, true, n_samples, comp, comp_cap, comp_off, text_len);
+}
+
+}  // extern "C"

@@ -22,13 +22,6 @@ int vcf_lut_device(bvc_ctx *ctx)
     return BVC_OK;
 }
 
-static int fail_text_cap(bvc_ctx *ctx, int64_t need, int64_t text_cap)
-{
-    char msg[160];
-    std::snprintf(msg, sizeof msg, "text_cap is %lld bytes, the called sites' slots need %lld", (long long)text_cap, (long long)need);
-    return fail(ctx, BVC_ERR_ARG, msg);
-}
-
 extern "C" {
 
 // The BP sub-field of a covered sample, "d.dddddd" = 1 - 10^(-qual / 10) as %.6f, for every 8-bit quality: the expression and the
@@ -71,7 +64,7 @@ int bvc_vcf_samples_csr(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, c
         BVC_HIP_D(ctx, io.d2h(&need, scr.head + 1, 8));
         BVC_HIP_D(ctx, wait_stream(ctx));
         io.deliver();
-        if (need > text_cap) return fail_text_cap(ctx, need, text_cap);
+        if (need > text_cap) return fail_cap(ctx, "text_cap", text_cap, "the called sites' slots", need);
         BVC_HIP(ctx, launch_vcf_samples(ctx->stream, n_sites, offsets, entries, samples, ref_base, results, n_samples, text_off, scr,
                                         ctx->d_vcf_lut.p, text, text_cap));
         return BVC_OK;
@@ -84,7 +77,7 @@ int bvc_vcf_samples_csr(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, c
     int64_t need = 0;
     for (int64_t s = 0; s < n_sites; ++s)
         if (results[s].called) need += bvc_vcf_samples_slot(n_samples, offsets[s + 1] - offsets[s]);
-    if (need > text_cap) return fail_text_cap(ctx, need, text_cap);
+    if (need > text_cap) return fail_cap(ctx, "text_cap", text_cap, "the called sites' slots", need);
     rc = vcf_lut_device(ctx);
     if (rc != BVC_OK) return rc;
     int64_t *d_off, *d_toff, *d_tlen; bvc_pileup_entry *d_ent; int32_t *d_smp; int8_t *d_ref; bvc_site_result *d_res; char *d_text, *d_scr;

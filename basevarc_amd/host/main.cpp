@@ -40,7 +40,7 @@
 #include "bam.h"
 #include "bgzf.h"
 #include "pileup.h"
-#include "../../include/bvc_bgzf.h"
+#include "../../include/bvc.h"
 
 using namespace bvchost;
 
@@ -303,6 +303,48 @@ struct Window {
 // binary records (bvc_pileup_begin / bvc_pileup_begin_bin)
 enum class TileForm { Sites, Text, Records };
 
+// Bytes in page-locked memory of the library's (bvc_host_alloc), which go over the link from where they lie: a tile's compressed blocks
+// on their way up, gathered one after the other (append), or room for what the device sends down (reserve).
+struct PinnedBytes {
+    unsigned char *p = nullptr;
+    size_t n = 0, cap = 0;
+    PinnedBytes() = default;
+    PinnedBytes(const PinnedBytes &) = delete;
+    PinnedBytes &operator=(const PinnedBytes &) = delete;
+    ~PinnedBytes() { bvc_host_free(p); }
+    size_t size() const { return n; }
+    bool empty() const { return n == 0; }
+    unsigned char *data() { return p; }
+    void clear() { n = 0; }
+    // room for `need` bytes (and a quarter more where it has to grow); what was there is gone
+    void reserve(size_t need)
+    {
+        n = 0;
+        if (need <= cap) return;
+        bvc_host_free(p);
+        p = nullptr; cap = 0;
+        const size_t want = need + need / 4 + 4096;
+        p = static_cast<unsigned char *>(bvc_host_alloc(want));
+        if (!p) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
+        cap = want;
+    }
+    void append(const unsigned char *src, size_t len)
+    {
+        const size_t need = ((n + len + 3) & ~(size_t)3) + 16;
+        if (need > cap) {
+            const size_t want = std::max(need + need / 2, (size_t)1 << 20);
+            unsigned char *q = static_cast<unsigned char *>(bvc_host_alloc(want));
+            if (!q) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
+            if (n) std::memcpy(q, p, n);
+            bvc_host_free(p);
+            p = q; cap = want;
+        }
+        std::memcpy(p + n, src, len);
+        n += len;
+        while (n & 3) p[n++] = 0;                                // every payload from a 4-byte boundary
+    }
+};
+
 // One tile of positions on its way through a runner: parsed (stage 1), handed to libbvc (stage 2), written out (stage 3).
 struct Tile {
     TileForm form = TileForm::Sites;
@@ -336,19 +378,12 @@ struct Tile {
     std::vector<bvc_pileup_indel> indels;
     std::vector<bvc_site_stats> stats;   // per position, where the device computed them (empty: vcf_line tallies the entries itself)
     // the called positions' sample columns where the device formatted them (BVC_HOST_DEVICE_SAMPLES): position t's are vtext_len[t] bytes
-    // at vtext + vtext_off[t]; page-locked memory that grows on demand and lives as long as the tile.  vtext_len empty: vcf_line formats
-    char *vtext = nullptr;
-    size_t vtext_cap = 0;
+    // at vout + vtext_off[t]; page-locked memory that grows on demand and lives as long as the tile.  vtext_len empty: vcf_line formats
+    PinnedBytes vout;
     std::vector<int64_t> vtext_off, vtext_len;
-    // ... or deflated them too (BVC_HOST_DEVICE_DEFLATE): position t's BGZF blocks are vcomp[vcomp_off[t] .. vcomp_off[t + 1]), page-locked
-    // as vtext; vtext_len then says how long the text would have been and vtext_off stays empty
-    unsigned char *vcomp = nullptr;
-    size_t vcomp_cap = 0;
+    // ... or deflated them too (BVC_HOST_DEVICE_DEFLATE): position t's BGZF blocks are vout[vcomp_off[t] .. vcomp_off[t + 1]) instead;
+    // vtext_len then says how long the text would have been and vtext_off stays empty
     std::vector<int64_t> vcomp_off;
-    Tile() = default;
-    Tile(const Tile &) = delete;
-    Tile &operator=(const Tile &) = delete;
-    ~Tile() { bvc_host_free(vtext); bvc_host_free(vcomp); }
     bool handed_back = false;            // a line was not regular: the tile went through the CPU parser and its columns are in `sites`
     void reset()
     {
@@ -517,6 +552,15 @@ struct TileRunner {
         if (T.n_used) run_device(T);
     }
 
+    // One of the bvc_pileup_finish* calls: the arguments they all begin with, then `tail`, the call's own.
+    template <class Fn, class... Tail>
+    int finish_call(Fn fn, Tile &T, uint8_t carry_out[5], Tail... tail)
+    {
+        const int ng = groups ? (int)groups->names.size() : 0;
+        return fn(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
+                  ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(), tail...);
+    }
+
     // bvc_pileup_finish into the tile's arrays (after a begin that returned BVC_OK).  text_on_device: the indel tokens' text comes back
     // in T.text (the tile's own text never was on the host).
     void finish_tile(Tile &T, int64_t n_ent, int64_t n_ind, int64_t ind_bytes, bool text_on_device)
@@ -530,6 +574,8 @@ struct TileRunner {
         T.res.resize(T.n_pos);
         T.gres.resize(T.n_pos * (size_t)ng);
         if (text_on_device) T.text.resize((size_t)ind_bytes + 1);
+        char *const ind_text = text_on_device ? T.text.data() : nullptr;
+        bvc_group_result *const gres = ng ? T.gres.data() : nullptr;
         uint8_t carry_out[5];
         int rc;
         T.stats.clear();
@@ -538,10 +584,7 @@ struct TileRunner {
             // no entry comes back: the statistics with the records, then the called positions' sample columns as text
             T.called_off.assign(T.n_pos + 1, 0);
             T.stats.resize(T.n_pos);
-            rc = bvc_pileup_finish_called_text(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
-                                               ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(),
-                                               T.indels.data(), text_on_device ? T.text.data() : nullptr, T.res.data(),
-                                               ng ? T.gres.data() : nullptr, T.stats.data());
+            rc = finish_call(bvc_pileup_finish_called_text, T, carry_out, T.indels.data(), ind_text, T.res.data(), gres, T.stats.data());
             bvc_check(ctx, rc);
             const bool deflate = knob::device_deflate();
             int64_t need = 0;
@@ -550,43 +593,27 @@ struct TileRunner {
                     const int64_t slot = bvc_vcf_samples_slot(n_samples, T.entry_off[t + 1] - T.entry_off[t]);
                     need += deflate ? bvc_bgzf_bound(slot) : slot;
                 }
-            // (page-locked memory of the tile's, grown on demand: the text, or its blocks)
-            auto grow = [&](void **buf, size_t *cap) {
-                if ((size_t)need <= *cap) return;
-                bvc_host_free(*buf);
-                *buf = nullptr; *cap = 0;
-                const size_t want = (size_t)need + (size_t)need / 4 + 4096;
-                *buf = bvc_host_alloc(want);
-                if (!*buf) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
-                *cap = want;
-            };
+            T.vout.reserve((size_t)need);                                // the text, or its blocks
             T.vtext_len.resize(T.n_pos + 1);
             if (deflate) {
-                grow(reinterpret_cast<void **>(&T.vcomp), &T.vcomp_cap);
                 T.vcomp_off.resize(T.n_pos + 1);
-                rc = bvc_pileup_sample_bgzf(ctx, n_samples, T.vcomp, (int64_t)T.vcomp_cap, T.vcomp_off.data(), T.vtext_len.data());
+                rc = bvc_pileup_sample_bgzf(ctx, n_samples, T.vout.data(), (int64_t)T.vout.cap, T.vcomp_off.data(), T.vtext_len.data());
                 tiles_dev_deflate += 1;
             } else {
-                grow(reinterpret_cast<void **>(&T.vtext), &T.vtext_cap);
                 T.vtext_off.resize(T.n_pos + 1);
-                rc = bvc_pileup_sample_text(ctx, n_samples, T.vtext, (int64_t)T.vtext_cap, T.vtext_off.data(), T.vtext_len.data());
+                rc = bvc_pileup_sample_text(ctx, n_samples, reinterpret_cast<char *>(T.vout.data()), (int64_t)T.vout.cap, T.vtext_off.data(),
+                                            T.vtext_len.data());
             }
             T.vtext_len.resize(T.n_pos);
             tiles_dev_samples += 1;
         } else if (knob::called_only()) {
             T.called_off.resize(T.n_pos + 1);
             if (knob::device_stats()) T.stats.resize(T.n_pos);
-            rc = bvc_pileup_finish_called_stats(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
-                                                ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(),
-                                                T.called_off.data(), n_ent, T.ent.data(), T.samples.data(), T.indels.data(),
-                                                text_on_device ? T.text.data() : nullptr, T.res.data(), ng ? T.gres.data() : nullptr,
-                                                T.stats.empty() ? nullptr : T.stats.data());
+            rc = finish_call(bvc_pileup_finish_called_stats, T, carry_out, T.called_off.data(), n_ent, T.ent.data(), T.samples.data(),
+                             T.indels.data(), ind_text, T.res.data(), gres, T.stats.empty() ? nullptr : T.stats.data());
         } else {
             T.called_off.clear();
-            rc = bvc_pileup_finish(ctx, T.refs.data(), min_af, carry, carry_out, ng ? groups->of_sample.data() : nullptr,
-                                   ng ? (int64_t)groups->of_sample.size() : 0, ng, T.entry_off.data(), T.tally.data(), T.ent.data(),
-                                   T.samples.data(), T.indels.data(), text_on_device ? T.text.data() : nullptr, T.res.data(),
-                                   ng ? T.gres.data() : nullptr);
+            rc = finish_call(bvc_pileup_finish, T, carry_out, T.ent.data(), T.samples.data(), T.indels.data(), ind_text, T.res.data(), gres);
         }
         bvc_check(ctx, rc);
         std::memcpy(carry, carry_out, 5);
@@ -729,7 +756,7 @@ struct TileRunner {
                         vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, "", 0);
                         vcf_pre[k].pop_back();
                     } else if (!T.vtext_off.empty())
-                        vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, T.vtext + T.vtext_off[t], (size_t)T.vtext_len[t]);
+                        vcf_pre[k] = vcf_line(T.res[t], chr, T.pos[t], T.refs[t], T.stats[t], info, reinterpret_cast<const char *>(T.vout.data()) + T.vtext_off[t], (size_t)T.vtext_len[t]);
                     else
                         vcf_pre[k] = vcf_line(T.res[t], chr, T.refs[t], T.view(t), info, n_samples);
                 }
@@ -766,7 +793,7 @@ struct TileRunner {
                 if (T.res[t].called) {
                     fvcf->write(vcf_pre[next_called++]);
                     if (!T.vcomp_off.empty()) {
-                        fvcf->write_blocks(T.vcomp + T.vcomp_off[t], (size_t)(T.vcomp_off[t + 1] - T.vcomp_off[t]));
+                        fvcf->write_blocks(T.vout.data() + T.vcomp_off[t], (size_t)(T.vcomp_off[t + 1] - T.vcomp_off[t]));
                         fvcf->write("\n", 1);
                     }
                     t1 = StageClock::now(); c.write += t1 - t0; t0 = t1;
@@ -1031,32 +1058,6 @@ static void feed_staged_tiles(TileRunner &tr, const Window &w, BatchInputs &in, 
         ip += T;
     }
 }
-
-// the tile's compressed blocks, one after the other, in page-locked memory of the library's: they go over the link from here
-struct PinnedBytes {
-    unsigned char *p = nullptr;
-    size_t n = 0, cap = 0;
-    ~PinnedBytes() { bvc_host_free(p); }
-    size_t size() const { return n; }
-    bool empty() const { return n == 0; }
-    unsigned char *data() { return p; }
-    void clear() { n = 0; }
-    void append(const unsigned char *src, size_t len)
-    {
-        const size_t need = ((n + len + 3) & ~(size_t)3) + 16;
-        if (need > cap) {
-            const size_t want = std::max(need + need / 2, (size_t)1 << 20);
-            unsigned char *q = static_cast<unsigned char *>(bvc_host_alloc(want));
-            if (!q) throw std::runtime_error("ERROR: page-locked host memory is not to be had (bvc_host_alloc)");
-            if (n) std::memcpy(q, p, n);
-            bvc_host_free(p);
-            p = q; cap = want;
-        }
-        std::memcpy(p + n, src, len);
-        n += len;
-        while (n & 3) p[n++] = 0;                                // every payload from a 4-byte boundary
-    }
-};
 
 // The blocks of one bvc_pileup_begin_bgzf call, gathered and not yet sent.
 struct Staged {

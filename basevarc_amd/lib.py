@@ -107,26 +107,16 @@ PROTOTYPES = {
     "bvc_synth_dense": (_int, [_vp, C.c_uint64, _i64, _i64, _i64, _i64, _u32, _vp, _vp, _vp]),
     "bvc_set_tuning": (_int, [_vp, C.c_char_p, _int]),
     "bvc_stream_read_ms": (_int, [_vp, _vp, _i64, _int, C.POINTER(_dbl)]),
-    # not in the header: diagnostic builds of the library only export it (-DBVC_CHECK_LDS, csrc/bvc_device.h)
-    "bvc_debug_report": (_int, [_vp, C.POINTER(_u32), _int]),
-}
-# The second header, include/bvc_vcf.h (the VCF sample columns): the same kind of table, in that header's order
-# (tests/test_vcf_samples_abi.py compares the two), bound by bind() with the first.
-VCF_PROTOTYPES = {
     "bvc_vcf_bp_lut": (None, [_vp]),
     "bvc_vcf_samples_csr": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _u32]),
     "bvc_pileup_finish_called_text": (_int, [_vp, _vp, _dbl, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bvc_pileup_sample_text": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
-}
-VCF_EXPORTS = list(VCF_PROTOTYPES)
-# The third header, include/bvc_bgzf.h (byte ranges deflated into BGZF blocks on the device): the same again
-# (tests/test_bgzf_deflate_abi.py compares the two).
-BGZF_PROTOTYPES = {
     "bvc_bgzf_deflate": (_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _u32]),
     "bvc_pileup_sample_bgzf": (_int, [_vp, _i64, _vp, _i64, _vp, _vp]),
+    # not in the header: diagnostic builds of the library only export it (-DBVC_CHECK_LDS, csrc/bvc_device.h)
+    "bvc_debug_report": (_int, [_vp, C.POINTER(_u32), _int]),
 }
-BGZF_EXPORTS = list(BGZF_PROTOTYPES)
-BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc_bgzf.h, BVC_BGZF_BLOCK_INPUT)
+BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
 EXPORTS = [name for name in PROTOTYPES if name not in OPTIONAL]   # what every build of the library exports
@@ -141,7 +131,7 @@ def library_path():
 def bind(cdll):
     """Gives every function of PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
     symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(VCF_PROTOTYPES.items()) + list(BGZF_PROTOTYPES.items()):
+    for name, (restype, argtypes) in PROTOTYPES.items():
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -166,7 +156,7 @@ def load_library():
 
 
 def vcf_samples_slot(n_samples, n_entries):
-    """bvc_vcf_samples_slot (include/bvc_vcf.h): bytes of a called site's slot in the text of vcf_samples_csr / pileup_sample_text."""
+    """bvc_vcf_samples_slot (include/bvc.h): bytes of a called site's slot in the text of vcf_samples_csr / pileup_sample_text."""
     return (4 * int(n_samples) + 13 * int(n_entries) + 15) // 16 * 16
 
 
@@ -178,12 +168,12 @@ def vcf_samples_need(n_samples, offsets, results):
 
 
 def bgzf_blocks(length):
-    """bvc_bgzf_blocks (include/bvc_bgzf.h): the BGZF blocks a piece of `length` bytes becomes."""
+    """bvc_bgzf_blocks (include/bvc.h): the BGZF blocks a piece of `length` bytes becomes."""
     return 0 if length <= 0 else (int(length) + BGZF_BLOCK_INPUT - 1) // BGZF_BLOCK_INPUT
 
 
 def bgzf_bound(length):
-    """bvc_bgzf_bound (include/bvc_bgzf.h): the most bytes the blocks of a piece of `length` bytes take."""
+    """bvc_bgzf_bound (include/bvc.h): the most bytes the blocks of a piece of `length` bytes take."""
     return 0 if length <= 0 else int(length) + 31 * bgzf_blocks(length)
 
 
@@ -490,14 +480,18 @@ class Context:
                                                        text_off_t, text_len_t))
         return text_t, text_off_t, text_len_t
 
+    def _pileup_sample(self, fn, n_positions, n_samples, buf, cap):
+        """bvc_pileup_sample_text / bvc_pileup_sample_bgzf: (buf, its offsets [T + 1], text_len [T])."""
+        off = np.zeros(n_positions + 1, dtype=np.int64)
+        ln = np.zeros(max(1, n_positions), dtype=np.int64)
+        cap = len(buf) if cap is None else int(cap)
+        self._check(fn(self._h, int(n_samples), _np_ptr(buf) if len(buf) else None, cap, _np_ptr(off), _np_ptr(ln)))
+        return buf, off, ln[:n_positions]
+
     def pileup_sample_text(self, n_positions, n_samples, text, text_cap=None):
         """bvc_pileup_sample_text after a tile finished with sample_text=True: the called positions' sample columns into text (uint8 array).
         Returns (text, text_off [T + 1], text_len [T])."""
-        off = np.zeros(n_positions + 1, dtype=np.int64)
-        ln = np.zeros(max(1, n_positions), dtype=np.int64)
-        cap = len(text) if text_cap is None else int(text_cap)
-        self._check(self._L.bvc_pileup_sample_text(self._h, int(n_samples), _np_ptr(text) if len(text) else None, cap, _np_ptr(off), _np_ptr(ln)))
-        return text, off, ln[:n_positions]
+        return self._pileup_sample(self._L.bvc_pileup_sample_text, n_positions, n_samples, text, text_cap)
 
     def bgzf_deflate(self, data, piece_off, piece_len, comp=None, comp_cap=None):
         """bvc_bgzf_deflate on host arrays: piece i = data[piece_off[i] : piece_off[i] + piece_len[i]] (uint8) as BGZF blocks.  comp: a uint8
@@ -528,11 +522,7 @@ class Context:
     def pileup_sample_bgzf(self, n_positions, n_samples, comp, comp_cap=None):
         """bvc_pileup_sample_bgzf after a tile finished with sample_text=True: the called positions' sample columns as BGZF blocks into comp
         (uint8 array).  Returns (comp, comp_off [T + 1], text_len [T])."""
-        off = np.zeros(n_positions + 1, dtype=np.int64)
-        ln = np.zeros(max(1, n_positions), dtype=np.int64)
-        cap = len(comp) if comp_cap is None else int(comp_cap)
-        self._check(self._L.bvc_pileup_sample_bgzf(self._h, int(n_samples), _np_ptr(comp) if len(comp) else None, cap, _np_ptr(off), _np_ptr(ln)))
-        return comp, off, ln[:n_positions]
+        return self._pileup_sample(self._L.bvc_pileup_sample_bgzf, n_positions, n_samples, comp, comp_cap)
 
     # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
     def pack_dense_device(self, bases_t, quals_t, packed_t=None):

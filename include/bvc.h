@@ -399,7 +399,7 @@ int bvc_pileup_finish_called_stats(bvc_ctx *ctx, const int8_t *ref_base, double 
                                    int32_t *samples, bvc_pileup_indel *indels, char *indel_text, bvc_site_result *results,
                                    bvc_group_result *grp_results, bvc_site_stats *stats);
 /* The called positions' VCF sample columns formatted on the device -- bvc_vcf_samples_csr, bvc_pileup_finish_called_text,
- * bvc_pileup_sample_text -- are declared in bvc_vcf.h beside this header. */
+ * bvc_pileup_sample_text -- are declared in their own section below. */
 /*
  * The same from the COMPRESSED temp batches: the BGZF blocks go to the device as they are in the files (a fifth of the bytes of
  * their text), are inflated there (bvc_inflate_blocks) and the text never exists on the host.  The caller no longer knows where the
@@ -561,6 +561,105 @@ int bvc_set_tuning(bvc_ctx *ctx, const char *key, int value);
 /* Streams `bytes` of device memory once with 16-byte loads per lane and nothing else; HIP-event time in ms.
  * The empirical HBM read ceiling to hold next to the spec peak when judging the histogram kernel. */
 int bvc_stream_read_ms(bvc_ctx *ctx, const void *device_ptr, int64_t bytes, int repeats, double *ms_per_pass);
+
+/* ---- the called positions' VCF sample columns formatted on the device (additive) ------------------- */
+/*
+ * Additive: the SAMPLE COLUMNS of a called position's VCF line (WriteVcf, src/BaseType.cpp:187-212: one GT:AB:SO:BP field per sample,
+ * 400 KB per position at 1e5 samples) formatted on the device from the position's entries and the sample each belongs to.  The text is,
+ * byte for byte, what the host program's vcf_line puts behind "GT:AB:SO:BP\t" (host/pileup.cpp):
+ *   - the entries count up to the first k with samples[k] < (one past the previous entry's sample, 0 at the start) or samples[k] outside
+ *     0 .. n_samples - 1; that entry and all behind it are ignored.  Indel entries and N bases are formatted like any other entry
+ *   - a sample without an entry is "./."; a sample with one is "g:B:S:d.dddddd": g = "0/." where base == ref_base[s] (as ints: a
+ *     negative ref_base matches nothing), else "./i" with i - 1 the LAST index below n_alt (n_alt > 3 is read as 3) whose
+ *     alt_base & 7 equals the base, else "./."; B = "ACGTNN"[min(base, 5)]; S = "-+"[strand & 1]; d.dddddd = 1 - 10^(-qual / 10) as %.6f
+ *     (the 256 strings of bvc_vcf_bp_lut).  The base is read & 7
+ *   - fields are separated by tabs: n_samples fields, text_len = max(0, 4 * n_samples + 13 * (entries that count) - 1) bytes
+ * Layout: site s has a slot iff results[s].called != 0, of bvc_vcf_samples_slot(n_samples, offsets[s + 1] - offsets[s]) bytes, the slots
+ * one after the other in site order from byte 0 of `text`: text_off [n_sites + 1] are their starts (text_off[n_sites] = their sum, which
+ * text_cap must reach), text_len [n_sites] the bytes of text in each (0 for a site that is not called).  The bytes of a slot behind its
+ * text are unspecified; nothing outside the slots is written.
+ * Host or device pointers (flags), as bvc_site_stats_csr: of `results` called, n_alt and alt_base are read and must be complete (overlap
+ * mode: bvc_join first).  Device `entries` / `samples` may start at any element, device `text` must start on a 16-byte boundary (the text
+ * is written with 16-byte stores); the device form waits once, for the sum of the slots, before it formats (asynchronously).  With host
+ * pointers the small arrays are staged through the context's page-locked buffer, the entries and samples go up from the caller's memory
+ * as it is and the text comes down straight into it (a DMA where that is bvc_host_alloc memory).  BVC_ERR_ARG: null pointers with work
+ * present, a negative n_sites, n_samples or text_cap, host offsets that do not start at 0 or that decrease, a text_cap smaller than the sum
+ * of the slots (bvc_last_error names the need; with host pointers nothing has been launched, with either the context stays usable).
+ */
+/* Bytes of a called site's slot, for callers to size `text`: 4 * n_samples + 13 * n_entries rounded up to 16. */
+static inline int64_t bvc_vcf_samples_slot(int64_t n_samples, int64_t n_entries)
+{
+    return (4 * n_samples + 13 * n_entries + 15) / 16 * 16;
+}
+/* The eight characters d.dddddd for quality q at out[8 * q], q = 0..255.  Needs no context and no device. */
+void bvc_vcf_bp_lut(char out[2048]);
+int bvc_vcf_samples_csr(bvc_ctx *ctx, int64_t n_sites, const int64_t *offsets, const bvc_pileup_entry *entries,
+                        const int32_t *samples, const int8_t *ref_base, const bvc_site_result *results, int64_t n_samples,
+                        char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len, uint32_t flags);
+/*
+ * The same behind the producer calls.  bvc_pileup_finish_called_text is bvc_pileup_finish_called_stats without the gather and the
+ * download of the called positions' entries and samples (stats is required): one wait.  It leaves the tile's columns and records on
+ * the device, and until the next bvc_pileup_begin* on the context bvc_pileup_sample_text formats the called positions' sample columns
+ * from them: text / text_off / text_len as above (host pointers), n_positions sites.  The caller sizes `text` from entry_off, results
+ * and bvc_vcf_samples_slot; a text_cap that is too small is BVC_ERR_ARG (bvc_last_error names the need) and consumes nothing: the call
+ * may be repeated with a larger buffer -- as it may be repeated anyway.  bvc_pileup_sample_text without a preceding
+ * bvc_pileup_finish_called_text, or after the next begin: BVC_ERR_ARG.  One wait; the text comes straight into the caller's memory.
+ */
+int bvc_pileup_finish_called_text(bvc_ctx *ctx, const int8_t *ref_base, double min_af, const uint8_t carry_in[5], uint8_t carry_out[5],
+                                  const uint8_t *group_of_sample, int64_t n_samples, int32_t n_groups,
+                                  int64_t *entry_off, int32_t *tally, bvc_pileup_indel *indels, char *indel_text,
+                                  bvc_site_result *results, bvc_group_result *grp_results, bvc_site_stats *stats);
+int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t text_cap, int64_t *text_off, int64_t *text_len);
+
+/* ---- byte ranges in device memory deflated into finished BGZF blocks (additive) --------------------- */
+/*
+ * Additive: a device deflate encoder (RFC 1951) for BGZF (SAM specification 4.1), the format of the host program's .vcf.gz.  A "piece"
+ * is a range of bytes; a piece of len bytes becomes bvc_bgzf_blocks(len) blocks, each but the last of exactly BVC_BGZF_BLOCK_INPUT
+ * input bytes (htslib's block size: a stored block always fits 64 KiB); a piece of 0 bytes yields no block (an empty block is the
+ * end-of-file marker and never appears).  Every block is a complete, independent gzip member of at most 65536 bytes: the 18-byte
+ * header with the BC extra field (BSIZE - 1) as the host program's BgzfWriter writes it, one deflate block with BFINAL set (fixed
+ * Huffman codes, or stored where that is smaller) padded to a byte, CRC32 of the input bytes and ISIZE.  Matches stay inside the
+ * block's own input (distances 1..32768, lengths 4..258).  The output is a pure function of the input bytes: the same pieces give the
+ * same bytes on every run.  Concatenated in any order with other BGZF blocks and closed with the end-of-file marker they are a BGZF file.
+ */
+#define BVC_BGZF_BLOCK_INPUT 65280
+/* Blocks of a piece: ceil(len / 65280), 0 for len <= 0. */
+static inline int64_t bvc_bgzf_blocks(int64_t len)
+{
+    return len <= 0 ? 0 : (len + BVC_BGZF_BLOCK_INPUT - 1) / BVC_BGZF_BLOCK_INPUT;
+}
+/* The most bytes the blocks of a piece take (every block stored: 18 + 5 + 8 bytes around its input), for callers to size `comp`. */
+static inline int64_t bvc_bgzf_bound(int64_t len)
+{
+    return len <= 0 ? 0 : len + (len + BVC_BGZF_BLOCK_INPUT - 1) / BVC_BGZF_BLOCK_INPUT * 31;
+}
+/*
+ * Piece i is data[piece_off[i] .. piece_off[i] + piece_len[i]); pieces may start at any byte and need not be adjacent or ordered.  Its
+ * blocks are comp[comp_off[i] .. comp_off[i + 1]): comp_off [n_pieces + 1], comp_off[0] = 0, the blocks of all pieces one after the
+ * other in piece order without gaps.  Nothing beyond comp_off[n_pieces] is written.  comp_cap must reach the sum of
+ * bvc_bgzf_bound(piece_len[i]).
+ * Host or device pointers (flags).  With host pointers the bytes of the pieces go up through the context's page-locked buffer, nothing
+ * is launched before the arguments have been checked, and the call waits twice: for comp_off, then for the packed bytes (only they come
+ * down, never a bound-sized buffer).  With device pointers the call waits for piece_off and piece_len (the launches are sized from the lengths)
+ * and, briefly, for its table of (n_pieces + 1) * 8 bytes to have gone up; the blocks and comp_off are then written asynchronously on the
+ * context's stream.
+ * BVC_ERR_ARG: null pointers with work present, a negative n_pieces, piece_off, piece_len or comp_cap, a comp_cap smaller than the sum
+ * of the bounds (bvc_last_error names the need); the context stays usable.
+ */
+int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
+                     uint8_t *comp, int64_t comp_cap, int64_t *comp_off, uint32_t flags);
+/*
+ * bvc_pileup_sample_text's twin: after bvc_pileup_finish_called_text and until the next bvc_pileup_begin* on the context it
+ * formats the called positions' sample columns into device memory of the context's and delivers each position's text as BGZF blocks;
+ * the text never comes to the host.  Host pointers: comp_off [n_positions + 1] (an empty range for a position that is not called),
+ * text_len [n_positions] as bvc_pileup_sample_text reports it.  The caller sizes `comp` from entry_off, the results,
+ * bvc_vcf_samples_slot and bvc_bgzf_bound: comp_cap must reach the sum of bvc_bgzf_bound(bvc_vcf_samples_slot(n_samples, entries of
+ * the position)) over the called positions; a comp_cap that is too small is BVC_ERR_ARG (bvc_last_error names the need) and consumes
+ * nothing.  The call may be repeated, and made beside bvc_pileup_sample_text in either order; out of sequence it is BVC_ERR_ARG as its
+ * twin.  Two waits, one more than its twin: for comp_off and text_len, then for the packed bytes, which come straight into the caller's
+ * memory.
+ */
+int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len);
 
 #ifdef __cplusplus
 }

@@ -7,7 +7,7 @@ import numpy as np
 
 from tests import vcf_samples_cases as vc
 
-B = 65280                                                          # input bytes of a block (include/bvc_bgzf.h)
+B = 65280                                                          # input bytes of a block (include/bvc.h)
 GRID = 256                                                         # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid)
 LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289,

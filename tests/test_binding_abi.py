@@ -48,9 +48,10 @@ def test_the_parser_reads_the_header():
 def test_the_table_names_what_the_header_declares():
     from basevarc_amd import lib as bl
     declared = set(header_declarations())
-    assert len(declared) == 47
+    assert len(declared) == 53
     assert len(bl.EXPORTS) == len(set(bl.EXPORTS))
     assert declared == set(bl.EXPORTS)
+    assert list(header_declarations()) == bl.EXPORTS             # the table is in the header's order
     assert declared == set(bl.PROTOTYPES) - {"bvc_debug_report"}
     assert "bvc_debug_report" in bl.PROTOTYPES                  # optional: diagnostic builds only export it
 

@@ -1,7 +1,7 @@
 """The VCF sample columns formatted on the device (bvc_vcf_samples_csr; GPU).
 
 Every byte of every called site's text is compared `==` with the plain Python model of tests/vcf_samples_cases.py and with the host
-program's own columns (bvchost_vcf_samples); the offsets and lengths with the slot formula of include/bvc_vcf.h.  The text buffers are
+program's own columns (bvchost_vcf_samples); the offsets and lengths with the slot formula of include/bvc.h.  The text buffers are
 prefilled with a guard byte: nothing outside the slots may change.  The `results` records are made by the tests (called, n_alt,
 alt_base): nothing here depends on the LRT."""
 import ctypes as C

@@ -1,5 +1,5 @@
 """The VCF sample columns formatted on the device, as far as a machine without a GPU can see them: both libraries export the new entry
-points, include/bvc_vcf.h declares them and the binding's second table is held against it, the slot formula and the kernel's tile are the ones the binding and
+points, include/bvc.h declares them and the binding's table names them, the slot formula and the kernel's tile are the ones the binding and
 the GPU tests use, the kernel is built from its own source under the rules of every kernel, the 256 BP strings the kernel copies are the
 host program's, the plain Python model of the text (tests/vcf_samples_cases.py) equals the host program's columns on the whole catalogue,
 and the VCF line built around existing columns equals the one built from the entries."""
@@ -39,7 +39,7 @@ def test_the_libraries_export_the_entry_points():
 
 def test_the_header_declares_them_and_the_binding_requires_them():
     from basevarc_amd import lib as bl
-    header = open(os.path.join(ROOT, "include", "bvc_vcf.h")).read()
+    header = open(os.path.join(ROOT, "include", "bvc.h")).read()
     assert re.search(r"static inline int64_t bvc_vcf_samples_slot\(int64_t n_samples, int64_t n_entries\)", header)
     assert re.search(r"\bvoid bvc_vcf_bp_lut\(char out\[2048\]\);", header)
     assert re.search(r"\bint bvc_vcf_samples_csr\(bvc_ctx \*ctx, int64_t n_sites, const int64_t \*offsets, const bvc_pileup_entry \*entries,",
@@ -47,26 +47,10 @@ def test_the_header_declares_them_and_the_binding_requires_them():
     assert re.search(r"\bint bvc_pileup_finish_called_text\(bvc_ctx \*ctx, const int8_t \*ref_base, double min_af,", header)
     assert re.search(r"\bint bvc_pileup_sample_text\(bvc_ctx \*ctx, int64_t n_samples, char \*text, int64_t text_cap, int64_t \*text_off, "
                      r"int64_t \*text_len\);", header)
-    # the binding's second table against the second header, as tests/test_binding_abi.py holds the first against bvc.h: the same
-    # functions, pointers bound as pointers, every scalar with the header's width and signedness, the same return types
+    # declared in this order, and rows of the binding's one table (tests/test_binding_abi.py compares every row with its declaration)
     from tests import test_binding_abi as ta
-    txt = re.sub(r"//[^\n]*", " ", re.sub(r"/\*.*?\*/", " ", header, flags=re.S))
-    decls = {name: (" ".join(ret.split()), [p.strip() for p in " ".join(params.split()).split(",")])
-             for ret, name, params in re.findall(r"\b((?:const\s+)?\w+\s*\*?)\s*\b(bvc_\w+)\s*\(([^;{}()]*)\)\s*;", txt)}
-    assert list(decls) == list(SYMBOLS) == bl.VCF_EXPORTS == list(bl.VCF_PROTOTYPES)
-    assert not set(bl.VCF_PROTOTYPES) & set(bl.PROTOTYPES)
-    for name, (ret, params) in decls.items():
-        restype, argtypes = bl.VCF_PROTOTYPES[name]
-        assert restype is ta.RETURNS[ret] and len(argtypes) == len(params), (name, ret, params)
-        for a, prm in zip(argtypes, params):
-            if "*" in prm or re.search(r"\[\d+\]$", prm):
-                assert ta.is_pointer(a), (name, prm, a)
-            else:
-                assert not ta.is_pointer(a) and a is ta.scalar_of(prm), (name, prm, a)
-    L = bl.bind(C.CDLL(bl.library_path(), mode=os.RTLD_LAZY))
-    for name in bl.VCF_EXPORTS:
-        fn = getattr(L, name)
-        assert fn.restype is bl.VCF_PROTOTYPES[name][0] and list(fn.argtypes) == bl.VCF_PROTOTYPES[name][1], name
+    assert [name for name in ta.header_declarations() if name in SYMBOLS] == list(SYMBOLS)
+    assert [name for name in bl.EXPORTS if name in SYMBOLS] == list(SYMBOLS)
     for m in ("vcf_samples_csr", "vcf_samples_csr_device", "pileup_sample_text"):
         assert callable(getattr(bl.Context, m, None)), m
 
@@ -75,7 +59,7 @@ def test_the_slot_formula_and_the_tile_are_the_ones_the_tests_use(tmp_path):
     from basevarc_amd import lib as bl
     # the header's inline function, compiled: against the binding's formula on every residue of both arguments and on large sizes
     src = tmp_path / "slot.c"
-    src.write_text('#include "bvc_vcf.h"\nlong long slot(long long n, long long e) { return bvc_vcf_samples_slot(n, e); }\n')
+    src.write_text('#include "bvc.h"\nlong long slot(long long n, long long e) { return bvc_vcf_samples_slot(n, e); }\n')
     so = tmp_path / "slot.so"
     import subprocess
     subprocess.check_call(["gcc", "-shared", "-fPIC", "-I", os.path.join(ROOT, "include"), "-o", str(so), str(src)])

@@ -1,4 +1,4 @@
-"""The sample columns of a called site's VCF line: a plain Python model of the text (include/bvc_vcf.h, bvc_vcf_samples_csr), the host
+"""The sample columns of a called site's VCF line: a plain Python model of the text (include/bvc.h, bvc_vcf_samples_csr), the host
 program's own columns through libbvchost.so (bvchost_vcf_samples, the reference), and the hand-built catalogue of sites both the CPU and
 the GPU tests walk.  Nothing here needs a device."""
 import ctypes as C
