@@ -6,8 +6,14 @@
 
 #include <zlib.h>
 
+#include <fcntl.h>
+#include <sys/mman.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
 #include <cstdlib>
 #include <cstring>
+#include <stdexcept>
 
 #if defined(__x86_64__)
 #include <immintrin.h>
@@ -264,6 +270,65 @@ bool BgzfWriter::close()
     return good;
 }
 
+size_t bgzf_block_size(const unsigned char h[18])
+{
+    if (h[0] != 0x1f || h[1] != 0x8b || h[12] != 'B' || h[13] != 'C') return 0;
+    const size_t bsize = ((size_t)h[16] | ((size_t)h[17] << 8)) + 1;
+    return bsize < 18 + 8 ? 0 : bsize;
+}
+
+bool bgzf_block_trailer(const unsigned char t[8], uint32_t &crc32, uint32_t &isize)
+{
+    crc32 = le32u(t);
+    isize = le32u(t + 4);
+    return isize <= 65536;
+}
+
+MappedBlocks::MappedBlocks(const std::vector<std::string> &paths)
+{
+    for (auto const &f : paths) {
+        File m;
+        m.fd = ::open(f.c_str(), O_RDONLY);
+        if (m.fd < 0) { release(); throw std::runtime_error("ERROR: can not open " + f); }
+        struct stat st;
+        if (::fstat(m.fd, &st) != 0) { ::close(m.fd); release(); throw std::runtime_error("ERROR: can not open " + f); }
+        m.n = (size_t)st.st_size;
+        if (m.n) {
+            void *p = ::mmap(nullptr, m.n, PROT_READ, MAP_PRIVATE, m.fd, 0);
+            if (p == MAP_FAILED) { ::close(m.fd); release(); throw std::runtime_error("ERROR: can not map " + f); }
+            (void)::madvise(p, m.n, MADV_SEQUENTIAL);
+            m.p = static_cast<const unsigned char *>(p);
+        }
+        f_.push_back(m);
+    }
+}
+
+void MappedBlocks::release()
+{
+    for (auto &m : f_) {
+        if (m.p) ::munmap(const_cast<unsigned char *>(m.p), m.n);
+        if (m.fd >= 0) ::close(m.fd);
+    }
+    f_.clear();
+}
+
+bool MappedBlocks::pop(size_t b, RawBlock &out)
+{
+    File &m = f_[b];
+    for (;;) {
+        if (m.at == m.n) return false;
+        const unsigned char *h = m.p + m.at;
+        const size_t bsize = m.n - m.at < 18 ? 0 : bgzf_block_size(h);
+        if (bsize == 0) throw std::runtime_error("ERROR: a temp batch is not BGZF");
+        if (m.n - m.at < bsize) throw std::runtime_error("ERROR: truncated temp batch (it ends inside a BGZF block)");
+        out.payload = h + 18; out.len = bsize - 18 - 8;
+        m.at += bsize;
+        if (!bgzf_block_trailer(h + bsize - 8, out.crc32, out.isize))
+            throw std::runtime_error("ERROR: a temp batch is not BGZF (a block of more than 64 KiB)");
+        if (out.isize != 0) return true;                      // (empty blocks: the EOF marker)
+    }
+}
+
 BgzfReader::BgzfReader(const std::string &path)
     : fp_(std::fopen(path.c_str(), "rb")), bgzf_(false), block_addr_(0), next_addr_(0), pos_(0), eof_(false)
 {
@@ -291,20 +356,17 @@ bool BgzfReader::fetch(uint64_t from, std::vector<unsigned char> &out, uint64_t 
         if (file_at_ != at && std::fseek(fp_, (long)at, SEEK_SET) != 0) return false;
         file_at_ = UINT64_MAX;
         if (std::fread(h, 1, 18, fp_) != 18) return false;
-        if (h[0] != 0x1f || h[1] != 0x8b || h[12] != 'B' || h[13] != 'C') return false;
-        const size_t bsize = ((size_t)h[16] | ((size_t)h[17] << 8)) + 1;
-        if (bsize < 18 + 8) return false;
+        const size_t bsize = bgzf_block_size(h);
+        if (bsize == 0) return false;
         comp_.resize(bsize - 18);
         if (std::fread(comp_.data(), 1, comp_.size(), fp_) != comp_.size()) return false;
         next = at + bsize;
         file_at_ = next;
         const size_t clen = comp_.size() - 8;
-        uint32_t isize = 0;
-        for (int i = 0; i < 4; ++i) isize |= (uint32_t)comp_[clen + 4 + i] << (8 * i);
+        uint32_t isize = 0, want_crc = 0;
+        if (!bgzf_block_trailer(comp_.data() + clen, want_crc, isize)) return false;
         if (isize == 0) { from = next; continue; }      // empty block (the EOF marker): try the next one
         out.resize(isize);
-        uint32_t want_crc = 0;
-        for (int i = 0; i < 4; ++i) want_crc |= (uint32_t)comp_[clen + i] << (8 * i);
         // BVC_HOST_NO_CRC=1: the trailer's CRC32 is not compared (measurement aid; htslib always compares)
         static const bool check_crc = getenv("BVC_HOST_NO_CRC") == nullptr;
         auto crc_ok = [&]() {

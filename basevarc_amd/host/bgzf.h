@@ -58,6 +58,35 @@ class BgzfWriter {
     bool closing_ = false;
 };
 
+// ---- the frame of a BGZF block (SAM specification 4.1), parsed here for every reader of one ---------------------------------------
+inline uint32_t le32u(const unsigned char *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+// The block's bytes in the file, from its 18-byte header: gzip magic, the 'BC' subfield, BSIZE.  0: not a BGZF header, or a block too
+// short for its own frame (header and the 8 bytes of CRC32 and ISIZE).
+size_t bgzf_block_size(const unsigned char h[18]);
+// CRC32 and ISIZE from the block's last 8 bytes; false: an ISIZE of more than 64 KiB, which no BGZF block has.
+bool bgzf_block_trailer(const unsigned char t[8], uint32_t &crc32, uint32_t &isize);
+
+// A BGZF block of a temp-batch file as it lies in the file's pages: its deflate payload, the size it inflates to and its CRC32 (the
+// file is mapped: nothing is copied before the one copy into the tile's page-locked buffer, and no thread reads ahead -- round 5: a
+// read-ahead thread that fread one block at a time into a vector of its own delivered 1.2 GB/s and was what a position loop waited for).
+struct RawBlock { const unsigned char *payload = nullptr; size_t len = 0; uint32_t isize = 0, crc32 = 0; };
+
+// The temp-batch files of a thread, mapped, as RAW BGZF blocks (the device inflates them: bvc_pileup_begin_bgzf).
+class MappedBlocks {
+ public:
+    explicit MappedBlocks(const std::vector<std::string> &paths);       // throws when a file cannot be opened or mapped
+    ~MappedBlocks() { release(); }
+    MappedBlocks(const MappedBlocks &) = delete;
+    MappedBlocks &operator=(const MappedBlocks &) = delete;
+    // the next non-empty block of batch b; false when the file has ended (throws on a damaged file)
+    bool pop(size_t b, RawBlock &out);
+    const unsigned char *data(size_t b) const { return f_[b].p; }       // batch b's file as mapped (what a block's payload points into)
+ private:
+    struct File { const unsigned char *p = nullptr; size_t n = 0, at = 0; int fd = -1; };
+    void release();
+    std::vector<File> f_;
+};
+
 class BgzfReader;
 
 // Read-ahead for BgzfReaders: a few threads that inflate, for every reader attached to the pool, the block after the one

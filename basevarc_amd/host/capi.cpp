@@ -50,7 +50,7 @@ void bvchost_reset_parser(void) { reset_parser_carry(); }
 
 // inflate.cpp against zlib (tests): bytes written or -1
 long bvchost_fast_inflate(const unsigned char *in, size_t n, unsigned char *out, size_t cap) { return fast_inflate(in, n, out, cap); }
-// orchestration hooks (tests/test_host.py): the functions main.cpp itself calls
+// orchestration hooks (tests/test_host.py): the functions the host program (main.cpp and the headers it is made of) itself calls
 void bvchost_thread_window(int64_t psize, int32_t thread, int32_t ithread, int64_t *lo, int64_t *hi)
 {
     size_t l, h;
@@ -90,6 +90,22 @@ int64_t bvchost_bgzf_read_lines(const char *path, int64_t n_per_call, int32_t th
     }
     *n_lines = lines;
     return total;
+}
+// MappedBlocks::pop until the file ends: per block the offset of its payload in the file, the payload's length, ISIZE and CRC32 (up to
+// cap of them).  Returns the number of blocks, or -1 with what was thrown in err.
+int64_t bvchost_bgzf_walk(const char *path, int64_t cap, int64_t *payload_off, int64_t *len, uint32_t *isize, uint32_t *crc, char *err, size_t err_cap)
+{
+    try {
+        MappedBlocks m(std::vector<std::string>(1, path));
+        RawBlock rb;
+        int64_t n = 0;
+        for (; m.pop(0, rb); ++n)
+            if (n < cap) { payload_off[n] = rb.payload - m.data(0); len[n] = (int64_t)rb.len; isize[n] = rb.isize; crc[n] = rb.crc32; }
+        return n;
+    } catch (const std::exception &e) {
+        copy_out(e.what(), err, err_cap);
+        return -1;
+    }
 }
 long bvchost_zlib_fallbacks(void) { return bgzf_zlib_fallbacks(); }
 long bvchost_crc_errors(void) { return bgzf_crc_errors(); }
@@ -229,6 +245,41 @@ bvchost_site *bvchost_site_from_arrays(const bvc_pileup_entry *entries, const in
         s->col.add(a, samples[k]);
     }
     return s;
+}
+// pack_ragged / pack_dense over sites made by bvchost_site_from_arrays.  Returns 1 where the tile fits one byte per observation: offsets
+// [n + 1] and `packed`; 0: offsets, bases and quals (the caller's buffers hold every observation / n * stride bytes).
+static std::vector<SiteColumn> columns_of(const bvchost_site *const *sites, int64_t n)
+{
+    std::vector<SiteColumn> cols;
+    for (int64_t i = 0; i < n; ++i) cols.push_back(sites[i]->col);
+    return cols;
+}
+static int32_t copy_packed(bool fits, const PackedTile &t, uint8_t *packed, int8_t *bases, int8_t *quals)
+{
+    if (fits) std::copy(t.packed.begin(), t.packed.end(), packed);
+    else { std::copy(t.bases.begin(), t.bases.end(), bases); std::copy(t.quals.begin(), t.quals.end(), quals); }
+    return fits ? 1 : 0;
+}
+int32_t bvchost_pack_ragged(const bvchost_site *const *sites, int64_t n, int32_t two_byte_only, int64_t *offsets, uint8_t *packed, int8_t *bases, int8_t *quals)
+{
+    const std::vector<SiteColumn> cols = columns_of(sites, n);
+    PackedTile t;
+    const bool fits = pack_ragged(cols.data(), cols.size(), two_byte_only != 0, t);
+    std::copy(t.offsets.begin(), t.offsets.end(), offsets);
+    return copy_packed(fits, t, packed, bases, quals);
+}
+// of_sample [n_samples]: group per sample (255: none), through Groups::order_columns; column_of [n_samples] comes back
+int32_t bvchost_pack_dense(const bvchost_site *const *sites, int64_t n, const uint8_t *of_sample, int32_t n_samples, int64_t stride,
+                           int32_t two_byte_only, int32_t *column_of, uint8_t *packed, int8_t *bases, int8_t *quals)
+{
+    const std::vector<SiteColumn> cols = columns_of(sites, n);
+    Groups g;
+    g.of_sample.assign(of_sample, of_sample + n_samples);
+    g.order_columns();
+    std::copy(g.column_of.begin(), g.column_of.end(), column_of);
+    PackedTile t;
+    const bool fits = pack_dense(cols.data(), cols.size(), stride, g.column_of.data(), two_byte_only != 0, t);
+    return copy_packed(fits, t, packed, bases, quals);
 }
 // The sample columns of bvchost_vcf_line alone (what libbvc's bvc_vcf_samples_csr formats on the device): bytes needed with the
 // terminating NUL; the output is truncated to cap.
@@ -371,7 +422,7 @@ int64_t bvchost_write_synth_batches(const char *out_prefix, int32_t n_samples, i
                                 z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL; return z ^ (z >> 31); };
     const int32_t nb = 1 + (n_samples - 1) / batch;
     const size_t window = (size_t)n_pos % thread + (size_t)n_pos / thread;
-    // text and binary batches at zlib's level 6, what bt_r (host/main.cpp) and the reference's bgzf_write write; "raw": stored.
+    // text and binary batches at zlib's level 6, what bt_r (the load phase, host/main.cpp) and the reference's bgzf_write write; "raw": stored.
     // BVC_SYNTH_LEVEL overrides it (round 4's records were taken on level-1 files).
     const int level = bin == 2 ? 0 : (getenv("BVC_SYNTH_LEVEL") ? atoi(getenv("BVC_SYNTH_LEVEL")) : 6);
     std::atomic<int64_t> entries(0);

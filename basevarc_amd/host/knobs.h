@@ -1,0 +1,74 @@
+// knobs.h -- the compute phase's knobs in the environment: every name, default and meaning once (none changes an output).  Read once,
+// in run_basetype before any thread starts, and passed on by const reference.
+#ifndef BVC_HOST_KNOBS_H
+#define BVC_HOST_KNOBS_H
+
+#include <sched.h>
+
+#include <algorithm>
+#include <cstdlib>
+#include <fstream>
+#include <string>
+#include <thread>
+
+namespace bvchost {
+
+// CPUs this process may use: the cgroup's quota when it has one (cpu.max: "<quota> <period>"), else the CPUs of its affinity mask.
+inline double process_cpus()
+{
+    double c = (double)std::max(1u, std::thread::hardware_concurrency());
+    cpu_set_t set;
+    if (sched_getaffinity(0, sizeof set, &set) == 0) c = (double)CPU_COUNT(&set);
+    std::ifstream f("/sys/fs/cgroup/cpu.max");
+    std::string q; double period = 0;
+    if (f >> q >> period && q != "max" && period > 0) c = std::min(c, std::max(1.0, atof(q.c_str()) / period));
+    return c;
+}
+
+struct Knobs {
+    static bool set(const char *name) { return getenv(name) != nullptr; }
+    static int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+    explicit Knobs(int threads) : cpus_per_loop(process_cpus() / (double)std::max(1, threads)) {}
+    // A position loop runs helper threads beside its own (the tile formatter, the deflaters of its two outputs, the call that finishes
+    // a tile while the next one's blocks are gathered); how many it starts goes by the CPUs per loop -- past the quota they only get the
+    // whole process throttled (round 5, 16 CPUs: three VCF deflaters per loop +50 % with one loop, +18 % with four, -15 % with eight).
+    const double cpus_per_loop;
+    const bool profile = set("BVC_HOST_PROFILE");                            // set: the stage clocks of every thread and of main
+    const bool profile_tiles = num("BVC_HOST_PROFILE", 0) >= 2;              // 2: and what every tile of the BGZF feed cost its thread
+    const bool device_parse = num("BVC_HOST_DEVICE_PARSE", 1) != 0;          // 0: the CPU parser, not the device's (A/B runs)
+    const bool device_inflate = num("BVC_HOST_DEVICE_INFLATE", 1) != 0;      // 0: the text batches are inflated on the CPU
+    // 0: a device-parsed tile's entries come back for every position, not for the called ones only (WriteVcf is their one reader,
+    // src/BaseVarC.cpp:664; as up to round 5's first form of this feed)
+    const bool called_only = num("BVC_HOST_CALLED_ONLY", 1) != 0;
+    // 1: the rank sums and strand counts of a called position's VCF line are computed on the device, where the tile's entries lie
+    // (bvc_pileup_finish_called_stats), not from its entries on this CPU (three sorts per called position); needs called_only.  On since the
+    // eight-thread comparison of profiles/site_stats/README.txt item 3; 0: the CPU's own tallies (A/B runs)
+    const bool device_stats = num("BVC_HOST_DEVICE_STATS", 1) != 0;
+    // 1: the sample columns of a called position's VCF line -- one GT:AB:SO:BP field per sample -- are formatted on the device too
+    // (bvc_pileup_finish_called_text + bvc_pileup_sample_text) and no entry of a device-parsed tile comes to this CPU at all; implies the
+    // device's statistics for those tiles -- BVC_HOST_DEVICE_STATS=0 therefore turns this off as well; needs called_only.  On since the
+    // eight-thread comparison of profiles/vcf_samples/README.txt; 0: vcf_line's sample loop on the CPU (A/B runs)
+    const bool device_samples = num("BVC_HOST_DEVICE_SAMPLES", 1) != 0 && device_stats;
+    // 1: those sample columns are also deflated on the device (bvc_pileup_sample_bgzf): their text never comes to this CPU, and a called
+    // position's line is written as the text in front of the columns, the columns' finished BGZF blocks (BgzfWriter::write_blocks) and the
+    // newline.  The .vcf.gz inflates to the same bytes; it is larger than zlib's level 6 makes it (profiles/vcf_deflate/README.txt).  Needs
+    // device_samples; acts on device-parsed tiles only.  Off by default
+    const bool device_deflate = num("BVC_HOST_DEVICE_DEFLATE", 0) != 0 && device_samples;
+    const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
+    const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
+    // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
+    // fit one byte per observation (quality >= 63)
+    const int qual_shift = num("BVC_HOST_QUAL_SHIFT", 0);
+    // threads that inflate the blocks of the temp batches ahead of a position loop that reads them on the CPU (the loop takes a line of
+    // every batch per position; inflating was 70 % of it with the text form); 0 = none
+    const int inflate_threads = num("BVC_HOST_INFLATE_THREADS", 2);
+    // MB a tile should hold: of text or records in the tiles staged on the host, of compressed blocks in the BGZF feed
+    const int tile_mb_staged = std::max(1, num("BVC_HOST_TILE_MB", 32)), tile_mb_bgzf = std::max(1, num("BVC_HOST_TILE_MB", 128));
+    const int device_slots = std::max(1, num("BVC_HOST_DEVICE_SLOTS", 8));   // threads per device inside its part of a tile at a time
+    // the BGZF feed gathers the next tile's blocks beside the call that finishes this one; threads that deflate a loop's VCF text
+    const bool gather_ahead = num("BVC_HOST_GATHER_AHEAD", cpus_per_loop >= 3 ? 1 : 0) != 0;
+    const int vcf_deflaters = std::max(1, num("BVC_HOST_VCF_DEFLATERS", cpus_per_loop >= 4 ? 3 : (cpus_per_loop >= 3 ? 2 : 1)));
+};
+
+}  // namespace bvchost
+#endif

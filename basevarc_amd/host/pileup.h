@@ -124,6 +124,67 @@ struct Groups {
     bool empty() const { return names.empty(); }
 };
 
+// ---- a tile of positions in the form libbvc takes -------------------------------------------------------
+// ONE byte per observation (base << 6 | qual: half the bytes over the host link) while every base quality of the tile is below 63,
+// else two (bases, quals).  Indel entries are no observations.  The vectors live as long as their tile: refilled, not reallocated.
+struct PackedTile {
+    std::vector<int64_t> offsets;
+    std::vector<uint8_t> packed;
+    std::vector<int8_t> bases, quals;
+};
+// Ragged form, exactly the vectors bt_f builds (src/BaseVarC.cpp:550-559): site i's observations are [offsets[i], offsets[i + 1]) of
+// `packed` (returns true; a base that is not A/C/G/T is 0xFF) or of `bases` and `quals` (false; base and quality as they are).
+inline bool pack_ragged(const SiteColumn *sites, size_t n_sites, bool two_byte_only, PackedTile &o)
+{
+    o.offsets.assign(1, 0);
+    o.packed.clear();
+    bool fits = !two_byte_only;
+    for (size_t i = 0; i < n_sites && fits; ++i) {
+        for (auto const &a : sites[i].aiv)
+            if (a.is_indel == 0) {
+                if (a.qual > 62u) { fits = false; break; }
+                o.packed.push_back(a.base > 3u ? (uint8_t)0xFF : (uint8_t)((a.base << 6) | a.qual));
+            }
+        o.offsets.push_back((int64_t)o.packed.size());
+    }
+    if (fits) return true;
+    o.offsets.assign(1, 0);
+    o.bases.clear(); o.quals.clear();
+    for (size_t i = 0; i < n_sites; ++i) {
+        for (auto const &a : sites[i].aiv)
+            if (a.is_indel == 0) { o.bases.push_back((int8_t)a.base); o.quals.push_back((int8_t)a.qual); }
+        o.offsets.push_back((int64_t)o.bases.size());
+    }
+    return false;
+}
+// Dense [site][column] form of `stride` bytes a site; column_of: sample -> column (Groups::order_columns).  `packed` with 0xFF for
+// "no observation", which a base that is not A/C/G/T is too (returns true), or `bases` / `quals` with -1 / 0 for it and base and
+// quality as they are elsewhere (false).
+inline bool pack_dense(const SiteColumn *sites, size_t n_sites, int64_t stride, const int32_t *column_of, bool two_byte_only, PackedTile &o)
+{
+    bool fits = !two_byte_only;
+    if (fits) o.packed.assign(n_sites * (size_t)stride, (uint8_t)0xFF);
+    for (size_t s = 0; s < n_sites && fits; ++s)
+        for (size_t k = 0; k < sites[s].aiv.size(); ++k) {
+            const Entry &a = sites[s].aiv[k];
+            if (a.is_indel != 0 || a.base > 3u) continue;             // not A/C/G/T: no observation, as in the two-byte tile
+            if (a.qual > 62u) { fits = false; break; }
+            o.packed[s * (size_t)stride + (size_t)column_of[sites[s].sample[k]]] = (uint8_t)((a.base << 6) | a.qual);
+        }
+    if (fits) return true;
+    o.bases.assign(n_sites * (size_t)stride, (int8_t)-1);
+    o.quals.assign(n_sites * (size_t)stride, (int8_t)0);
+    for (size_t s = 0; s < n_sites; ++s)
+        for (size_t k = 0; k < sites[s].aiv.size(); ++k) {
+            const Entry &a = sites[s].aiv[k];
+            if (a.is_indel != 0) continue;
+            const size_t at = s * (size_t)stride + (size_t)column_of[sites[s].sample[k]];
+            o.bases[at] = (int8_t)a.base;
+            o.quals[at] = (int8_t)a.qual;
+        }
+    return false;
+}
+
 // ---- temp-batch pileup text (f1) -----------------------------------------------------------------------
 // One line per position; per sample one space-terminated token: "." | "base,mapq,qual,rpr,strand" | indel.
 void format_pileup_token(const AlleleInfo *a, std::string &out);           // a == nullptr -> ". "

@@ -796,3 +796,225 @@ def test_read_lines_hands_over_whole_lines_with_their_starts(H, tmp_path):
                 nl = C.c_int64(0)
                 got = H.bvchost_bgzf_read_lines(f, n_per_call, threads, out, len(data) + 16, C.byref(nl))
                 assert got == len(want) and out.raw[:got] == want and nl.value == want.count(b"\n"), (ci, n_per_call, threads, got)
+
+
+# ---- the host program's pure pieces: the BGZF block walk of its device feed, the packing of its tiles ------------------------------
+def bgzf_block(data, isize=None, subfield=b"BC", bsize=None):
+    """One BGZF block (SAM specification 4.1) around `data`; isize / subfield / bsize: what the frame SAYS instead."""
+    import struct
+    import zlib
+    co = zlib.compressobj(6, zlib.DEFLATED, -15)
+    comp = co.compress(data) + co.flush()
+    total = 18 + len(comp) + 8
+    return (b"\x1f\x8b\x08\x04\0\0\0\0\0\xff\x06\0" + subfield + b"\x02\0" + struct.pack("<H", (total if bsize is None else bsize) - 1) + comp
+            + struct.pack("<II", zlib.crc32(data), len(data) if isize is None else isize))
+
+
+def walk_model(raw):
+    """The non-empty blocks of a BGZF file image: (payload offset, payload bytes, ISIZE, CRC32, sum of the payload's bytes)."""
+    import struct
+    blocks, off = [], 0
+    while off < len(raw):
+        assert raw[off:off + 4] == b"\x1f\x8b\x08\x04" and raw[off + 12:off + 14] == b"BC"
+        bsize = struct.unpack_from("<H", raw, off + 16)[0] + 1
+        crc, isize = struct.unpack_from("<II", raw, off + bsize - 8)
+        if isize:
+            blocks.append((off + 18, bsize - 26, isize, crc, sum(raw[off + 18:off + bsize - 8]) & 0xFFFFFFFF))
+        off += bsize
+    return blocks
+
+
+def block_files(H, tmp_path):
+    """name -> (path, the blocks the walk must find | the text it must refuse with)."""
+    import zlib
+    H.bvchost_bgzf_write.restype = C.c_int
+    H.bvchost_bgzf_write.argtypes = [C.c_char_p, C.c_char_p, C.c_int64, C.c_int64, C.c_int, C.c_int]
+    rng = np.random.default_rng(31)
+    text = b"".join(b"%d,60,%d,7,1 . " % (int(rng.integers(0, 4)), int(rng.integers(2, 42))) * int(rng.integers(1, 60)) + b"\n" for _ in range(600))
+    text = text[:2 * 0xff00 + 5000]
+    text = text[:text.rfind(b"\n") + 1]
+    three = str(tmp_path / "three.gz")
+    assert H.bvchost_bgzf_write(three.encode(), text, len(text), 4096, 6, 0) == 1
+    raw = open(three, "rb").read()
+    model = walk_model(raw)
+    assert len(model) == 3 and raw[-28:-26] == b"\x1f\x8b" and sum(b[2] for b in model) == len(text)
+    for off, n, isize, crc, _ in model:                      # (the model itself: every payload inflates to ISIZE bytes of that CRC32)
+        data = zlib.decompress(raw[off:off + n], -15)
+        assert len(data) == isize and zlib.crc32(data) == crc
+    eof = raw[-28:]
+    a, b = bgzf_block(b"first block\n"), bgzf_block(b"second block\n")
+    images = {
+        "three": (raw, model),
+        "empty": (b"", []),
+        "gap": (a + eof + b + eof, walk_model(a + b + eof)[:1] + [(len(a) + 28 + 18,) + walk_model(b)[0][1:]]),
+        "cut": (raw[:model[1][0] + 100], "ERROR: truncated temp batch (it ends inside a BGZF block)"),
+        "no_bc": (bgzf_block(b"a gzip member, not BGZF\n", subfield=b"XY") + eof, "ERROR: a temp batch is not BGZF"),
+        "bsize": (bgzf_block(b"x" * 40, bsize=25) + eof, "ERROR: a temp batch is not BGZF"),
+        "isize": (bgzf_block(b"y" * 40, isize=65537) + eof, "ERROR: a temp batch is not BGZF (a block of more than 64 KiB)"),
+    }
+    files = {}
+    for name, (image, want) in images.items():
+        path = str(tmp_path / (name + ".blocks"))
+        open(path, "wb").write(image)
+        files[name] = (path, want)
+    return files, three, text
+
+
+def test_bgzf_block_walk_against_a_struct_walk(H, tmp_path):
+    """MappedBlocks::pop, the walk of the host program's device feed, over whole, empty and damaged files: per block the payload's place,
+    length, ISIZE and CRC32 as a Python struct walk finds them, empty blocks (the EOF marker) skipped, a damaged file refused with the
+    program's own text.  BgzfReader shares the block-header parser: it reads the three-block file to the bytes written."""
+    H.bvchost_bgzf_walk.restype = C.c_int64
+    H.bvchost_bgzf_walk.argtypes = [C.c_char_p, C.c_int64] + [C.c_void_p] * 4 + [C.c_char_p, C.c_size_t]
+    files, three, text = block_files(H, tmp_path)
+    for name, (path, want) in files.items():
+        off, ln = np.zeros(8, np.int64), np.zeros(8, np.int64)
+        isize, crc = np.zeros(8, np.uint32), np.zeros(8, np.uint32)
+        err = C.create_string_buffer(256)
+        n = H.bvchost_bgzf_walk(path.encode(), 8, off.ctypes.data, ln.ctypes.data, isize.ctypes.data, crc.ctypes.data, err, 256)
+        if isinstance(want, str):
+            assert n == -1 and err.value.decode() == want, (name, n, err.value)
+        else:
+            got = [(int(off[i]), int(ln[i]), int(isize[i]), int(crc[i])) for i in range(n)]
+            assert got == [b[:4] for b in want], (name, got)
+    H.bvchost_bgzf_read_lines.restype = C.c_int64
+    H.bvchost_bgzf_read_lines.argtypes = [C.c_char_p, C.c_int64, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]
+    out, nl = C.create_string_buffer(len(text) + 16), C.c_int64(0)
+    assert H.bvchost_bgzf_read_lines(three.encode(), 50, 0, out, len(text) + 16, C.byref(nl)) == len(text)
+    assert out.raw[:len(text)] == text and nl.value == text.count(b"\n")
+
+
+def entries_of(rows):
+    """(base, qual, is_indel, sample) rows -> entries in bvc_pileup_entry layout and their samples."""
+    from basevarc_amd.lib import ENTRY_DTYPE
+    e = np.zeros(len(rows), dtype=ENTRY_DTYPE)
+    for k, (base, qual, is_indel, _) in enumerate(rows):
+        e["base"][k], e["qual"][k], e["is_indel"][k], e["mapq"][k], e["rpr"][k], e["strand"][k] = base, qual, is_indel, 60, 9, k & 1
+    return e, np.array([r[3] for r in rows], dtype=np.int32)
+
+
+def ragged_model(sites, two_byte_only):
+    """fits, offsets, packed | bases, quals of a ragged tile: indel entries are no observations; one byte (base << 6 | qual, 0xFF for a base
+    that is not A/C/G/T) while no quality of the tile is above 62, else base and quality as they are."""
+    obs = [[(b, q) for b, q, indel, _ in rows if not indel] for rows in sites]
+    offsets = np.cumsum([0] + [len(o) for o in obs]).astype(np.int64)
+    flat = np.array([x for o in obs for x in o], dtype=np.int64).reshape(-1, 2)
+    if not two_byte_only and not (flat[:, 1] > 62).any():
+        return True, offsets, np.where(flat[:, 0] > 3, 0xFF, (flat[:, 0] << 6) | flat[:, 1]).astype(np.uint8), None
+    return False, offsets, flat[:, 0].astype(np.int8), flat[:, 1].astype(np.int8)
+
+
+def dense_model(sites, of_sample, stride, two_byte_only):
+    """fits, column_of, packed | bases, quals of a dense tile: columns are the samples in stable order of their group; one byte with 0xFF
+    for no observation (a base that is not A/C/G/T is none) while no quality of an A/C/G/T observation is above 62, else base and quality
+    as they are over -1 / 0."""
+    order = np.argsort(np.asarray(of_sample), kind="stable")
+    column_of = np.empty(len(of_sample), np.int32)
+    column_of[order] = np.arange(len(of_sample), dtype=np.int32)
+    obs = [(s, column_of[j], b, q) for s, rows in enumerate(sites) for b, q, indel, j in rows if not indel]
+    if not two_byte_only and not any(q > 62 for _, _, b, q in obs if b <= 3):
+        packed = np.full((len(sites), stride), 0xFF, np.uint8)
+        for s, c, b, q in obs:
+            if b <= 3:
+                packed[s, c] = (b << 6) | q
+        return True, column_of, packed.ravel(), None
+    bases, quals = np.full((len(sites), stride), -1, np.int8), np.zeros((len(sites), stride), np.int8)
+    for s, c, b, q in obs:
+        bases[s, c], quals[s, c] = b, q
+    return False, column_of, bases.ravel(), quals.ravel()
+
+
+# (base, qual, is_indel, sample): an empty site, one of indel entries only, one with a base-4 entry and a quality of exactly 62, the same
+# with 63, a plain one
+RAGGED_SITES = [[], [(5, 0, 1, 0), (5, 0, 1, 3)], [(0, 30, 0, 0), (4, 20, 0, 1), (5, 0, 1, 2), (3, 62, 0, 4)],
+                [(0, 30, 0, 0), (4, 20, 0, 1), (5, 0, 1, 2), (3, 63, 0, 4)], [(1, 41, 0, 1), (2, 2, 0, 2), (3, 0, 0, 6)]]
+# ... and a base that is not A/C/G/T with a quality of 63: the ragged form looks at the quality first, so the tile goes to two bytes (the
+# dense form skips such an entry: DENSE_SITES has one, and stays at one byte)
+RAGGED_TILES = [(RAGGED_SITES, 0), (RAGGED_SITES, 1), (RAGGED_SITES[:3] + RAGGED_SITES[4:], 0), (RAGGED_SITES[:3] + RAGGED_SITES[4:], 1), ([], 0),
+                (RAGGED_SITES[:2], 0), ([[(1, 20, 0, 0), (4, 63, 0, 1), (2, 5, 0, 2)]], 0)]
+# 7 samples in 3 groups (in no order) and one in none; stride 128
+DENSE_GROUPS = [2, 0, 1, 255, 0, 2, 1, 0]
+DENSE_SITES = [[(0, 30, 0, 0), (1, 62, 0, 1), (5, 0, 1, 2), (4, 63, 0, 3), (2, 7, 0, 7)], [(3, 40, 0, 3), (5, 0, 1, 4), (2, 12, 0, 5), (4, 9, 0, 6)], []]
+DENSE_TILES = [(DENSE_SITES, 0), (DENSE_SITES, 1), (DENSE_SITES + [[(1, 63, 0, 2), (4, 5, 0, 0)]], 0)]
+
+
+def test_tile_packers_against_numpy(H):
+    """pack_ragged and pack_dense, the one place where a tile of SiteColumns becomes libbvc's input, against the numpy statement of the
+    four forms: indel entries skipped everywhere, 0xFF for a base above 3 in the one-byte forms, base and quality as they are in the
+    two-byte forms, one quality above 62 sends the whole tile to two bytes, and so does two_byte_only."""
+    from tests.vcf_samples_cases import HostSite
+    H.bvchost_site_from_arrays.restype = C.c_void_p
+    H.bvchost_site_from_arrays.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32]
+    H.bvchost_pack_ragged.restype = C.c_int32
+    H.bvchost_pack_ragged.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_int32] + [C.c_void_p] * 4
+    H.bvchost_pack_dense.restype = C.c_int32
+    H.bvchost_pack_dense.argtypes = [C.POINTER(C.c_void_p), C.c_int64, C.c_void_p, C.c_int32, C.c_int64, C.c_int32] + [C.c_void_p] * 4
+    fits_seen = set()
+    for sites, two in RAGGED_TILES:
+        hs = [HostSite(H, *entries_of(rows)) for rows in sites]
+        arr = (C.c_void_p * max(1, len(hs)))(*[h.h for h in hs])
+        fits, offsets, a, b = ragged_model(sites, two)
+        n = int(offsets[-1])
+        got_off, packed = np.full(len(sites) + 1, -1, np.int64), np.zeros(n + 1, np.uint8)
+        bases, quals = np.zeros(n + 1, np.int8), np.zeros(n + 1, np.int8)
+        got = H.bvchost_pack_ragged(arr, len(hs), two, got_off.ctypes.data, packed.ctypes.data, bases.ctypes.data, quals.ctypes.data)
+        assert got == int(fits) and (got_off == offsets).all(), (sites, two)
+        if fits:
+            assert (packed[:n] == a).all(), (sites, two)
+        else:
+            assert (bases[:n] == a).all() and (quals[:n] == b).all(), (sites, two)
+        fits_seen.add((fits, two))
+    assert fits_seen == {(True, 0), (False, 0), (False, 1)}
+    gs = np.array(DENSE_GROUPS, np.uint8)
+    for sites, two in DENSE_TILES:
+        hs = [HostSite(H, *entries_of(rows)) for rows in sites]
+        arr = (C.c_void_p * len(hs))(*[h.h for h in hs])
+        fits, column_of, a, b = dense_model(sites, DENSE_GROUPS, 128, two)
+        n = len(sites) * 128
+        got_col, packed = np.zeros(8, np.int32), np.zeros(n, np.uint8)
+        bases, quals = np.zeros(n, np.int8), np.zeros(n, np.int8)
+        got = H.bvchost_pack_dense(arr, len(hs), gs.ctypes.data, 8, 128, two, got_col.ctypes.data, packed.ctypes.data, bases.ctypes.data, quals.ctypes.data)
+        assert got == int(fits) and (got_col == column_of).all(), (sites, two)
+        if fits:
+            assert (packed == a).all(), (sites, two)
+        else:
+            assert (bases == a).all() and (quals == b).all(), (sites, two)
+    assert [dense_model(s, DENSE_GROUPS, 128, t)[0] for s, t in DENSE_TILES] == [True, False, False]
+
+
+def test_block_walk_and_tile_packers_under_the_address_sanitizer(H, tmp_path):
+    """The same walk and the same tiles in a stand-alone program (tests/cpp/host_tiles_main.cpp + host/bgzf.cpp, inflate.cpp; the
+    packers are pileup.h's) built with -fsanitize=address,undefined: it must exit 0 and print what the struct walk and the numpy model say."""
+    import struct
+    import subprocess
+    files, _, _ = block_files(H, tmp_path)
+    want = []
+    for name, (path, blocks) in files.items():
+        want.append("walk refused: " + blocks if isinstance(blocks, str) else "walk %d:" % len(blocks) + "".join(" %d,%d,%d,%d,%d" % b for b in blocks))
+    tiles = [(0, s, t) for s, t in RAGGED_TILES] + [(1, s, t) for s, t in DENSE_TILES]
+    blob = struct.pack("<I", len(tiles))
+    for dense, sites, two in tiles:
+        blob += struct.pack("<III", dense, two, len(sites))
+        for rows in sites:
+            e, s = entries_of(rows)
+            blob += struct.pack("<I", len(rows)) + e.tobytes() + s.tobytes()
+        if dense:
+            blob += struct.pack("<I", len(DENSE_GROUPS)) + bytes(DENSE_GROUPS) + struct.pack("<I", 128)
+            fits, _, a, b = dense_model(sites, DENSE_GROUPS, 128, two)
+            offsets = ""
+        else:
+            fits, off, a, b = ragged_model(sites, two)
+            offsets = ",".join(str(int(o)) for o in off)
+        want.append("tile fits=%d offsets=%s a=%s b=%s" % (fits, offsets, a.astype(np.uint8).tobytes().hex(), "" if b is None else b.astype(np.uint8).tobytes().hex()))
+    path = tmp_path / "tiles.bin"
+    path.write_bytes(blob)
+    exe = str(tmp_path / "host_tiles")
+    host = os.path.join(ROOT, "basevarc_amd", "host")
+    subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+                           "-static-libasan", "-fno-omit-frame-pointer", "-pthread", "-I", host, "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "host_tiles_main.cpp")] +
+                          [os.path.join(host, f) for f in ("bgzf.cpp", "inflate.cpp")] + ["-lz", "-o", exe])
+    r = subprocess.run([exe, str(path)] + [p for p, _ in files.values()], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=120)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, text[-4000:]
+    assert text.split("\n")[:-1] == want
