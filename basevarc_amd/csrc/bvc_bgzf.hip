@@ -1,6 +1,8 @@
-// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip).
+// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip; with tuning key
+// "bgzf_codes" = 1 the block kernel of bgzf_dynamic_kernel.hip), and bvc_bgzf_code_lengths: that kernel's code-length builder on its own.
 // bvc_pileup_sample_bgzf (bvc_pileup.hip) hands a tile's sample columns to the same kernels where they are made.
 #include "bvc_ctx.h"
+#include "../../include/bvc_bgzf_codes.h"
 
 int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_data, const int64_t *d_off, const int64_t *d_len,
                         const int64_t *upper, uint8_t *d_comp, int64_t comp_cap, int64_t *d_comp_off, bool wait_for_upload)
@@ -16,7 +18,7 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
     // a call that returns with its launches in flight must not leave a transfer out of the page-locked buffer in flight too: the next
     // call on the context fills that buffer at once.  (The stream holds nothing but this copy here: its caller has just waited.)
     if (wait_for_upload) BVC_HIP_D(ctx, wait_stream(ctx));
-    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off));
+    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_codes));
     return BVC_OK;
 }
 
@@ -108,6 +110,38 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
     rc = bgzf_deflate_device(ctx, io, n_pieces, d_data, d_off, d_len, piece_len, d_comp, need, d_coff, false);
     if (rc != BVC_OK) return rc;
     return bgzf_blocks_down(ctx, io, n_pieces, d_comp, d_coff, comp, comp_off);
+}
+
+int bvc_bgzf_code_lengths(bvc_ctx *ctx, int64_t n_sets, const uint32_t *counts, int32_t n_symbols, int32_t limit, uint8_t *lengths)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (n_sets < 0 || n_sets > ((int64_t)1 << 22)) return fail(ctx, BVC_ERR_ARG, "n_sets < 0 or above 2^22");
+    if (n_symbols < 1 || n_symbols > 288) return fail(ctx, BVC_ERR_ARG, "n_symbols outside 1..288");
+    if (limit < 1 || limit > 15 || (1 << limit) < (n_symbols > 2 ? n_symbols : 2)) return fail(ctx, BVC_ERR_ARG, "limit outside 1..15 or 2^limit below n_symbols");
+    if (n_sets == 0) return BVC_OK;
+    if (!counts || !lengths) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    const size_t total = (size_t)n_sets * (size_t)n_symbols;
+    for (int64_t i = 0; i < n_sets; ++i) {
+        uint64_t sum = 0;
+        for (int32_t s = 0; s < n_symbols; ++s) sum += counts[(size_t)i * (size_t)n_symbols + (size_t)s];
+        if (sum >= ((uint64_t)1 << 24)) return fail(ctx, BVC_ERR_ARG, "the counts of a set sum to 2^24 or more");
+    }
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    uint32_t *d_counts; uint8_t *d_len;
+    int rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
+        d_counts = L.take<uint32_t>(total);
+        d_len = L.take<uint8_t>(total);
+    });
+    if (rc != BVC_OK) return rc;
+    PinIO io(ctx);
+    rc = io.reserve(total * 4 + 256, total + 256);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, io.h2d(d_counts, counts, total * 4));
+    BVC_HIP_D(ctx, launch_bgzf_code_lengths(ctx->stream, n_sets, d_counts, n_symbols, limit, d_len));
+    BVC_HIP_D(ctx, io.d2h(lengths, d_len, total));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    return BVC_OK;
 }
 
 }  // extern "C"

@@ -54,6 +54,9 @@ struct Knobs {
     // newline.  The .vcf.gz inflates to the same bytes; it is larger than zlib's level 6 makes it (profiles/vcf_deflate/README.txt).  Needs
     // device_samples; acts on device-parsed tiles only.  Off by default
     const bool device_deflate = num("BVC_HOST_DEVICE_DEFLATE", 0) != 0 && device_samples;
+    // 1: those blocks take a Huffman code of their own where that is smaller (tuning key "bgzf_codes" of the contexts, include/bvc.h):
+    // a smaller .vcf.gz that inflates to the same bytes.  Acts only with device_deflate.  Off by default
+    const bool device_deflate_codes = num("BVC_HOST_DEVICE_DEFLATE_CODES", 0) != 0 && device_deflate;
     const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

@@ -116,6 +116,12 @@ PROTOTYPES = {
     # not in the header: diagnostic builds of the library only export it (-DBVC_CHECK_LDS, csrc/bvc_device.h)
     "bvc_debug_report": (_int, [_vp, C.POINTER(_u32), _int]),
 }
+# The second header, include/bvc_bgzf_codes.h: the same kind of table, in that header's order (tests/test_bgzf_dynamic_abi.py compares
+# the two as tests/test_binding_abi.py compares the first with bvc.h), bound by bind() with the first.
+BGZF_CODES_PROTOTYPES = {
+    "bvc_bgzf_code_lengths": (_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
+}
+BGZF_CODES_EXPORTS = list(BGZF_CODES_PROTOTYPES)
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
@@ -129,9 +135,9 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
+    """Gives every function of PROTOTYPES and BGZF_CODES_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
     symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -309,7 +315,8 @@ class Context:
         return {tu: [int(x) for x in out[8 * i:8 * i + 6]] for i, tu in enumerate(("hist_kernel", "em_kernel", "em_items"))}
 
     def set_tuning(self, key, value):
-        """Launch policy of this context (include/bvc.h); results never depend on it."""
+        """Launch policy of this context (include/bvc.h); results never depend on it (but for "em_engine", "em_tiny_regions", "em_prune"
+        and "bgzf_codes", which the header describes)."""
         self._check(self._L.bvc_set_tuning(self._h, key.encode(), int(value)))
 
     def host_alloc(self, nbytes):
@@ -523,6 +530,16 @@ class Context:
         """bvc_pileup_sample_bgzf after a tile finished with sample_text=True: the called positions' sample columns as BGZF blocks into comp
         (uint8 array).  Returns (comp, comp_off [T + 1], text_len [T])."""
         return self._pileup_sample(self._L.bvc_pileup_sample_bgzf, n_positions, n_samples, comp, comp_cap)
+
+    def bgzf_code_lengths(self, counts, limit):
+        """bvc_bgzf_code_lengths (include/bvc_bgzf_codes.h): the code lengths (uint8, the shape of counts) the device deflate encoder's rule gives each row of counts
+        (uint32 [n_sets, n_symbols] or one row), none above limit (docs/BGZF_DYNAMIC.md)."""
+        c = _as(counts, np.uint32)
+        rows = c.reshape(-1, c.shape[-1]) if c.ndim else c.reshape(1, 1)
+        out = np.zeros(rows.shape, dtype=np.uint8)
+        self._check(self._L.bvc_bgzf_code_lengths(self._h, rows.shape[0], _np_ptr(rows) if rows.size else None, rows.shape[1], int(limit),
+                                                  _np_ptr(out) if out.size else None))
+        return out.reshape(c.shape)
 
     # ---- packed tiles: one byte per sample (base << 6 | qual, qual <= 62; 0xFF = no observation) ----
     def pack_dense_device(self, bases_t, quals_t, packed_t=None):

@@ -554,7 +554,12 @@ int bvc_synth_dense(bvc_ctx *ctx, uint64_t seed, int64_t site0, int64_t n_sites,
  *                      that subset's log-likelihood (every class marginal <= 1; the left-out allele's observations have
  *                      marginal e exactly) puts its chi above the minimum of the others: the decision, and every field of the
  *                      record the reference defines, is unchanged, the diagnostics n_fits / n_passes count what was run.  0 =
- *                      the subset is always run (n_fits / n_passes then equal the reference's counts).  Environment: BVC_EM_PRUNE. */
+ *                      the subset is always run (n_fits / n_passes then equal the reference's counts).  Environment: BVC_EM_PRUNE.
+ *   "bgzf_codes"       0 (default) / 1.  bvc_bgzf_deflate (host and device pointers) and bvc_pileup_sample_bgzf: with 0 every block is
+ *                      written in the fixed Huffman code, or stored; with 1 each block takes the smallest of stored, fixed and a
+ *                      Huffman code of its own (RFC 1951 BTYPE = 10; the rule is with bvc_bgzf_deflate below).  It changes the BYTES of
+ *                      the blocks, never what they inflate to, their number, their framing or the waits of the calls.  With 0
+ *                      nothing differs by a byte from a library without the key.  Environment: BVC_BGZF_CODES. */
 int bvc_set_tuning(bvc_ctx *ctx, const char *key, int value);
 
 /* ---- measurement aid ------------------------------------------------------------------------------- */
@@ -621,6 +626,22 @@ int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t 
  * Huffman codes, or stored where that is smaller) padded to a byte, CRC32 of the input bytes and ISIZE.  Matches stay inside the
  * block's own input (distances 1..32768, lengths 4..258).  The output is a pure function of the input bytes: the same pieces give the
  * same bytes on every run.  Concatenated in any order with other BGZF blocks and closed with the end-of-file marker they are a BGZF file.
+ *
+ * Tuning key "bgzf_codes" = 1 (bvc_set_tuning; default 0): the parse of a block -- its literals, lengths and distances -- stays the one
+ * above, and the block is written in a Huffman code of its own (BTYPE = 10) iff its deflate data is then SMALLER, in bytes, than in the
+ * form above (fixed, or stored); otherwise it is exactly the block key 0 writes.  Still one deflate block with BFINAL a BGZF block,
+ * still a pure function of the input bytes.  The code is a function of the block's symbol counts alone (docs/BGZF_DYNAMIC.md, in short):
+ *   (a) lengths of the literal/length alphabet (286 symbols, end of block counted once) and of the distance alphabet (30), limit 15:
+ *       the used symbols in the order of (count, symbol); a Huffman tree by two queues, a leaf before an internal node of the same weight,
+ *       internal nodes in the order they were made; leaves deeper than the limit are set to it and the Kraft sum is repaired by zlib's
+ *       move (the deepest leaf above the limit's level one level down, a leaf of the limit's level made its sibling) once per unit of
+ *       2^-limit; the multiset of lengths is then handed out longest first in the order of (count, symbol).  With fewer than two used
+ *       symbols the used one (if any) and the smallest unused symbols of 0 and 1, two in all, get length 1
+ *   (b) HLIT + HDIST lengths as ONE row (runs cross from the first alphabet into the second), greedily from the front: 11 or more zeros ->
+ *       symbol 18 (at most 138), 3..10 zeros -> 17, 3 or more repeats of the length just written -> 16 (at most 6), else the length itself
+ *   (c) HLIT, HDIST and HCLEN trimmed to the last used symbol (at least 257, 1 and 4)
+ *   (d) the code-length code (19 symbols, limit 7) by rule (a)    (e) canonical codes, RFC 1951 3.2.2
+ * bvc_bgzf_code_lengths (bvc_bgzf_codes.h) runs rule (a) on counts of the caller's.
  */
 #define BVC_BGZF_BLOCK_INPUT 65280
 /* Blocks of a piece: ceil(len / 65280), 0 for len <= 0. */
@@ -660,6 +681,7 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
  * memory.
  */
 int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len);
+/* Rule (a) of "bgzf_codes" on counts of the caller's -- bvc_bgzf_code_lengths -- is declared in bvc_bgzf_codes.h beside this header. */
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bgzf_deflate_kernel alone (bvc_bgzf_deflate, device pointers): the rate at which sample-column text becomes BGZF blocks.
 
-  python tools/bgzf_deflate_bench.py [--samples 100000] [--out profiles/vcf_deflate/kernel.txt]
+  python tools/bgzf_deflate_bench.py [--samples 100000] [--codes 0|1] [--out profiles/vcf_deflate/kernel.txt]
+
+--codes: the context's tuning key "bgzf_codes" (1: bgzf_deflate_dynamic_kernel, each block the smallest of stored, fixed and dynamic).
 
 The texts are the three of tests/bgzf_deflate_cases.py (one called site's sample columns at coverage 0.10, 0.01 and 1.0), each as one
 piece (one called position: 7 - 27 blocks, as many workgroups busy), as seven pieces (a tile's called positions) and as 64 pieces (more
@@ -45,6 +47,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--samples", type=int, default=100_000)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "vcf_deflate", "kernel.txt"))
+    ap.add_argument("--codes", type=int, default=0, choices=(0, 1))
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -52,7 +55,9 @@ def main():
     from basevarc_amd.lib import bgzf_blocks, bgzf_bound
     from tests import bgzf_deflate_cases as dc
     ctx = Context(0, stream=torch.cuda.current_stream())
-    lines = ["# tools/bgzf_deflate_bench.py: bvc_bgzf_deflate with device pointers; per row a warm-up, then "
+    if a.codes:
+        ctx.set_tuning("bgzf_codes", a.codes)
+    lines = [f"# tools/bgzf_deflate_bench.py --codes {a.codes}: bvc_bgzf_deflate with device pointers; per row a warm-up, then "
              f"{REPEATS} calls timed with HIP events (the wait for the pieces' lengths and the five launches)",
              "# out/in = packed bytes / input bytes; /z1, /z6 = packed bytes against zlib level 1 and 6 on the same 65280-byte cuts (+ 26 a block)",
              f"{'coverage':>8s} {'pieces':>6s} {'blocks':>6s} {'input MB':>9s} {'ms (3 repeats)':>26s} {'ms':>8s} {'GB/s':>7s} {'out/in':>7s} {'/z1':>6s} "
