@@ -1,0 +1,217 @@
+// bvc_bam.hip -- bvc_bam_pileup and bvc_bam_pileup_bgzf (include/bvc_bam.h): the inflated BAM records of a batch of samples -> the batch's
+// position records in the binary temp-batch form (bam_pileup_kernel.hip).  Two passes over the positions in tiles: sizes, one wait for
+// the total and the statuses, then the records.
+#include "bvc_ctx.h"
+#include "../../include/bvc_bam.h"
+
+namespace {
+
+// a call's inputs where the kernels read them (device memory), and its sizes
+struct BamCall {
+    int32_t n_samples = 0, n_positions = 0, beg0 = 0, end0 = 0, min_mapq = 0, rg_s = 0;
+    const uint8_t *bam = nullptr, *eof = nullptr, *ref = nullptr;
+    const int64_t *off = nullptr, *end = nullptr;
+    const int32_t *rid = nullptr, *pos = nullptr;
+    int64_t bam_bytes = 0, refseq_len = 0;
+};
+
+int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_positions, int64_t refseq_len, int64_t records_cap)
+{
+    if (n_samples < 0 || bam_bytes < 0 || n_positions < 0 || refseq_len < 0 || records_cap < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    return BVC_OK;
+}
+
+int check_host_arrays(bvc_ctx *ctx, int32_t n_samples, const int64_t *sample_off, const int64_t *sample_end, int64_t bam_bytes, int32_t n_positions,
+                      const int32_t *positions)
+{
+    for (int32_t s = 0; s < n_samples; ++s)
+        if (!(sample_off[s] >= (s ? sample_end[s - 1] : 0) && sample_end[s] >= sample_off[s] && sample_end[s] <= bam_bytes))
+            return fail(ctx, BVC_ERR_ARG, "the samples' ranges must lie inside bam, one behind the other");
+    for (int32_t t = 1; t < n_positions; ++t)
+        if (positions[t] <= positions[t - 1]) return fail(ctx, BVC_ERR_ARG, "positions must be strictly ascending");
+    return BVC_OK;
+}
+
+// The kernels of one call on inputs in device memory.  out_device: records, rec_start and sample_status are device memory and the call
+// returns with the second pass enqueued; else they are host memory (d_status: the statuses' place on the device) and the call waits.
+int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, uint32_t *d_status, uint8_t *records, int64_t records_cap,
+                   int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status)
+{
+    const size_t ns = (size_t)c.n_samples, np = (size_t)c.n_positions;
+    BamPileupScratch S;
+    int rc = carve(ctx, ctx->d_bam, 256, [&](Layout &L) { S = bam_pileup_scratch(L, c.bam_bytes, c.n_samples, c.n_positions); });
+    if (rc != BVC_OK) return rc;
+    auto tiles = [&](bool place, uint8_t *out) -> hipError_t {
+        for (int32_t t0 = 0; t0 < c.n_positions; t0 += S.tile) {
+            const int32_t tn = c.n_positions - t0 < S.tile ? c.n_positions - t0 : S.tile;
+            const hipError_t e = launch_bam_tile(ctx->stream, place, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.pos, t0, tn, c.rg_s, c.ref,
+                                                 c.refseq_len, S, d_status, out);
+            if (e != hipSuccess) return e;
+        }
+        return hipSuccess;
+    };
+    BVC_HIP_D(ctx, launch_bam_index(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.eof, c.rid, c.beg0, c.end0, c.min_mapq, S, d_status));
+    BVC_HIP_D(ctx, tiles(false, nullptr));
+    BVC_HIP_D(ctx, launch_bam_scan(ctx->stream, c.n_positions, c.n_samples, S, d_status));
+    int64_t head[4] = {0, 0, 0, 0};
+    BVC_HIP_D(ctx, io.d2h(head, S.head, sizeof head));
+    if (!out_device && ns) BVC_HIP_D(ctx, io.d2h(sample_status, d_status, ns * 4));
+    BVC_HIP_D(ctx, wait_stream(ctx));               // the one wait of a device-pointer call: the size and the statuses decide what it returns
+    io.deliver();
+    const int64_t none = 0x7FFFFFFF, bad = head[2] < head[3] ? head[2] : head[3];
+    char msg[160];
+    if (bad != none) {
+        std::snprintf(msg, sizeof msg, "sample %lld: %s", (long long)bad,
+                      head[2] == bad ? "truncated or corrupt BAM record" : "index offset is out of range of the sequence");
+        return fail(ctx, BVC_ERR_DATA, msg);
+    }
+    if (head[1] != none) {
+        std::snprintf(msg, sizeof msg, "sample %lld: the bytes ran out before a stop record", (long long)head[1]);
+        return fail(ctx, BVC_BAM_MORE, msg);
+    }
+    const int64_t need = head[0];
+    *records_needed = need;
+    if (need > (int64_t)0xFFFFFF00u) return fail(ctx, BVC_ERR_ARG, "the records exceed 0xFFFFFF00 bytes (split the positions)");
+    if (need > records_cap) {
+        (void)fail_cap(ctx, "records", records_cap, "the batch's records", need);
+        return BVC_BAM_MORE;
+    }
+    uint8_t *d_records = records;
+    if (!out_device) {
+        rc = ensure(ctx, ctx->d_bam_out, (size_t)need + 256);
+        if (rc != BVC_OK) return rc;
+        d_records = reinterpret_cast<uint8_t *>(ctx->d_bam_out.p);
+    }
+    BVC_HIP_D(ctx, hipMemsetAsync(S.carry, 0, ns ? ns : 1, ctx->stream));
+    BVC_HIP_D(ctx, tiles(true, d_records));
+    if (out_device) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(rec_start, S.rec_start, (np + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        return BVC_OK;
+    }
+    BVC_HIP_D(ctx, io.d2h(rec_start, S.rec_start, (np + 1) * 4));
+    if (need) BVC_HIP_D(ctx, hipMemcpyAsync(records, d_records, (size_t)need, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    return BVC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bvc_bam_pileup(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                   const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq,
+                   int32_t n_positions, const int32_t *positions, int32_t rg_s, const char *refseq, int64_t refseq_len,
+                   uint8_t *records, int64_t records_cap, int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status,
+                   uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (records_needed) *records_needed = 0;
+    int rc = check_sizes(ctx, n_samples, bam_bytes, n_positions, refseq_len, records_cap);
+    if (rc != BVC_OK) return rc;
+    if (!records_needed || !rec_start || (n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) ||
+        (bam_bytes > 0 && !bam) || (n_positions > 0 && !positions) || (refseq_len > 0 && !refseq) || (records_cap > 0 && !records))
+        return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const bool device = (flags & BVC_PTR_DEVICE) != 0;
+    const size_t ns = (size_t)n_samples, np = (size_t)n_positions;
+    if (!device) {
+        rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions);
+        if (rc != BVC_OK) return rc;
+    }
+    PinIO io(ctx);
+    rc = io.reserve(device ? 0 : ns * 21 + np * 4 + 1024, 64 + ns * 4 + (np + 1) * 4 + 1024);
+    if (rc != BVC_OK) return rc;
+    BamCall c;
+    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
+    c.bam = bam; c.eof = sample_eof; c.ref = reinterpret_cast<const uint8_t *>(refseq); c.off = sample_off; c.end = sample_end; c.rid = rid;
+    c.pos = positions; c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
+    uint32_t *d_status = sample_status;
+    if (!device) {                                  // host pointers: the inputs live in the staging buffer for the length of the call
+        uint8_t *u_bam, *u_eof, *u_ref; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
+        rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+            u_bam = L.take<uint8_t>((size_t)bam_bytes); u_ref = L.take<uint8_t>((size_t)refseq_len);
+            u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
+            u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
+        });
+        if (rc != BVC_OK) return rc;
+        // the records and the reference are the bulk: straight from the caller's memory (a DMA where it is page-locked)
+        if (bam_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, bam, (size_t)bam_bytes, hipMemcpyHostToDevice, ctx->stream));
+        if (refseq_len) BVC_HIP_D(ctx, hipMemcpyAsync(u_ref, refseq, (size_t)refseq_len, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
+        BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
+        BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
+        BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
+        BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
+        c.bam = u_bam; c.ref = u_ref; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
+    }
+    return run_bam_pileup(ctx, io, c, device, d_status, records, records_cap, records_needed, rec_start, sample_status);
+}
+
+int bvc_bam_pileup_bgzf(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                        int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                        int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                        const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
+                        uint32_t *rec_start, uint32_t *sample_status)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (records_needed) *records_needed = 0;
+    int rc = check_sizes(ctx, n_samples, bam_bytes, n_positions, refseq_len, records_cap);
+    if (rc != BVC_OK) return rc;
+    if (comp_bytes < 0 || n_blocks < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    if (!records_needed || !rec_start || (n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) ||
+        (n_blocks > 0 && (!comp || !blocks)) || (n_positions > 0 && !positions) || (refseq_len > 0 && !refseq) || (records_cap > 0 && !records))
+        return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    for (int64_t i = 0; i < n_blocks; ++i) {
+        const bvc_bgzf_block &b = blocks[i];
+        if (b.comp_off < 0 || b.comp_len < 0 || b.comp_off + b.comp_len > comp_bytes || b.isize < 0 || b.isize > 65536 || b.out_off < 0 ||
+            b.out_off + b.isize > bam_bytes)
+            return fail(ctx, BVC_ERR_ARG, "block outside its buffer");
+    }
+    rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions);
+    if (rc != BVC_OK) return rc;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ns = (size_t)n_samples, np = (size_t)n_positions, nb = (size_t)n_blocks;
+    PinIO io(ctx);
+    rc = io.reserve(ns * 21 + np * 4 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + (np + 1) * 4 + nb * 4 + 1024);
+    if (rc != BVC_OK) return rc;
+    uint8_t *u_comp, *u_bam, *u_eof, *u_ref; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
+        u_bam = L.take<uint8_t>((size_t)bam_bytes); u_ref = L.take<uint8_t>((size_t)refseq_len);
+        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
+        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
+    });
+    if (rc != BVC_OK) return rc;
+    std::vector<uint32_t> block_status(nb);
+    if (nb) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
+        // (the bytes between the blocks' outputs, if the caller left any, are no sample's: nothing reads them)
+        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
+        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
+    }
+    if (refseq_len) BVC_HIP_D(ctx, hipMemcpyAsync(u_ref, refseq, (size_t)refseq_len, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
+    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
+    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
+    BamCall c;
+    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
+    c.bam = u_bam; c.ref = u_ref; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos; c.bam_bytes = bam_bytes;
+    c.refseq_len = refseq_len;
+    // the pileup's first wait delivers the blocks' statuses too: a block that did not inflate (or failed its CRC32) outranks what the
+    // kernels made of its bytes
+    rc = run_bam_pileup(ctx, io, c, false, d_status, records, records_cap, records_needed, rec_start, sample_status);
+    for (size_t i = 0; i < nb; ++i)
+        if (block_status[i] != 0) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "BGZF block %lld: %s", (long long)i, block_status[i] == 10 ? "CRC32 mismatch" : "not valid deflate of its ISIZE bytes");
+            *records_needed = 0;
+            return fail(ctx, BVC_ERR_DATA, msg);
+        }
+    return rc;
+}
+
+}  // extern "C"

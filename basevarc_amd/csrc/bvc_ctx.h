@@ -95,6 +95,7 @@ struct bvc_ctx {
     PileupState pile;
     DevBuf d_vcf, d_vcf_lut;           // vcf_samples_kernel.hip: the plan's scratch (device-pointer calls); the 256 x 8 bytes of bvc_vcf_bp_lut
     DevBuf d_bgzf, d_bgzf_io;          // bgzf_deflate_kernel.hip: block tables, match rows, staged blocks; a call's staged pieces (host pointers), its packed blocks and comp_off
+    DevBuf d_bam, d_bam_out;           // bam_pileup_kernel.hip: the read table, one tile's size matrix, the per-position sizes; a host-pointer call's records
     // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
     // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
     char *h_up = nullptr, *h_down = nullptr;

@@ -263,6 +263,34 @@ hipError_t launch_bgzf_code_lengths(hipStream_t stream, int64_t n_sets, const ui
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);
 
+// bam_pileup_kernel.hip: inflated BAM alignment records of a batch of samples -> the batch's position records in the binary temp-batch
+// form (include/bvc_bam.h, bvc_bam_pileup).  launch_bam_index fills the read table (the kept reads of sample s from slot
+// sample_off[s] / kBamMinRecord on: a record takes at least that many bytes, so the slices cannot meet) and sample_status 0..3;
+// launch_bam_tile(place = false) leaves rec_len of the tile's positions (and status 4); launch_bam_scan leaves rec_start and head (the
+// total, the first sample of status 2, 3, 4 or 0x7FFFFFFF); launch_bam_tile(place = true) writes the tile's records.  The scratch is the
+// read table + a size matrix of one tile of positions + O(n_positions + n_samples).
+constexpr int64_t kBamMinRecord = 36;    // block_size word + the 32 fixed bytes read_record insists on
+struct BamRead { int64_t off; int32_t pos, end; };      // the record's block_size word in bam; 0-based start; end_pos
+// positions per tile: 1024, fewer for wide batches (about 4 Mi cells), never below a wavefront's 64
+inline int32_t bam_pileup_tile(int32_t n_samples)
+{
+    const int64_t t = (((int64_t)1 << 22) / (n_samples > 0 ? n_samples : 1)) / 64 * 64;
+    return (int32_t)(t < 64 ? 64 : t > 1024 ? 1024 : t);
+}
+struct BamPileupScratch {
+    int32_t tile = 0;
+    BamRead *reads = nullptr; int32_t *runmax = nullptr; uint32_t *n_reads = nullptr; uint8_t *carry = nullptr; uint32_t *cell = nullptr;
+    uint64_t *rec_len = nullptr; uint32_t *rec_start = nullptr; int64_t *head = nullptr;
+};
+BamPileupScratch bam_pileup_scratch(Layout &L, int64_t bam_bytes, int32_t n_samples, int32_t n_positions);
+hipError_t launch_bam_index(hipStream_t stream, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                            const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq,
+                            const BamPileupScratch &s, uint32_t *sample_status);
+hipError_t launch_bam_tile(hipStream_t stream, bool place, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                           const int64_t *sample_end, const int32_t *positions, int32_t t0, int32_t tile_n, int32_t rg_s, const uint8_t *refseq, int64_t refseq_len,
+                           const BamPileupScratch &s, uint32_t *sample_status, uint8_t *records);
+hipError_t launch_bam_scan(hipStream_t stream, int32_t n_positions, int32_t n_samples, const BamPileupScratch &s, const uint32_t *sample_status);
+
 #ifdef BVC_CHECK_LDS
 hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);

@@ -112,7 +112,7 @@ static bool read_record(BgzfReader &r, BamRecord &rec, std::vector<unsigned char
 }
 
 // Smallest virtual offset of an alignment overlapping the 16 kbp window of `beg`, from the .bai linear index.
-static bool bai_linear_offset(const std::string &bam_path, int rid, int32_t beg, uint64_t &voff)
+bool bai_linear_offset(const std::string &bam_path, int rid, int32_t beg, uint64_t &voff, bool clamp)
 {
     FILE *f = std::fopen((bam_path + ".bai").c_str(), "rb");
     if (!f) {
@@ -140,7 +140,7 @@ static bool bai_linear_offset(const std::string &bam_path, int rid, int32_t beg,
                 int32_t w = beg >> 14;
                 if (w < 0) w = 0;
                 if (n_intv > 0) {
-                    if (w >= n_intv) w = n_intv - 1;
+                    if (w >= n_intv) { if (!clamp) break; w = n_intv - 1; }
                     if (std::fseek(f, (long)w * 8, SEEK_CUR) == 0 && std::fread(b, 1, 8, f) == 8) {
                         voff = 0;
                         for (int i = 0; i < 8; ++i) voff |= (uint64_t)b[i] << (8 * i);

@@ -40,11 +40,17 @@ class BamFile {
     // Records overlapping [beg, end) of reference `rid` (0-based), duplicates and MAPQ < mapq dropped
     // (src/BamProcess.cpp:295-300).  Uses the .bai linear index when present, else scans the file.
     bool fetch(int rid, int32_t beg, int32_t end, int min_mapq, std::vector<BamRecord> &out);
+    const std::string &path() const { return path_; }
+    uint64_t first_record() const { return first_record_; }   // virtual offset of the first alignment record
  private:
     std::string path_, header_;
     std::vector<std::string> ref_names_;
     uint64_t first_record_ = 0;
 };
+
+// Smallest virtual offset of an alignment overlapping the 16 kbp window of `beg` (.bai linear index); false: no index, no such
+// reference, an empty slot.  clamp: a window past the index takes the last one (fetch's start); else it is "not found"
+bool bai_linear_offset(const std::string &bam_path, int rid, int32_t beg, uint64_t &voff, bool clamp = true);
 
 typedef std::unordered_map<int32_t, AlleleInfo> PosAlleleMap;   // src/BamProcess.h:40
 // BamProcess::FindSnpAtPos (src/BamProcess.cpp:4-94): first usable read per position.

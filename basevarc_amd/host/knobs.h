@@ -57,6 +57,10 @@ struct Knobs {
     // 1: those blocks take a Huffman code of their own where that is smaller (tuning key "bgzf_codes" of the contexts, include/bvc.h):
     // a smaller .vcf.gz that inflates to the same bytes.  Acts only with device_deflate.  Off by default
     const bool device_deflate_codes = num("BVC_HOST_DEVICE_DEFLATE_CODES", 0) != 0 && device_deflate;
+    // 1: phase 1 (bt_r) on the device -- the batch's BAM blocks are gathered, inflated and piled up there (bvc_bam_pileup_bgzf) and the
+    // temp batches written from the records that come back; acts with --tmp-format bin|raw, ignored with text.  The batch files inflate
+    // to the same bytes.  Off by default (profiles/bam_pileup/README.txt)
+    const bool device_pileup = num("BVC_HOST_DEVICE_PILEUP", 0) != 0;
     const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

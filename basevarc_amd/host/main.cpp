@@ -14,7 +14,9 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <ctime>
+#include <deque>
 #include <fstream>
 #include <iostream>
 #include <map>
@@ -25,7 +27,9 @@
 #include <tuple>
 #include <unordered_map>
 
+#include "../../include/bvc_bam.h"
 #include "bam.h"
+#include "bam_blocks.h"
 #include "feeds.h"
 
 using namespace bvchost;
@@ -200,6 +204,121 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
     }
     for (auto &fp : fpv)
         if (!fp.close()) std::cerr << "warning: file cannot be closed" << std::endl;
+}
+
+// ---- phase 1 on the device (BVC_HOST_DEVICE_PILEUP, --tmp-format bin|raw): the batch's BAM blocks are gathered as they lie in the files,
+// inflated and piled up by ONE library call, and the records that come back are cut at the threads' windows as bt_r cuts them.  Headers
+// and the .bai index stay on the CPU.
+static std::atomic<long> g_device_batches(0);
+static std::atomic<int> g_load_threads(0);
+// a pool thread's context and page-locked buffer: made at its first batch, on the device device_of_thread gives, gone with the thread
+struct LoadDevice {
+    bvc_ctx *ctx = nullptr;
+    unsigned char *pin = nullptr;
+    size_t pin_cap = 0;
+    ~LoadDevice() { if (pin) bvc_host_free(pin); if (ctx) bvc_destroy(ctx); }
+};
+
+static void bt_r_device(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
+                        const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus)
+{
+    static thread_local LoadDevice dev;
+    if (!dev.ctx && bvc_create(&dev.ctx, device_of_thread(g_load_threads++, gpus, opt::gpus)) != BVC_OK)
+        throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
+    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    std::string names;
+    std::vector<std::string> sms;
+    std::vector<int32_t> rid(ns);
+    std::vector<uint64_t> first_record(ns);
+    std::deque<MappedFile> files;
+    for (size_t b = b0; b < b1; ++b) {
+        BamFile reader;
+        if (!reader.open(bams[b])) throw std::runtime_error("ERROR: can not open file " + bams[b]);
+        if (!reader.sorted())
+            throw std::runtime_error("ERROR: BAM file does not appear to be sorted (no SO:coordinate) found in header.\n       Sorted BAMs are required.");
+        sms.push_back(reader.sample_name());
+        names += sms.back() + '\t';
+        rid[b - b0] = reader.ref_index(chr);
+        first_record[b - b0] = reader.first_record();
+        files.emplace_back(bams[b]);
+        if (!files.back().ok()) throw std::runtime_error("ERROR: can not open file " + bams[b]);
+    }
+    names += "\n";
+    std::vector<BamBlocks> lists(ns);
+    std::vector<uint8_t> to_eof(ns, 0), eof(ns);
+    std::vector<int64_t> off(ns), end(ns);
+    std::vector<uint32_t> status(ns), rec_start(pv.size() + 1);
+    std::vector<bvc_bgzf_block> table;
+    std::vector<uint8_t> records;
+    for (int attempt = 0;; ++attempt) {
+        std::string err;
+        size_t comp_bytes = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            if (rid[s] < 0) { lists[s] = BamBlocks(); lists[s].to_eof = true; continue; }
+            if (attempt > 0 && !to_eof[s]) continue;                  // (its list stands)
+            if (!bam_region_blocks(files[s], bams[b0 + s], first_record[s], rid[s], beg0, end0, to_eof[s] != 0, lists[s], err)) throw std::runtime_error(err);
+        }
+        for (auto const &l : lists) comp_bytes += l.comp_bytes;
+        if (comp_bytes + 16 > dev.pin_cap) {
+            if (dev.pin) bvc_host_free(dev.pin);
+            dev.pin_cap = comp_bytes + comp_bytes / 4 + 4096;
+            dev.pin = static_cast<unsigned char *>(bvc_host_alloc(dev.pin_cap));
+            if (!dev.pin) { dev.pin_cap = 0; throw std::runtime_error("ERROR: page-locked allocation failed"); }
+        }
+        table.clear();
+        int64_t comp_at = 0, out_at = 0;
+        for (size_t s = 0; s < ns; ++s) {
+            off[s] = out_at + lists[s].first_off;
+            for (auto const &blk : lists[s].blocks) {
+                std::memcpy(dev.pin + comp_at, blk.payload, blk.len);
+                table.push_back(bvc_bgzf_block{comp_at, out_at, (int32_t)blk.len, (int32_t)blk.isize, blk.crc32, 1u});
+                comp_at += (int64_t)blk.len;
+                out_at += (int64_t)blk.isize;
+            }
+            end[s] = out_at;
+            if (off[s] > end[s]) off[s] = end[s];
+            eof[s] = lists[s].to_eof ? 1 : 0;
+        }
+        int64_t need = 0;
+        int rc;
+        for (;;) {
+            rc = bvc_bam_pileup_bgzf(dev.ctx, (int32_t)ns, dev.pin, comp_at, table.data(), (int64_t)table.size(), out_at, off.data(), end.data(),
+                                     eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(), rg_s, refseq.data(),
+                                     (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(), status.data());
+            if (rc != BVC_BAM_MORE || need <= (int64_t)records.size()) break;
+            records.resize((size_t)need);
+        }
+        if (rc == BVC_OK) { records.resize((size_t)need); break; }
+        if (rc == BVC_BAM_MORE && attempt == 0) {                     // a list that stopped short of its region's end: that sample to the file's end, once
+            for (size_t s = 0; s < ns; ++s) to_eof[s] = status[s] == 2u;
+            continue;
+        }
+        if (rc == BVC_ERR_DATA)
+            for (size_t s = 0; s < ns; ++s) {
+                // the messages of the CPU path: fetch's, and find_snp_at_pos's std::out_of_range
+                if (status[s] == 3u) throw std::runtime_error("ERROR: truncated or corrupt BAM record in " + bams[b0 + s]);
+                if (status[s] == 4u) throw std::out_of_range("index offset is out of range of the sequence");
+            }
+        throw std::runtime_error(std::string("ERROR: device pileup failed: ") + bvc_last_error(dev.ctx));
+    }
+    for (size_t s = 0; s < ns; ++s)
+        if (rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << sms[s] << " region " << opt::region << " is empty." << std::endl;
+    const int level = opt::tmp_format == "raw" ? 0 : 6;
+    const std::vector<size_t> cuts = window_cuts(pv.size(), thread);
+    size_t lo = 0;
+    for (int i = 0; i < thread; ++i) {
+        BgzfWriter fp(tmp_name(i, ib), level);
+        if (!fp.ok()) throw std::runtime_error("ERROR: fail to write " + tmp_name(i, ib));
+        std::string h;
+        bin_batch_header((uint32_t)ns, names, h);
+        fp.write(h);
+        const size_t hi = cuts[(size_t)i];
+        fp.write(reinterpret_cast<const char *>(records.data()) + rec_start[lo], (size_t)(rec_start[hi] - rec_start[lo]));
+        lo = hi;
+        if (!fp.close()) std::cerr << "warning: file cannot be closed" << std::endl;
+    }
+    ++g_device_batches;
 }
 
 // ---- phase 2: temp batches -> tiles -> libbvc -> CVG/VCF (successor of bt_s + bt_f; the tiles' three stages: tile_runner.h, what
@@ -399,15 +518,21 @@ static void run_basetype(int argc, char **argv)                          // src/
     int first_batch = 0;
     bool extract = true;
     if (opt::rerun && ngz > 0) { extract = ngz != thread * nb; first_batch = bk; }
+    const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
     if (extract) {
         std::cerr << "begin to extract reads from bam" << std::endl;
-        run_pool(nb - first_batch, thread, [&](int t) { bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread); });
+        if (knobs.device_pileup && opt::tmp_format != "text") {
+            const int load_gpus = bvc_device_count();
+            if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus); });
+            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches (bvc_bam_pileup_bgzf)" << std::endl;
+        } else
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread); });
     }
     time_t tim1 = time(0);
     const double t_loaded = StageClock::now();
     std::cout << "basetype loading done -- " << ctime(&tim1);
     if (opt::load) std::exit(EXIT_SUCCESS);
-    const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
     DeviceSlots slots(knobs.device_slots);
     const int gpus = bvc_device_count();
     if (gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");

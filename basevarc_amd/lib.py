@@ -122,6 +122,14 @@ BGZF_CODES_PROTOTYPES = {
     "bvc_bgzf_code_lengths": (_int, [_vp, _i64, _vp, _i32, _i32, _vp]),
 }
 BGZF_CODES_EXPORTS = list(BGZF_CODES_PROTOTYPES)
+# The third header, include/bvc_bam.h (tests/test_bam_pileup_abi.py compares the two), bound by bind() with the others.
+BAM_PROTOTYPES = {
+    "bvc_bam_pileup": (_int, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64, _pi64, _vp, _vp, _u32]),
+    "bvc_bam_pileup_bgzf": (_int, [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _i64, _vp, _i64,
+                                   _pi64, _vp, _vp]),
+}
+BAM_EXPORTS = list(BAM_PROTOTYPES)
+BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
@@ -135,9 +143,9 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES and BGZF_CODES_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES and BAM_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
     symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()):
+    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -741,6 +749,51 @@ class Context:
         status = np.zeros(max(1, len(blocks)), dtype=np.uint32)
         self._call(self._L.bvc_inflate_blocks, False, (buf, len(buf), tab, len(blocks), out, at, status))
         return [out[int(t["out_off"]):int(t["out_off"]) + int(t["isize"])].tobytes() for t in tab[:len(blocks)]], status[:len(blocks)]
+
+    def bam_pileup(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq, records=None, records_cap=None,
+                   rec_start=None, sample_status=None):
+        """bvc_bam_pileup (include/bvc_bam.h): the inflated BAM records of a batch of samples -> the batch's binary temp-batch records.
+        numpy arrays (synchronous) or tensors on this context's device (asynchronous but for one wait): bam uint8, sample_off and
+        sample_end int64 [n], sample_eof uint8 [n], rid int32 [n], positions int32 (1-based, ascending), refseq uint8 (the reference's characters).
+        records / rec_start / sample_status: buffers to write into (uint8, uint32 [P + 1], uint32 [n]); without records the call is made
+        twice, the second time with a buffer of the size the first reports.  records_cap: what to tell the library instead of len(records).
+        Returns (rc, records, rec_start, sample_status, records_needed): rc 0, or BAM_MORE (2) when a sample's status is 2 or records is
+        too small -- nothing is written then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4)."""
+        device = hasattr(bam, "data_ptr")
+        if device:
+            import torch
+            new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=bam.device)
+            u8, u32, size = torch.uint8, torch.int32, lambda a: a.numel()
+        else:
+            bam, sample_off, sample_end = _as(bam, np.uint8), _as(sample_off, np.int64), _as(sample_end, np.int64)
+            sample_eof, rid = _as(sample_eof, np.uint8), _as(rid, np.int32)
+            positions, refseq = _as(positions, np.int32), _as(refseq, np.uint8)
+            new = lambda n, dt: np.zeros(max(1, n), dtype=dt)
+            u8, u32, size = np.uint8, np.uint32, len
+        n, P = size(rid), size(positions)
+        if size(sample_off) != n or size(sample_end) != n or size(sample_eof) != n:
+            raise ValueError("sample_off, sample_end and sample_eof must be [n_samples]")
+        rec_start = new(P + 1, u32) if rec_start is None else rec_start
+        sample_status = new(n, u32) if sample_status is None else sample_status
+        need = C.c_int64(0)
+        ptr = _dev_ptr if device else _np_ptr
+        opt = lambda a: a if a is not None and size(a) else None
+
+        def call(buf, cap):
+            rc = self._L.bvc_bam_pileup(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0), int(end0),
+                                                               int(min_mapq), P, opt(positions), int(rg_s), opt(refseq), size(refseq), opt(buf), cap),
+                                                              ptr), C.byref(need), ptr(rec_start), ptr(sample_status) if n else None,
+                                        BVC_PTR_DEVICE if device else BVC_PTR_HOST)
+            if rc not in (0, BAM_MORE):
+                self._check(rc)
+            return rc
+        if records is None:
+            rc = call(None, 0)
+            if rc == 0 or need.value == 0:
+                return rc, new(0, u8)[:0], rec_start, sample_status, need.value
+            records = new(need.value, u8)
+        rc = call(records, size(records) if records_cap is None else int(records_cap))
+        return rc, records[:need.value] if rc == 0 else records, rec_start, sample_status, need.value
 
     # ---- a cohort in sample chunks: counts that accumulate (include/bvc.h).  `counts` is added to IN PLACE: a uint32 / int32 array of
     # [n_sites, 512] (plain) or [n_sites, n_groups + 1, 512] (groups; slot n_groups = in no group), numpy with the host calls, a tensor

@@ -44,6 +44,8 @@ extern "C" {
                                     bvc_pileup_begin_bin: a binary record is malformed.  The context stays usable */
 #define BVC_PILEUP_IRREGULAR 1   /* bvc_pileup_begin only, not an error: a line of the tile is not of the shape the reference's
                                     writer produces; nothing was computed, parse this tile with the reference's own rules */
+#define BVC_BAM_MORE         2   /* bvc_bam_pileup only (bvc_bam.h), not an error: a sample's bytes ran out before its stop record, or
+                                    records_cap is below *records_needed; nothing was written, supply more and call again */
 
 /* flags for the compute entry points */
 #define BVC_PTR_HOST    0u       /* every data pointer is host memory; the call is synchronous */
@@ -682,6 +684,8 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
  */
 int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len);
 /* Rule (a) of "bgzf_codes" on counts of the caller's -- bvc_bgzf_code_lengths -- is declared in bvc_bgzf_codes.h beside this header. */
+/* Phase 1 on the device -- bvc_bam_pileup: inflated BAM records of a batch of samples -> the batch's binary position records -- is declared
+ * in bvc_bam.h beside this header. */
 
 #ifdef __cplusplus
 }

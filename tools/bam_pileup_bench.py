@@ -1,0 +1,118 @@
+#!/usr/bin/env python3
+"""Phase 1 of `BaseVarC basetype` with BVC_HOST_DEVICE_PILEUP at 0 and at 1 (needs a gfx950 device): the load phase (--load) of the host
+program on the 100 test BAMs and on a larger list that names each of them several times, at 1, 4 and 8 threads; and bvc_bam_pileup alone
+on the inflated records of the 100 test BAMs in device memory, next to a plain streaming read of the same bytes.
+
+  python tools/bam_pileup_bench.py [--copies 20] [--repeats 3] [--out profiles/bam_pileup/README.txt]
+
+The larger list repeats the same files (and so the same sample names, which the load phase does not look at): the page cache serves both
+runs alike.  Every time is the best of --repeats wall-clock runs of the whole process, start-up and the context's creation included."""
+import argparse
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+class Lines(list):
+    """The report's lines, shown as they come."""
+
+    def append(self, line):
+        list.append(self, line)
+        print(line, flush=True)
+
+
+def load_seconds(exe, lst, fa, region, out, threads, batch, knob, fmt, repeats):
+    best = None
+    for _ in range(repeats):
+        t = time.perf_counter()
+        r = subprocess.run([exe, "basetype", "--load", "--tmp-format", fmt, "-q", "20", "-t", str(threads), "-b", str(batch), "-i", lst, "-s", region,
+                            "-r", fa, "-o", out], capture_output=True, text=True, env=dict(os.environ, BVC_HOST_DEVICE_PILEUP=str(knob)))
+        dt = time.perf_counter() - t
+        if r.returncode != 0:
+            raise RuntimeError(r.stderr[-2000:])
+        best = dt if best is None else min(best, dt)
+    return best
+
+
+def kernel_pair(lines, repeats):
+    import numpy as np
+    import torch
+    from basevarc_amd import Context
+    from tests.test_bam_pileup_abi import bam_data_bytes, bam_data_call
+    contig, beg0, end0, mapq, pv, rg_s, refseq = bam_data_call()
+    data = bam_data_bytes()
+    bam = b"".join(d for d, _, _ in data)
+    off, end, at = [], [], 0
+    n_records = 0
+    for d, first, _ in data:
+        off.append(at + first)
+        at += len(d)
+        end.append(at)
+        q = first
+        while q < len(d):
+            q += 4 + int.from_bytes(d[q:q + 4], "little")
+            n_records += 1
+    dev = lambda a: torch.from_numpy(a).cuda()
+    ctx = Context(0)
+    d_bam = dev(np.frombuffer(bam, dtype=np.uint8).copy())
+    args = (d_bam, dev(np.array(off, dtype=np.int64)), dev(np.array(end, dtype=np.int64)), torch.ones(len(data), dtype=torch.uint8, device="cuda"),
+            dev(np.array([refs.index(contig) for _, _, refs in data], dtype=np.int32)), beg0, end0, mapq, dev(np.array(pv, dtype=np.int32)), rg_s,
+            dev(np.frombuffer(refseq.encode(), dtype=np.uint8).copy()))
+    rc, rec, rs, st, need = ctx.bam_pileup(*args)                        # sizes the scratch and the records
+    assert rc == 0
+    best = None
+    for _ in range(repeats + 2):
+        ctx.synchronize()
+        t = time.perf_counter()
+        ctx.bam_pileup(*args, records=rec, rec_start=rs, sample_status=st)
+        ctx.synchronize()
+        dt = time.perf_counter() - t
+        best = dt if best is None else min(best, dt)
+    gbs = ctx.stream_read_gbs(d_bam, repeats=5)
+    lines.append(f"bvc_bam_pileup alone, device pointers, 100 samples x {len(pv)} positions, {len(bam)} inflated bytes, {n_records} alignment records, "
+                 f"{need} bytes of position records:")
+    lines.append(f"  {best * 1e3:.2f} ms a call (index + two passes of sizes + placement, one wait): {n_records / best / 1e6:.2f} M alignment records/s, "
+                 f"{len(bam) / best / 1e9:.3f} GB/s of BAM bytes, {len(pv) * len(data) / best / 1e6:.1f} M (position, sample) cells/s")
+    lines.append(f"  bvc_stream_read_ms on the same bytes: {gbs:.0f} GB/s")
+    ctx.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--copies", type=int, default=20)
+    ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    from basevarc_amd import build as b
+    from tests import hostref
+    exe, _ = b.build_host()
+    lines = Lines()
+    lines.append("# phase 1 (bt_r) with BVC_HOST_DEVICE_PILEUP = 0 | 1: tools/bam_pileup_bench.py, best of %d runs, seconds of the whole --load process" % a.repeats)
+    with tempfile.TemporaryDirectory() as d:
+        fa = hostref.write_fasta(os.path.join(d, "chr17.fa"))
+        lst = hostref.write_bam_list(os.path.join(d, "bam.list"))
+        big = os.path.join(d, "big.list")
+        with open(big, "w") as f:
+            f.write(open(lst).read() * a.copies)
+        for name, path, batch in (("100 test BAMs, batches of 10", lst, 10), (f"{100 * a.copies} samples (each test BAM {a.copies} times), batches of 100", big, 100)):
+            lines.append(f"{name}, --tmp-format raw")
+            lines.append(f"  {'threads':>7s} {'knob 0':>9s} {'knob 1':>9s} {'1 / 0':>7s}")
+            for threads in (1, 4, 8):
+                t0 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o0"), threads, batch, 0, "raw", a.repeats)
+                t1 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o1"), threads, batch, 1, "raw", a.repeats)
+                lines.append(f"  {threads:7d} {t0:9.2f} {t1:9.2f} {t1 / t0:7.2f}")
+    kernel_pair(lines, a.repeats)
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
