@@ -291,6 +291,15 @@ hipError_t launch_bam_tile(hipStream_t stream, bool place, int32_t n_samples, co
                            const BamPileupScratch &s, uint32_t *sample_status, uint8_t *records);
 hipError_t launch_bam_scan(hipStream_t stream, int32_t n_positions, int32_t n_samples, const BamPileupScratch &s, const uint32_t *sample_status);
 
+// bam_popmatrix_kernel.hip: the same records and a list of (position, REF, ALT) -> one row of '0' / '1' / '.' per sample
+// (include/bvc_popmatrix.h, bvc_bam_popmatrix).  launch_bam_index as above; launch_bam_popmatrix writes matrix[s * row_stride + t] for every
+// sample and position (and status 4); launch_bam_scan with n_positions = 0 leaves head[1..3].  The scratch is the read table + O(n_samples):
+// of a BamPileupScratch only reads, runmax, n_reads, one word of rec_start and head are set.
+BamPileupScratch bam_popmatrix_scratch(Layout &L, int64_t bam_bytes, int32_t n_samples);
+hipError_t launch_bam_popmatrix(hipStream_t stream, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                                const int64_t *sample_end, int32_t n_positions, const int32_t *positions, const uint8_t *ref, const uint8_t *alt,
+                                int32_t rg_s, int64_t refseq_len, const BamPileupScratch &s, uint8_t *matrix, int64_t row_stride, uint32_t *sample_status);
+
 #ifdef BVC_CHECK_LDS
 hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);

@@ -300,6 +300,114 @@ void find_snp_at_pos(const std::vector<BamRecord> &rv, int32_t rg_s, const std::
     }
 }
 
+// ---- popmatrix's rule ----------------------------------------------------------------------------------------
+// BamProcess::GetOffset (src/BamProcess.cpp:232-261), in its unsigned 32-bit arithmetic.
+static uint32_t get_offset(const BamRecord &r, uint32_t pos)
+{
+    uint32_t offset = pos - (uint32_t)(r.pos + 1);
+    uint32_t track = (uint32_t)r.pos;
+    for (auto const &cf : r.cigar) {
+        const char t = cf.first;
+        if (t != 'I' && t != 'S' && t != 'H') track += (uint32_t)cf.second;
+        if (track < pos) {
+            switch (t) {
+            case 'I': case 'S': offset += (uint32_t)cf.second; break;
+            case 'D': case 'P': case 'N': offset -= (uint32_t)cf.second; break;
+            default: break;
+            }
+        } else {
+            break;
+        }
+    }
+    // (an empty sequence: the reference compares with size_t(-1) and then reads seq[offset]; out of range here, as in find_snp_at_pos)
+    if (r.seq.empty() || offset > r.seq.length() - 1) throw std::out_of_range("index offset is out of range of the sequence");
+    return offset;
+}
+
+std::string fetch_allele_type(const std::vector<BamRecord> &rv, int32_t rg_s, const std::string &refseq, const std::vector<PosInfo> &pv)
+{
+    std::string snps;
+    snps.reserve(pv.size());
+    if (rv.empty()) { snps.assign(pv.size(), '.'); return snps; }
+    std::vector<int32_t> ends(rv.size());
+    for (size_t a = 0; a < rv.size(); ++a) ends[a] = rv[a].end_pos();
+    size_t i = 0, j = 0, k = 0, nc, sk, ri = 0;    // ri: the index of the reference's `r`
+    int32_t sx, sy, indel;
+    bool eof = false, next = false, is_indel, is_del, is_refskip;
+    for (auto const &s : pv) {
+        const int32_t pos = s.pos;
+        if (pos < rv[ri].pos + 1) {
+            snps.push_back('.');
+            continue;
+        }
+        while (pos > ends[ri]) {
+            if (i == rv.size() - 1) { eof = true; break; }
+            ri = ++i; j = i;
+            if (pos < rv[ri].pos + 1) { next = true; break; }
+        }
+        if (next || eof) {
+            snps.push_back('.');
+            eof = false; next = false;
+            continue;
+        }
+        while (true) {
+            const BamRecord &r = rv[ri];
+            nc = r.cigar.size();
+            for (k = 0, sx = r.pos, sy = 0; k < nc; ++k) {
+                const char op = r.cigar[k].first;
+                const int32_t l = r.cigar[k].second;
+                if (op == 'M' || op == 'I' || op == 'S' || op == 'X') sy += l;
+                if (op == 'H' || op == 'I') continue;
+                else sx += l;
+                if (pos <= sx) break;
+            }
+            if (k >= nc) { snps.push_back('.'); break; }             // (the reference asserts)
+            sk = k;
+            is_indel = is_del = is_refskip = false; indel = 0;
+            {
+                const char op = r.cigar[sk].first;
+                if (sx == pos && sk + 1 < nc) {
+                    const char op2 = r.cigar[sk + 1].first;
+                    const int32_t l2 = r.cigar[sk + 1].second;
+                    // the token is built before it is discarded: substr throws where it starts past its source (one message for
+                    // every out-of-range case of the rule, the one the device path reports)
+                    if (op2 == 'D') {
+                        indel = -l2;
+                        if ((size_t)(pos - rg_s + 1) > refseq.size()) throw std::out_of_range("index offset is out of range of the sequence");
+                    } else if (op2 == 'I') {
+                        indel = l2;
+                        if ((size_t)sy > r.seq.size()) throw std::out_of_range("index offset is out of range of the sequence");
+                    }
+                    // (a pad next: the reference's scan for an insertion behind it re-reads the current operation, never an insertion)
+                }
+                if (indel != 0) is_indel = true;
+                if (op == 'D') is_del = true;
+                else if (op == 'N') is_refskip = true;
+            }
+            if (is_indel) {
+                snps.push_back('.');
+                break;
+            }
+            if (!is_del && !is_refskip) {
+                const char x = r.seq[get_offset(r, (uint32_t)pos)];   // GetSnpCode
+                snps.push_back(x == s.ref ? '0' : x == s.alt ? '1' : '.');
+                break;
+            } else if (j < rv.size() - 1) {
+                ri = ++j;
+                if (pos < rv[ri].pos + 1 || pos > ends[ri]) {
+                    snps.push_back('.');
+                    break;
+                }
+            } else {
+                snps.push_back('.');
+                break;
+            }
+        }
+        ri = i; j = i;                              // all back to index i
+    }
+    return snps;
+}
+
 // ---- faidx -------------------------------------------------------------------------------------------
 bool fetch_reference(const std::string &fasta, const std::string &chr, int32_t start1, int32_t end1, std::string &seq,
                      std::string &err)

@@ -57,6 +57,18 @@ typedef std::unordered_map<int32_t, AlleleInfo> PosAlleleMap;   // src/BamProces
 void find_snp_at_pos(const std::vector<BamRecord> &rv, int32_t rg_s, const std::string &refseq,
                      const std::vector<int32_t> &pv, PosAlleleMap &allele_m);
 
+// A line of a position file <CHR POS REF ALT> (src/BamProcess.h:8-27).
+struct PosInfo {
+    std::string chr;
+    int32_t pos = 0;
+    char ref = 0, alt = 0;
+};
+// BamProcess::FetchAlleleType + GetSnpCode (src/BamProcess.cpp:96-212) behind GetBRV: one character per line of pv -- '0' the first usable
+// read's base is the line's REF, '1' its ALT, '.' anything else.  Follows the reference's text statement by statement, the read cursor
+// kept across positions included, so a position file that is not sorted gets the reference's answer too.  Departure: no read at all is
+// a row of '.' (the reference indexes an empty vector).  Throws std::out_of_range where the reference does.
+std::string fetch_allele_type(const std::vector<BamRecord> &rv, int32_t rg_s, const std::string &refseq, const std::vector<PosInfo> &pv);
+
 // RefReader::GetTargetBase: 1-based inclusive region of a faidx-indexed FASTA (plain or BGZF + .gzi),
 // upper-cased.
 bool fetch_reference(const std::string &fasta, const std::string &chr, int32_t start1, int32_t end1, std::string &seq,

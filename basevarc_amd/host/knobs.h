@@ -61,6 +61,10 @@ struct Knobs {
     // temp batches written from the records that come back; acts with --tmp-format bin|raw, ignored with text.  The batch files inflate
     // to the same bytes.  Off by default (profiles/bam_pileup/README.txt)
     const bool device_pileup = num("BVC_HOST_DEVICE_PILEUP", 0) != 0;
+    // 1: `BaseVarC popmatrix` makes the matrix's rows on the device -- per batch of -b samples (default 100) the region's BAM blocks are
+    // gathered, inflated and resolved there (bvc_bam_popmatrix_bgzf); taken only when the position file's positions do not descend, else
+    // the CPU path runs and says so.  The matrix inflates to the same bytes.  Off by default (profiles/popmatrix/README.txt)
+    const bool device_popmatrix = num("BVC_HOST_DEVICE_POPMATRIX", 0) != 0;
     const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

@@ -1,4 +1,4 @@
-// main.cpp -- `BaseVarC basetype` on MI355X: the reference's command line, temp-batch files and outputs, with
+// main.cpp -- `BaseVarC basetype`, `popmatrix` and `concat` on MI355X: the reference's command line, temp-batch files and outputs, with
 // the per-site BaseType work of a whole tile of positions handed to libbvc in one call.
 //
 // Counterparts in the reference (src/BaseVarC.cpp): main :151-174, runBaseType :176-314, bt_r :467-534,
@@ -28,9 +28,12 @@
 #include <unordered_map>
 
 #include "../../include/bvc_bam.h"
+#include "../../include/bvc_popmatrix.h"
 #include "bam.h"
 #include "bam_blocks.h"
+#include "bam_gather.h"
 #include "feeds.h"
+#include "popmatrix.h"
 
 using namespace bvchost;
 
@@ -64,8 +67,25 @@ static const char *BASETYPE_MESSAGE =
     "  --tmp-format     <STR>   Temp-batch files written by the load phase: text (as BaseVarC), bin (binary\n"
     "                           records, deflated) or raw (binary records, stored: fastest to read back) [text]\n";
 
+static const char *POPMATRIX_MESSAGE =
+    "Commands: BaseVarC popmatrix\n"
+    "Usage   : BaseVarC popmatrix [options]\n\n"
+    "Options :\n"
+    "  --input,      -i        BAM/CRAM files list, one file per row.\n"
+    "  --output,     -o        Output file path\n"
+    "  --posfile,    -p        Position file without header <CHR POS REF ALT>\n"
+    "  --reference,  -r        Reference file\n"
+    "  --mapq,       -q <INT>  Mapping quality >= INT [10]\n";
+
+static const char *CONCAT_MESSAGE =
+    "Commands: BaseVarC concat\n"
+    "Usage   : BaseVarC concat [options]\n\n"
+    "Options :\n"
+    "  --input,      -i       List of matrix files for concat, one file per row.\n"
+    "  --output,     -o       Output filename prefix(.gz will be added auto)\n";
+
 namespace opt {
-static bool verbose = false, rerun = false, load = false, keep_tmp = false;
+static bool verbose = false, rerun = false, load = false, keep_tmp = false, batch_given = false;
 static int mapq = 10, thread = 1, batch = 10, gpus = 0, tile = 4096;
 static double maf = 0.001;
 static std::string input, reference, posfile, group, region, output, tmp_format = "text";
@@ -91,7 +111,7 @@ static void parse_options(int argc, char **argv, const char *msg)          // sr
         std::istringstream arg(optarg != NULL ? optarg : "");
         switch (c) {
         case 'q': arg >> opt::mapq; break;
-        case 'b': arg >> opt::batch; break;
+        case 'b': arg >> opt::batch; opt::batch_given = true; break;
         case 't': arg >> opt::thread; break;
         case 'i': arg >> opt::input; break;
         case 'r': arg >> opt::reference; break;
@@ -211,87 +231,39 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
 // and the .bai index stay on the CPU.
 static std::atomic<long> g_device_batches(0);
 static std::atomic<int> g_load_threads(0);
-// a pool thread's context and page-locked buffer: made at its first batch, on the device device_of_thread gives, gone with the thread
-struct LoadDevice {
-    bvc_ctx *ctx = nullptr;
-    unsigned char *pin = nullptr;
-    size_t pin_cap = 0;
-    ~LoadDevice() { if (pin) bvc_host_free(pin); if (ctx) bvc_destroy(ctx); }
-};
-
 static void bt_r_device(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
                         const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus)
 {
+    // a pool thread's context and page-locked buffer: made at its first batch, on the device device_of_thread gives, gone with the thread
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, device_of_thread(g_load_threads++, gpus, opt::gpus)) != BVC_OK)
         throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
     const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
     const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    BamBatch batch;                                 // (headers, the mapped files, the blocks' gathering: bam_gather.h)
+    batch.open(bams, b0, b1, chr);
+    const std::vector<std::string> &sms = batch.sms;
+    const std::vector<int32_t> &rid = batch.rid;
     std::string names;
-    std::vector<std::string> sms;
-    std::vector<int32_t> rid(ns);
-    std::vector<uint64_t> first_record(ns);
-    std::deque<MappedFile> files;
-    for (size_t b = b0; b < b1; ++b) {
-        BamFile reader;
-        if (!reader.open(bams[b])) throw std::runtime_error("ERROR: can not open file " + bams[b]);
-        if (!reader.sorted())
-            throw std::runtime_error("ERROR: BAM file does not appear to be sorted (no SO:coordinate) found in header.\n       Sorted BAMs are required.");
-        sms.push_back(reader.sample_name());
-        names += sms.back() + '\t';
-        rid[b - b0] = reader.ref_index(chr);
-        first_record[b - b0] = reader.first_record();
-        files.emplace_back(bams[b]);
-        if (!files.back().ok()) throw std::runtime_error("ERROR: can not open file " + bams[b]);
-    }
+    for (auto const &sm : sms) names += sm + '\t';
     names += "\n";
-    std::vector<BamBlocks> lists(ns);
-    std::vector<uint8_t> to_eof(ns, 0), eof(ns);
-    std::vector<int64_t> off(ns), end(ns);
     std::vector<uint32_t> status(ns), rec_start(pv.size() + 1);
-    std::vector<bvc_bgzf_block> table;
     std::vector<uint8_t> records;
     for (int attempt = 0;; ++attempt) {
-        std::string err;
-        size_t comp_bytes = 0;
-        for (size_t s = 0; s < ns; ++s) {
-            if (rid[s] < 0) { lists[s] = BamBlocks(); lists[s].to_eof = true; continue; }
-            if (attempt > 0 && !to_eof[s]) continue;                  // (its list stands)
-            if (!bam_region_blocks(files[s], bams[b0 + s], first_record[s], rid[s], beg0, end0, to_eof[s] != 0, lists[s], err)) throw std::runtime_error(err);
-        }
-        for (auto const &l : lists) comp_bytes += l.comp_bytes;
-        if (comp_bytes + 16 > dev.pin_cap) {
-            if (dev.pin) bvc_host_free(dev.pin);
-            dev.pin_cap = comp_bytes + comp_bytes / 4 + 4096;
-            dev.pin = static_cast<unsigned char *>(bvc_host_alloc(dev.pin_cap));
-            if (!dev.pin) { dev.pin_cap = 0; throw std::runtime_error("ERROR: page-locked allocation failed"); }
-        }
-        table.clear();
-        int64_t comp_at = 0, out_at = 0;
-        for (size_t s = 0; s < ns; ++s) {
-            off[s] = out_at + lists[s].first_off;
-            for (auto const &blk : lists[s].blocks) {
-                std::memcpy(dev.pin + comp_at, blk.payload, blk.len);
-                table.push_back(bvc_bgzf_block{comp_at, out_at, (int32_t)blk.len, (int32_t)blk.isize, blk.crc32, 1u});
-                comp_at += (int64_t)blk.len;
-                out_at += (int64_t)blk.isize;
-            }
-            end[s] = out_at;
-            if (off[s] > end[s]) off[s] = end[s];
-            eof[s] = lists[s].to_eof ? 1 : 0;
-        }
+        batch.gather(beg0, end0, attempt > 0, dev);
         int64_t need = 0;
         int rc;
         for (;;) {
-            rc = bvc_bam_pileup_bgzf(dev.ctx, (int32_t)ns, dev.pin, comp_at, table.data(), (int64_t)table.size(), out_at, off.data(), end.data(),
-                                     eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(), rg_s, refseq.data(),
-                                     (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(), status.data());
+            rc = bvc_bam_pileup_bgzf(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
+                                     batch.off.data(), batch.end.data(), batch.eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(),
+                                     rg_s, refseq.data(), (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(),
+                                     status.data());
             if (rc != BVC_BAM_MORE || need <= (int64_t)records.size()) break;
             records.resize((size_t)need);
         }
         if (rc == BVC_OK) { records.resize((size_t)need); break; }
         if (rc == BVC_BAM_MORE && attempt == 0) {                     // a list that stopped short of its region's end: that sample to the file's end, once
-            for (size_t s = 0; s < ns; ++s) to_eof[s] = status[s] == 2u;
+            batch.mark_short(status);
             continue;
         }
         if (rc == BVC_ERR_DATA)
@@ -584,6 +556,112 @@ static void run_basetype(int argc, char **argv)                          // src/
     std::cout << "basetype done" << std::endl;
 }
 
+// ---- popmatrix (runPopMatrix, src/BaseVarC.cpp:671-729) -----------------------------------------------------------------------
+// The rows of the BAMs in list order from the device (BVC_HOST_DEVICE_POPMATRIX): batches of `bc` samples, per batch the region's BGZF
+// blocks gathered as phase 1 of basetype gathers them (bam_gather.h) and ONE library call; one context, one thread.  Returns the batches.
+static long popmatrix_device(const std::vector<std::string> &bams, const std::vector<PosInfo> &pv, const std::string &chr, const std::string &rg,
+                             int32_t rg_s, int32_t beg0, int32_t end0, int64_t refseq_len, int bc, BgzfWriter &fp)
+{
+    if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+    LoadDevice dev;
+    if (bvc_create(&dev.ctx, device_of_thread(0, bvc_device_count(), opt::gpus)) != BVC_OK)
+        throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    const size_t M = pv.size();
+    std::vector<int32_t> positions(M);
+    std::vector<uint8_t> ref(M), alt(M), matrix;
+    for (size_t t = 0; t < M; ++t) { positions[t] = pv[t].pos; ref[t] = (uint8_t)pv[t].ref; alt[t] = (uint8_t)pv[t].alt; }
+    long batches = 0;
+    std::string row;
+    for (size_t b0 = 0, count = 0; b0 < bams.size(); b0 += (size_t)bc, ++batches) {
+        const size_t b1 = std::min(bams.size(), b0 + (size_t)bc), ns = b1 - b0;
+        BamBatch batch;
+        batch.open(bams, b0, b1, chr);
+        std::vector<uint32_t> status(ns);
+        matrix.resize(ns * M);
+        for (int attempt = 0;; ++attempt) {
+            batch.gather(beg0, end0, attempt > 0, dev);
+            const int rc = bvc_bam_popmatrix_bgzf(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(),
+                                                  batch.out_bytes, batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0,
+                                                  opt::mapq, (int32_t)M, positions.data(), ref.data(), alt.data(), rg_s, refseq_len, matrix.data(),
+                                                  (int64_t)M, status.data());
+            if (rc == BVC_OK) break;
+            if (rc == BVC_BAM_MORE && attempt == 0) {                 // a list that stopped short of its region's end: that sample to the file's end, once
+                batch.mark_short(status);
+                continue;
+            }
+            if (rc == BVC_ERR_DATA)
+                for (size_t s = 0; s < ns; ++s) {
+                    // the messages of the CPU path: fetch's, and fetch_allele_type's std::out_of_range
+                    if (status[s] == 3u) throw std::runtime_error("ERROR: truncated or corrupt BAM record in " + bams[b0 + s]);
+                    if (status[s] == 4u) throw std::out_of_range("index offset is out of range of the sequence");
+                }
+            throw std::runtime_error(std::string("ERROR: device popmatrix failed: ") + bvc_last_error(dev.ctx));
+        }
+        for (size_t s = 0; s < ns; ++s) {
+            if (!(++count % 1000)) std::cerr << "Processing the number " << count / 1000 << "k bam" << std::endl;
+            if (batch.rid[s] < 0) std::cerr << batch.sms[s] << ": region " << rg << " is empty." << std::endl;
+            row.assign(reinterpret_cast<const char *>(matrix.data()) + s * M, M);
+            row += "\n";
+            fp.write(row);
+        }
+    }
+    return batches;
+}
+
+static void run_popmatrix(int argc, char **argv)
+{
+    parse_options(argc, argv, POPMATRIX_MESSAGE);
+    if (opt::reference.empty() || opt::posfile.empty()) throw std::invalid_argument(POPMATRIX_MESSAGE);
+    std::cerr << "popmatrix start" << std::endl;
+    const clock_t ctb = clock();
+    std::ifstream ibam(opt::input);
+    std::vector<PosInfo> pv;
+    if (!ibam.is_open() || !read_posfile(opt::posfile, pv)) throw std::runtime_error("ERROR: bamlist or posifle fail to be opend");
+    std::vector<std::string> bams;
+    for (std::string l; std::getline(ibam, l);) bams.push_back(l);
+    if (pv.empty()) throw std::invalid_argument("ERROR: no position in " + opt::posfile);   // (the reference takes front() of an empty vector)
+    const size_t N = bams.size(), M = pv.size();
+    BgzfWriter fp(opt::output);
+    if (!fp.ok()) throw std::runtime_error("ERROR: fail to write");
+    fp.write(std::to_string(N) + "\t" + std::to_string(M) + "\n");
+    const std::string rg = posfile_region(pv);
+    std::string chr;
+    int32_t rg_s, rg_e;
+    std::tie(chr, rg_s, rg_e) = splitrg(rg);
+    std::string refseq, err;
+    // (only its length reaches the rule, but the reference fetches it and fails where it cannot)
+    if (!fetch_reference(opt::reference, chr, rg_s, rg_e + 1000, refseq, err)) throw std::runtime_error(err);
+    // the region padded by 1000 on both sides (gr.Pad(1000), src/BamProcess.cpp:290), as bt_r has it; [beg, end) 0-based
+    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    const Knobs knobs(1);
+    bool device = knobs.device_popmatrix;
+    if (device && !positions_do_not_descend(pv)) {
+        std::cerr << "popmatrix: the position file is not sorted, the rows are made on the CPU" << std::endl;
+        device = false;
+    }
+    long batches = 0;
+    if (device)
+        batches = popmatrix_device(bams, pv, chr, rg, rg_s, beg0, end0, (int64_t)refseq.size(), opt::batch_given ? std::max(1, opt::batch) : 100, fp);
+    else
+        for (size_t i = 0, count = 0; i < N; ++i) {
+            if (!(++count % 1000)) std::cerr << "Processing the number " << count / 1000 << "k bam" << std::endl;
+            fp.write(popmatrix_row(bams[i], chr, rg, beg0, end0, opt::mapq, rg_s, refseq, pv) + "\n");
+        }
+    if (knobs.profile) std::cerr << "[profile] main: popmatrix on the device, " << batches << " batches (bvc_bam_popmatrix_bgzf)" << std::endl;
+    if (!fp.close()) std::cerr << "warning: fail to close file" << std::endl;
+    std::cout << "elapsed secs : " << double(clock() - ctb) / CLOCKS_PER_SEC << std::endl;
+    std::cerr << "popmatrix done" << std::endl;
+}
+
+static void run_concat(int argc, char **argv)                            // runConcat, src/BaseVarC.cpp:731-795
+{
+    parse_options(argc, argv, CONCAT_MESSAGE);
+    const clock_t ctb = clock();
+    concat_matrices(opt::input, opt::output);                           // (-o is opened as given: the reference adds no ".gz" either)
+    std::cout << "elapsed secs : " << double(clock() - ctb) / CLOCKS_PER_SEC << std::endl;
+    std::cout << "concat done" << std::endl;
+}
+
 int main(int argc, char **argv)
 {
     if (argc <= 1) { std::cerr << BASEVARC_USAGE_MESSAGE; return 0; }
@@ -593,10 +671,9 @@ int main(int argc, char **argv)
     const std::string command(argv[1]);
     try {
         if (command == "basetype") run_basetype(argc - 1, argv + 1);
-        else if (command == "popmatrix" || command == "concat") {
-            std::cerr << "BaseVarC " << command << " is not part of the MI355X build (only the basetype path is)" << std::endl;
-            return 1;
-        } else { std::cerr << BASEVARC_USAGE_MESSAGE; return 0; }
+        else if (command == "popmatrix") run_popmatrix(argc - 1, argv + 1);
+        else if (command == "concat") run_concat(argc - 1, argv + 1);
+        else { std::cerr << BASEVARC_USAGE_MESSAGE; return 0; }
     } catch (const std::exception &e) {
         std::cerr << e.what() << std::endl;
         return 1;

@@ -129,6 +129,13 @@ BAM_PROTOTYPES = {
                                    _pi64, _vp, _vp]),
 }
 BAM_EXPORTS = list(BAM_PROTOTYPES)
+# The fourth header, include/bvc_popmatrix.h (tests/test_popmatrix_abi.py compares the two), bound by bind() with the others.
+POPMATRIX_PROTOTYPES = {
+    "bvc_bam_popmatrix": (_int, [_vp, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp, _i64, _vp, _u32]),
+    "bvc_bam_popmatrix_bgzf": (_int, [_vp, _i32, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _i64, _vp,
+                                      _i64, _vp]),
+}
+POPMATRIX_EXPORTS = list(POPMATRIX_PROTOTYPES)
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
@@ -143,9 +150,10 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES and BAM_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required
-    symbol that the library lacks is an AttributeError."""
-    for name, (restype, argtypes) in list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()):
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES and POPMATRIX_PROTOTYPES its restype / argtypes on `cdll`
+    (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
+                                      list(POPMATRIX_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -794,6 +802,61 @@ class Context:
             records = new(need.value, u8)
         rc = call(records, size(records) if records_cap is None else int(records_cap))
         return rc, records[:need.value] if rc == 0 else records, rec_start, sample_status, need.value
+
+    def bam_popmatrix(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, ref, alt, rg_s, refseq_len, matrix=None,
+                      row_stride=None, sample_status=None):
+        """bvc_bam_popmatrix (include/bvc_popmatrix.h): the inflated BAM records of a batch of samples and a position file's lines -> one
+        row of '0' / '1' / '.' per sample.  numpy arrays (synchronous) or tensors on this context's device (asynchronous but for one wait
+        at the end): the sample arrays as bam_pileup takes them; positions int32 (1-based, not descending, repeats allowed), ref / alt
+        uint8 [P] (the lines' REF and ALT characters).  matrix / sample_status: buffers to write into (uint8 of at least n * row_stride
+        bytes, uint32 [n]); row_stride defaults to P.  Returns (rc, matrix, sample_status): rc 0, or BAM_MORE (2) when a sample's status
+        is 2; the rows of samples with status 0 or 1 are defined either way.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a
+        sample of status 3 or 4; the buffers given keep what the call wrote)."""
+        device = hasattr(bam, "data_ptr")
+        if device:
+            import torch
+            new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=bam.device)
+            u8, u32, size = torch.uint8, torch.int32, lambda a: a.numel()
+        else:
+            bam, sample_off, sample_end = _as(bam, np.uint8), _as(sample_off, np.int64), _as(sample_end, np.int64)
+            sample_eof, rid = _as(sample_eof, np.uint8), _as(rid, np.int32)
+            positions, ref, alt = _as(positions, np.int32), _as(ref, np.uint8), _as(alt, np.uint8)
+            new = lambda n, dt: np.zeros(max(1, n), dtype=dt)
+            u8, u32, size = np.uint8, np.uint32, len
+        n, P = size(rid), size(positions)
+        if size(sample_off) != n or size(sample_end) != n or size(sample_eof) != n:
+            raise ValueError("sample_off, sample_end and sample_eof must be [n_samples]")
+        if size(ref) != P or size(alt) != P:
+            raise ValueError("ref and alt must be [n_positions]")
+        row_stride = P if row_stride is None else int(row_stride)
+        matrix = new(n * max(row_stride, 0), u8) if matrix is None else matrix
+        sample_status = new(n, u32) if sample_status is None else sample_status
+        ptr = _dev_ptr if device else _np_ptr
+        opt = lambda a: a if a is not None and size(a) else None
+        rc = self._L.bvc_bam_popmatrix(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0),
+                                                              int(end0), int(min_mapq), P, opt(positions), opt(ref), opt(alt), int(rg_s), int(refseq_len),
+                                                              matrix, row_stride, sample_status if n else None), ptr),
+                                       BVC_PTR_DEVICE if device else BVC_PTR_HOST)
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        return rc, matrix, sample_status
+
+    def bam_popmatrix_bgzf(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, ref, alt, rg_s,
+                           refseq_len):
+        """bvc_bam_popmatrix_bgzf: the same from BGZF blocks still compressed.  comp: uint8 array; blocks: a BLOCK_DTYPE table (out_off: where
+        each block's output lies among the bam_bytes inflated bytes).  Host arrays only.  Returns (rc, matrix [n, P], sample_status)."""
+        comp, tab = _as(comp, np.uint8), np.ascontiguousarray(blocks, dtype=BLOCK_DTYPE)
+        sample_off, sample_end, sample_eof, rid = _as(sample_off, np.int64), _as(sample_end, np.int64), _as(sample_eof, np.uint8), _as(rid, np.int32)
+        positions, ref, alt = _as(positions, np.int32), _as(ref, np.uint8), _as(alt, np.uint8)
+        n, P = len(rid), len(positions)
+        matrix, status = np.zeros((max(1, n), max(1, P)), dtype=np.uint8), np.zeros(max(1, n), dtype=np.uint32)
+        opt = lambda a: a if len(a) else None
+        rc = self._L.bvc_bam_popmatrix_bgzf(self._h, n, *_pointers((opt(comp), len(comp), opt(tab), len(tab), int(bam_bytes), opt(sample_off), opt(sample_end),
+                                                                   opt(sample_eof), opt(rid), int(beg0), int(end0), int(min_mapq), P, opt(positions), opt(ref),
+                                                                   opt(alt), int(rg_s), int(refseq_len), matrix, max(1, P) if n and P else P, status), _np_ptr))
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        return rc, matrix[:n, :P], status[:n]
 
     # ---- a cohort in sample chunks: counts that accumulate (include/bvc.h).  `counts` is added to IN PLACE: a uint32 / int32 array of
     # [n_sites, 512] (plain) or [n_sites, n_groups + 1, 512] (groups; slot n_groups = in no group), numpy with the host calls, a tensor
