@@ -1,4 +1,5 @@
-// bam_resolve_device.h -- what the kernels over a batch's inflated BAM records share (bam_pileup_kernel.hip, bam_popmatrix_kernel.hip):
+// bam_resolve_device.h -- what the kernels over a batch's inflated BAM records share (bam_pileup_kernel.hip, bam_popmatrix_kernel.hip,
+// bam_text_kernel.hip):
 // the byte loads (records lie at any byte address), the lane helpers, a sample's clamped byte range and resolve(), the per-position
 // rule of find_snp_at_pos / fetch_allele_type (host/bam.cpp) for ONE position over the read table bam_index_kernel leaves.  Device
 // code only; every function is inlined into its kernel.
@@ -56,7 +57,8 @@ struct Hit {
     uint32_t fields = 0;        // base | mapq << 8 | qual << 16 | rpr << 24 (an indel entry's mapq comes from the carry)
     uint32_t flags = 0;         // bit 0 strand, bit 1 indel entry
     uint32_t nib = 0;           // a base entry: the read's 4-bit base code (its character: nt16_char)
-    uint32_t text_len = 0;      // the sign included
+    uint32_t text_len = 0;      // the sign included, bounded by the binary entry's 16-bit length field
+    uint32_t text_full = 0;     // the sign included, whole (the text form has no such field: bam_text_kernel.hip)
     uint32_t text_at = 0;       // insertion: index of the first base in the read
     int64_t text_src = 0;       // insertion: where the read's packed bases begin in bam; deletion: index into refseq
     bool deletion = false;
@@ -122,6 +124,7 @@ __device__ __forceinline__ Hit resolve(const uint8_t *__restrict__ bam, const Ba
                 }
                 const int64_t tl = (int64_t)l2 < avail ? (int64_t)l2 : avail;
                 h.text_len = tl + 1 < 0xffff ? (uint32_t)(tl + 1) : 0xffffu;
+                h.text_full = (uint32_t)(tl + 1);
                 h.size = 11u + h.text_len;
                 h.fields = 5u | (mapq << 16);
                 h.flags = strand | 2u;

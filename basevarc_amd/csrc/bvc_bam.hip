@@ -1,11 +1,14 @@
 // bvc_bam.hip -- bvc_bam_pileup and bvc_bam_pileup_bgzf (include/bvc_bam.h): the inflated BAM records of a batch of samples -> the batch's
 // position records in the binary temp-batch form (bam_pileup_kernel.hip).  Two passes over the positions in tiles: sizes, one wait for
 // the total and the statuses, then the records.
+// bvc_bam_pileup_text and bvc_bam_pileup_text_bgzf (include/bvc_bam_text.h): the same call with the batch's lines in the text temp-batch
+// form as its output (bam_text_kernel.hip); each shares its whole body with its binary twin (bam_pileup_call, bam_pileup_bgzf_call).
 // bvc_bam_popmatrix and bvc_bam_popmatrix_bgzf (include/bvc_popmatrix.h): the same records -> one row of '0' / '1' / '.' per sample
 // (bam_popmatrix_kernel.hip).  One pass and one wait.  The two families share the call's inputs (BamCall), their checks and the verdicts
 // on the statuses and the blocks; the matrix's two entry points share one tail (bam_popmatrix_from_host, run_bam_popmatrix).
 #include "bvc_ctx.h"
 #include "../../include/bvc_bam.h"
+#include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
 
 namespace {
@@ -81,7 +84,8 @@ int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status)
 
 // The kernels of one call on inputs in device memory.  out_device: records, rec_start and sample_status are device memory and the call
 // returns with the second pass enqueued; else they are host memory (d_status: the statuses' place on the device) and the call waits.
-int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, uint32_t *d_status, uint8_t *records, int64_t records_cap,
+// text: the output is the batch's lines (records: the text, rec_start: line_start) instead of its binary records.
+int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool out_device, uint32_t *d_status, uint8_t *records, int64_t records_cap,
                    int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status)
 {
     const size_t ns = (size_t)c.n_samples, np = (size_t)c.n_positions;
@@ -91,8 +95,8 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, u
     auto tiles = [&](bool place, uint8_t *out) -> hipError_t {
         for (int32_t t0 = 0; t0 < c.n_positions; t0 += S.tile) {
             const int32_t tn = c.n_positions - t0 < S.tile ? c.n_positions - t0 : S.tile;
-            const hipError_t e = launch_bam_tile(ctx->stream, place, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.pos, t0, tn, c.rg_s, c.ref,
-                                                 c.refseq_len, S, d_status, out);
+            const hipError_t e = (text ? launch_bam_text_tile : launch_bam_tile)(ctx->stream, place, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.pos,
+                                                                                 t0, tn, c.rg_s, c.ref, c.refseq_len, S, d_status, out);
             if (e != hipSuccess) return e;
         }
         return hipSuccess;
@@ -109,9 +113,10 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, u
     if (rc != BVC_OK) return rc;
     const int64_t need = head[0];
     *records_needed = need;
-    if (need > (int64_t)0xFFFFFF00u) return fail(ctx, BVC_ERR_ARG, "the records exceed 0xFFFFFF00 bytes (split the positions)");
+    if (need > (int64_t)0xFFFFFF00u)
+        return fail(ctx, BVC_ERR_ARG, text ? "the text exceeds 0xFFFFFF00 bytes (split the positions)" : "the records exceed 0xFFFFFF00 bytes (split the positions)");
     if (need > records_cap) {
-        (void)fail_cap(ctx, "records", records_cap, "the batch's records", need);
+        (void)fail_cap(ctx, text ? "text" : "records", records_cap, text ? "the batch's lines" : "the batch's records", need);
         return BVC_BAM_MORE;
     }
     uint8_t *d_records = records;
@@ -120,7 +125,7 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, u
         if (rc != BVC_OK) return rc;
         d_records = reinterpret_cast<uint8_t *>(ctx->d_bam_out.p);
     }
-    BVC_HIP_D(ctx, hipMemsetAsync(S.carry, 0, ns ? ns : 1, ctx->stream));
+    if (!text) BVC_HIP_D(ctx, hipMemsetAsync(S.carry, 0, ns ? ns : 1, ctx->stream));   // (a text indel token shows no fields: no carry)
     BVC_HIP_D(ctx, tiles(true, d_records));
     if (out_device) {
         BVC_HIP_D(ctx, hipMemcpyAsync(rec_start, S.rec_start, (np + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -227,11 +232,8 @@ int check_popmatrix(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_byt
     return BVC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bvc_bam_pileup(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+// bvc_bam_pileup (text = false) and bvc_bam_pileup_text (text = true): one body, the output's form apart.
+int bam_pileup_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
                    const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq,
                    int32_t n_positions, const int32_t *positions, int32_t rg_s, const char *refseq, int64_t refseq_len,
                    uint8_t *records, int64_t records_cap, int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status,
@@ -277,10 +279,11 @@ int bvc_bam_pileup(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t 
         BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
         c.bam = u_bam; c.ref = u_ref; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
     }
-    return run_bam_pileup(ctx, io, c, device, d_status, records, records_cap, records_needed, rec_start, sample_status);
+    return run_bam_pileup(ctx, io, c, text, device, d_status, records, records_cap, records_needed, rec_start, sample_status);
 }
 
-int bvc_bam_pileup_bgzf(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true)
+int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
                         int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
                         int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
                         const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
@@ -331,12 +334,56 @@ int bvc_bam_pileup_bgzf(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, in
     c.refseq_len = refseq_len;
     // the pileup's first wait delivers the blocks' statuses too: a block that did not inflate (or failed its CRC32) outranks what the
     // kernels made of its bytes
-    rc = run_bam_pileup(ctx, io, c, false, d_status, records, records_cap, records_needed, rec_start, sample_status);
+    rc = run_bam_pileup(ctx, io, c, text, false, d_status, records, records_cap, records_needed, rec_start, sample_status);
     if (block_verdict(ctx, block_status) != BVC_OK) {
         *records_needed = 0;
         return BVC_ERR_DATA;
     }
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bvc_bam_pileup(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                   const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq,
+                   int32_t n_positions, const int32_t *positions, int32_t rg_s, const char *refseq, int64_t refseq_len,
+                   uint8_t *records, int64_t records_cap, int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status,
+                   uint32_t flags)
+{
+    return bam_pileup_call(false, ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions,
+                           rg_s, refseq, refseq_len, records, records_cap, records_needed, rec_start, sample_status, flags);
+}
+
+int bvc_bam_pileup_bgzf(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                        int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                        int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                        const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
+                        uint32_t *rec_start, uint32_t *sample_status)
+{
+    return bam_pileup_bgzf_call(false, ctx, n_samples, comp, comp_bytes, blocks, n_blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0,
+                                min_mapq, n_positions, positions, rg_s, refseq, refseq_len, records, records_cap, records_needed, rec_start,
+                                sample_status);
+}
+
+int bvc_bam_pileup_text(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                        const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq,
+                        int32_t n_positions, const int32_t *positions, int32_t rg_s, const char *refseq, int64_t refseq_len,
+                        uint8_t *text, int64_t text_cap, int64_t *text_needed, uint32_t *line_start, uint32_t *sample_status, uint32_t flags)
+{
+    return bam_pileup_call(true, ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions,
+                           rg_s, refseq, refseq_len, text, text_cap, text_needed, line_start, sample_status, flags);
+}
+
+int bvc_bam_pileup_text_bgzf(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                             int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                             int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                             const char *refseq, int64_t refseq_len, uint8_t *text, int64_t text_cap, int64_t *text_needed,
+                             uint32_t *line_start, uint32_t *sample_status)
+{
+    return bam_pileup_bgzf_call(true, ctx, n_samples, comp, comp_bytes, blocks, n_blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0,
+                                min_mapq, n_positions, positions, rg_s, refseq, refseq_len, text, text_cap, text_needed, line_start, sample_status);
 }
 
 int bvc_bam_popmatrix(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,

@@ -291,6 +291,13 @@ hipError_t launch_bam_tile(hipStream_t stream, bool place, int32_t n_samples, co
                            const BamPileupScratch &s, uint32_t *sample_status, uint8_t *records);
 hipError_t launch_bam_scan(hipStream_t stream, int32_t n_positions, int32_t n_samples, const BamPileupScratch &s, const uint32_t *sample_status);
 
+// bam_text_kernel.hip: the same call with the batch's lines in the text temp-batch form as its output (include/bvc_bam_text.h,
+// bvc_bam_pileup_text).  launch_bam_index, launch_bam_scan and the scratch are the ones above (carry stays unused; rec_len holds a line's
+// bytes less the 4 the scan adds, rec_start is line_start); launch_bam_text_tile is launch_bam_tile's twin, `text` the lines' bytes.
+hipError_t launch_bam_text_tile(hipStream_t stream, bool place, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                                const int64_t *sample_end, const int32_t *positions, int32_t t0, int32_t tile_n, int32_t rg_s, const uint8_t *refseq,
+                                int64_t refseq_len, const BamPileupScratch &s, uint32_t *sample_status, uint8_t *text);
+
 // bam_popmatrix_kernel.hip: the same records and a list of (position, REF, ALT) -> one row of '0' / '1' / '.' per sample
 // (include/bvc_popmatrix.h, bvc_bam_popmatrix).  launch_bam_index as above; launch_bam_popmatrix writes matrix[s * row_stride + t] for every
 // sample and position (and status 4); launch_bam_scan with n_positions = 0 leaves head[1..3].  The scratch is the read table + O(n_samples):

@@ -61,6 +61,11 @@ struct Knobs {
     // temp batches written from the records that come back; acts with --tmp-format bin|raw, ignored with text.  The batch files inflate
     // to the same bytes.  Off by default (profiles/bam_pileup/README.txt)
     const bool device_pileup = num("BVC_HOST_DEVICE_PILEUP", 0) != 0;
+    // 1: the same with --tmp-format text (bvc_bam_pileup_text_bgzf): the batch's lines come back and are written behind the names line; a
+    // knob of its own because the one above is documented and tested as ignored with text; ignored with bin|raw.  A batch whose lines
+    // cannot fit 0xFFFFFF00 bytes takes the CPU path, said once.  The batch files inflate to the same bytes.  Off by default
+    // (profiles/bam_pileup_text/README.txt)
+    const bool device_pileup_text = num("BVC_HOST_DEVICE_PILEUP_TEXT", 0) != 0;
     // 1: `BaseVarC popmatrix` makes the matrix's rows on the device -- per batch of -b samples (default 100) the region's BAM blocks are
     // gathered, inflated and resolved there (bvc_bam_popmatrix_bgzf); taken only when the position file's positions do not descend, else
     // the CPU path runs and says so.  The matrix inflates to the same bytes.  Off by default (profiles/popmatrix/README.txt)

@@ -28,6 +28,7 @@
 #include <unordered_map>
 
 #include "../../include/bvc_bam.h"
+#include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
 #include "bam.h"
 #include "bam_blocks.h"
@@ -229,11 +230,25 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
 // ---- phase 1 on the device (BVC_HOST_DEVICE_PILEUP, --tmp-format bin|raw): the batch's BAM blocks are gathered as they lie in the files,
 // inflated and piled up by ONE library call, and the records that come back are cut at the threads' windows as bt_r cuts them.  Headers
 // and the .bai index stay on the CPU.
+// text (BVC_HOST_DEVICE_PILEUP_TEXT, --tmp-format text): the same gathering and the same retries around bvc_bam_pileup_text_bgzf, and the
+// lines that come back are cut at the same windows behind the names line.  line_start is 32-bit: a batch whose lines cannot fit
+// 0xFFFFFF00 bytes -- by their floor of 2 bytes a sample and a newline a position, or by what the call reports -- goes to bt_r, said once.
 static std::atomic<long> g_device_batches(0);
 static std::atomic<int> g_load_threads(0);
+static std::atomic<bool> g_text_fallback_said(false);
 static void bt_r_device(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
-                        const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus)
+                        const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus, bool text)
 {
+    const int64_t kTextMax = (int64_t)0xFFFFFF00u;
+    auto on_the_cpu = [&]() {
+        if (!g_text_fallback_said.exchange(true))
+            std::cerr << "basetype: a batch's lines exceed 0xFFFFFF00 bytes, such batches are extracted on the CPU" << std::endl;
+        bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, ib, thread);
+    };
+    {
+        const int64_t n = (int64_t)((ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc) - (int64_t)ib * bc;
+        if (text && (2 * n + 1) * (int64_t)pv.size() > kTextMax) return on_the_cpu();
+    }
     // a pool thread's context and page-locked buffer: made at its first batch, on the device device_of_thread gives, gone with the thread
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, device_of_thread(g_load_threads++, gpus, opt::gpus)) != BVC_OK)
@@ -254,10 +269,12 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
         int64_t need = 0;
         int rc;
         for (;;) {
-            rc = bvc_bam_pileup_bgzf(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
-                                     batch.off.data(), batch.end.data(), batch.eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(),
-                                     rg_s, refseq.data(), (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(),
-                                     status.data());
+            // (the two calls take the same arguments: records and rec_start hold the lines and line_start with text)
+            rc = (text ? bvc_bam_pileup_text_bgzf : bvc_bam_pileup_bgzf)(
+                dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes, batch.off.data(),
+                batch.end.data(), batch.eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(), rg_s, refseq.data(),
+                (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(), status.data());
+            if (text && rc == BVC_ERR_ARG && need > kTextMax) return on_the_cpu();
             if (rc != BVC_BAM_MORE || need <= (int64_t)records.size()) break;
             records.resize((size_t)need);
         }
@@ -282,9 +299,12 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
     for (int i = 0; i < thread; ++i) {
         BgzfWriter fp(tmp_name(i, ib), level);
         if (!fp.ok()) throw std::runtime_error("ERROR: fail to write " + tmp_name(i, ib));
-        std::string h;
-        bin_batch_header((uint32_t)ns, names, h);
-        fp.write(h);
+        if (text) fp.write(names);
+        else {
+            std::string h;
+            bin_batch_header((uint32_t)ns, names, h);
+            fp.write(h);
+        }
         const size_t hi = cuts[(size_t)i];
         fp.write(reinterpret_cast<const char *>(records.data()) + rec_start[lo], (size_t)(rec_start[hi] - rec_start[lo]));
         lo = hi;
@@ -496,8 +516,13 @@ static void run_basetype(int argc, char **argv)                          // src/
         if (knobs.device_pileup && opt::tmp_format != "text") {
             const int load_gpus = bvc_device_count();
             if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
-            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus); });
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, false); });
             if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches (bvc_bam_pileup_bgzf)" << std::endl;
+        } else if (knobs.device_pileup_text && opt::tmp_format == "text") {
+            const int load_gpus = bvc_device_count();
+            if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, true); });
+            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches (bvc_bam_pileup_text_bgzf)" << std::endl;
         } else
             run_pool(nb - first_batch, thread, [&](int t) { bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread); });
     }

@@ -136,6 +136,13 @@ POPMATRIX_PROTOTYPES = {
                                       _i64, _vp]),
 }
 POPMATRIX_EXPORTS = list(POPMATRIX_PROTOTYPES)
+# The fifth header, include/bvc_bam_text.h (tests/test_bam_text_abi.py compares the two), bound by bind() with the others: the twins of
+# BAM_PROTOTYPES' calls for the text temp batches, argument for argument.
+BAM_TEXT_PROTOTYPES = {
+    "bvc_bam_pileup_text": BAM_PROTOTYPES["bvc_bam_pileup"],
+    "bvc_bam_pileup_text_bgzf": BAM_PROTOTYPES["bvc_bam_pileup_bgzf"],
+}
+BAM_TEXT_EXPORTS = list(BAM_TEXT_PROTOTYPES)
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
@@ -150,10 +157,10 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES and POPMATRIX_PROTOTYPES its restype / argtypes on `cdll`
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES and BAM_TEXT_PROTOTYPES its restype / argtypes on `cdll`
     (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
-                                      list(POPMATRIX_PROTOTYPES.items())):
+                                      list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -767,6 +774,12 @@ class Context:
         twice, the second time with a buffer of the size the first reports.  records_cap: what to tell the library instead of len(records).
         Returns (rc, records, rec_start, sample_status, records_needed): rc 0, or BAM_MORE (2) when a sample's status is 2 or records is
         too small -- nothing is written then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4)."""
+        return self._bam_pileup(self._L.bvc_bam_pileup, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq, records,
+                                records_cap, rec_start, sample_status)
+
+    def _bam_pileup(self, fn, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq, records, records_cap, rec_start,
+                    sample_status):
+        """bam_pileup and bam_pileup_text: fn is bvc_bam_pileup or its twin of the same arguments."""
         device = hasattr(bam, "data_ptr")
         if device:
             import torch
@@ -788,7 +801,7 @@ class Context:
         opt = lambda a: a if a is not None and size(a) else None
 
         def call(buf, cap):
-            rc = self._L.bvc_bam_pileup(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0), int(end0),
+            rc = fn(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0), int(end0),
                                                                int(min_mapq), P, opt(positions), int(rg_s), opt(refseq), size(refseq), opt(buf), cap),
                                                               ptr), C.byref(need), ptr(rec_start), ptr(sample_status) if n else None,
                                         BVC_PTR_DEVICE if device else BVC_PTR_HOST)
@@ -802,6 +815,46 @@ class Context:
             records = new(need.value, u8)
         rc = call(records, size(records) if records_cap is None else int(records_cap))
         return rc, records[:need.value] if rc == 0 else records, rec_start, sample_status, need.value
+
+    def bam_pileup_text(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq, text=None, text_cap=None,
+                        line_start=None, sample_status=None):
+        """bvc_bam_pileup_text (include/bvc_bam_text.h): the same records -> the batch's lines in the text temp-batch form.  Everything as
+        bam_pileup, with text / text_cap / line_start in the places of records / records_cap / rec_start.  Returns (rc, text, line_start,
+        sample_status, text_needed)."""
+        return self._bam_pileup(self._L.bvc_bam_pileup_text, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                                text, text_cap, line_start, sample_status)
+
+    def bam_pileup_text_bgzf(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                             text=None, text_cap=None, line_start=None, sample_status=None):
+        """bvc_bam_pileup_text_bgzf: the same from BGZF blocks still compressed.  comp: uint8 array; blocks: a BLOCK_DTYPE table (out_off:
+        where each block's output lies among the bam_bytes inflated bytes).  Host arrays only.  Without text the call is made twice, as
+        bam_pileup makes it.  Returns (rc, text, line_start, sample_status, text_needed)."""
+        comp, tab = _as(comp, np.uint8), np.ascontiguousarray(blocks, dtype=BLOCK_DTYPE)
+        sample_off, sample_end, sample_eof, rid = _as(sample_off, np.int64), _as(sample_end, np.int64), _as(sample_eof, np.uint8), _as(rid, np.int32)
+        positions, refseq = _as(positions, np.int32), _as(refseq, np.uint8)
+        n, P = len(rid), len(positions)
+        if len(sample_off) != n or len(sample_end) != n or len(sample_eof) != n:
+            raise ValueError("sample_off, sample_end and sample_eof must be [n_samples]")
+        line_start = np.zeros(P + 1, dtype=np.uint32) if line_start is None else line_start
+        sample_status = np.zeros(max(1, n), dtype=np.uint32) if sample_status is None else sample_status
+        need = C.c_int64(0)
+        opt = lambda a: a if a is not None and len(a) else None
+
+        def call(buf, cap):
+            rc = self._L.bvc_bam_pileup_text_bgzf(self._h, n, *_pointers((opt(comp), len(comp), opt(tab), len(tab), int(bam_bytes), opt(sample_off), opt(sample_end),
+                                                                         opt(sample_eof), opt(rid), int(beg0), int(end0), int(min_mapq), P, opt(positions),
+                                                                         int(rg_s), opt(refseq), len(refseq), opt(buf), cap), _np_ptr), C.byref(need),
+                                                  _np_ptr(line_start), _np_ptr(sample_status) if n else None)
+            if rc not in (0, BAM_MORE):
+                self._check(rc)
+            return rc
+        if text is None:
+            rc = call(None, 0)
+            if rc == 0 or need.value == 0:
+                return rc, np.zeros(0, dtype=np.uint8), line_start, sample_status, need.value
+            text = np.zeros(need.value, dtype=np.uint8)
+        rc = call(text, len(text) if text_cap is None else int(text_cap))
+        return rc, text[:need.value] if rc == 0 else text, line_start, sample_status, need.value
 
     def bam_popmatrix(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, ref, alt, rg_s, refseq_len, matrix=None,
                       row_stride=None, sample_status=None):

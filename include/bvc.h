@@ -685,7 +685,8 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
 int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int64_t *text_len);
 /* Rule (a) of "bgzf_codes" on counts of the caller's -- bvc_bgzf_code_lengths -- is declared in bvc_bgzf_codes.h beside this header. */
 /* Phase 1 on the device -- bvc_bam_pileup: inflated BAM records of a batch of samples -> the batch's binary position records -- is declared
- * in bvc_bam.h beside this header. */
+ * in bvc_bam.h beside this header; its twin for the text temp batches -- bvc_bam_pileup_text: the same records -> the batch's lines -- in
+ * bvc_bam_text.h. */
 /* `BaseVarC popmatrix` on the device -- bvc_bam_popmatrix: the same records and a position file's lines -> one row of '0' / '1' / '.' per
  * sample (BVC_BAM_MORE there: some sample's bytes ran out) -- is declared in bvc_popmatrix.h beside this header. */
 

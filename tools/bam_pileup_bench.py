@@ -4,6 +4,10 @@ program on the 100 test BAMs and on a larger list that names each of them severa
 on the inflated records of the 100 test BAMs in device memory, next to a plain streaming read of the same bytes.
 
   python tools/bam_pileup_bench.py [--copies 20] [--repeats 3] [--out profiles/bam_pileup/README.txt]
+  python tools/bam_pileup_bench.py --form text [--copies 50] [--out profiles/bam_pileup_text/README.txt]
+
+--form text: the same with --tmp-format text and BVC_HOST_DEVICE_PILEUP_TEXT, and bvc_bam_pileup_text next to bvc_bam_pileup on the same
+input, with the bytes of text a second.
 
 The larger list repeats the same files (and so the same sample names, which the load phase does not look at): the page cache serves both
 runs alike.  Every time is the best of --repeats wall-clock runs of the whole process, start-up and the context's creation included."""
@@ -26,12 +30,15 @@ class Lines(list):
         print(line, flush=True)
 
 
+KNOB = dict(raw="BVC_HOST_DEVICE_PILEUP", text="BVC_HOST_DEVICE_PILEUP_TEXT")
+
+
 def load_seconds(exe, lst, fa, region, out, threads, batch, knob, fmt, repeats):
     best = None
     for _ in range(repeats):
         t = time.perf_counter()
         r = subprocess.run([exe, "basetype", "--load", "--tmp-format", fmt, "-q", "20", "-t", str(threads), "-b", str(batch), "-i", lst, "-s", region,
-                            "-r", fa, "-o", out], capture_output=True, text=True, env=dict(os.environ, BVC_HOST_DEVICE_PILEUP=str(knob)))
+                            "-r", fa, "-o", out], capture_output=True, text=True, env=dict(os.environ, **{KNOB[fmt]: str(knob)}))
         dt = time.perf_counter() - t
         if r.returncode != 0:
             raise RuntimeError(r.stderr[-2000:])
@@ -39,7 +46,7 @@ def load_seconds(exe, lst, fa, region, out, threads, batch, knob, fmt, repeats):
     return best
 
 
-def kernel_pair(lines, repeats):
+def kernel_pair(lines, repeats, text=False):
     import numpy as np
     import torch
     from basevarc_amd import Context
@@ -79,6 +86,20 @@ def kernel_pair(lines, repeats):
     lines.append(f"  {best * 1e3:.2f} ms a call (index + two passes of sizes + placement, one wait): {n_records / best / 1e6:.2f} M alignment records/s, "
                  f"{len(bam) / best / 1e9:.3f} GB/s of BAM bytes, {len(pv) * len(data) / best / 1e6:.1f} M (position, sample) cells/s")
     lines.append(f"  bvc_stream_read_ms on the same bytes: {gbs:.0f} GB/s")
+    if text:
+        rc, txt, ls, st, need = ctx.bam_pileup_text(*args)               # sizes the lines
+        assert rc == 0
+        tbest = None
+        for _ in range(repeats + 2):
+            ctx.synchronize()
+            t = time.perf_counter()
+            ctx.bam_pileup_text(*args, text=txt, line_start=ls, sample_status=st)
+            ctx.synchronize()
+            dt = time.perf_counter() - t
+            tbest = dt if tbest is None else min(tbest, dt)
+        lines.append(f"bvc_bam_pileup_text alone on the same input, {need} bytes of text:")
+        lines.append(f"  {tbest * 1e3:.2f} ms a call (index + two passes of sizes + filler rows + tokens, one wait): {need / tbest / 1e9:.3f} GB/s of text, "
+                     f"{len(pv) * len(data) / tbest / 1e6:.1f} M (position, sample) cells/s, {tbest / best:.2f} x the binary call")
     ctx.close()
 
 
@@ -87,12 +108,13 @@ def main():
     ap.add_argument("--copies", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--form", choices=("raw", "text"), default="raw")
     a = ap.parse_args()
     from basevarc_amd import build as b
     from tests import hostref
     exe, _ = b.build_host()
     lines = Lines()
-    lines.append("# phase 1 (bt_r) with BVC_HOST_DEVICE_PILEUP = 0 | 1: tools/bam_pileup_bench.py, best of %d runs, seconds of the whole --load process" % a.repeats)
+    lines.append("# phase 1 (bt_r) with %s = 0 | 1: tools/bam_pileup_bench.py, best of %d runs, seconds of the whole --load process" % (KNOB[a.form], a.repeats))
     with tempfile.TemporaryDirectory() as d:
         fa = hostref.write_fasta(os.path.join(d, "chr17.fa"))
         lst = hostref.write_bam_list(os.path.join(d, "bam.list"))
@@ -100,13 +122,13 @@ def main():
         with open(big, "w") as f:
             f.write(open(lst).read() * a.copies)
         for name, path, batch in (("100 test BAMs, batches of 10", lst, 10), (f"{100 * a.copies} samples (each test BAM {a.copies} times), batches of 100", big, 100)):
-            lines.append(f"{name}, --tmp-format raw")
+            lines.append(f"{name}, --tmp-format {a.form}")
             lines.append(f"  {'threads':>7s} {'knob 0':>9s} {'knob 1':>9s} {'1 / 0':>7s}")
             for threads in (1, 4, 8):
-                t0 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o0"), threads, batch, 0, "raw", a.repeats)
-                t1 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o1"), threads, batch, 1, "raw", a.repeats)
+                t0 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o0"), threads, batch, 0, a.form, a.repeats)
+                t1 = load_seconds(exe, path, fa, hostref.REGION, os.path.join(d, "o1"), threads, batch, 1, a.form, a.repeats)
                 lines.append(f"  {threads:7d} {t0:9.2f} {t1:9.2f} {t1 / t0:7.2f}")
-    kernel_pair(lines, a.repeats)
+    kernel_pair(lines, a.repeats, a.form == "text")
     text = "\n".join(lines) + "\n"
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
