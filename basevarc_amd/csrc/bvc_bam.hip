@@ -85,8 +85,10 @@ int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status)
 // The kernels of one call on inputs in device memory.  out_device: records, rec_start and sample_status are device memory and the call
 // returns with the second pass enqueued; else they are host memory (d_status: the statuses' place on the device) and the call waits.
 // text: the output is the batch's lines (records: the text, rec_start: line_start) instead of its binary records.
+// sink (host statuses, out_device false): the records and rec_start go to the device memory it names once the size is known, and the call
+// returns with both complete there; records, records_cap and rec_start are unused.
 int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool out_device, uint32_t *d_status, uint8_t *records, int64_t records_cap,
-                   int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status)
+                   int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink = nullptr)
 {
     const size_t ns = (size_t)c.n_samples, np = (size_t)c.n_positions;
     BamPileupScratch S;
@@ -115,20 +117,25 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool ou
     *records_needed = need;
     if (need > (int64_t)0xFFFFFF00u)
         return fail(ctx, BVC_ERR_ARG, text ? "the text exceeds 0xFFFFFF00 bytes (split the positions)" : "the records exceed 0xFFFFFF00 bytes (split the positions)");
-    if (need > records_cap) {
+    if (!sink && need > records_cap) {
         (void)fail_cap(ctx, text ? "text" : "records", records_cap, text ? "the batch's lines" : "the batch's records", need);
         return BVC_BAM_MORE;
     }
     uint8_t *d_records = records;
-    if (!out_device) {
+    uint32_t *d_rec_start = rec_start;
+    if (sink) {
+        rc = sink->reserve(ctx, need, &d_records, &d_rec_start);
+        if (rc != BVC_OK) return rc;
+    } else if (!out_device) {
         rc = ensure(ctx, ctx->d_bam_out, (size_t)need + 256);
         if (rc != BVC_OK) return rc;
         d_records = reinterpret_cast<uint8_t *>(ctx->d_bam_out.p);
     }
     if (!text) BVC_HIP_D(ctx, hipMemsetAsync(S.carry, 0, ns ? ns : 1, ctx->stream));   // (a text indel token shows no fields: no carry)
     BVC_HIP_D(ctx, tiles(true, d_records));
-    if (out_device) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(rec_start, S.rec_start, (np + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    if (out_device || sink) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(d_rec_start, S.rec_start, (np + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
+        if (sink) BVC_HIP_D(ctx, wait_stream(ctx));
         return BVC_OK;
     }
     BVC_HIP_D(ctx, io.d2h(rec_start, S.rec_start, (np + 1) * 4));
@@ -282,19 +289,21 @@ int bam_pileup_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *b
     return run_bam_pileup(ctx, io, c, text, device, d_status, records, records_cap, records_needed, rec_start, sample_status);
 }
 
-// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true)
+}  // namespace
+
+// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true); with a sink bvc_bam_pileup_bgzf_store (bvc_store.hip)
 int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
-                        int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
-                        int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
-                        const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
-                        uint32_t *rec_start, uint32_t *sample_status)
+                         int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                         int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                         const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
+                         uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink)
 {
     if (!ctx) return BVC_ERR_ARG;
     if (records_needed) *records_needed = 0;
     int rc = check_sizes(ctx, n_samples, bam_bytes, n_positions, refseq_len, records_cap);
     if (rc != BVC_OK) return rc;
     if (comp_bytes < 0 || n_blocks < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
-    if (!records_needed || !rec_start || (n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) ||
+    if (!records_needed || (!rec_start && !sink) || (n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) ||
         (n_blocks > 0 && (!comp || !blocks)) || (n_positions > 0 && !positions) || (refseq_len > 0 && !refseq) || (records_cap > 0 && !records))
         return fail(ctx, BVC_ERR_ARG, "null data pointer");
     rc = check_blocks(ctx, blocks, n_blocks, comp_bytes, bam_bytes);
@@ -334,15 +343,13 @@ int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8
     c.refseq_len = refseq_len;
     // the pileup's first wait delivers the blocks' statuses too: a block that did not inflate (or failed its CRC32) outranks what the
     // kernels made of its bytes
-    rc = run_bam_pileup(ctx, io, c, text, false, d_status, records, records_cap, records_needed, rec_start, sample_status);
+    rc = run_bam_pileup(ctx, io, c, text, false, d_status, records, records_cap, records_needed, rec_start, sample_status, sink);
     if (block_verdict(ctx, block_status) != BVC_OK) {
         *records_needed = 0;
         return BVC_ERR_DATA;
     }
     return rc;
 }
-
-}  // namespace
 
 extern "C" {
 

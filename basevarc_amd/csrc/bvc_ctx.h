@@ -319,6 +319,31 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
 int bgzf_blocks_down(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_comp, const int64_t *d_comp_off, uint8_t *comp,
                      int64_t *comp_off);
 
+// bvc_pileup.hip, shared with bvc_store.hip (a tile gathered from kept batches is laid out, checked and begun as bvc_pileup_begin_bin's):
+// the slices of a tile's meta buffer (returns the bytes from the status to the end of the tallies: what a begin call clears) ...
+size_t carve_tile(Layout &L, PileupTile &P, int32_t n_batches, int32_t n_pos, size_t batch_pad, uint32_t *&line_start, int32_t *&sample0,
+                  int32_t *&n_in_batch);
+// ... what a begin call checks of a batch's row of binary records before a kernel indexes with it ...
+int check_records(bvc_ctx *ctx, const uint8_t *records, const uint32_t *rs, int32_t n_positions, int64_t records_bytes);
+// ... and the end of a begin call whose count pass is enqueued: the one wait for the status and the totals, the verdict on them, the
+// tile marked begun.  *indel_text_bytes (may be null): the bytes of the tile's indel tokens
+int pileup_begin_verdict(bvc_ctx *ctx, bool bin, int64_t *n_entries, int64_t *n_indels, int64_t *indel_text_bytes);
+
+// bvc_bam.hip, shared with bvc_store.hip: where bvc_bam_pileup_bgzf's records go when they stay on the device.  reserve() is called between
+// the call's two passes, once the size is known, and names the device memory the second pass writes (anything but BVC_OK ends the call with
+// that code); the call returns BVC_OK with both complete on the device.
+struct BatchSink {
+    virtual int reserve(bvc_ctx *ctx, int64_t records_bytes, uint8_t **d_records, uint32_t **d_rec_start) = 0;
+protected:
+    ~BatchSink() = default;
+};
+// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true); sink (binary only): records, records_cap and rec_start are unused
+int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                         int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                         int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                         const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
+                         uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink = nullptr);
+
 // bvc_vcf.hip: the device copy of bvc_vcf_bp_lut in ctx->d_vcf_lut, made at the context's first use of it
 int vcf_lut_device(bvc_ctx *ctx);
 

@@ -307,6 +307,19 @@ hipError_t launch_bam_popmatrix(hipStream_t stream, int32_t n_samples, const uin
                                 const int64_t *sample_end, int32_t n_positions, const int32_t *positions, const uint8_t *ref, const uint8_t *alt,
                                 int32_t rg_s, int64_t refseq_len, const BamPileupScratch &s, uint8_t *matrix, int64_t row_stride, uint32_t *sample_status);
 
+// store_kernel.hip: temp batches kept on the device (include/bvc_store.h).  A kept batch as the kernels see it: the device addresses of its
+// rec_start row and of its records, and the records' bytes (what every word of the row is clamped with).
+constexpr int kStoreGrid = 1024;         // workgroups of store_gather_kernel at most: a tile of more items sends each round its loop again
+struct StoreBatch { uint64_t rec_start, records, bytes; };
+// What one bvc_pileup_begin_store call plans (the context's memory): per batch its slice's start in its records, the slice's bytes, its place
+// in the tile buffer and its first work item ([n_batches + 1]: the last word is the items' number); *used: the tile buffer's bytes in use
+struct StorePlan { uint32_t *lo, *len, *dst, *first_item; unsigned long long *used; };
+// cum[i] += rec_start[i], i < n_words
+hipError_t launch_store_cum(hipStream_t stream, const uint32_t *rec_start, int32_t n_words, unsigned long long *cum);
+// positions [t0, t0 + T] of every batch -> tile (16-byte aligned, tile_cap bytes: the slices' bytes and 16 a batch) and rows [n_batches][T + 1]
+hipError_t launch_store_gather(hipStream_t stream, const StoreBatch *batches, int32_t n_batches, int32_t t0, int32_t T, const StorePlan &plan,
+                               uint8_t *tile, int64_t tile_cap, uint32_t *rows);
+
 #ifdef BVC_CHECK_LDS
 hipError_t debug_read_inflate(uint32_t *out8, bool reset);
 hipError_t debug_read_pileup(uint32_t *out8, bool reset);

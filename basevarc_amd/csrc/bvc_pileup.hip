@@ -41,11 +41,13 @@ int bvc_inflate_blocks(bvc_ctx *ctx, const uint8_t *comp, int64_t comp_bytes, co
 }
 
 // ---- temp-batch pileup text -> columns -> records (pileup_kernel.hip) -------------------------------------------------------
+}  // extern "C": the three helpers below are shared with bvc_store.hip (bvc_ctx.h)
+
 // The slices of a tile's meta buffer that both begin calls lay out alike: the line table, the first sample and the size of every
 // batch (each slice batch_pad bytes longer), the per-line words, 256 bytes of status (the totals at +64), the two offset arrays
 // and the tallies.  Returns the bytes from the status to the end of the tallies: what a begin call clears.
-static size_t carve_tile(Layout &L, PileupTile &P, int32_t n_batches, int32_t n_pos, size_t batch_pad, uint32_t *&line_start,
-                         int32_t *&sample0, int32_t *&n_in_batch)
+size_t carve_tile(Layout &L, PileupTile &P, int32_t n_batches, int32_t n_pos, size_t batch_pad, uint32_t *&line_start,
+                  int32_t *&sample0, int32_t *&n_in_batch)
 {
     const size_t T = (size_t)n_pos, nb = (size_t)n_batches;
     P.n_batches = n_batches; P.n_pos = n_pos; P.line_stride = n_pos + 1;
@@ -75,7 +77,7 @@ static int check_lines(bvc_ctx *ctx, const uint32_t *ls, int32_t n_positions, in
 }
 
 // Binary records: every record inside the buffer, as long as its length word says (the kernel bounds every load with the table).
-static int check_records(bvc_ctx *ctx, const uint8_t *records, const uint32_t *rs, int32_t n_positions, int64_t records_bytes)
+int check_records(bvc_ctx *ctx, const uint8_t *records, const uint32_t *rs, int32_t n_positions, int64_t records_bytes)
 {
     for (int32_t t = 0; t < n_positions; ++t) {
         const int64_t r0 = rs[t], r1 = rs[t + 1];
@@ -86,6 +88,33 @@ static int check_records(bvc_ctx *ctx, const uint8_t *records, const uint32_t *r
     }
     return BVC_OK;
 }
+
+// The end of a begin call whose count pass is enqueued: the one wait, the verdict on the status, the tile marked begun.
+int pileup_begin_verdict(bvc_ctx *ctx, bool bin, int64_t *n_entries, int64_t *n_indels, int64_t *indel_text_bytes)
+{
+    PileupState::Tile &tile = ctx->pile.tile;
+    const PileupTile &P = tile.P;
+    uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    int64_t tot[2] = {0, 0};
+    BVC_HIP_D(ctx, hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    if (st[0] != 0) {
+        if (!bin) return BVC_PILEUP_IRREGULAR;                           // the caller parses such a tile on the host
+        const std::string what = std::to_string(st[0]) + " malformed record(s) in the tile (an entry or an indel text runs past its record's end, or a "
+                                 "sample index is not below the batch's size)";
+        return fail(ctx, BVC_ERR_DATA, what.c_str());
+    }
+    tile.entries = tot[0]; tile.obs = tot[1]; tile.indels = st[1];
+    // pileup_finish_impl gathers indel_bytes of indel text on the device: a text tile's caller has the text itself and its tile gathers none
+    tile.indel_bytes = bin ? st[4] : 0;
+    tile.begun = true;
+    *n_entries = tot[0]; *n_indels = st[1];
+    if (indel_text_bytes) *indel_text_bytes = tile.indel_bytes;
+    return BVC_OK;
+}
+
+extern "C" {
 
 // bvc_pileup_begin (bin = false: `data` is the text, row_start its line table) and bvc_pileup_begin_bin (true: the binary records of the same
 // content (host/pileup.h) go where the text goes, rec_start where line_start goes, and the tile is marked so that the count and write passes
@@ -131,23 +160,7 @@ static int pileup_begin_impl(bvc_ctx *ctx, bool bin, const uint8_t *data, int64_
         BVC_HIP_D(ctx, hipMemcpyAsync(d_nib, n_in_batch, nb * 4, hipMemcpyHostToDevice, ctx->stream));
         BVC_HIP_D(ctx, launch_pileup_count(ctx->stream, P));
     }
-    uint32_t st[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    int64_t tot[2] = {0, 0};
-    BVC_HIP_D(ctx, hipMemcpyAsync(st, P.status, sizeof st, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(ctx, hipMemcpyAsync(tot, P.totals, sizeof tot, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(ctx, wait_stream(ctx));
-    if (st[0] != 0) {
-        if (!bin) return BVC_PILEUP_IRREGULAR;                           // the caller parses such a tile on the host
-        const std::string what = std::to_string(st[0]) + " malformed record(s) in the tile (an entry or an indel text runs past its record's end, or a "
-                                 "sample index is not below the batch's size)";
-        return fail(ctx, BVC_ERR_DATA, what.c_str());
-    }
-    tile.entries = tot[0]; tile.obs = tot[1]; tile.indels = st[1];
-    // pileup_finish_impl gathers indel_bytes of indel text on the device: a text tile's caller has the text itself and its tile gathers none
-    tile.indel_bytes = bin ? st[4] : 0;
-    tile.begun = true;
-    *n_entries = tot[0]; *n_indels = st[1];
-    return BVC_OK;
+    return pileup_begin_verdict(ctx, bin, n_entries, n_indels, nullptr);
 }
 
 int bvc_pileup_begin(bvc_ctx *ctx, const char *text, int64_t text_bytes, const uint32_t *line_start,

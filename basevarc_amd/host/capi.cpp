@@ -11,6 +11,7 @@
 
 #include <sstream>
 
+#include "../../include/bvc_store.h"
 #include "bam.h"
 #include "bgzf.h"
 #include "inflate.h"
@@ -106,6 +107,12 @@ int64_t bvchost_bgzf_walk(const char *path, int64_t cap, int64_t *payload_off, i
         copy_out(e.what(), err, err_cap);
         return -1;
     }
+}
+// bvc_store_tile's arithmetic (include/bvc_store.h), which needs no device
+int32_t bvchost_store_tile_fit(const int64_t *cum, int32_t n_positions, int32_t n_batches, int32_t t0, int32_t max_positions, int64_t max_bytes,
+                               int64_t *bytes)
+{
+    return bvc_store_tile_fit(cum, n_positions, n_batches, t0, max_positions, max_bytes, bytes);
 }
 long bvchost_zlib_fallbacks(void) { return bgzf_zlib_fallbacks(); }
 long bvchost_crc_errors(void) { return bgzf_crc_errors(); }

@@ -28,6 +28,7 @@ inline double process_cpus()
 struct Knobs {
     static bool set(const char *name) { return getenv(name) != nullptr; }
     static int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
+    static double real(const char *name, double dflt) { const char *v = getenv(name); return v ? atof(v) : dflt; }
     explicit Knobs(int threads) : cpus_per_loop(process_cpus() / (double)std::max(1, threads)) {}
     // A position loop runs helper threads beside its own (the tile formatter, the deflaters of its two outputs, the call that finishes
     // a tile while the next one's blocks are gathered); how many it starts goes by the CPUs per loop -- past the quota they only get the
@@ -70,6 +71,9 @@ struct Knobs {
     // gathered, inflated and resolved there (bvc_bam_popmatrix_bgzf); taken only when the position file's positions do not descend, else
     // the CPU path runs and says so.  The matrix inflates to the same bytes.  Off by default (profiles/popmatrix/README.txt)
     const bool device_popmatrix = num("BVC_HOST_DEVICE_POPMATRIX", 0) != 0;
+    // --tmp-format mem: GB (a fraction will do) of device memory the batches kept there may take together (bvc_store_create's byte_budget);
+    // a batch past it ends the run with a line that names --tmp-format bin.  0: no cap but the device's
+    const double store_gb = std::max(0.0, real("BVC_HOST_STORE_GB", 0));
     const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

@@ -30,6 +30,7 @@
 #include "../../include/bvc_bam.h"
 #include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
+#include "../../include/bvc_store.h"
 #include "bam.h"
 #include "bam_blocks.h"
 #include "bam_gather.h"
@@ -66,7 +67,9 @@ static const char *BASETYPE_MESSAGE =
     "  --gpus           <INT>   MI355X devices to use [all]\n"
     "  --tile           <INT>   Positions per device call [4096]\n"
     "  --tmp-format     <STR>   Temp-batch files written by the load phase: text (as BaseVarC), bin (binary\n"
-    "                           records, deflated) or raw (binary records, stored: fastest to read back) [text]\n";
+    "                           records, deflated) or raw (binary records, stored: fastest to read back) [text];\n"
+    "                           mem: no files at all, the batches stay in the memory of one device (BVC_HOST_STORE_GB\n"
+    "                           caps them; not with --load, --keep_tmp or --gpus above 1)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -131,7 +134,7 @@ static void parse_options(int argc, char **argv, const char *msg)          // sr
         default: die = true;
         }
     }
-    if (opt::tmp_format != "text" && opt::tmp_format != "bin" && opt::tmp_format != "raw") die = true;
+    if (opt::tmp_format != "text" && opt::tmp_format != "bin" && opt::tmp_format != "raw" && opt::tmp_format != "mem") die = true;
     if (die || opt::input.empty() || opt::output.empty()) {
         std::cerr << msg;
         std::exit(die ? EXIT_FAILURE : EXIT_SUCCESS);
@@ -236,6 +239,36 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
 static std::atomic<long> g_device_batches(0);
 static std::atomic<int> g_load_threads(0);
 static std::atomic<bool> g_text_fallback_said(false);
+// The gathering and the retries around one of phase 1's library calls, shared by its forms: the batch's blocks are gathered, `call` makes
+// the library call and returns its code, and a sample whose list stopped short of its region's end is gathered to its file's end, once.
+// Returns false when `call` gave the batch up (kBatchGivenUp); throws the CPU path's messages for the statuses 3 and 4.
+static const int kBatchGivenUp = -1000;
+template <class Call>
+static bool device_batch_loop(BamBatch &batch, LoadDevice &dev, const std::vector<std::string> &bams, size_t b0, int32_t beg0, int32_t end0,
+                              std::vector<uint32_t> &status, Call call)
+{
+    for (int attempt = 0;; ++attempt) {
+        batch.gather(beg0, end0, attempt > 0, dev);
+        const int rc = call();
+        if (rc == BVC_OK) return true;
+        if (rc == kBatchGivenUp) return false;
+        if (rc == BVC_BAM_MORE && attempt == 0) {                     // a list that stopped short of its region's end: that sample to the file's end, once
+            batch.mark_short(status);
+            continue;
+        }
+        if (rc == BVC_ERR_DATA)
+            for (size_t s = 0; s < status.size(); ++s) {
+                // the messages of the CPU path: fetch's, and find_snp_at_pos's std::out_of_range
+                if (status[s] == 3u) throw std::runtime_error("ERROR: truncated or corrupt BAM record in " + bams[b0 + s]);
+                if (status[s] == 4u) throw std::out_of_range("index offset is out of range of the sequence");
+            }
+        if (rc == BVC_ERR_ALLOC)
+            throw std::runtime_error(std::string("ERROR: the batches do not fit the device's store (") + bvc_last_error(dev.ctx) +
+                                     "); --tmp-format bin keeps them in files");
+        throw std::runtime_error(std::string("ERROR: device pileup failed: ") + bvc_last_error(dev.ctx));
+    }
+}
+
 static void bt_r_device(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
                         const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus, bool text)
 {
@@ -264,8 +297,7 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
     names += "\n";
     std::vector<uint32_t> status(ns), rec_start(pv.size() + 1);
     std::vector<uint8_t> records;
-    for (int attempt = 0;; ++attempt) {
-        batch.gather(beg0, end0, attempt > 0, dev);
+    const bool done = device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
         int64_t need = 0;
         int rc;
         for (;;) {
@@ -274,23 +306,14 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
                 dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes, batch.off.data(),
                 batch.end.data(), batch.eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(), rg_s, refseq.data(),
                 (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(), status.data());
-            if (text && rc == BVC_ERR_ARG && need > kTextMax) return on_the_cpu();
+            if (text && rc == BVC_ERR_ARG && need > kTextMax) return kBatchGivenUp;
             if (rc != BVC_BAM_MORE || need <= (int64_t)records.size()) break;
             records.resize((size_t)need);
         }
-        if (rc == BVC_OK) { records.resize((size_t)need); break; }
-        if (rc == BVC_BAM_MORE && attempt == 0) {                     // a list that stopped short of its region's end: that sample to the file's end, once
-            batch.mark_short(status);
-            continue;
-        }
-        if (rc == BVC_ERR_DATA)
-            for (size_t s = 0; s < ns; ++s) {
-                // the messages of the CPU path: fetch's, and find_snp_at_pos's std::out_of_range
-                if (status[s] == 3u) throw std::runtime_error("ERROR: truncated or corrupt BAM record in " + bams[b0 + s]);
-                if (status[s] == 4u) throw std::out_of_range("index offset is out of range of the sequence");
-            }
-        throw std::runtime_error(std::string("ERROR: device pileup failed: ") + bvc_last_error(dev.ctx));
-    }
+        if (rc == BVC_OK) records.resize((size_t)need);
+        return rc;
+    });
+    if (!done) return on_the_cpu();
     for (size_t s = 0; s < ns; ++s)
         if (rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << sms[s] << " region " << opt::region << " is empty." << std::endl;
     const int level = opt::tmp_format == "raw" ? 0 : 6;
@@ -310,6 +333,36 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
         lo = hi;
         if (!fp.close()) std::cerr << "warning: file cannot be closed" << std::endl;
     }
+    ++g_device_batches;
+}
+
+// ---- phase 1 into the device's memory (--tmp-format mem): the same gathering and the same retries around bvc_bam_pileup_bgzf_store; the
+// batch's records stay on device 0 as batch `ib` of the process's one store, and nothing is written.  The batch's sample names are kept
+// here for the VCF header.
+struct MemBatches {
+    bvc_store *store = nullptr;
+    std::vector<std::vector<std::string>> names;    // per batch, filled by the thread that extracts it
+    ~MemBatches() { bvc_store_destroy(store); }
+};
+static void bt_r_mem(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                     int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, MemBatches &mem)
+{
+    static thread_local LoadDevice dev;
+    if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
+    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    BamBatch batch;
+    batch.open(bams, b0, b1, chr);
+    std::vector<uint32_t> status(ns);
+    device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
+        int64_t bytes = 0;
+        return bvc_bam_pileup_bgzf_store(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
+                                         batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(),
+                                         pv.data(), rg_s, refseq.data(), (int64_t)refseq.size(), mem.store, ib, &bytes, status.data());
+    });
+    for (size_t s = 0; s < ns; ++s)
+        if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
+    mem.names[(size_t)ib] = batch.sms;
     ++g_device_batches;
 }
 
@@ -340,7 +393,8 @@ static Groups read_groups(const std::vector<std::string> &names, int32_t N)
 }
 
 static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32_t> &pv, const std::string &refseq,
-                 const std::string &chr, int32_t rg_s, int32_t N, int thread, int ithread, int device, const Knobs &knobs, DeviceSlots &slots)
+                 const std::string &chr, int32_t rg_s, int32_t N, int thread, int ithread, int device, const Knobs &knobs, DeviceSlots &slots,
+                 const MemBatches *mem)
 {
     const double t_start = StageClock::now();
     // the outputs are deflated by threads of their writers' own (a VCF line carries a field per SAMPLE, a megabyte at 1e5 samples: up
@@ -361,6 +415,8 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     if (!sams.empty()) sams.pop_back();                                 // names are tab-terminated
     std::vector<std::string> names;
     { std::istringstream iss(sams); std::string id; while (std::getline(iss, id, '\t')) names.push_back(id); }
+    if (mem)                                                            // (no batch files: the names phase 1 kept, in batch order)
+        for (auto const &of_batch : mem->names) names.insert(names.end(), of_batch.begin(), of_batch.end());
     const Groups groups = read_groups(names, N);
     if (ithread == 0) {
         fpc.write(cvg_header(groups));
@@ -393,7 +449,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     // BVC_HOST_DEVICE_PARSE=0 keeps the CPU parser (A/B runs, and what the quality-shift test hook and a mix of text and binary files
     // use) ...
     const int qual_shift = knobs.qual_shift;
-    bool dev_parse = !qual_shift && knobs.device_parse;
+    bool dev_parse = (!qual_shift && knobs.device_parse) || mem;
     size_t n_bin_files = 0;
     for (auto const &fp : in) if (fp.bin) ++n_bin_files;
     if (n_bin_files != 0 && n_bin_files != in.size()) dev_parse = false;
@@ -412,7 +468,8 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
         }
         get_parser_carry(tr.carry);                                     // (zeros: reset_parser_carry above)
     }
-    if (dev_inflate) {
+    if (mem) feed_store_tiles(tr, w, mem->store, slots, device);
+    else if (dev_inflate) {
         std::vector<int32_t> skip;
         for (auto const &fp : in) skip.push_back((int32_t)fp.names.size() + 1);      // the names line and its newline
         in.clear();                                                     // closed before the feed maps the same files
@@ -467,6 +524,14 @@ static void run_pool(int n_tasks, int n_threads, F fn)
 static void run_basetype(int argc, char **argv)                          // src/BaseVarC.cpp:176-314
 {
     parse_options(argc, argv, BASETYPE_MESSAGE);
+    const bool in_memory = opt::tmp_format == "mem";
+    if (in_memory && opt::load) throw std::invalid_argument("ERROR: --tmp-format mem with --load: nothing would be left to compute from");
+    if (in_memory && opt::keep_tmp) throw std::invalid_argument("ERROR: --tmp-format mem with --keep_tmp: there are no temp files to keep");
+    if (in_memory && opt::gpus > 1) throw std::invalid_argument("ERROR: --tmp-format mem with --gpus above 1: the batches stay in the memory of one device");
+    if (in_memory && opt::rerun) {
+        std::cerr << "basetype: --rerun has nothing to reuse with --tmp-format mem, it is ignored" << std::endl;
+        opt::rerun = false;
+    }
     if (opt::reference.empty()) throw std::invalid_argument("reference must be feed");
     time_t tim = time(0);
     const clock_t ctb = clock();
@@ -487,7 +552,7 @@ static void run_basetype(int argc, char **argv)                          // src/
         if (c == 'A' || c == 'C' || c == 'G' || c == 'T') pv.push_back((int32_t)i + rg_s);
     }
     const int thread = std::max(1, opt::thread);
-    for (int i = 0; i < thread; ++i) {
+    for (int i = 0; i < thread && !in_memory; ++i) {
         const std::string d = opt::output + ".tmp.thread." + std::to_string(i);
         if (::mkdir(d.c_str(), 0777) != 0 && !file_exists(d)) throw std::runtime_error("ERROR: fail to run mkdir");
     }
@@ -495,7 +560,7 @@ static void run_basetype(int argc, char **argv)                          // src/
     const int nb = 1 + (N - 1) / bc;
     std::vector<std::vector<std::string>> ftmp_vv((size_t)thread);
     int ngz = 0, bk = nb - 1;
-    for (int j = 0; j < nb; ++j) {
+    for (int j = 0; j < nb && !in_memory; ++j) {
         int k = 0;
         for (int i = 0; i < thread; ++i) {
             const std::string f = tmp_name(i, j);
@@ -511,9 +576,27 @@ static void run_basetype(int argc, char **argv)                          // src/
     bool extract = true;
     if (opt::rerun && ngz > 0) { extract = ngz != thread * nb; first_batch = bk; }
     const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
+    MemBatches mem;
     if (extract) {
         std::cerr << "begin to extract reads from bam" << std::endl;
-        if (knobs.device_pileup && opt::tmp_format != "text") {
+        if (in_memory) {
+            if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+            if (bvc_store_create(&mem.store, 0, (int32_t)pv.size(), nb, (int64_t)(knobs.store_gb * 1073741824.0)) != BVC_OK)
+                throw std::runtime_error("ERROR: no usable gfx950 device for the store of the batches");
+            mem.names.resize((size_t)nb);
+            run_pool(nb, thread, [&](int t) { bt_r_mem(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, mem); });
+            {
+                LoadDevice dev;                                         // (sealing takes a context; any of the store's device)
+                if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+                bvc_check(dev.ctx, bvc_store_seal(dev.ctx, mem.store));
+            }
+            if (knobs.profile) {
+                int64_t used = 0;
+                bvc_store_bytes(mem.store, &used, nullptr);
+                std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches kept there (bvc_bam_pileup_bgzf_store), "
+                          << used << " bytes" << std::endl;
+            }
+        } else if (knobs.device_pileup && opt::tmp_format != "text") {
             const int load_gpus = bvc_device_count();
             if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
             run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, false); });
@@ -539,7 +622,8 @@ static void run_basetype(int argc, char **argv)                          // src/
         std::string werr;
         for (int i = 0; i < thread; ++i)
             workers.emplace_back([&, i]() {
-                try { bt_s(ftmp_vv[(size_t)i], pv, refseq, chr, rg_s, N, thread, i, device_of_thread(i, gpus, opt::gpus), knobs, slots); }
+                try { bt_s(in_memory ? std::vector<std::string>() : ftmp_vv[(size_t)i], pv, refseq, chr, rg_s, N, thread, i,
+                           in_memory ? 0 : device_of_thread(i, gpus, opt::gpus), knobs, slots, in_memory ? &mem : nullptr); }
                 catch (const std::exception &e) { std::lock_guard<std::mutex> g(mu); if (werr.empty()) werr = e.what(); }
             });
         // Every worker is joined BEFORE anything can throw: unwinding past a joinable std::thread is std::terminate,
@@ -574,7 +658,7 @@ static void run_basetype(int argc, char **argv)                          // src/
                       << (double)ru.ru_utime.tv_sec + 1e-6 * (double)ru.ru_utime.tv_usec << ")" << std::endl;
         }
     }
-    for (int i = 0; i < thread; ++i) ::rmdir((opt::output + ".tmp.thread." + std::to_string(i)).c_str());
+    for (int i = 0; i < thread && !in_memory; ++i) ::rmdir((opt::output + ".tmp.thread." + std::to_string(i)).c_str());
     time_t tim2 = time(0);
     std::cout << "basetype computing done -- " << ctime(&tim2);
     std::cout << "basetype elapsed cpu secs : " << double(clock() - ctb) / CLOCKS_PER_SEC << std::endl;

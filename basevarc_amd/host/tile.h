@@ -32,8 +32,8 @@ struct Window {
 };
 
 // What stage 1 put into a tile: the columns the CPU parser built, or what the device parses -- the lines of its positions, or their
-// binary records (bvc_pileup_begin / bvc_pileup_begin_bin)
-enum class TileForm { Sites, Text, Records };
+// binary records (bvc_pileup_begin / bvc_pileup_begin_bin), or its positions of the batches kept on the device (bvc_pileup_begin_store)
+enum class TileForm { Sites, Text, Records, Stored };
 // Where the VCF columns of a device-parsed tile's called positions come from: the entries of every position on the host (entry_off
 // says where), the entries of the called positions alone (called_off), the columns' text from the device (vtext_off / vtext_len), or
 // their finished BGZF blocks (vcomp_off).  TileRunner::finish_tile sets it.

@@ -143,6 +143,22 @@ BAM_TEXT_PROTOTYPES = {
     "bvc_bam_pileup_text_bgzf": BAM_PROTOTYPES["bvc_bam_pileup_bgzf"],
 }
 BAM_TEXT_EXPORTS = list(BAM_TEXT_PROTOTYPES)
+# The sixth header, include/bvc_store.h (tests/test_store_abi.py compares the two), bound by bind() with the others: temp batches kept on
+# the device.  bvc_bam_pileup_bgzf_store takes bvc_bam_pileup_bgzf's arguments up to refseq_len, then the store and the batch's index.
+STORE_PROTOTYPES = {
+    "bvc_store_create": (_int, [C.POINTER(_vp), _int, _i32, _i32, _i64]),
+    "bvc_store_destroy": (None, [_vp]),
+    "bvc_store_put": (_int, [_vp, _vp, _i32, _i32, _vp, _i64, _vp]),
+    "bvc_bam_pileup_bgzf_store": (_int, BAM_PROTOTYPES["bvc_bam_pileup_bgzf"][1][:19] + [_vp, _i32, _pi64, _vp]),
+    "bvc_store_get": (_int, [_vp, _vp, _i32, _vp, _i64, _pi64, _vp]),
+    "bvc_store_seal": (_int, [_vp, _vp]),
+    "bvc_store_tile": (_int, [_vp, _i32, _i32, _i64, C.POINTER(_i32), _pi64]),
+    "bvc_store_bytes": (_int, [_vp, _pi64, _pi64]),
+    "bvc_pileup_begin_store": (_int, [_vp, _vp, _i32, _i32, _pi64, _pi64, _pi64]),
+}
+STORE_EXPORTS = list(STORE_PROTOTYPES)
+STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
+STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
 BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
@@ -157,10 +173,10 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES and BAM_TEXT_PROTOTYPES its restype / argtypes on `cdll`
-    (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES and STORE_PROTOTYPES its
+    restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
-                                      list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items())):
+                                      list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -829,22 +845,39 @@ class Context:
         """bvc_bam_pileup_text_bgzf: the same from BGZF blocks still compressed.  comp: uint8 array; blocks: a BLOCK_DTYPE table (out_off:
         where each block's output lies among the bam_bytes inflated bytes).  Host arrays only.  Without text the call is made twice, as
         bam_pileup makes it.  Returns (rc, text, line_start, sample_status, text_needed)."""
+        return self._bam_pileup_bgzf(self._L.bvc_bam_pileup_text_bgzf, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq,
+                                     positions, rg_s, refseq, text, text_cap, line_start, sample_status)
+
+    def bam_pileup_bgzf(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                        records=None, records_cap=None, rec_start=None, sample_status=None):
+        """bvc_bam_pileup_bgzf (include/bvc_bam.h): bam_pileup_text_bgzf's binary twin.  Returns (rc, records, rec_start, sample_status,
+        records_needed)."""
+        return self._bam_pileup_bgzf(self._L.bvc_bam_pileup_bgzf, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq,
+                                     positions, rg_s, refseq, records, records_cap, rec_start, sample_status)
+
+    @staticmethod
+    def _bgzf_inputs(comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq):
+        """The arguments the _bgzf calls share, from comp to refseq_len, as host arrays and numbers in the header's order."""
         comp, tab = _as(comp, np.uint8), np.ascontiguousarray(blocks, dtype=BLOCK_DTYPE)
         sample_off, sample_end, sample_eof, rid = _as(sample_off, np.int64), _as(sample_end, np.int64), _as(sample_eof, np.uint8), _as(rid, np.int32)
         positions, refseq = _as(positions, np.int32), _as(refseq, np.uint8)
         n, P = len(rid), len(positions)
         if len(sample_off) != n or len(sample_end) != n or len(sample_eof) != n:
             raise ValueError("sample_off, sample_end and sample_eof must be [n_samples]")
+        opt = lambda a: a if a is not None and len(a) else None
+        return n, P, (opt(comp), len(comp), opt(tab), len(tab), int(bam_bytes), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0),
+                      int(end0), int(min_mapq), P, opt(positions), int(rg_s), opt(refseq), len(refseq))
+
+    def _bam_pileup_bgzf(self, fn, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                         text, text_cap, line_start, sample_status):
+        n, P, shared = self._bgzf_inputs(comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq)
         line_start = np.zeros(P + 1, dtype=np.uint32) if line_start is None else line_start
         sample_status = np.zeros(max(1, n), dtype=np.uint32) if sample_status is None else sample_status
         need = C.c_int64(0)
-        opt = lambda a: a if a is not None and len(a) else None
 
         def call(buf, cap):
-            rc = self._L.bvc_bam_pileup_text_bgzf(self._h, n, *_pointers((opt(comp), len(comp), opt(tab), len(tab), int(bam_bytes), opt(sample_off), opt(sample_end),
-                                                                         opt(sample_eof), opt(rid), int(beg0), int(end0), int(min_mapq), P, opt(positions),
-                                                                         int(rg_s), opt(refseq), len(refseq), opt(buf), cap), _np_ptr), C.byref(need),
-                                                  _np_ptr(line_start), _np_ptr(sample_status) if n else None)
+            rc = fn(self._h, n, *_pointers((*shared, buf if buf is not None and len(buf) else None, cap), _np_ptr), C.byref(need),
+                    _np_ptr(line_start), _np_ptr(sample_status) if n else None)
             if rc not in (0, BAM_MORE):
                 self._check(rc)
             return rc
@@ -855,6 +888,35 @@ class Context:
             text = np.zeros(need.value, dtype=np.uint8)
         rc = call(text, len(text) if text_cap is None else int(text_cap))
         return rc, text[:need.value] if rc == 0 else text, line_start, sample_status, need.value
+
+    def bam_pileup_bgzf_store(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                              store, batch, sample_status=None):
+        """bvc_bam_pileup_bgzf_store (include/bvc_store.h): bam_pileup_bgzf, but the records and rec_start stay on the device as batch `batch`
+        of `store` (a Store).  Returns (rc, sample_status, records_bytes): rc 0, or BAM_MORE (2) -- nothing is put then.  Raises BvcError for
+        the errors."""
+        n, _, shared = self._bgzf_inputs(comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq)
+        sample_status = np.zeros(max(1, n), dtype=np.uint32) if sample_status is None else sample_status
+        need = C.c_int64(0)
+        rc = self._L.bvc_bam_pileup_bgzf_store(self._h, n, *_pointers(shared, _np_ptr), store._h, int(batch), C.byref(need),
+                                               _np_ptr(sample_status) if n else None)
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        return rc, sample_status, need.value
+
+    def pileup_begin_store(self, store, t0, n_positions):
+        """bvc_pileup_begin_store (include/bvc_store.h): positions [t0, t0 + n_positions) of every batch of the sealed Store gathered into
+        this context's tile.  Returns (n_entries, n_indels, indel_text_bytes): what pileup_finish_store needs."""
+        ne, ni, nt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self._L.bvc_pileup_begin_store(self._h, store._h, int(t0), int(n_positions), C.byref(ne), C.byref(ni), C.byref(nt)))
+        return ne.value, ni.value, nt.value
+
+    def pileup_tile_store(self, store, t0, n_positions, ref_base, min_af, carry_in=(0, 0, 0, 0, 0), group_of_sample=None, n_groups=0,
+                          called_only=False, stats=False, sample_text=False):
+        """pileup_begin_store + one of the finish calls: the dict of pileup_tile_bin, the indel records' text_off offsets into its
+        "indel_text" (the tile's records are on the device only)."""
+        ne, ni, nt = self.pileup_begin_store(store, t0, n_positions)
+        return self._pileup_finish(int(n_positions), ne, ni, nt, ref_base, min_af, carry_in, group_of_sample, n_groups, called_only, stats=stats,
+                                   sample_text=sample_text)
 
     def bam_popmatrix(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, ref, alt, rg_s, refseq_len, matrix=None,
                       row_stride=None, sample_status=None):
@@ -1002,6 +1064,75 @@ class Context:
         ns = ref_t.numel()
         assert grp_counts_t.numel() == ns * (n_groups + 1) * NCLASS and grp_counts_t.is_contiguous()
         return self._lrt_hist_groups(True, ns, grp_counts_t, ref_t, min_af, n_groups, results_t, grp_results_t)
+
+
+class Store:
+    """One bvc_store (include/bvc_store.h): the binary temp-batch records of n_batches batches of n_positions positions each, kept in the
+    memory of one device.  Filled through any contexts of that device (put, Context.bam_pileup_bgzf_store; different batches may be put
+    from different threads at once), sealed, then read by Context.pileup_begin_store."""
+
+    def __init__(self, device, n_positions, n_batches, byte_budget=0):
+        self._L = load_library()
+        h = C.c_void_p()
+        rc = self._L.bvc_store_create(C.byref(h), int(device), int(n_positions), int(n_batches), int(byte_budget))
+        if rc != 0:
+            raise BvcError(f"bvc_store_create(device={device}) failed with code {rc}")
+        self._h = h
+        self.device, self.n_positions, self.n_batches = int(device), int(n_positions), int(n_batches)
+
+    create = classmethod(lambda cls, *a, **kw: cls(*a, **kw))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.bvc_store_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def put(self, ctx, batch, n_in_batch, records, rec_start):
+        """bvc_store_put: records (bytes or uint8 array) and rec_start (uint32 [n_positions + 1]) of batch `batch` from host memory."""
+        buf = np.frombuffer(bytes(records), dtype=np.uint8) if not isinstance(records, np.ndarray) else _as(records, np.uint8)
+        rs = _as(rec_start, np.uint32)
+        if rs.shape != (self.n_positions + 1,):
+            raise ValueError("rec_start must be [n_positions + 1]")
+        ctx._check(self._L.bvc_store_put(ctx._h, self._h, int(batch), int(n_in_batch), _np_ptr(buf) if len(buf) else None, len(buf), _np_ptr(rs)))
+
+    def get(self, ctx, batch):
+        """bvc_store_get: (records as bytes, rec_start uint32 [n_positions + 1]) of a kept batch."""
+        need = C.c_int64(0)
+        ctx._check(self._L.bvc_store_get(ctx._h, self._h, int(batch), None, 0, C.byref(need), None))
+        records = np.zeros(max(1, need.value), dtype=np.uint8)
+        rs = np.zeros(self.n_positions + 1, dtype=np.uint32)
+        ctx._check(self._L.bvc_store_get(ctx._h, self._h, int(batch), _np_ptr(records), need.value, C.byref(need), _np_ptr(rs)))
+        return records[:need.value].tobytes(), rs
+
+    def seal(self, ctx):
+        ctx._check(self._L.bvc_store_seal(ctx._h, self._h))
+
+    def tile(self, t0, max_positions, max_bytes):
+        """bvc_store_tile: (n_positions, bytes) of the largest tile from t0 on that the two limits admit; raises ValueError where the
+        library refuses (a store that is not sealed, t0 outside it, max_positions < 1)."""
+        T, nbytes = C.c_int32(0), C.c_int64(0)
+        rc = self._L.bvc_store_tile(self._h, int(t0), int(max_positions), int(max_bytes), C.byref(T), C.byref(nbytes))
+        if rc != 0:
+            raise ValueError(f"bvc_store_tile refused (code {rc})")
+        return T.value, nbytes.value
+
+    def bytes(self):
+        """bvc_store_bytes: (used, budget)."""
+        used, budget = C.c_int64(0), C.c_int64(0)
+        self._L.bvc_store_bytes(self._h, C.byref(used), C.byref(budget))
+        return used.value, budget.value
 
 
 def results_from_tensor(results_t):

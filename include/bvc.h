@@ -689,6 +689,8 @@ int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64
  * bvc_bam_text.h. */
 /* `BaseVarC popmatrix` on the device -- bvc_bam_popmatrix: the same records and a position file's lines -> one row of '0' / '1' / '.' per
  * sample (BVC_BAM_MORE there: some sample's bytes ran out) -- is declared in bvc_popmatrix.h beside this header. */
+/* Temp batches that stay on the device -- bvc_store_*: a batch's records kept in device memory, bvc_pileup_begin_store: a tile of positions
+ * gathered from all kept batches -- are declared in bvc_store.h beside this header. */
 
 #ifdef __cplusplus
 }
