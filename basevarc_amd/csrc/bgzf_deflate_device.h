@@ -1,7 +1,7 @@
-// bgzf_deflate_device.h -- what the two block kernels of the device deflate encoder share (bgzf_deflate_kernel.hip: fixed code or stored;
-// bgzf_dynamic_kernel.hip: a code of the block's own as well): the layout of a workgroup's LDS, the input's way into it, passes A (matches)
-// and B (path), the fixed code, the workgroup scan of pass C and the block's way out to its staging slot.  The passes are described at
-// the top of bgzf_deflate_kernel.hip.  Every function is inlined into its kernel; all of a workgroup's 1024 threads call each of them.
+// bgzf_deflate_device.h -- what the block kernels of the device deflate encoder share (bgzf_deflate_kernel.hip: fixed code or stored;
+// bgzf_dynamic_kernel.hip: a code of the block's own as well; bgzf_fields_kernel.hip: both behind another pass A): the layout of a
+// workgroup's LDS, the input's way into it, passes A (matches) and B (path), the fixed code, the workgroup scan of pass C and the
+// block's way out to its staging slot.  The passes are described at the top of bgzf_deflate_kernel.hip.  Every function is inlined into its kernel; all of a workgroup's 1024 threads call each of them.
 #pragma once
 #include "bvc_device.h"
 #include "bvc_internal.h"
@@ -336,6 +336,33 @@ __device__ __forceinline__ uint32_t bd_write_slot(uint8_t *slot, const uint32_t 
         slot32[k] = v;
     }
     return bs;
+}
+
+// ---- C for the fixed code, whole: the block behind pass B (whichever parse filled the match row) into its slot, fixed or stored.
+// s_out = s_in (the image takes the input's place), s_sym = the bytes of s_tab, s_ism = s_first.  Returns the block's size.
+__device__ __forceinline__ uint32_t bd_fixed_block(uint8_t *slot, uint32_t *s_in, const uint32_t *s_tab, const uint32_t *s_ism, const uint32_t *s_path,
+                                                   uint32_t *s_scan, const uint32_t *match, uint32_t n, uint32_t tid)
+{
+    const uint32_t lane = tid & (kWave - 1), wave = tid >> 6;
+    uint32_t *const s_out = s_in;
+    const uint8_t *const s_sym = reinterpret_cast<const uint8_t *>(s_tab);
+    const uint64_t mask = bd_my_symbols(s_path, n, tid);
+    const uint32_t my_bits = bd_fixed_bits(s_sym, s_ism, match, mask, n, tid);
+    uint32_t all;
+    const uint32_t before = bd_scan(my_bits, s_scan, lane, wave, all);
+    const uint32_t total_bits = 3u + all + 7u;                           // block header, symbols, end of block
+    const uint32_t coded = (total_bits + 7u) >> 3;
+    const bool stored = coded > n + 5u;                                   // (workgroup-uniform)
+    const uint32_t csize = stored ? n + 5u : coded;
+    const uint32_t out_words = (csize + 3u) >> 2;                         // <= (65280 + 5 + 3) / 4 < kBdInWords
+    if (!stored) {
+        // (the input's last readers were pass B's: its place takes the image)
+        for (uint32_t w = tid; w < out_words; w += kBdThreads) s_out[w] = 0u;
+        __syncthreads();
+        bd_fixed_write(s_out, out_words, s_sym, s_ism, match, mask, 3u + before, n, tid);     // this thread's first bit
+        __syncthreads();
+    }
+    return bd_write_slot(slot, s_in, s_out, n, csize, stored, tid);
 }
 
 }  // namespace

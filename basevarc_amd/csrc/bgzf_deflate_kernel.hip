@@ -6,7 +6,8 @@
 //   bgzf_plan_kernel     block b of the call -> (source, length): piece i holds blocks first_block[i] .. first_block[i + 1], of which
 //                        those behind the piece's real length are empty (the host may know an upper bound of a length only)
 //   bgzf_deflate_kernel  the block, written to its own 64 KiB slot of a staging buffer, and its size (tuning key "bgzf_codes" = 1:
-//                        bgzf_deflate_dynamic_kernel of bgzf_dynamic_kernel.hip in its place; the passes both run are in bgzf_deflate_device.h)
+//                        bgzf_deflate_dynamic_kernel of bgzf_dynamic_kernel.hip in its place; "bgzf_parse" = 1: the kernels of
+//                        bgzf_fields_kernel.hip, with another pass A; the passes they share are in bgzf_deflate_device.h)
 //   bgzf_crc_kernel      CRC32 of the block's input into its trailer: one wavefront a block, crc32_device.h
 //   bgzf_scan_kernel     exclusive prefix sums of the sizes: where each block goes, comp_off of every piece
 //   bgzf_pack_kernel     the blocks laid down one after the other, no gaps
@@ -67,10 +68,9 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_kernel(
     __shared__ uint32_t s_first[kBdBitWords];
     __shared__ uint32_t s_path[kBdBitWords];
     __shared__ uint32_t s_scan[32];
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     uint32_t *const match = match_rows + (size_t)blockIdx.x * kBdIn;
-    uint32_t *const s_out = s_in;                                             // pass C
-    uint8_t *const s_sym = reinterpret_cast<uint8_t *>(s_tab);               // passes B and C: the literal, or length - 3
+    // (pass C: the image of the output lies in s_in; passes B and C: the bytes of s_tab are the literal, or length - 3)
     uint32_t *const s_ism = s_first;                                          // passes B and C: bit p = position p holds a match
 
     for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {       // (workgroup-uniform)
@@ -84,24 +84,7 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_kernel(
         bd_matches(s_in, s_tab, s_first, match, n, tid);
         bd_path(s_in, s_tab, s_ism, s_path, match, n, tid);
 
-        // ---- C: bits
-        const uint64_t mask = bd_my_symbols(s_path, n, tid);
-        const uint32_t my_bits = bd_fixed_bits(s_sym, s_ism, match, mask, n, tid);
-        uint32_t all;
-        const uint32_t before = bd_scan(my_bits, s_scan, lane, wave, all);
-        const uint32_t total_bits = 3u + all + 7u;                           // block header, symbols, end of block
-        const uint32_t coded = (total_bits + 7u) >> 3;
-        const bool stored = coded > n + 5u;                                   // (workgroup-uniform)
-        const uint32_t csize = stored ? n + 5u : coded;
-        const uint32_t out_words = (csize + 3u) >> 2;                         // <= (65280 + 5 + 3) / 4 < kBdInWords
-        if (!stored) {
-            // (the input's last readers were pass B's: its place takes the image)
-            for (uint32_t w = tid; w < out_words; w += kBdThreads) s_out[w] = 0u;
-            __syncthreads();
-            bd_fixed_write(s_out, out_words, s_sym, s_ism, match, mask, 3u + before, n, tid);     // this thread's first bit
-            __syncthreads();
-        }
-        const uint32_t bs = bd_write_slot(slot, s_in, s_out, n, csize, stored, tid);
+        const uint32_t bs = bd_fixed_block(slot, s_in, s_tab, s_ism, s_path, s_scan, match, n, tid);     // ---- C: bits
         if (tid == 0u) bsize[blk] = bs;
         __syncthreads();                                                      // the LDS belongs to the next block from here
     }
@@ -204,14 +187,15 @@ BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_b
 }
 
 hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
-                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int codes)
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int codes, int parse)
 {
     BlockDesc *const desc = reinterpret_cast<BlockDesc *>(s.desc);
     if (n_blocks > 0) {
         const unsigned grid = (unsigned)(n_blocks < kBgzfDeflateGrid ? n_blocks : kBgzfDeflateGrid);
         hipLaunchKernelGGL(bgzf_plan_kernel, dim3((unsigned)((n_blocks + 255) / 256 < 1024 ? (n_blocks + 255) / 256 : 1024)), dim3(256), 0, stream,
                            n_pieces, piece_off, piece_len, s.first_block, n_blocks, desc);
-        if (codes == 1) launch_bgzf_deflate_dynamic_blocks(stream, grid, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
+        if (parse == 1) launch_bgzf_deflate_field_blocks(stream, grid, codes, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
+        else if (codes == 1) launch_bgzf_deflate_dynamic_blocks(stream, grid, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
         else hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, desc, n_blocks, s.staging, s.bsize, s.match_rows);
         const uintptr_t a = reinterpret_cast<uintptr_t>(data);
         hipLaunchKernelGGL(bgzf_crc_kernel, dim3((unsigned)(n_blocks < 65536 ? n_blocks : 65536)), dim3(kWave), 0, stream,

@@ -3,7 +3,7 @@
 // same 1024 threads a block, same staging slot and bsize; the plan, CRC, scan and pack kernels run unchanged around it.
 //
 // Passes A and B are the shared ones (bgzf_deflate_device.h): the parse -- literals, lengths, distances -- is the one the fixed code gets.
-// Behind them:
+// Behind them (bgzf_dynamic_device.h: the field parse's kernel of bgzf_fields_kernel.hip runs the same):
 //   COUNTS   thread t counts the symbols of positions 64 t .. 64 t + 63 into 316 LDS counters (atomicAdd), end of block once
 //   LENGTHS  wavefront 0 builds both alphabets' lengths, the code-length sequence, its code and all canonical codes by the rule of
 //            docs/BGZF_DYNAMIC.md (bgzf_codes_device.h), and the block's size in the dynamic (D) and in the fixed code; the other fifteen
@@ -16,10 +16,9 @@
 // bgzf_code_lengths_kernel runs the same length builder on counts of the caller's, one wavefront a set (bvc_bgzf_code_lengths).
 #include "bgzf_deflate_device.h"
 #include "bgzf_codes_device.h"
+#include "bgzf_dynamic_device.h"
 
 namespace bvc {
-
-static_assert((kBdInWords + kBdTabWords + 2 * kBdBitWords + 32) * 4 + sizeof(CodeTables) <= 160 * 1024, "one workgroup's LDS");
 
 __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_dynamic_kernel(
     const uint8_t *__restrict__ data, const BlockDesc *__restrict__ desc, int64_t n_blocks, uint8_t *__restrict__ staging,
@@ -32,10 +31,9 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_dynamic_kernel(
     __shared__ uint32_t s_path[kBdBitWords];
     __shared__ uint32_t s_scan[32];
     __shared__ CodeTables s_codes;
-    const uint32_t tid = threadIdx.x, lane = tid & (kWave - 1), wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     uint32_t *const match = match_rows + (size_t)blockIdx.x * kBdIn;
-    uint32_t *const s_out = s_in;                                             // the image of the output
-    uint8_t *const s_sym = reinterpret_cast<uint8_t *>(s_tab);               // behind pass B: the literal, or length - 3
+    // (behind pass B the image of the output lies in s_in, and the bytes of s_tab are the literal, or length - 3)
     uint32_t *const s_ism = s_first;                                          // behind pass B: bit p = position p holds a match
 
     for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {       // (workgroup-uniform)
@@ -49,94 +47,7 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_dynamic_kernel(
         bd_matches(s_in, s_tab, s_first, match, n, tid);
         bd_path(s_in, s_tab, s_ism, s_path, match, n, tid);
 
-        // ---- counts
-        const uint64_t mask = bd_my_symbols(s_path, n, tid);
-        const uint32_t base = 64u * tid;
-        const uint64_t ism = base < n ? (uint64_t)s_ism[2u * tid] | ((uint64_t)s_ism[2u * tid + 1u] << 32) : 0u;
-        for (uint32_t w = tid; w < kDcRow; w += kBdThreads) s_codes.counts[w] = 0u;
-        __syncthreads();
-        for (uint64_t left = mask; left != 0u; left &= left - 1u) {
-            const uint32_t p = base + (uint32_t)__builtin_ctzll(left);
-            if ((ism >> (p - base)) & 1u) {
-                uint32_t le, lx, de, dx;
-                const uint32_t sym = length_symbol((uint32_t)s_sym[p] + 3u, le, lx), ds = distance_symbol((match[p] & 0x7FFFu) + 1u, de, dx);
-                if (BVC_LDS_OK(0x921, sym, kDcLit)) atomicAdd(&s_codes.counts[sym], 1u);
-                if (BVC_LDS_OK(0x922, ds, kDcDist)) atomicAdd(&s_codes.counts[kDcLit + ds], 1u);
-            } else {
-                atomicAdd(&s_codes.counts[s_sym[p]], 1u);                    // (a byte: below 256)
-            }
-        }
-        if (tid == 0u) atomicAdd(&s_codes.counts[256], 1u);                  // end of block
-        __syncthreads();
-
-        // ---- lengths, codes, sizes: one wavefront
-        if (wave == 0u) dc_build_block(s_codes, lane, kWave);
-        __syncthreads();
-
-        // ---- choice (workgroup-uniform)
-        const uint32_t coded = (s_codes.fixed_bits + 7u) >> 3, dyn = (s_codes.dyn_bits + 7u) >> 3;
-        const bool fixed_stored = coded > n + 5u;                             // today's rule: F
-        const uint32_t f_size = fixed_stored ? n + 5u : coded;
-        const bool dynamic = dyn < f_size;
-        const bool stored = !dynamic && fixed_stored;
-        const uint32_t csize = dynamic ? dyn : f_size;
-        const uint32_t out_words = (csize + 3u) >> 2;                         // <= (65280 + 5 + 3) / 4 < kBdInWords
-
-        // ---- bits
-        uint32_t my_bits = 0u;
-        if (dynamic) {
-            for (uint64_t left = mask; left != 0u; left &= left - 1u) {
-                const uint32_t p = base + (uint32_t)__builtin_ctzll(left);
-                if ((ism >> (p - base)) & 1u) {
-                    uint32_t le, lx, de, dx;
-                    const uint32_t sym = length_symbol((uint32_t)s_sym[p] + 3u, le, lx), ds = distance_symbol((match[p] & 0x7FFFu) + 1u, de, dx);
-                    if (BVC_LDS_OK(0x923, sym, kDcLit) && BVC_LDS_OK(0x924, ds, kDcDist))
-                        my_bits += (s_codes.codes[sym] >> 16) + le + (s_codes.codes[kDcLit + ds] >> 16) + de;
-                } else {
-                    my_bits += s_codes.codes[s_sym[p]] >> 16;
-                }
-            }
-        } else if (!stored) {
-            my_bits = bd_fixed_bits(s_sym, s_ism, match, mask, n, tid);
-        }
-        uint32_t all;
-        const uint32_t before = bd_scan(my_bits, s_scan, lane, wave, all);
-        if (!stored) {
-            // (the input's last readers were pass B's: its place takes the image)
-            for (uint32_t w = tid; w < out_words; w += kBdThreads) s_out[w] = 0u;
-            __syncthreads();
-            if (dynamic) {
-                const uint32_t first = 3u + s_codes.header_bits;              // where thread 0's symbols begin
-                BitSink w;
-                if (tid == 0u) { w.start(s_out, out_words, 0u); dc_put_header(w, s_codes); }
-                else w.start(s_out, out_words, first + before);
-                for (uint64_t left = mask; left != 0u; left &= left - 1u) {
-                    const uint32_t p = base + (uint32_t)__builtin_ctzll(left);
-                    if ((ism >> (p - base)) & 1u) {
-                        uint32_t le, lx, de, dx;
-                        const uint32_t sym = length_symbol((uint32_t)s_sym[p] + 3u, le, lx), ds = distance_symbol((match[p] & 0x7FFFu) + 1u, de, dx);
-                        if (BVC_LDS_OK(0x925, sym, kDcLit) && BVC_LDS_OK(0x926, ds, kDcDist)) {
-                            const uint32_t lc = s_codes.codes[sym], dcode = s_codes.codes[kDcLit + ds];
-                            w.put((lc & 0xFFFFu) | (lx << (lc >> 16)), (lc >> 16) + le);          // up to 15 + 5 bits
-                            w.put((dcode & 0xFFFFu) | (dx << (dcode >> 16)), (dcode >> 16) + de);  // up to 15 + 13 bits
-                        }
-                    } else {
-                        w.code(s_codes.codes[s_sym[p]]);
-                    }
-                }
-                w.finish();
-                if (tid == 0u) {                                              // the end-of-block code behind the last thread's symbols
-                    BitSink e;
-                    e.start(s_out, out_words, first + all);
-                    e.code(s_codes.codes[256]);
-                    e.finish();
-                }
-            } else {
-                bd_fixed_write(s_out, out_words, s_sym, s_ism, match, mask, 3u + before, n, tid);
-            }
-            __syncthreads();
-        }
-        const uint32_t bs = bd_write_slot(slot, s_in, s_out, n, csize, stored, tid);
+        const uint32_t bs = bd_dynamic_block(slot, s_in, s_tab, s_ism, s_path, s_scan, s_codes, match, n, tid);
         if (tid == 0u) bsize[blk] = bs;
         __syncthreads();                                                      // the LDS belongs to the next block from here
     }

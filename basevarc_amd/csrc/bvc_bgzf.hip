@@ -1,5 +1,5 @@
 // bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip; with tuning key
-// "bgzf_codes" = 1 the block kernel of bgzf_dynamic_kernel.hip), and bvc_bgzf_code_lengths: that kernel's code-length builder on its own.
+// "bgzf_codes" = 1 the block kernel of bgzf_dynamic_kernel.hip, with "bgzf_parse" = 1 those of bgzf_fields_kernel.hip), and bvc_bgzf_code_lengths: that kernel's code-length builder on its own.
 // bvc_pileup_sample_bgzf (bvc_pileup.hip) hands a tile's sample columns to the same kernels where they are made.
 #include "bvc_ctx.h"
 #include "../../include/bvc_bgzf_codes.h"
@@ -18,7 +18,8 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
     // a call that returns with its launches in flight must not leave a transfer out of the page-locked buffer in flight too: the next
     // call on the context fills that buffer at once.  (The stream holds nothing but this copy here: its caller has just waited.)
     if (wait_for_upload) BVC_HIP_D(ctx, wait_stream(ctx));
-    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_codes));
+    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_codes,
+                                       ctx->ls.bgzf_parse));
     return BVC_OK;
 }
 

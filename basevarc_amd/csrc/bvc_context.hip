@@ -139,6 +139,7 @@ const Knob kKnobs[] = {
     {"em_tiny_regions", "BVC_EM_TINY_REGIONS", 0, 1, 1, 0, &LaunchState::em_tiny_regions},
     {"em_prune", "BVC_EM_PRUNE", 0, 1, 1, 1, &LaunchState::em_prune},
     {"bgzf_codes", "BVC_BGZF_CODES", 0, 1, 1, 0, &LaunchState::bgzf_codes},
+    {"bgzf_parse", "BVC_BGZF_PARSE", 0, 1, 1, 0, &LaunchState::bgzf_parse},
     {"csr_scatter_max", "BVC_CSR_SCATTER_MAX", 0, 1 << 30, 1, 64, &LaunchState::csr_scatter_max},
     {"stats_copies_log2", "BVC_STATS_LOG2C", 0, kStatsMaxLog2c, 1, 2, &LaunchState::stats_log2c},
     {"host_chunk_kib", nullptr, 1, 1 << 21, 1, 1 << 19, &LaunchState::host_chunk_kib},
@@ -384,6 +385,8 @@ int bvc_debug_report(bvc_ctx *ctx, uint32_t *out24, int reset)
     BVC_HIP(ctx, debug_read_bgzf_deflate(pl, reset != 0));
     if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
     BVC_HIP(ctx, debug_read_bgzf_dynamic(pl, reset != 0));
+    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
+    BVC_HIP(ctx, debug_read_bgzf_fields(pl, reset != 0));
     if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
     return BVC_OK;
 }

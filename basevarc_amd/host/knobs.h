@@ -58,6 +58,10 @@ struct Knobs {
     // 1: those blocks take a Huffman code of their own where that is smaller (tuning key "bgzf_codes" of the contexts, include/bvc.h):
     // a smaller .vcf.gz that inflates to the same bytes.  Acts only with device_deflate.  Off by default
     const bool device_deflate_codes = num("BVC_HOST_DEVICE_DEFLATE_CODES", 0) != 0 && device_deflate;
+    // 1: those blocks are parsed as fields ended by tabs and colons -- what the sample columns are -- instead of searched position by
+    // position (tuning key "bgzf_parse" of the contexts, include/bvc.h, docs/BGZF_FIELDS.md): other bytes that inflate to the same text.
+    // Acts only with device_deflate; independent of the knob above.  Off by default (profiles/vcf_deflate_fields/README.txt)
+    const bool device_deflate_fields = num("BVC_HOST_DEVICE_DEFLATE_FIELDS", 0) != 0 && device_deflate;
     // 1: phase 1 (bt_r) on the device -- the batch's BAM blocks are gathered, inflated and piled up there (bvc_bam_pileup_bgzf) and the
     // temp batches written from the records that come back; acts with --tmp-format bin|raw, ignored with text.  The batch files inflate
     // to the same bytes.  Off by default (profiles/bam_pileup/README.txt)

@@ -429,6 +429,8 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     if (bvc_create(&tr.ctx, device) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
     if (knobs.device_deflate_codes && bvc_set_tuning(tr.ctx, "bgzf_codes", 1) != BVC_OK)
         throw std::runtime_error(std::string("ERROR: libbvc: ") + bvc_last_error(tr.ctx));
+    if (knobs.device_deflate_fields && bvc_set_tuning(tr.ctx, "bgzf_parse", 1) != BVC_OK)
+        throw std::runtime_error(std::string("ERROR: libbvc: ") + bvc_last_error(tr.ctx));
     const double create_s = StageClock::now() - t_create;
     tr.groups = groups.empty() ? nullptr : &groups;
     tr.chr = chr;

@@ -354,8 +354,8 @@ class Context:
         return {tu: [int(x) for x in out[8 * i:8 * i + 6]] for i, tu in enumerate(("hist_kernel", "em_kernel", "em_items"))}
 
     def set_tuning(self, key, value):
-        """Launch policy of this context (include/bvc.h); results never depend on it (but for "em_engine", "em_tiny_regions", "em_prune"
-        and "bgzf_codes", which the header describes)."""
+        """Launch policy of this context (include/bvc.h); results never depend on it (but for "em_engine", "em_tiny_regions", "em_prune",
+        "bgzf_codes" and "bgzf_parse", which the header describes)."""
         self._check(self._L.bvc_set_tuning(self._h, key.encode(), int(value)))
 
     def host_alloc(self, nbytes):

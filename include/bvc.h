@@ -561,7 +561,14 @@ int bvc_synth_dense(bvc_ctx *ctx, uint64_t seed, int64_t site0, int64_t n_sites,
  *                      written in the fixed Huffman code, or stored; with 1 each block takes the smallest of stored, fixed and a
  *                      Huffman code of its own (RFC 1951 BTYPE = 10; the rule is with bvc_bgzf_deflate below).  It changes the BYTES of
  *                      the blocks, never what they inflate to, their number, their framing or the waits of the calls.  With 0
- *                      nothing differs by a byte from a library without the key.  Environment: BVC_BGZF_CODES. */
+ *                      nothing differs by a byte from a library without the key.  Environment: BVC_BGZF_CODES.
+ *   "bgzf_parse"       0 (default) / 1.  The same calls: with 0 a block's matches come from a search at every position; with 1 from the
+ *                      FIELD PARSE for tab-separated text (the rule is with bvc_bgzf_deflate below and in docs/BGZF_FIELDS.md): a field that
+ *                      repeats the field in front of it is a match at the distance of one field, the others look a hash of their bytes
+ *                      up, no other position has a match.  Independent of "bgzf_codes": all four combinations are valid.  It changes
+ *                      the BYTES of the blocks, never what they inflate to, their number, their framing or the waits of the calls;
+ *                      text without tabs or colons becomes literals, hence mostly stored blocks.  With 0 nothing differs by a byte
+ *                      from a library without the key.  Environment: BVC_BGZF_PARSE. */
 int bvc_set_tuning(bvc_ctx *ctx, const char *key, int value);
 
 /* ---- measurement aid ------------------------------------------------------------------------------- */
@@ -644,6 +651,15 @@ int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t 
  *   (c) HLIT, HDIST and HCLEN trimmed to the last used symbol (at least 257, 1 and 4)
  *   (d) the code-length code (19 symbols, limit 7) by rule (a)    (e) canonical codes, RFC 1951 3.2.2
  * bvc_bgzf_code_lengths (bvc_bgzf_codes.h) runs rule (a) on counts of the caller's.
+ *
+ * Tuning key "bgzf_parse" = 1 (default 0): another parse, for text made of short fields ended by tabs, with colons inside; whatever
+ * "bgzf_codes" says is then done with ITS literals, lengths and distances.  A pure function of a block's input bytes x[0 .. n)
+ * (docs/BGZF_FIELDS.md, in short): position p is a CUT iff p = 0 or x[p - 1] is a tab or a colon; a FIELD runs from a cut to the next, or
+ * to n.  A field is a REPEAT iff the field in front of it has the same length L and the same bytes, else a HEAD.  A repeat's match has
+ * distance L and the length min(e - p, 258) rounded down to a multiple of L, e the next head's start or n.  A head of 4..32 bytes looks
+ * for earlier heads with the same hash of (L, bytes) -- seventeen candidates at the most, a function of the bytes -- extends each up to
+ * 258 bytes, drops those that hold fewer than L, cuts the others back to the last cut (or n) they reach and keeps the longest, the
+ * nearest among equals.  No other position has a match, a match is used from 4 bytes on, and the path is the greedy walk of key 0.
  */
 #define BVC_BGZF_BLOCK_INPUT 65280
 /* Blocks of a piece: ceil(len / 65280), 0 for len <= 0. */
