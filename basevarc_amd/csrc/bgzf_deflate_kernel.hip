@@ -187,14 +187,14 @@ BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_b
 }
 
 hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
-                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int codes, int parse)
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int cuts, int codes, int parse)
 {
     BlockDesc *const desc = reinterpret_cast<BlockDesc *>(s.desc);
     if (n_blocks > 0) {
         const unsigned grid = (unsigned)(n_blocks < kBgzfDeflateGrid ? n_blocks : kBgzfDeflateGrid);
         hipLaunchKernelGGL(bgzf_plan_kernel, dim3((unsigned)((n_blocks + 255) / 256 < 1024 ? (n_blocks + 255) / 256 : 1024)), dim3(256), 0, stream,
                            n_pieces, piece_off, piece_len, s.first_block, n_blocks, desc);
-        if (parse == 1) launch_bgzf_deflate_field_blocks(stream, grid, codes, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
+        if (parse == 1) launch_bgzf_deflate_field_blocks(stream, grid, codes, cuts, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
         else if (codes == 1) launch_bgzf_deflate_dynamic_blocks(stream, grid, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
         else hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, desc, n_blocks, s.staging, s.bsize, s.match_rows);
         const uintptr_t a = reinterpret_cast<uintptr_t>(data);

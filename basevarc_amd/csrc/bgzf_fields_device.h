@@ -2,7 +2,8 @@
 // tests/bgzf_fields_model.py its plain Python copy): bd_field_matches fills the match row that bd_matches of bgzf_deflate_device.h fills
 // for the general parse, in the same format, so that pass B and everything behind it run as they are.
 //
-// The text is fields ended by a tab or a colon.  Two bitmaps of one bit a position say where a field starts (CUTS; bit n, the block's
+// The text is fields ended by one of two bytes: a tab or a colon, or with tuning key "bgzf_cuts" = 1 a space or a newline (kBfDelimsTabColon,
+// kBfDelimsSpaceNewline; the pair is a kernel argument).  Two bitmaps of one bit a position say where a field starts (CUTS; bit n, the block's
 // end, is set too) and which fields are no byte-for-byte repeat of the field in front of them (HEADS).  A repeat's match is the run it
 // stands in, at the distance of one field: nothing is searched.  A head of 4..32 bytes looks its key -- a hash of its length and bytes --
 // up in pass A's tables, which only such heads enter: rounds of 256 positions, way (r mod 16) = the largest position of an earlier round
@@ -20,6 +21,7 @@ namespace {
 
 constexpr uint32_t kBfMinKeyed = 4, kBfMaxKeyed = 32;    // the lengths of the heads that have a key
 constexpr uint32_t kBfNone = 0xFFFFFFFFu;
+constexpr uint32_t kBfDelimsTabColon = 0x09u | (0x3Au << 8), kBfDelimsSpaceNewline = 0x20u | (0x0Au << 8);   // the two bytes that end a field
 
 __device__ __forceinline__ bool bf_bit(const uint32_t *bm, uint32_t p)
 {
@@ -113,9 +115,10 @@ __device__ __forceinline__ uint32_t bf_key(const uint32_t *s_in, uint32_t p, uin
 // ---- A for the field parse.  s_cut lies in s_path's place (pass B clears it behind this); s_head and s_best (a word a position of a
 // round: the best match of the head there) are this parse's own.
 __device__ __forceinline__ void bd_field_matches(const uint32_t *s_in, uint32_t *s_tab, uint32_t *s_first, uint32_t *s_cut, uint32_t *s_head,
-                                                 uint32_t *s_best, uint32_t *match, uint32_t n, uint32_t tid)
+                                                 uint32_t *s_best, uint32_t *match, uint32_t n, uint32_t tid, uint32_t delims)
 {
-    // cuts: position p starts a field iff p = 0 or byte p - 1 is a tab or a colon (the bytes behind the block read as zero); bit n
+    // cuts: position p starts a field iff p = 0 or byte p - 1 is one of the two delimiters (the bytes behind the block read as zero); bit n
+    const uint32_t d0 = delims & 0xFFu, d1 = (delims >> 8) & 0xFFu;
     for (uint32_t g = tid; g < (uint32_t)kBdBitWords; g += kBdThreads) {
         uint32_t delim = 0u;                                              // bit j: byte 32 g + j ends a field
 #pragma unroll
@@ -124,11 +127,11 @@ __device__ __forceinline__ void bd_field_matches(const uint32_t *s_in, uint32_t 
 #pragma unroll
             for (uint32_t k = 0; k < 4u; ++k) {
                 const uint32_t b = (w >> (8u * k)) & 0xFFu;
-                delim |= (b == 0x09u || b == 0x3Au ? 1u : 0u) << (4u * j + k);
+                delim |= (b == d0 || b == d1 ? 1u : 0u) << (4u * j + k);
             }
         }
-        const uint32_t before = g != 0u ? s_in[8u * g - 1u] >> 24 : 0x09u;
-        uint32_t cuts = (delim << 1) | (before == 0x09u || before == 0x3Au ? 1u : 0u);
+        const uint32_t before = g != 0u ? s_in[8u * g - 1u] >> 24 : d0;
+        uint32_t cuts = (delim << 1) | (before == d0 || before == d1 ? 1u : 0u);
         if ((n >> 5) == g) cuts |= 1u << (n & 31u);
         s_cut[g] = cuts;
     }

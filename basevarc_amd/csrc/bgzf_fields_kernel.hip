@@ -3,7 +3,8 @@
 // bgzf_deflate_fields_dynamic_kernel).  Same grid, same 1024 threads a block, same staging slot and bsize; the plan, CRC, scan and pack
 // kernels of bgzf_deflate_kernel.hip run unchanged around them.
 //
-// Only pass A differs: bd_field_matches (bgzf_fields_device.h) fills the match row from two bitmaps of the block -- where fields start,
+// Only pass A differs: bd_field_matches (bgzf_fields_device.h) fills the match row from two bitmaps of the block -- where fields start (behind
+// a tab or a colon; with tuning key "bgzf_cuts" = 1 behind a space or a newline: the pair of bytes is the kernels' last argument),
 // which fields repeat the field in front of them -- and a table look-up for the others, where bd_matches searches at every position.
 // The row's format is the same, so pass B (the path) and what follows it are the shared ones: bd_fixed_block of bgzf_deflate_device.h,
 // bd_dynamic_block of bgzf_dynamic_device.h.  The cuts' bitmap lies where pass B keeps the path bits; the heads' bitmap and a round's best
@@ -19,7 +20,7 @@ static_assert((kBdInWords + kBdTabWords + 3 * kBdBitWords + kBdRound + 32) * 4 +
 
 __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_kernel(
     const uint8_t *__restrict__ data, const BlockDesc *__restrict__ desc, int64_t n_blocks, uint8_t *__restrict__ staging,
-    uint32_t *__restrict__ bsize, uint32_t *__restrict__ match_rows)
+    uint32_t *__restrict__ bsize, uint32_t *__restrict__ match_rows, uint32_t delims)
 {
     BVC_POISON_LDS();
     __shared__ __attribute__((aligned(16))) uint32_t s_in[kBdInWords];
@@ -41,7 +42,7 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_kernel(
             continue;
         }
         bd_load(s_in, s_tab, s_first, data + desc[blk].src, n, tid);
-        bd_field_matches(s_in, s_tab, s_first, s_path, s_head, s_best, match, n, tid);
+        bd_field_matches(s_in, s_tab, s_first, s_path, s_head, s_best, match, n, tid, delims);
         bd_path(s_in, s_tab, s_ism, s_path, match, n, tid);
         const uint32_t bs = bd_fixed_block(slot, s_in, s_tab, s_ism, s_path, s_scan, match, n, tid);
         if (tid == 0u) bsize[blk] = bs;
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_kernel(
 
 __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_dynamic_kernel(
     const uint8_t *__restrict__ data, const BlockDesc *__restrict__ desc, int64_t n_blocks, uint8_t *__restrict__ staging,
-    uint32_t *__restrict__ bsize, uint32_t *__restrict__ match_rows)
+    uint32_t *__restrict__ bsize, uint32_t *__restrict__ match_rows, uint32_t delims)
 {
     BVC_POISON_LDS();
     __shared__ __attribute__((aligned(16))) uint32_t s_in[kBdInWords];
@@ -74,7 +75,7 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_dynamic_kernel
             continue;
         }
         bd_load(s_in, s_tab, s_first, data + desc[blk].src, n, tid);
-        bd_field_matches(s_in, s_tab, s_first, s_path, s_head, s_best, match, n, tid);
+        bd_field_matches(s_in, s_tab, s_first, s_path, s_head, s_best, match, n, tid, delims);
         bd_path(s_in, s_tab, s_ism, s_path, match, n, tid);
         const uint32_t bs = bd_dynamic_block(slot, s_in, s_tab, s_ism, s_path, s_scan, s_codes, match, n, tid);
         if (tid == 0u) bsize[blk] = bs;
@@ -82,14 +83,15 @@ __global__ __launch_bounds__(kBdThreads) void bgzf_deflate_fields_dynamic_kernel
     }
 }
 
-void launch_bgzf_deflate_field_blocks(hipStream_t stream, unsigned grid, int codes, const uint8_t *data, const char *desc, int64_t n_blocks,
+void launch_bgzf_deflate_field_blocks(hipStream_t stream, unsigned grid, int codes, int cuts, const uint8_t *data, const char *desc, int64_t n_blocks,
                                       uint8_t *staging, uint32_t *bsize, uint32_t *match_rows)
 {
     const BlockDesc *const d = reinterpret_cast<const BlockDesc *>(desc);
+    const uint32_t delims = cuts == 1 ? kBfDelimsSpaceNewline : kBfDelimsTabColon;   // tuning key "bgzf_cuts"
     if (codes == 1)
-        hipLaunchKernelGGL(bgzf_deflate_fields_dynamic_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, d, n_blocks, staging, bsize, match_rows);
+        hipLaunchKernelGGL(bgzf_deflate_fields_dynamic_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, d, n_blocks, staging, bsize, match_rows, delims);
     else
-        hipLaunchKernelGGL(bgzf_deflate_fields_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, d, n_blocks, staging, bsize, match_rows);
+        hipLaunchKernelGGL(bgzf_deflate_fields_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, d, n_blocks, staging, bsize, match_rows, delims);
 }
 
 #ifdef BVC_CHECK_LDS

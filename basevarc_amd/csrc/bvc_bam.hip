@@ -86,7 +86,8 @@ int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status)
 // returns with the second pass enqueued; else they are host memory (d_status: the statuses' place on the device) and the call waits.
 // text: the output is the batch's lines (records: the text, rec_start: line_start) instead of its binary records.
 // sink (host statuses, out_device false): the records and rec_start go to the device memory it names once the size is known, and the call
-// returns with both complete there; records, records_cap and rec_start are unused.
+// returns with both complete there (sink->wait false: enqueued); records, records_cap and rec_start are unused.  With sink->h_rec_start the
+// row comes to the host with the first wait too: the scan has made it, the second pass only reads it.
 int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool out_device, uint32_t *d_status, uint8_t *records, int64_t records_cap,
                    int64_t *records_needed, uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink = nullptr)
 {
@@ -109,6 +110,7 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool ou
     int64_t head[4] = {0, 0, 0, 0};
     BVC_HIP_D(ctx, io.d2h(head, S.head, sizeof head));
     if (!out_device && ns) BVC_HIP_D(ctx, io.d2h(sample_status, d_status, ns * 4));
+    if (sink && sink->h_rec_start) BVC_HIP_D(ctx, io.d2h(sink->h_rec_start, S.rec_start, (np + 1) * 4));
     BVC_HIP_D(ctx, wait_stream(ctx));               // the one wait of a device-pointer call: the size and the statuses decide what it returns
     io.deliver();
     rc = status_verdict(ctx, head);
@@ -135,7 +137,7 @@ int run_bam_pileup(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool text, bool ou
     BVC_HIP_D(ctx, tiles(true, d_records));
     if (out_device || sink) {
         BVC_HIP_D(ctx, hipMemcpyAsync(d_rec_start, S.rec_start, (np + 1) * 4, hipMemcpyDeviceToDevice, ctx->stream));
-        if (sink) BVC_HIP_D(ctx, wait_stream(ctx));
+        if (sink && sink->wait) BVC_HIP_D(ctx, wait_stream(ctx));
         return BVC_OK;
     }
     BVC_HIP_D(ctx, io.d2h(rec_start, S.rec_start, (np + 1) * 4));

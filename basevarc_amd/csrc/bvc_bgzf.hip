@@ -18,19 +18,20 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
     // a call that returns with its launches in flight must not leave a transfer out of the page-locked buffer in flight too: the next
     // call on the context fills that buffer at once.  (The stream holds nothing but this copy here: its caller has just waited.)
     if (wait_for_upload) BVC_HIP_D(ctx, wait_stream(ctx));
-    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_codes,
-                                       ctx->ls.bgzf_parse));
+    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_cuts,
+                                       ctx->ls.bgzf_codes, ctx->ls.bgzf_parse));
     return BVC_OK;
 }
 
 int bgzf_blocks_down(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_comp, const int64_t *d_comp_off, uint8_t *comp,
-                     int64_t *comp_off)
+                     int64_t *comp_off, int64_t comp_cap)
 {
     BVC_HIP_D(ctx, io.d2h(comp_off, d_comp_off, ((size_t)n_pieces + 1) * 8));
     BVC_HIP_D(ctx, wait_stream(ctx));
     io.deliver();
     // the second wait: only the packed bytes come down, and how many they are was not known before
     const int64_t packed = comp_off[n_pieces];
+    if (comp_cap >= 0 && packed > comp_cap) return BVC_BAM_MORE;
     if (packed > 0) {
         BVC_HIP_D(ctx, hipMemcpyAsync(comp, d_comp, (size_t)packed, hipMemcpyDeviceToHost, ctx->stream));
         BVC_HIP_D(ctx, wait_stream(ctx));

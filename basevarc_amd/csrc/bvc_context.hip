@@ -140,6 +140,7 @@ const Knob kKnobs[] = {
     {"em_prune", "BVC_EM_PRUNE", 0, 1, 1, 1, &LaunchState::em_prune},
     {"bgzf_codes", "BVC_BGZF_CODES", 0, 1, 1, 0, &LaunchState::bgzf_codes},
     {"bgzf_parse", "BVC_BGZF_PARSE", 0, 1, 1, 0, &LaunchState::bgzf_parse},
+    {"bgzf_cuts", "BVC_BGZF_CUTS", 0, 1, 1, 0, &LaunchState::bgzf_cuts},
     {"csr_scatter_max", "BVC_CSR_SCATTER_MAX", 0, 1 << 30, 1, 64, &LaunchState::csr_scatter_max},
     {"stats_copies_log2", "BVC_STATS_LOG2C", 0, kStatsMaxLog2c, 1, 2, &LaunchState::stats_log2c},
     {"host_chunk_kib", nullptr, 1, 1 << 21, 1, 1 << 19, &LaunchState::host_chunk_kib},

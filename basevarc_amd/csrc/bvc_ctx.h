@@ -96,6 +96,8 @@ struct bvc_ctx {
     DevBuf d_vcf, d_vcf_lut;           // vcf_samples_kernel.hip: the plan's scratch (device-pointer calls); the 256 x 8 bytes of bvc_vcf_bp_lut
     DevBuf d_bgzf, d_bgzf_io;          // bgzf_deflate_kernel.hip: block tables, match rows, staged blocks; a call's staged pieces (host pointers), its packed blocks and comp_off
     DevBuf d_bam, d_bam_out;           // bam_pileup_kernel.hip: the read table, one tile's size matrix, the per-position sizes; a host-pointer call's records
+    DevBuf d_bamz, d_bamz_out;         // bvc_bam_deflate.hip: a batch's records or lines and their rec_start row; the pieces' tables, the packed blocks, out_off
+    int64_t bamz_kept = -1;            // >= 0: the packed bytes at the front of d_bamz_out that bvc_bam_pileup_deflate_fetch delivers
     // pinned host memory the pileup calls bounce their transfers through: a copy from or to pageable memory makes the calling thread
     // wait inside the runtime -- spinning -- for the whole transfer; from pinned memory it is a DMA the thread sleeps behind (wait_stream)
     char *h_up = nullptr, *h_down = nullptr;
@@ -316,8 +318,10 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
 // The tail of a call that delivers blocks to the host: comp_off [n_pieces + 1] comes down through io and is waited for and delivered (with
 // whatever else io has coming down), then only the comp_off[n_pieces] packed bytes come straight into the caller's memory (a DMA where
 // that is bvc_host_alloc memory), with a second wait.  io: (n_pieces + 1) * 8 + 64 bytes reserved coming down.
+// comp_cap >= 0: a caller that could not size comp before -- where comp_off[n_pieces] exceeds it nothing more comes down and the call returns
+// BVC_BAM_MORE (comp_off is written; the blocks stay where they are).
 int bgzf_blocks_down(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t *d_comp, const int64_t *d_comp_off, uint8_t *comp,
-                     int64_t *comp_off);
+                     int64_t *comp_off, int64_t comp_cap = -1);
 
 // bvc_pileup.hip, shared with bvc_store.hip (a tile gathered from kept batches is laid out, checked and begun as bvc_pileup_begin_bin's):
 // the slices of a tile's meta buffer (returns the bytes from the status to the end of the tallies: what a begin call clears) ...
@@ -333,11 +337,13 @@ int pileup_begin_verdict(bvc_ctx *ctx, bool bin, int64_t *n_entries, int64_t *n_
 // the call's two passes, once the size is known, and names the device memory the second pass writes (anything but BVC_OK ends the call with
 // that code); the call returns BVC_OK with both complete on the device.
 struct BatchSink {
+    uint32_t *h_rec_start = nullptr;   // not null: rec_start [n_positions + 1] comes down to it with the call's first wait, before reserve()
+    bool wait = true;                  // false: the call returns with its second pass enqueued on the context's stream, as a device-pointer call
     virtual int reserve(bvc_ctx *ctx, int64_t records_bytes, uint8_t **d_records, uint32_t **d_rec_start) = 0;
 protected:
     ~BatchSink() = default;
 };
-// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true); sink (binary only): records, records_cap and rec_start are unused
+// bvc_bam_pileup_bgzf (text = false) and bvc_bam_pileup_text_bgzf (text = true); sink: records, records_cap and rec_start are unused
 int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
                          int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
                          int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,

@@ -43,6 +43,8 @@ struct LaunchState {
                                    // the block's own (bgzf_deflate_dynamic_kernel).  Not a launch policy: it changes the bytes
     int bgzf_parse = 0;            // device deflate: 0 = the general parse (a search at every position, bd_matches), 1 = the field parse for
                                    // tab-separated text (bd_field_matches, bgzf_fields_kernel.hip).  Independent of bgzf_codes; it changes the bytes
+    int bgzf_cuts = 0;             // the field parse (bgzf_parse = 1; nothing otherwise): what ends a field -- 0 = a tab or a colon, 1 = a space or a
+                                   // newline (the text temp batches' lines).  It changes the bytes
     int dbg_levels = 0;            // BVC_DBG_LEVELS (timing only, records wrong): cut region_kernel short after a phase; 0 = run all
     mutable uint32_t em_epoch = 0; // stage-2 launches of this context so far (em_items.hip: the narrow launch tells the wide one)
     struct RaisedLds { const void *kernel; size_t bytes; };
@@ -255,14 +257,15 @@ struct BgzfDeflateScratch { int64_t *first_block, *block_off; char *desc; uint32
 size_t bgzf_deflate_scratch_bytes(int64_t n_pieces, int64_t n_blocks);
 BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_blocks, Layout *sized = nullptr);
 hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
-                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int codes, int parse);
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int cuts, int codes, int parse);
 // bgzf_dynamic_kernel.hip: the block kernel of codes = 1 (launch_bgzf_deflate launches it in bgzf_deflate_kernel's place; desc: its block
 // table), and the code-length builder on counts of the caller's: lengths[set][s] from counts[set][s], device pointers
 void launch_bgzf_deflate_dynamic_blocks(hipStream_t stream, unsigned grid, const uint8_t *data, const char *desc, int64_t n_blocks, uint8_t *staging,
                                         uint32_t *bsize, uint32_t *match_rows);
 hipError_t launch_bgzf_code_lengths(hipStream_t stream, int64_t n_sets, const uint32_t *counts, int32_t n_symbols, int32_t limit, uint8_t *lengths);
-// bgzf_fields_kernel.hip: the block kernels of parse = 1, with the fixed code (codes = 0) or a code of the block's own (codes = 1)
-void launch_bgzf_deflate_field_blocks(hipStream_t stream, unsigned grid, int codes, const uint8_t *data, const char *desc, int64_t n_blocks,
+// bgzf_fields_kernel.hip: the block kernels of parse = 1, with the fixed code (codes = 0) or a code of the block's own (codes = 1);
+// cuts: what ends a field (0: a tab or a colon, 1: a space or a newline)
+void launch_bgzf_deflate_field_blocks(hipStream_t stream, unsigned grid, int codes, int cuts, const uint8_t *data, const char *desc, int64_t n_blocks,
                                       uint8_t *staging, uint32_t *bsize, uint32_t *match_rows);
 
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes

@@ -71,6 +71,19 @@ struct Knobs {
     // cannot fit 0xFFFFFF00 bytes takes the CPU path, said once.  The batch files inflate to the same bytes.  Off by default
     // (profiles/bam_pileup_text/README.txt)
     const bool device_pileup_text = num("BVC_HOST_DEVICE_PILEUP_TEXT", 0) != 0;
+    // 1: the batch is also deflated on the device (bvc_bam_pileup_bgzf_deflate / bvc_bam_pileup_text_bgzf_deflate, include/bvc_bam_deflate.h):
+    // only finished BGZF blocks come back, cut at the threads' windows, and each batch file is its names line (or binary header) through the
+    // writer, then its window's blocks (BgzfWriter::write_blocks).  Acts with device_pileup on --tmp-format bin, or with device_pileup_text
+    // on text; ignored with raw (stored blocks are that form's point) and mem (no files).  The batch files inflate to the same bytes; they are
+    // larger than zlib's level 6 makes them.  Off by default (profiles/bam_pileup_deflate/README.txt)
+    const bool device_pileup_deflate = num("BVC_HOST_DEVICE_PILEUP_DEFLATE", 0) != 0 && (device_pileup || device_pileup_text);
+    // 1: those blocks take a Huffman code of their own where that is smaller (tuning key "bgzf_codes" of the load contexts).  Acts only
+    // with device_pileup_deflate.  Off by default
+    const bool device_pileup_deflate_codes = num("BVC_HOST_DEVICE_PILEUP_DEFLATE_CODES", 0) != 0 && device_pileup_deflate;
+    // 1, text only: those blocks are parsed as tokens ended by a space or a newline -- what a text batch's lines are -- instead of searched
+    // position by position (tuning keys "bgzf_parse" = 1 and "bgzf_cuts" = 1 of the load contexts, docs/BGZF_FIELDS.md).  Acts only with
+    // device_pileup_deflate and device_pileup_text; independent of the knob above.  Off by default
+    const bool device_pileup_deflate_tokens = num("BVC_HOST_DEVICE_PILEUP_DEFLATE_TOKENS", 0) != 0 && device_pileup_deflate && device_pileup_text;
     // 1: `BaseVarC popmatrix` makes the matrix's rows on the device -- per batch of -b samples (default 100) the region's BAM blocks are
     // gathered, inflated and resolved there (bvc_bam_popmatrix_bgzf); taken only when the position file's positions do not descend, else
     // the CPU path runs and says so.  The matrix inflates to the same bytes.  Off by default (profiles/popmatrix/README.txt)

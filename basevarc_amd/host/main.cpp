@@ -31,6 +31,7 @@
 #include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
 #include "../../include/bvc_store.h"
+#include "../../include/bvc_bam_deflate.h"
 #include "bam.h"
 #include "bam_blocks.h"
 #include "bam_gather.h"
@@ -236,6 +237,8 @@ static void bt_r(const std::vector<std::string> &bams, const std::vector<int32_t
 // text (BVC_HOST_DEVICE_PILEUP_TEXT, --tmp-format text): the same gathering and the same retries around bvc_bam_pileup_text_bgzf, and the
 // lines that come back are cut at the same windows behind the names line.  line_start is 32-bit: a batch whose lines cannot fit
 // 0xFFFFFF00 bytes -- by their floor of 2 bytes a sample and a newline a position, or by what the call reports -- goes to bt_r, said once.
+// With BVC_HOST_DEVICE_PILEUP_DEFLATE (bin and text, not raw) the calls are their _deflate twins (include/bvc_bam_deflate.h): the windows are the
+// call's pieces, and a thread's file is its header through the writer, then its piece's finished blocks.
 static std::atomic<long> g_device_batches(0);
 static std::atomic<int> g_load_threads(0);
 static std::atomic<bool> g_text_fallback_said(false);
@@ -270,7 +273,7 @@ static bool device_batch_loop(BamBatch &batch, LoadDevice &dev, const std::vecto
 }
 
 static void bt_r_device(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq,
-                        const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus, bool text)
+                        const std::string &chr, int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, int thread, int gpus, bool text, const Knobs &knobs)
 {
     const int64_t kTextMax = (int64_t)0xFFFFFF00u;
     auto on_the_cpu = [&]() {
@@ -284,8 +287,16 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
     }
     // a pool thread's context and page-locked buffer: made at its first batch, on the device device_of_thread gives, gone with the thread
     static thread_local LoadDevice dev;
-    if (!dev.ctx && bvc_create(&dev.ctx, device_of_thread(g_load_threads++, gpus, opt::gpus)) != BVC_OK)
-        throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    // deflate (BVC_HOST_DEVICE_PILEUP_DEFLATE, not with raw): the batch comes back as finished BGZF blocks, a piece a thread's window
+    const bool deflate = knobs.device_pileup_deflate && opt::tmp_format != "raw";
+    if (!dev.ctx) {
+        if (bvc_create(&dev.ctx, device_of_thread(g_load_threads++, gpus, opt::gpus)) != BVC_OK)
+            throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+        const bool tokens = deflate && text && knobs.device_pileup_deflate_tokens;
+        if ((deflate && knobs.device_pileup_deflate_codes && bvc_set_tuning(dev.ctx, "bgzf_codes", 1) != BVC_OK) ||
+            (tokens && (bvc_set_tuning(dev.ctx, "bgzf_parse", 1) != BVC_OK || bvc_set_tuning(dev.ctx, "bgzf_cuts", 1) != BVC_OK)))
+            throw std::runtime_error(std::string("ERROR: libbvc: ") + bvc_last_error(dev.ctx));
+    }
     const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
     const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
     BamBatch batch;                                 // (headers, the mapped files, the blocks' gathering: bam_gather.h)
@@ -297,9 +308,27 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
     names += "\n";
     std::vector<uint32_t> status(ns), rec_start(pv.size() + 1);
     std::vector<uint8_t> records;
+    const std::vector<size_t> cuts = window_cuts(pv.size(), thread);
+    std::vector<int32_t> piece_pos(1, 0);
+    for (size_t c : cuts) piece_pos.push_back((int32_t)c);
+    std::vector<int64_t> out_off((size_t)thread + 1, 0), piece_bytes((size_t)thread, 0);
+    static thread_local std::vector<uint8_t> blocks; // (kept from batch to batch: a batch of the same size needs no second step)
     const bool done = device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
         int64_t need = 0;
         int rc;
+        if (deflate) {
+            rc = (text ? bvc_bam_pileup_text_bgzf_deflate : bvc_bam_pileup_bgzf_deflate)(
+                dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes, batch.off.data(),
+                batch.end.data(), batch.eof.data(), rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(), rg_s, refseq.data(),
+                (int64_t)refseq.size(), (int32_t)thread, piece_pos.data(), blocks.data(), (int64_t)blocks.size(), &need, out_off.data(),
+                piece_bytes.data(), status.data());
+            if (text && rc == BVC_ERR_ARG && need > kTextMax) return kBatchGivenUp;
+            if (rc == BVC_BAM_MORE && need > (int64_t)blocks.size()) {  // the blocks are finished and kept: room for them, and a fetch
+                blocks.resize((size_t)need + (size_t)need / 8);
+                rc = bvc_bam_pileup_deflate_fetch(dev.ctx, blocks.data(), (int64_t)blocks.size());
+            }
+            return rc;
+        }
         for (;;) {
             // (the two calls take the same arguments: records and rec_start hold the lines and line_start with text)
             rc = (text ? bvc_bam_pileup_text_bgzf : bvc_bam_pileup_bgzf)(
@@ -317,7 +346,6 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
     for (size_t s = 0; s < ns; ++s)
         if (rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << sms[s] << " region " << opt::region << " is empty." << std::endl;
     const int level = opt::tmp_format == "raw" ? 0 : 6;
-    const std::vector<size_t> cuts = window_cuts(pv.size(), thread);
     size_t lo = 0;
     for (int i = 0; i < thread; ++i) {
         BgzfWriter fp(tmp_name(i, ib), level);
@@ -329,7 +357,8 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
             fp.write(h);
         }
         const size_t hi = cuts[(size_t)i];
-        fp.write(reinterpret_cast<const char *>(records.data()) + rec_start[lo], (size_t)(rec_start[hi] - rec_start[lo]));
+        if (deflate) fp.write_blocks(blocks.data() + out_off[(size_t)i], (size_t)(out_off[(size_t)i + 1] - out_off[(size_t)i]));
+        else fp.write(reinterpret_cast<const char *>(records.data()) + rec_start[lo], (size_t)(rec_start[hi] - rec_start[lo]));
         lo = hi;
         if (!fp.close()) std::cerr << "warning: file cannot be closed" << std::endl;
     }
@@ -601,13 +630,15 @@ static void run_basetype(int argc, char **argv)                          // src/
         } else if (knobs.device_pileup && opt::tmp_format != "text") {
             const int load_gpus = bvc_device_count();
             if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
-            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, false); });
-            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches (bvc_bam_pileup_bgzf)" << std::endl;
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, false, knobs); });
+            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches ("
+                                         << (knobs.device_pileup_deflate && opt::tmp_format != "raw" ? "bvc_bam_pileup_bgzf_deflate" : "bvc_bam_pileup_bgzf") << ")" << std::endl;
         } else if (knobs.device_pileup_text && opt::tmp_format == "text") {
             const int load_gpus = bvc_device_count();
             if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
-            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, true); });
-            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches (bvc_bam_pileup_text_bgzf)" << std::endl;
+            run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, true, knobs); });
+            if (knobs.profile) std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches ("
+                                         << (knobs.device_pileup_deflate ? "bvc_bam_pileup_text_bgzf_deflate" : "bvc_bam_pileup_text_bgzf") << ")" << std::endl;
         } else
             run_pool(nb - first_batch, thread, [&](int t) { bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread); });
     }

@@ -157,6 +157,14 @@ STORE_PROTOTYPES = {
     "bvc_pileup_begin_store": (_int, [_vp, _vp, _i32, _i32, _pi64, _pi64, _pi64]),
 }
 STORE_EXPORTS = list(STORE_PROTOTYPES)
+# The seventh header, include/bvc_bam_deflate.h (tests/test_bam_deflate_abi.py compares the two), bound by bind() with the others: phase 1's temp
+# batches deflated on the device.  The two calls take bvc_bam_pileup_bgzf's arguments up to refseq_len, then the pieces and the outputs.
+BAM_DEFLATE_PROTOTYPES = {
+    "bvc_bam_pileup_bgzf_deflate": (_int, BAM_PROTOTYPES["bvc_bam_pileup_bgzf"][1][:19] + [_i32, _vp, _vp, _i64, _pi64, _vp, _vp, _vp]),
+    "bvc_bam_pileup_text_bgzf_deflate": (_int, BAM_PROTOTYPES["bvc_bam_pileup_bgzf"][1][:19] + [_i32, _vp, _vp, _i64, _pi64, _vp, _vp, _vp]),
+    "bvc_bam_pileup_deflate_fetch": (_int, [_vp, _vp, _i64]),
+}
+BAM_DEFLATE_EXPORTS = list(BAM_DEFLATE_PROTOTYPES)
 STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
@@ -173,10 +181,11 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES and STORE_PROTOTYPES its
-    restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES and
+    BAM_DEFLATE_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
-                                      list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items())):
+                                      list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items()) +
+                                      list(BAM_DEFLATE_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -355,7 +364,7 @@ class Context:
 
     def set_tuning(self, key, value):
         """Launch policy of this context (include/bvc.h); results never depend on it (but for "em_engine", "em_tiny_regions", "em_prune",
-        "bgzf_codes" and "bgzf_parse", which the header describes)."""
+        "bgzf_codes", "bgzf_parse" and "bgzf_cuts", which the header describes)."""
         self._check(self._L.bvc_set_tuning(self._h, key.encode(), int(value)))
 
     def host_alloc(self, nbytes):
@@ -888,6 +897,45 @@ class Context:
             text = np.zeros(need.value, dtype=np.uint8)
         rc = call(text, len(text) if text_cap is None else int(text_cap))
         return rc, text[:need.value] if rc == 0 else text, line_start, sample_status, need.value
+
+    def bam_pileup_bgzf_deflate(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
+                                piece_pos, text=False, out=None, out_cap=None, out_off=None, piece_bytes=None, sample_status=None):
+        """bvc_bam_pileup_bgzf_deflate / bvc_bam_pileup_text_bgzf_deflate (text=True; include/bvc_bam_deflate.h): bam_pileup_bgzf /
+        bam_pileup_text_bgzf with the batch deflated on the device into finished BGZF blocks.  piece_pos: int32 [n_pieces + 1], indices
+        into positions from 0 to len(positions); piece i's blocks are out[out_off[i]:out_off[i + 1]].  out / out_off / piece_bytes /
+        sample_status: buffers to write into (uint8, int64 [n_pieces + 1], int64 [n_pieces], uint32 [n]); without out the call is made
+        with out_cap 0 and the blocks it leaves in the context are fetched (bam_pileup_deflate_fetch).  out_cap: what to tell the
+        library instead of len(out).  Returns (rc, out, out_off, piece_bytes, sample_status, out_needed): rc 0, or BAM_MORE (2) when a
+        sample's status is 2 (out_needed 0) or out is too small (out_needed the packed size; out_off and piece_bytes are written).
+        Raises BvcError for the errors."""
+        n, _, shared = self._bgzf_inputs(comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq)
+        piece_pos = _as(piece_pos, np.int32)
+        if len(piece_pos) < 1:
+            raise ValueError("piece_pos must be [n_pieces + 1]")
+        k = len(piece_pos) - 1
+        out_off = np.zeros(k + 1, dtype=np.int64) if out_off is None else out_off
+        piece_bytes = np.zeros(max(1, k), dtype=np.int64) if piece_bytes is None else piece_bytes
+        sample_status = np.zeros(max(1, n), dtype=np.uint32) if sample_status is None else sample_status
+        need = C.c_int64(0)
+        fn = self._L.bvc_bam_pileup_text_bgzf_deflate if text else self._L.bvc_bam_pileup_bgzf_deflate
+        cap = (len(out) if out is not None else 0) if out_cap is None else int(out_cap)
+        rc = fn(self._h, n, *_pointers((*shared, k, piece_pos, out if out is not None and len(out) else None, cap), _np_ptr), C.byref(need),
+                _np_ptr(out_off), _np_ptr(piece_bytes), _np_ptr(sample_status) if n else None)
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        if out is None:
+            out = np.zeros(0, dtype=np.uint8)
+            if rc == BAM_MORE and need.value > 0 and out_cap is None:
+                out = self.bam_pileup_deflate_fetch(need.value)
+                rc = 0
+        return rc, out[:need.value] if rc == 0 else out, out_off, piece_bytes, sample_status, need.value
+
+    def bam_pileup_deflate_fetch(self, size, out=None, out_cap=None):
+        """bvc_bam_pileup_deflate_fetch: the blocks the last bam_pileup_bgzf_deflate left in the context when out was too small, `size`
+        bytes (its out_needed), as a uint8 array.  Raises BvcError (BVC_ERR_ARG) when nothing is kept or the room is too small."""
+        out = np.zeros(int(size), dtype=np.uint8) if out is None else out
+        self._check(self._L.bvc_bam_pileup_deflate_fetch(self._h, _np_ptr(out) if len(out) else None, len(out) if out_cap is None else int(out_cap)))
+        return out
 
     def bam_pileup_bgzf_store(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq,
                               store, batch, sample_status=None):

@@ -568,7 +568,12 @@ int bvc_synth_dense(bvc_ctx *ctx, uint64_t seed, int64_t site0, int64_t n_sites,
  *                      up, no other position has a match.  Independent of "bgzf_codes": all four combinations are valid.  It changes
  *                      the BYTES of the blocks, never what they inflate to, their number, their framing or the waits of the calls;
  *                      text without tabs or colons becomes literals, hence mostly stored blocks.  With 0 nothing differs by a byte
- *                      from a library without the key.  Environment: BVC_BGZF_PARSE. */
+ *                      from a library without the key.  Environment: BVC_BGZF_PARSE.
+ *   "bgzf_cuts"        0 (default) / 1.  Acts only with "bgzf_parse" = 1 (with 0 it changes nothing): the two bytes that end a field of the
+ *                      field parse.  0: a tab or a colon (VCF sample columns).  1: a space or a newline -- the text temp batches' lines
+ *                      (bvc_bam_text.h), where ". " is a two-byte field whose runs become matches at the distance of one field and a
+ *                      "b,m,q,r,s " token is a head with a key.  Everything else of the rule is unchanged; it changes the BYTES of the
+ *                      blocks, never what they inflate to.  Environment: BVC_BGZF_CUTS. */
 int bvc_set_tuning(bvc_ctx *ctx, const char *key, int value);
 
 /* ---- measurement aid ------------------------------------------------------------------------------- */
@@ -660,6 +665,7 @@ int bvc_pileup_sample_text(bvc_ctx *ctx, int64_t n_samples, char *text, int64_t 
  * for earlier heads with the same hash of (L, bytes) -- seventeen candidates at the most, a function of the bytes -- extends each up to
  * 258 bytes, drops those that hold fewer than L, cuts the others back to the last cut (or n) they reach and keeps the longest, the
  * nearest among equals.  No other position has a match, a match is used from 4 bytes on, and the path is the greedy walk of key 0.
+ * Tuning key "bgzf_cuts" = 1 (default 0) reads "a space or a newline" for "a tab or a colon" in the rule above, and changes nothing else.
  */
 #define BVC_BGZF_BLOCK_INPUT 65280
 /* Blocks of a piece: ceil(len / 65280), 0 for len <= 0. */
@@ -707,6 +713,8 @@ int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64
  * sample (BVC_BAM_MORE there: some sample's bytes ran out) -- is declared in bvc_popmatrix.h beside this header. */
 /* Temp batches that stay on the device -- bvc_store_*: a batch's records kept in device memory, bvc_pileup_begin_store: a tile of positions
  * gathered from all kept batches -- are declared in bvc_store.h beside this header. */
+/* Phase 1's temp batches deflated where they are made -- bvc_bam_pileup_bgzf_deflate, bvc_bam_pileup_text_bgzf_deflate: BAM blocks in, the
+ * batch's finished BGZF blocks out -- are declared in bvc_bam_deflate.h beside this header. */
 
 #ifdef __cplusplus
 }
