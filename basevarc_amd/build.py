@@ -133,7 +133,7 @@ def build_host(force=False):
     if force or not os.path.exists(HOST_EXE) or os.path.getmtime(HOST_EXE) < max(newest, os.path.getmtime(LIB)):
         subprocess.check_call(["g++"] + flags + inc + ["-o", HOST_EXE] +
                               [os.path.join(HOST, f) for f in HOST_SOURCES + ["main.cpp"]] +
-                              ["-L", HERE, "-lbvc", "-lz", "-Wl,-rpath,$ORIGIN"])
+                              ["-L", HERE, "-lbvc", "-lz", "-ldl", "-Wl,-rpath,$ORIGIN"])
     return HOST_EXE, HOST_LIB
 
 

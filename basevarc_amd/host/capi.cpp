@@ -15,6 +15,7 @@
 #include "bam.h"
 #include "bgzf.h"
 #include "inflate.h"
+#include "knobs.h"
 #include "pileup.h"
 #include "stats.h"
 
@@ -57,6 +58,29 @@ void bvchost_thread_window(int64_t psize, int32_t thread, int32_t ithread, int64
     size_t l, h;
     thread_window((size_t)psize, thread, ithread, l, h);
     *lo = (int64_t)l; *hi = (int64_t)h;
+}
+// the position windows of --tmp-format mem (BVC_HOST_STORE_WINDOWS): a, b [windows].  Returns 0, or -1 where the host program refuses
+// (thread or windows below 1, thread * windows above kStoreWindowsMaxThreads)
+int32_t bvchost_store_windows(int64_t psize, int32_t thread, int32_t windows, int64_t *a, int64_t *b)
+{
+    if (psize < 0 || store_windows_refused(windows, thread)) return -1;
+    std::vector<size_t> lo((size_t)windows), hi((size_t)windows);
+    store_windows((size_t)psize, thread, windows, lo.data(), hi.data());
+    for (int32_t w = 0; w < windows; ++w) { a[w] = (int64_t)lo[(size_t)w]; b[w] = (int64_t)hi[(size_t)w]; }
+    return 0;
+}
+// and their fetch ranges (store_window_ranges); positions: the region's 1-based position list
+void bvchost_store_window_ranges(const int32_t *positions, int32_t windows, const int64_t *a, const int64_t *b, int32_t beg0, int32_t end0,
+                                 int32_t *wbeg, int32_t *wend)
+{
+    std::vector<size_t> lo(a, a + windows), hi(b, b + windows);
+    store_window_ranges(positions, windows, lo.data(), hi.data(), beg0, end0, wbeg, wend);
+}
+// BVC_HOST_STORE_WINDOWS as the host program reads it: K >= 1, 0 for "auto", -1 for a value it refuses
+int32_t bvchost_parse_store_windows(const char *value, int32_t thread)
+{
+    const int k = parse_store_windows(value);
+    return k > 0 && store_windows_refused(k, thread) ? -1 : k;
 }
 int32_t bvchost_device_of_thread(int32_t ithread, int32_t devices_present, int32_t gpus_option) { return device_of_thread(ithread, devices_present, gpus_option); }
 int32_t bvchost_merge_subfiles(const char *out_prefix, const char *suffix, int32_t thread)

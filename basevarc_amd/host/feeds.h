@@ -107,14 +107,15 @@ inline void feed_staged_tiles(TileRunner &tr, const Window &w, BatchInputs &in, 
 // Tiles of the batches that phase 1 left on the device (--tmp-format mem): nothing is read, staged or uploaded.  A tile: --tile positions
 // at most and BVC_HOST_TILE_MB of records (bvc_store_tile: host arithmetic on the store's cumulative sizes), gathered there from every
 // kept batch by bvc_pileup_begin_store.  Like the BGZF feed this thread does stage 2's work itself, inside one of its device's slots,
-// and finishes the tile by the knobs every device-parsed tile goes by; stage 3 runs beside it.
-inline void feed_store_tiles(TileRunner &tr, const Window &w, const bvc_store *store, DeviceSlots &slots, int device)
+// and finishes the tile by the knobs every device-parsed tile goes by; stage 3 runs beside it.  base: the store's position 0 is w.pv[base]
+// (0 for a store of the whole region; a position window's first position, BVC_HOST_STORE_WINDOWS).
+inline void feed_store_tiles(TileRunner &tr, const Window &w, const bvc_store *store, size_t base, DeviceSlots &slots, int device)
 {
     const int64_t max_bytes = (int64_t)1048576 * tr.knobs.tile_mb_staged;
     for (size_t ip = w.lo; ip < w.hi;) {
         int32_t T = 0;
         int64_t bytes = 0, n_ent = 0, n_ind = 0, ind_bytes = 0;
-        if (bvc_store_tile(store, (int32_t)ip, (int32_t)std::min<int64_t>(w.tile, (int64_t)(w.hi - ip)), max_bytes, &T, &bytes) != BVC_OK)
+        if (bvc_store_tile(store, (int32_t)(ip - base), (int32_t)std::min<int64_t>(w.tile, (int64_t)(w.hi - ip)), max_bytes, &T, &bytes) != BVC_OK)
             throw std::runtime_error("ERROR: the store of the batches does not hold the window's positions");
         Tile &tl = *tr.cur;
         tl.form = TileForm::Stored;
@@ -122,7 +123,7 @@ inline void feed_store_tiles(TileRunner &tr, const Window &w, const bvc_store *s
         {
             const double t1 = StageClock::now();
             DeviceSlot slot(slots, device);
-            const int rc = bvc_pileup_begin_store(tr.ctx, store, (int32_t)ip, T, &n_ent, &n_ind, &ind_bytes);
+            const int rc = bvc_pileup_begin_store(tr.ctx, store, (int32_t)(ip - base), T, &n_ent, &n_ind, &ind_bytes);
             if (rc == BVC_ERR_DATA) throw std::runtime_error(std::string("ERROR: malformed temp batch record (") + bvc_last_error(tr.ctx) + ")");
             bvc_check(tr.ctx, rc);
             tr.finish_tile(tl, n_ent, n_ind, ind_bytes, true);

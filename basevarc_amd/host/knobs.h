@@ -6,10 +6,14 @@
 #include <sched.h>
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
 #include <fstream>
 #include <string>
 #include <thread>
+#include <vector>
+
+#include "pileup.h"
 
 namespace bvchost {
 
@@ -23,6 +27,49 @@ inline double process_cpus()
     std::string q; double period = 0;
     if (f >> q >> period && q != "max" && period > 0) c = std::min(c, std::max(1.0, atof(q.c_str()) / period));
     return c;
+}
+
+// BVC_HOST_STORE_WINDOWS as text: an integer K >= 1 in plain digits, or "auto" (0).  nullptr (unset) is 1.  -1: none of these.
+inline int parse_store_windows(const char *v)
+{
+    if (!v) return 1;
+    const std::string s(v);
+    if (s == "auto") return 0;
+    if (s.empty() || s.size() > 9) return -1;
+    for (char c : s) if (c < '0' || c > '9') return -1;
+    const int k = atoi(s.c_str());
+    return k >= 1 ? k : -1;
+}
+// K windows of `thread` threads are the ranges of a run with thread * K threads: that many sub-files, 65536 at the most
+const int kStoreWindowsMaxThreads = 65536;
+inline bool store_windows_refused(int windows, int thread)
+{
+    return windows < 1 || thread < 1 || (int64_t)windows * (int64_t)thread > (int64_t)kStoreWindowsMaxThreads;
+}
+// "auto" sizes the windows from ONE batch's bytes per position scaled to the cohort: the other batches' samples may be covered more
+// deeply than batch 0's, and where they are, by how much is not known before they are piled up.  Half as much again is allowed for.
+const double kStoreWindowsSafety = 1.5;
+// "auto": the smallest K (at most max_k) whose largest window, estimated and times kStoreWindowsSafety, fits `budget` bytes; max_k where
+// none does.  rec_start [psize + 1]: batch 0's record offsets over the whole region; scale: the cohort's samples over batch 0's;
+// n_batches rows of (positions + 1) 32-bit offsets are a window's fixed cost.
+inline int auto_store_windows(const uint32_t *rec_start, size_t psize, int thread, int max_k, double scale, int n_batches, double budget)
+{
+    auto estimate = [&](size_t a, size_t b) {
+        return kStoreWindowsSafety * (scale * (double)(rec_start[b] - rec_start[a]) + 4.0 * (double)n_batches * (double)(b - a + 1));
+    };
+    // (the largest window is at least the average one: no K below whole / budget can fit)
+    int k = (int)std::min<double>((double)max_k, std::max(1.0, estimate(0, psize) / std::max(1.0, budget)));
+    std::vector<size_t> a, b;
+    for (size_t t = 0; t < psize; ++t)
+        if (estimate(t, t + 1) > budget) return max_k;                   // (a position that fits no budget: no K does)
+    for (; k < max_k; ++k) {
+        a.assign((size_t)k, 0); b.assign((size_t)k, 0);
+        store_windows(psize, thread, k, a.data(), b.data());
+        double largest = 0;
+        for (int w = 0; w < k; ++w) largest = std::max(largest, a[(size_t)w] == b[(size_t)w] ? 0.0 : estimate(a[(size_t)w], b[(size_t)w]));
+        if (largest <= budget) break;
+    }
+    return k;
 }
 
 struct Knobs {
@@ -91,7 +138,19 @@ struct Knobs {
     // --tmp-format mem: GB (a fraction will do) of device memory the batches kept there may take together (bvc_store_create's byte_budget);
     // a batch past it ends the run with a line that names --tmp-format bin.  0: no cap but the device's
     const double store_gb = std::max(0.0, real("BVC_HOST_STORE_GB", 0));
-    const bool two_byte_tiles = set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
+    // --tmp-format mem only (the other forms ignore it): the region is cut into K windows of positions, and per window a store is filled,
+    // its positions are called and the store is dropped, so that BVC_HOST_STORE_GB is the budget of ONE window's store and a cohort of any
+    // size fits.  The windows are the ranges of a run with -t T*K taken T at a time (store_windows, pileup.h), compute thread i of window w
+    // works as thread w*T+i of T*K, and the outputs inflate to the bytes of --tmp-format bin -t T*K.  Unset or 1: one window, the whole
+    // region.  "auto" (0 here): the smallest K whose largest window fits the budget, going by batch 0's bytes per position scaled to the
+    // cohort and kStoreWindowsSafety; the K chosen is printed on a [profile] line, and an estimate that was too small ends the run with
+    // the overflow line.  0, a negative number, anything that is no number and K*T above 65536 end the run before anything is written
+    // (run_basetype).  Default 1 (profiles/store_windows/README.txt)
+    const int store_windows = parse_store_windows(getenv("BVC_HOST_STORE_WINDOWS"));
+    // 1, with K > 1 only: window w+1 is loaded while window w is computed, in lock-step (both are joined before the next pair starts); two
+    // stores are alive at a time, each with half of BVC_HOST_STORE_GB.  The outputs are those of 0.  Default 0
+    const bool store_overlap = num("BVC_HOST_STORE_OVERLAP", 0) != 0;
+    const bool two_byte_tiles =set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not
     // fit one byte per observation (quality >= 63)

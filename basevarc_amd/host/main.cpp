@@ -5,6 +5,7 @@
 // bt_s :316-465, bt_f :536-669, parseOptions :797-827.  Same options and defaults, same file names
 // (<out>.vcf.gz, <out>.cvg.gz, <out>.tmp.thread.<t>/batch.<b>), same --load/--rerun/--keep_tmp behaviour.
 // Additive: --gpus <n> (devices to spread the threads over; default all), --tile <sites per device call>.
+#include <dlfcn.h>
 #include <getopt.h>
 #include <sys/resource.h>
 #include <sys/stat.h>
@@ -70,7 +71,8 @@ static const char *BASETYPE_MESSAGE =
     "  --tmp-format     <STR>   Temp-batch files written by the load phase: text (as BaseVarC), bin (binary\n"
     "                           records, deflated) or raw (binary records, stored: fastest to read back) [text];\n"
     "                           mem: no files at all, the batches stay in the memory of one device (BVC_HOST_STORE_GB\n"
-    "                           caps them; not with --load, --keep_tmp or --gpus above 1)\n";
+    "                           caps them; not with --load, --keep_tmp or --gpus above 1)\n"
+    "                           (BVC_HOST_STORE_WINDOWS=K|auto: in K windows of positions, one at a time, as -t T*K cuts them)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -246,6 +248,10 @@ static std::atomic<bool> g_text_fallback_said(false);
 // the library call and returns its code, and a sample whose list stopped short of its region's end is gathered to its file's end, once.
 // Returns false when `call` gave the batch up (kBatchGivenUp); throws the CPU path's messages for the statuses 3 and 4.
 static const int kBatchGivenUp = -1000;
+static std::string store_overflow_line(bvc_ctx *ctx)
+{
+    return std::string("ERROR: the batches do not fit the device's store (") + bvc_last_error(ctx) + "); --tmp-format bin keeps them in files";
+}
 template <class Call>
 static bool device_batch_loop(BamBatch &batch, LoadDevice &dev, const std::vector<std::string> &bams, size_t b0, int32_t beg0, int32_t end0,
                               std::vector<uint32_t> &status, Call call)
@@ -265,9 +271,7 @@ static bool device_batch_loop(BamBatch &batch, LoadDevice &dev, const std::vecto
                 if (status[s] == 3u) throw std::runtime_error("ERROR: truncated or corrupt BAM record in " + bams[b0 + s]);
                 if (status[s] == 4u) throw std::out_of_range("index offset is out of range of the sequence");
             }
-        if (rc == BVC_ERR_ALLOC)
-            throw std::runtime_error(std::string("ERROR: the batches do not fit the device's store (") + bvc_last_error(dev.ctx) +
-                                     "); --tmp-format bin keeps them in files");
+        if (rc == BVC_ERR_ALLOC) throw std::runtime_error(store_overflow_line(dev.ctx));
         throw std::runtime_error(std::string("ERROR: device pileup failed: ") + bvc_last_error(dev.ctx));
     }
 }
@@ -368,30 +372,72 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
 // ---- phase 1 into the device's memory (--tmp-format mem): the same gathering and the same retries around bvc_bam_pileup_bgzf_store; the
 // batch's records stay on device 0 as batch `ib` of the process's one store, and nothing is written.  The batch's sample names are kept
 // here for the VCF header.
+// With BVC_HOST_STORE_WINDOWS=K the region's positions are cut into K windows (store_windows, pileup.h) and a MemBatches is ONE window's
+// store: positions pv[a .. b) piled up from the fetch range [beg0, end0) (store_window_ranges), filled, computed from and dropped before
+// the next one's (beside it with BVC_HOST_STORE_OVERLAP).  What outlives a window -- the sample names, which window 0 keeps, and the
+// samples that had reads in some window -- is the run's (MemRun).
+struct MemRun {
+    std::vector<std::vector<std::string>> names;    // per batch, filled by the thread that extracts it (window 0)
+    std::vector<std::string> sms;                   // per sample of the list: its name as the warning prints it (window 0)
+    std::vector<char> has_reads;                    // per sample of the list: not empty (status 1 or no such reference) in some window
+    int windows = 1;
+    // the line that ends a run whose batches pass the budget also proposes a K: with K > 1, and with the knob unset
+    bool propose_windows = false;
+};
 struct MemBatches {
-    bvc_store *store = nullptr;
-    std::vector<std::vector<std::string>> names;    // per batch, filled by the thread that extracts it
+    bvc_store *store = nullptr;                     // (none for a window without positions)
+    size_t a = 0, b = 0;                            // the window's positions: pv[a .. b); the store's position 0 is pv[a]
+    int32_t beg0 = 0, end0 = 0;                     // its fetch range
+    std::atomic<int> kept{0};                       // batches put so far
+    double load_s = 0;
+    MemRun *run = nullptr;
+    MemBatches() = default;
+    MemBatches(const MemBatches &) = delete;
+    MemBatches &operator=(const MemBatches &) = delete;
     ~MemBatches() { bvc_store_destroy(store); }
+    void drop() { bvc_store_destroy(store); store = nullptr; }
 };
 static void bt_r_mem(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
-                     int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, MemBatches &mem)
+                     int32_t rg_s, int nb, int bc, int ib, MemBatches &mem, int iwindow)
 {
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
     const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
-    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    const int32_t beg0 = mem.beg0, end0 = mem.end0;
+    MemRun &run = *mem.run;
     BamBatch batch;
     batch.open(bams, b0, b1, chr);
     std::vector<uint32_t> status(ns);
     device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
         int64_t bytes = 0;
-        return bvc_bam_pileup_bgzf_store(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
-                                         batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(),
-                                         pv.data(), rg_s, refseq.data(), (int64_t)refseq.size(), mem.store, ib, &bytes, status.data());
+        // (rg_s and refseq stay the region's: deletion text is cut from them)
+        const int rc = bvc_bam_pileup_bgzf_store(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(),
+                                                 batch.out_bytes, batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq,
+                                                 (int32_t)(mem.b - mem.a), pv.data() + mem.a, rg_s, refseq.data(), (int64_t)refseq.size(), mem.store, ib,
+                                                 &bytes, status.data());
+        if (rc == BVC_ERR_ALLOC && run.propose_windows) {
+            // the windows that would fit, going by the share of the batches that did: K x (batches in all / batches kept), rounded up
+            // (a run that kept none: as if it had kept half a batch)
+            const int kept = mem.kept.load();
+            const int64_t k = ((int64_t)run.windows * nb * 2 + std::max(1, 2 * kept) - 1) / std::max(1, 2 * kept);
+            throw std::runtime_error(store_overflow_line(dev.ctx) + "; BVC_HOST_STORE_WINDOWS=" + std::to_string(std::max<int64_t>(k, run.windows + 1)) +
+                                     " (or auto) cuts the region into windows of positions that fit one after the other");
+        }
+        return rc;
     });
-    for (size_t s = 0; s < ns; ++s)
-        if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
-    mem.names[(size_t)ib] = batch.sms;
+    if (run.windows == 1) {
+        for (size_t s = 0; s < ns; ++s)
+            if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
+    } else {
+        // (a sample is empty in the region exactly when it is in every window: the warnings are printed after the last one)
+        for (size_t s = 0; s < ns; ++s)
+            if (!(batch.rid[s] < 0 || status[s] == 1u)) run.has_reads[b0 + s] = 1;
+    }
+    if (iwindow == 0) {
+        run.names[(size_t)ib] = batch.sms;
+        for (size_t s = 0; s < ns; ++s) run.sms[b0 + s] = batch.sms[s];
+    }
+    ++mem.kept;
     ++g_device_batches;
 }
 
@@ -445,7 +491,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     std::vector<std::string> names;
     { std::istringstream iss(sams); std::string id; while (std::getline(iss, id, '\t')) names.push_back(id); }
     if (mem)                                                            // (no batch files: the names phase 1 kept, in batch order)
-        for (auto const &of_batch : mem->names) names.insert(names.end(), of_batch.begin(), of_batch.end());
+        for (auto const &of_batch : mem->run->names) names.insert(names.end(), of_batch.begin(), of_batch.end());
     const Groups groups = read_groups(names, N);
     if (ithread == 0) {
         fpc.write(cvg_header(groups));
@@ -499,7 +545,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
         }
         get_parser_carry(tr.carry);                                     // (zeros: reset_parser_carry above)
     }
-    if (mem) feed_store_tiles(tr, w, mem->store, slots, device);
+    if (mem) feed_store_tiles(tr, w, mem->store, mem->a, slots, device);       // (a window without positions has no store and no tile)
     else if (dev_inflate) {
         std::vector<int32_t> skip;
         for (auto const &fp : in) skip.push_back((int32_t)fp.names.size() + 1);      // the names line and its newline
@@ -552,6 +598,146 @@ static void run_pool(int n_tasks, int n_threads, F fn)
     if (!err.empty()) throw std::runtime_error(err);
 }
 
+// ---- --tmp-format mem: both phases, window by window (BVC_HOST_STORE_WINDOWS; one window = the whole region without it) -----------------
+// The free memory of the device, as the HIP runtime that libbvc brought into the process reports it (the library has no call for it and
+// the host program does not link the runtime itself); 0 where the runtime's symbol is not to be had.
+static double device_free_bytes()
+{
+    typedef int (*mem_info_fn)(size_t *, size_t *);
+    mem_info_fn fn = reinterpret_cast<mem_info_fn>(dlsym(RTLD_DEFAULT, "hipMemGetInfo"));
+    size_t free_b = 0, total_b = 0;
+    return fn && fn(&free_b, &total_b) == 0 ? (double)free_b : 0.0;
+}
+
+// BVC_HOST_STORE_WINDOWS=auto: batch 0 piled up once for the whole region (bvc_bam_pileup_bgzf, its records on the host); its rec_start
+// scaled to the cohort is the estimate auto_store_windows (knobs.h) sizes the windows by.  budget <= 0: the device's free memory.
+static int choose_store_windows(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                                int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, double budget)
+{
+    LoadDevice dev;
+    if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    const size_t ns = nb == 1 ? bams.size() : (size_t)bc;
+    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    BamBatch batch;
+    batch.open(bams, 0, ns, chr);
+    std::vector<uint32_t> status(ns), rec_start(pv.size() + 1);
+    std::vector<uint8_t> records;
+    device_batch_loop(batch, dev, bams, 0, beg0, end0, status, [&]() {
+        int64_t need = 0;
+        int rc;
+        for (;;) {
+            rc = bvc_bam_pileup_bgzf(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
+                                     batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(), pv.data(),
+                                     rg_s, refseq.data(), (int64_t)refseq.size(), records.data(), (int64_t)records.size(), &need, rec_start.data(), status.data());
+            if (rc != BVC_BAM_MORE || need <= (int64_t)records.size()) break;
+            records.resize((size_t)need);
+        }
+        return rc;
+    });
+    if (budget <= 0) budget = device_free_bytes();
+    if (budget <= 0) throw std::runtime_error("ERROR: BVC_HOST_STORE_WINDOWS=auto cannot learn the device's free memory; give BVC_HOST_STORE_GB");
+    return auto_store_windows(rec_start.data(), pv.size(), thread, kStoreWindowsMaxThreads / thread, (double)bams.size() / (double)ns, nb, budget);
+}
+
+template <class Compute>
+static void basetype_in_memory(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                               int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, const Knobs &knobs, int &n_sub, std::string &werr, std::mutex &mu,
+                               double &t_loaded, Compute compute)
+{
+    if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+    const int64_t budget = (int64_t)(knobs.store_gb * 1073741824.0);
+    int K = knobs.store_windows;
+    // (with BVC_HOST_STORE_OVERLAP two stores are alive at a time: each gets half of the budget)
+    const bool may_overlap = knobs.store_overlap && K != 1;
+    if (K == 0) {
+        K = choose_store_windows(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, (double)budget / (may_overlap ? 2.0 : 1.0));
+        if (knobs.profile) std::cerr << "[profile] main: BVC_HOST_STORE_WINDOWS=auto chose " << K << " windows" << std::endl;
+    }
+    const bool overlap = may_overlap && K > 1;
+    const int64_t window_budget = overlap ? std::max<int64_t>(budget / 2, budget > 0 ? 1 : 0) : budget;
+    n_sub = thread * K;
+    MemRun run;
+    run.windows = K;
+    run.propose_windows = K > 1 || knobs.store_windows != 1 || !Knobs::set("BVC_HOST_STORE_WINDOWS");
+    run.names.resize((size_t)nb);
+    run.sms.resize(bams.size());
+    run.has_reads.assign(bams.size(), 0);
+    std::vector<size_t> wa((size_t)K), wb((size_t)K);
+    std::vector<int32_t> wbeg((size_t)K), wend((size_t)K);
+    store_windows(pv.size(), thread, K, wa.data(), wb.data());
+    store_window_ranges(pv.data(), K, wa.data(), wb.data(), std::max(0, rg_s - 1 - 1000), rg_e + 1000, wbeg.data(), wend.data());
+    std::deque<MemBatches> wins;                    // (a deque: a window's store does not move)
+    for (int w = 0; w < K; ++w) {
+        wins.emplace_back();
+        MemBatches &m = wins.back();
+        m.a = wa[(size_t)w]; m.b = wb[(size_t)w]; m.beg0 = wbeg[(size_t)w]; m.end0 = wend[(size_t)w]; m.run = &run;
+    }
+    auto failed = [&]() { std::lock_guard<std::mutex> g(mu); return !werr.empty(); };
+    // a window's load: its store made, every batch piled up into it, the store sealed.  An error is kept as the compute threads' are
+    auto load = [&](int w) {
+        MemBatches &m = wins[(size_t)w];
+        if (m.a == m.b && w > 0) return;                                // (no positions: no store; window 0 keeps the names even so)
+        const double t0 = StageClock::now();
+        try {
+            if (bvc_store_create(&m.store, 0, (int32_t)(m.b - m.a), nb, window_budget) != BVC_OK)
+                throw std::runtime_error("ERROR: no usable gfx950 device for the store of the batches");
+            run_pool(nb, thread, [&](int t) { bt_r_mem(bams, pv, refseq, chr, rg_s, nb, bc, t, m, w); });
+            LoadDevice dev;                                             // (sealing takes a context; any of the store's device)
+            if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+            bvc_check(dev.ctx, bvc_store_seal(dev.ctx, m.store));
+        } catch (const std::exception &e) { std::lock_guard<std::mutex> g(mu); if (werr.empty()) werr = e.what(); }
+        m.load_s = StageClock::now() - t0;
+    };
+    auto used_bytes = [&](int w) { int64_t used = 0; if (wins[(size_t)w].store) bvc_store_bytes(wins[(size_t)w].store, &used, nullptr); return used; };
+    // once the last window is loaded: the samples that were empty in every window, in list order, and the line that ends the load phase
+    auto all_loaded = [&]() {
+        if (K > 1) {
+            std::ostringstream os;
+            for (size_t s = 0; s < bams.size(); ++s)
+                if (!run.has_reads[s]) os << "warning: " << run.sms[s] << " region " << opt::region << " is empty.\n";
+            std::cerr << os.str() << std::flush;
+        } else if (knobs.profile) {
+            std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches kept there (bvc_bam_pileup_bgzf_store), "
+                      << used_bytes(0) << " bytes" << std::endl;
+        }
+        time_t tim1 = time(0);
+        std::cout << "basetype loading done -- " << ctime(&tim1);
+    };
+    double compute_total = 0;
+    int64_t largest = 0;
+    int largest_w = 0;
+    load(0);
+    if (K == 1 && !failed()) all_loaded();
+    for (int w = 0; w < K && !failed(); ++w) {
+        // BVC_HOST_STORE_OVERLAP: the next window is loaded beside this one's compute threads, and both are joined before anything else
+        std::thread loader;
+        if (overlap && w + 1 < K) loader = std::thread([&, w]() { load(w + 1); });
+        const double t0 = StageClock::now();
+        compute(w * thread, &wins[(size_t)w], 0);
+        const double compute_s = StageClock::now() - t0;
+        if (loader.joinable()) loader.join();
+        compute_total += compute_s;
+        const int64_t used = used_bytes(w);
+        if (used > largest) { largest = used; largest_w = w; }
+        if (knobs.profile && K > 1) {
+            std::ostringstream os;
+            os << "[profile] main: window " << w << " of " << K << ": positions [" << wins[(size_t)w].a << ", " << wins[(size_t)w].b << "), fetch range ["
+               << wins[(size_t)w].beg0 << ", " << wins[(size_t)w].end0 << "), " << wins[(size_t)w].kept.load() << " batches kept, " << used << " bytes, load "
+               << wins[(size_t)w].load_s << " s, compute " << compute_s << " s\n";
+            if (overlap && w + 1 < K)
+                os << "[profile] main: windows " << w << " and " << w + 1 << " alive together: " << used << " + " << used_bytes(w + 1) << " = "
+                   << used + used_bytes(w + 1) << " bytes (budget " << budget << ")\n";
+            std::cerr << os.str() << std::flush;
+        }
+        wins[(size_t)w].drop();
+        if (!overlap && w + 1 < K && !failed()) load(w + 1);
+        if (K > 1 && w + 2 == K && !failed()) all_loaded();             // (the last window's load has just ended, either way)
+    }
+    if (knobs.profile && K > 1 && !failed())
+        std::cerr << "[profile] main: " << K << " windows, the largest store held " << largest << " bytes (window " << largest_w << ")" << std::endl;
+    t_loaded = StageClock::now() - compute_total;
+}
+
 static void run_basetype(int argc, char **argv)                          // src/BaseVarC.cpp:176-314
 {
     parse_options(argc, argv, BASETYPE_MESSAGE);
@@ -563,6 +749,11 @@ static void run_basetype(int argc, char **argv)                          // src/
         std::cerr << "basetype: --rerun has nothing to reuse with --tmp-format mem, it is ignored" << std::endl;
         opt::rerun = false;
     }
+    const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
+    // (BVC_HOST_STORE_WINDOWS acts with --tmp-format mem only; refused before anything is read, made or written)
+    if (in_memory && (knobs.store_windows < 0 || (knobs.store_windows > 0 && store_windows_refused(knobs.store_windows, std::max(1, opt::thread)))))
+        throw std::invalid_argument("ERROR: BVC_HOST_STORE_WINDOWS must be auto or an integer K >= 1 with K x threads <= " +
+                                    std::to_string(kStoreWindowsMaxThreads));
     if (opt::reference.empty()) throw std::invalid_argument("reference must be feed");
     time_t tim = time(0);
     const clock_t ctb = clock();
@@ -606,28 +797,31 @@ static void run_basetype(int argc, char **argv)                          // src/
     int first_batch = 0;
     bool extract = true;
     if (opt::rerun && ngz > 0) { extract = ngz != thread * nb; first_batch = bk; }
-    const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
-    MemBatches mem;
-    if (extract) {
+    int n_sub = thread;                                                  // the sub-files: one per compute thread (of every window)
+    DeviceSlots slots(knobs.device_slots);
+    std::mutex mu;
+    std::string werr;                                                    // the first error of a compute thread (or of a window's loader)
+    // The compute threads of the region, or of one position window: thread i works as thread sub0 + i of n_sub.  Every worker is joined
+    // BEFORE anything can throw: unwinding past a joinable std::thread is std::terminate, which would lose the error text and leave the
+    // other threads in the middle of their device calls.
+    auto compute = [&](int sub0, const MemBatches *mem, int gpus) {
+        std::vector<std::thread> workers;
+        for (int i = 0; i < thread; ++i)
+            workers.emplace_back([&, i]() {
+                try { bt_s(mem ? std::vector<std::string>() : ftmp_vv[(size_t)i], pv, refseq, chr, rg_s, N, n_sub, sub0 + i,
+                           mem ? 0 : device_of_thread(i, gpus, opt::gpus), knobs, slots, mem); }
+                catch (const std::exception &e) { std::lock_guard<std::mutex> g(mu); if (werr.empty()) werr = e.what(); }
+            });
+        for (auto &w : workers) w.join();
+    };
+    double t_loaded = 0, t_joined = 0;
+    if (in_memory) {
         std::cerr << "begin to extract reads from bam" << std::endl;
-        if (in_memory) {
-            if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
-            if (bvc_store_create(&mem.store, 0, (int32_t)pv.size(), nb, (int64_t)(knobs.store_gb * 1073741824.0)) != BVC_OK)
-                throw std::runtime_error("ERROR: no usable gfx950 device for the store of the batches");
-            mem.names.resize((size_t)nb);
-            run_pool(nb, thread, [&](int t) { bt_r_mem(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, mem); });
-            {
-                LoadDevice dev;                                         // (sealing takes a context; any of the store's device)
-                if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
-                bvc_check(dev.ctx, bvc_store_seal(dev.ctx, mem.store));
-            }
-            if (knobs.profile) {
-                int64_t used = 0;
-                bvc_store_bytes(mem.store, &used, nullptr);
-                std::cerr << "[profile] main: load phase on the device, " << g_device_batches.load() << " batches kept there (bvc_bam_pileup_bgzf_store), "
-                          << used << " bytes" << std::endl;
-            }
-        } else if (knobs.device_pileup && opt::tmp_format != "text") {
+        basetype_in_memory(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, n_sub, werr, mu, t_loaded, compute);
+        t_joined = StageClock::now();
+    } else if (extract) {
+        std::cerr << "begin to extract reads from bam" << std::endl;
+        if (knobs.device_pileup && opt::tmp_format != "text") {
             const int load_gpus = bvc_device_count();
             if (load_gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
             run_pool(nb - first_batch, thread, [&](int t) { bt_r_device(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread, load_gpus, false, knobs); });
@@ -642,31 +836,21 @@ static void run_basetype(int argc, char **argv)                          // src/
         } else
             run_pool(nb - first_batch, thread, [&](int t) { bt_r(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, first_batch + t, thread); });
     }
-    time_t tim1 = time(0);
-    const double t_loaded = StageClock::now();
-    std::cout << "basetype loading done -- " << ctime(&tim1);
-    if (opt::load) std::exit(EXIT_SUCCESS);
-    DeviceSlots slots(knobs.device_slots);
-    const int gpus = bvc_device_count();
-    if (gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+    if (!in_memory) {
+        time_t tim1 = time(0);
+        t_loaded = StageClock::now();
+        std::cout << "basetype loading done -- " << ctime(&tim1);
+        if (opt::load) std::exit(EXIT_SUCCESS);
+        const int gpus = bvc_device_count();
+        if (gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+        compute(0, nullptr, gpus);
+        t_joined = StageClock::now();
+    }
     {
-        std::vector<std::thread> workers;
-        std::mutex mu;
-        std::string werr;
-        for (int i = 0; i < thread; ++i)
-            workers.emplace_back([&, i]() {
-                try { bt_s(in_memory ? std::vector<std::string>() : ftmp_vv[(size_t)i], pv, refseq, chr, rg_s, N, thread, i,
-                           in_memory ? 0 : device_of_thread(i, gpus, opt::gpus), knobs, slots, in_memory ? &mem : nullptr); }
-                catch (const std::exception &e) { std::lock_guard<std::mutex> g(mu); if (werr.empty()) werr = e.what(); }
-            });
-        // Every worker is joined BEFORE anything can throw: unwinding past a joinable std::thread is std::terminate,
-        // which would lose the error text and leave the other threads in the middle of their device calls.
-        for (auto &w : workers) w.join();
-        const double t_joined = StageClock::now();
         {
             std::lock_guard<std::mutex> g(mu);
             if (!werr.empty()) {
-                for (int i = 0; i < thread; ++i) {                       // partial sub-files are of no use; the temp
+                for (int i = 0; i < n_sub; ++i) {                        // partial sub-files are of no use; the temp
                     std::remove((opt::output + "." + std::to_string(i) + ".vcf.gz").c_str());   // batches stay for --rerun
                     std::remove((opt::output + "." + std::to_string(i) + ".cvg.gz").c_str());
                 }
@@ -675,7 +859,7 @@ static void run_basetype(int argc, char **argv)                          // src/
         }
         // merge the per-thread sub-files in thread (= position) order (src/BaseVarC.cpp:268-296)
         BgzfWriter fov(opt::output + ".vcf.gz"), foc(opt::output + ".cvg.gz");
-        if (!merge_subfiles(opt::output, ".vcf.gz", thread, fov) || !merge_subfiles(opt::output, ".cvg.gz", thread, foc))
+        if (!merge_subfiles(opt::output, ".vcf.gz", n_sub, fov) || !merge_subfiles(opt::output, ".cvg.gz", n_sub, foc))
             throw std::runtime_error("ERROR: fail to write");
         std::cout << "merge subfiles done" << std::endl;
         if (!fov.close()) std::cerr << "warning: file cannot be closed" << std::endl;

@@ -522,6 +522,30 @@ void thread_window(size_t psize, int thread, int ithread, size_t &lo, size_t &hi
     hi = (ithread == thread - 1) ? psize : std::min(psize, (size_t)(ithread + 1) * window);
 }
 
+void store_windows(size_t psize, int thread, int windows, size_t *a, size_t *b)
+{
+    const int n = thread * windows;
+    for (int w = 0; w < windows; ++w) {
+        size_t lo, hi;
+        thread_window(psize, n, w * thread, a[w], hi);
+        thread_window(psize, n, w * thread + thread - 1, lo, b[w]);
+    }
+}
+
+void store_window_ranges(const int32_t *pv, int windows, const size_t *a, const size_t *b, int32_t beg0, int32_t end0, int32_t *wbeg,
+                         int32_t *wend)
+{
+    int32_t at = beg0;
+    for (int w = 0; w < windows; ++w) {
+        const bool last = w + 1 == windows || a[w + 1] == b[w + 1];       // (empty windows come last only)
+        wbeg[w] = at;
+        // (clamped: a region's padded end never lies in front of its last position, and its padded start never behind its first)
+        // (window 0 is fetched for even without positions: it keeps the sample names and says which samples are empty)
+        wend[w] = a[w] == b[w] && w > 0 ? at : last ? end0 : std::min(end0, std::max(at, pv[b[w] - 1]));
+        at = wend[w];
+    }
+}
+
 int device_of_thread(int ithread, int devices_present, int gpus_option)
 {
     int g = devices_present;

@@ -256,6 +256,18 @@ std::string fmt_fixed(double v, int prec);          // fmt's {:.Nf}
 // The reference's arithmetic (window = psize % T + psize / T) can run a non-last thread past the end when psize % T is
 // large; the range is clamped here.  The windows of threads 0..T-1 are disjoint, ascending and cover [0, psize).
 void thread_window(size_t psize, int thread, int ithread, size_t &lo, size_t &hi);
+// Position windows of --tmp-format mem (BVC_HOST_STORE_WINDOWS, additive): with `thread` threads and `windows` windows the region's
+// position list is cut as a run with n = thread * windows threads cuts it, and window w is the ranges of threads w * thread ..
+// w * thread + thread - 1 of n taken together: [a[w], b[w]).  Contiguous, ascending, disjoint, covering [0, psize); empty windows come
+// last only.  Compute thread i of window w then works as thread w * thread + i of n, so the outputs are those of a -t n run.
+void store_windows(size_t psize, int thread, int windows, size_t *a, size_t *b);
+// The windows' fetch ranges [wbeg[w], wend[w]) (0-based, as BamFile::fetch takes them): they tile the region's [beg0, end0).  Window 0
+// begins at beg0, the last window that has positions ends at end0, and the cut between a window and the next one that has positions is
+// the coordinate just behind the earlier window's last position (pv holds 1-based positions, so that coordinate is pv[b[w] - 1]): a
+// read that starts there or later covers nothing of the earlier window, and the later window keeps every read that has not ended at or
+// in front of that last position.  A window without positions gets an empty range (nothing is fetched for it).
+void store_window_ranges(const int32_t *pv, int windows, const size_t *a, const size_t *b, int32_t beg0, int32_t end0, int32_t *wbeg,
+                         int32_t *wend);
 // Device of a phase-2 thread (additive: the reference has one CPU path): thread i works on device i mod G, G = the devices present,
 // or --gpus when that is given and smaller.  Sites shard by position window, no device ever needs another's data.
 int device_of_thread(int ithread, int devices_present, int gpus_option);

@@ -7,6 +7,11 @@ memory and a device-to-device copy of the same bytes.
   python tools/store_bench.py [--copies 50] [--repeats 3] [--out profiles/store_feed/README.txt]
   python tools/store_bench.py --gather-only          # the tile alone: under `rocprofv3 --kernel-trace --stats -- python ...` the
                                                      # row of store_gather_kernel is the gather kernel's own time
+  python tools/store_bench.py --windows 4 [--overlap] [--out profiles/store_windows/README.txt]
+                                                     # mem in one window (the yardstick), in K position windows (BVC_HOST_STORE_WINDOWS)
+                                                     # and, with --overlap, in K windows with the next one loaded beside this one's threads
+                                                     # (BVC_HOST_STORE_OVERLAP); beside each the largest store's bytes and the windows'
+                                                     # load and compute seconds, from the profile lines of one more run
 
 Every process time is the best of --repeats wall-clock runs of the whole program, start-up and the contexts' creation included; the page
 cache serves all forms alike (the larger list repeats the same files)."""
@@ -45,6 +50,34 @@ def run_seconds(exe, lst, fa, region, out, threads, batch, extra, env, repeats):
             raise RuntimeError(r.stderr[-2000:])
         best = dt if best is None else min(best, dt)
     return best
+
+
+def windows_report(lines, exe, lst, fa, region, d, copies, windows, overlap, repeats):
+    """mem in one window, in `windows` windows and (overlap) in windows loaded beside the threads: the whole process, best of `repeats`;
+    then one run of each with BVC_HOST_PROFILE=1 for the stores' bytes and the windows' seconds (not timed: the profile costs)."""
+    import re
+    forms = [("mem, 1 window", {"BVC_HOST_STORE_WINDOWS": "1"}), (f"mem, {windows} windows", {"BVC_HOST_STORE_WINDOWS": str(windows)})]
+    if overlap:
+        forms.append((f"mem, {windows} windows, overlap", {"BVC_HOST_STORE_WINDOWS": str(windows), "BVC_HOST_STORE_OVERLAP": "1"}))
+    lines.append(f"{100 * copies} samples (each test BAM {copies} times), batches of 100")
+    lines.append(f"  {'threads':>7s} " + " ".join(f"{name:>30s}" for name, _ in forms))
+    detail = []
+    for threads in (1, 4, 8):
+        ts = []
+        for i, (name, env) in enumerate(forms):
+            out = os.path.join(d, f"w{i}")
+            ts.append(run_seconds(exe, lst, fa, region, out, threads, 100, ["--tmp-format", "mem"], env, repeats))
+            r = subprocess.run([exe, "basetype", "-q", "20", "-t", str(threads), "-b", "100", "-i", lst, "-s", region, "-r", fa, "-o", out,
+                                "--tmp-format", "mem"], capture_output=True, text=True, env=dict(os.environ, BVC_HOST_PROFILE="1", **env))
+            if r.returncode != 0:
+                raise RuntimeError(r.stderr[-2000:])
+            per = re.findall(r"window (\d+) of \d+: .*?, (\d+) bytes, load ([0-9.e+-]+) s, compute ([0-9.e+-]+) s", r.stderr)
+            whole = re.search(r"batches kept there \(bvc_bam_pileup_bgzf_store\), (\d+) bytes", r.stderr)
+            largest = max(int(b) for _, b, _, _ in per) if per else int(whole.group(1))
+            detail.append(f"  {threads} threads, {name}: largest store {largest} bytes" +
+                          ("; per window load / compute s: " + ", ".join(f"{float(a):.3f} / {float(c):.3f}" for _, _, a, c in per) if per else ""))
+        lines.append(f"  {threads:7d} " + " ".join(f"{t:30.2f}" for t in ts))
+    lines.extend(detail)
 
 
 def gather_alone(lines, repeats, n_batches=200, tile_mb=32):
@@ -119,13 +152,23 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     ap.add_argument("--gather-only", action="store_true")
+    ap.add_argument("--windows", type=int, default=0, help="K: mem in one window next to mem in K position windows, nothing else")
+    ap.add_argument("--overlap", action="store_true", help="with --windows: and K windows with BVC_HOST_STORE_OVERLAP=1")
     a = ap.parse_args()
     from basevarc_amd import build as b
     from tests import hostref
     exe, _ = b.build_host()
     lines = Lines()
     lines.append("# `BaseVarC basetype`, whole process: tools/store_bench.py, best of %d runs, seconds" % a.repeats)
-    if not a.gather_only:
+    if a.windows > 1:
+        with tempfile.TemporaryDirectory() as d:
+            fa = hostref.write_fasta(os.path.join(d, "chr17.fa"))
+            lst = hostref.write_bam_list(os.path.join(d, "bam.list"))
+            big = os.path.join(d, "big.list")
+            with open(big, "w") as f:
+                f.write(open(lst).read() * a.copies)
+            windows_report(lines, exe, big, fa, hostref.REGION, d, a.copies, a.windows, a.overlap, a.repeats)
+    elif not a.gather_only:
         with tempfile.TemporaryDirectory() as d:
             fa = hostref.write_fasta(os.path.join(d, "chr17.fa"))
             lst = hostref.write_bam_list(os.path.join(d, "bam.list"))
@@ -138,7 +181,8 @@ def main():
                 ts = [run_seconds(exe, big, fa, hostref.REGION, os.path.join(d, f"o{i}"), threads, 100, extra, env, a.repeats)
                       for i, (_, extra, env) in enumerate(FORMS)]
                 lines.append(f"  {threads:7d} " + " ".join(f"{t:30.2f}" for t in ts))
-    gather_alone(lines, a.repeats)
+    if a.windows <= 1:
+        gather_alone(lines, a.repeats)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
