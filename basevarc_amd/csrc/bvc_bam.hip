@@ -11,18 +11,7 @@
 #include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
 
-namespace {
-
-// a call's inputs where the kernels read them (device memory), and its sizes
-struct BamCall {
-    int32_t n_samples = 0, n_positions = 0, beg0 = 0, end0 = 0, min_mapq = 0, rg_s = 0;
-    const uint8_t *bam = nullptr, *eof = nullptr, *ref = nullptr;   // ref: the reference's text (the pileup only)
-    const uint8_t *pref = nullptr, *palt = nullptr;                 // the positions' REF and ALT characters (the matrix only)
-    const int64_t *off = nullptr, *end = nullptr;
-    const int32_t *rid = nullptr, *pos = nullptr;
-    int64_t bam_bytes = 0, refseq_len = 0;
-};
-
+// (BamCall, the checks and the two verdicts are declared in bvc_ctx.h: bvc_bam_counts.hip shares them)
 int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_positions, int64_t refseq_len, int64_t records_cap)
 {
     if (n_samples < 0 || bam_bytes < 0 || n_positions < 0 || refseq_len < 0 || records_cap < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
@@ -31,7 +20,7 @@ int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_po
 
 // strict: the positions ascend strictly (the records: one per position); else they may repeat (the matrix: a multi-allelic site is two lines)
 int check_host_arrays(bvc_ctx *ctx, int32_t n_samples, const int64_t *sample_off, const int64_t *sample_end, int64_t bam_bytes, int32_t n_positions,
-                      const int32_t *positions, bool strict = true)
+                      const int32_t *positions, bool strict)
 {
     for (int32_t s = 0; s < n_samples; ++s)
         if (!(sample_off[s] >= (s ? sample_end[s - 1] : 0) && sample_end[s] >= sample_off[s] && sample_end[s] <= bam_bytes))
@@ -81,6 +70,8 @@ int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status)
         }
     return BVC_OK;
 }
+
+namespace {
 
 // The kernels of one call on inputs in device memory.  out_device: records, rec_start and sample_status are device memory and the call
 // returns with the second pass enqueued; else they are host memory (d_status: the statuses' place on the device) and the call waits.

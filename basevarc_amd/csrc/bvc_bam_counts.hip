@@ -1,0 +1,286 @@
+// bvc_bam_counts.hip -- bvc_bam_counts, bvc_bam_counts_bgzf_acc and the accumulator bvc_site_acc (include/bvc_bam_counts.h): the inflated BAM
+// records of a batch of samples added into per-position class counts and tallies (bam_counts_kernel.hip).  The call's inputs (BamCall), their
+// checks and the verdicts on the statuses and the blocks are bvc_bam.hip's.  Order of work: index -> dry pass -> scan -> first wait ->
+// verdict -> add pass (-> second wait in the host forms): nothing is added unless the call returns BVC_OK.
+#include "bvc_ctx.h"
+#include "../../include/bvc_bam_counts.h"
+
+// An accumulator is no part of a context: its device memory is its own, and its bookkeeping is fixed when it is made (the adds are atomic).
+struct bvc_site_acc {
+    int device = -1;
+    int32_t n_positions = 0, n_groups = 0;
+    int64_t budget = 0, used = 0;
+    uint32_t *d_counts = nullptr;                    // [n_positions][slots][512]
+    bvc_bam_site_tally *d_tally = nullptr;           // [n_positions]
+    size_t slots() const { return n_groups > 0 ? (size_t)n_groups + 1 : 1; }
+    size_t row_words() const { return slots() * BVC_NCLASS; }
+};
+
+namespace {
+
+int check_acc(bvc_ctx *ctx, const bvc_site_acc *acc)
+{
+    if (!acc) return fail(ctx, BVC_ERR_ARG, "null accumulator");
+    if (acc->device != ctx->device) return fail(ctx, BVC_ERR_ARG, "the accumulator lies on another device than the context");
+    return BVC_OK;
+}
+
+int check_rows(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n)
+{
+    if (t0 < 0 || n < 0 || n > acc->n_positions - t0) return fail(ctx, BVC_ERR_ARG, "rows outside the accumulator");
+    return BVC_OK;
+}
+
+int check_counts_groups(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of_sample, int32_t n_groups)
+{
+    if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
+    if (n_groups > 0 && n_samples > 0 && !group_of_sample) return fail(ctx, BVC_ERR_ARG, "null group_of_sample with n_groups > 0");
+    return BVC_OK;
+}
+
+// Index, dry pass, scan and the call's first wait, on inputs in device memory: the statuses (to sample_status on the host unless
+// out_device) and the verdict -- the blocks' first (blocks: their statuses come down with the same wait; may be null), then the samples'.
+int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, uint32_t *d_status, uint32_t *sample_status,
+                       const std::vector<uint32_t> *blocks, BamPileupScratch &S)
+{
+    const size_t ns = (size_t)c.n_samples;
+    const int rc = carve(ctx, ctx->d_bam, 256, [&](Layout &L) { S = bam_popmatrix_scratch(L, c.bam_bytes, c.n_samples); });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, launch_bam_index(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.eof, c.rid, c.beg0, c.end0, c.min_mapq, S, d_status));
+    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
+                                     nullptr, 0, S, nullptr, nullptr, d_status));
+    BVC_HIP_D(ctx, launch_bam_scan(ctx->stream, 0, c.n_samples, S, d_status));
+    int64_t head[4] = {0, 0, 0, 0};
+    BVC_HIP_D(ctx, io.d2h(head, S.head, sizeof head));
+    if (!out_device && ns) BVC_HIP_D(ctx, io.d2h(sample_status, d_status, ns * 4));
+    BVC_HIP_D(ctx, wait_stream(ctx));               // the statuses decide whether anything is added
+    io.deliver();
+    // a block that did not inflate (or failed its CRC32) outranks what the kernels made of its bytes
+    if (blocks && block_verdict(ctx, *blocks) != BVC_OK) return BVC_ERR_DATA;
+    return status_verdict(ctx, head);
+}
+
+// The add pass, enqueued on the context's stream.
+int bam_counts_add(bvc_ctx *ctx, const BamCall &c, const uint8_t *d_group, int32_t n_groups, const BamPileupScratch &S, uint32_t *d_counts,
+                   bvc_bam_site_tally *d_tally, uint32_t *d_status)
+{
+    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
+                                     d_group, n_groups, S, d_counts, d_tally, d_status));
+    return BVC_OK;
+}
+
+// What both entry points check of the sample and position arguments before anything of the device is touched; fills what they share.
+int check_counts_call(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                      const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                      const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
+                      const uint32_t *sample_status)
+{
+    int rc = check_sizes(ctx, n_samples, bam_bytes, n_positions, refseq_len, 0);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_counts_groups(ctx, n_samples, group_of_sample, n_groups)) != BVC_OK) return rc;
+    if ((n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) || (n_positions > 0 && !positions))
+        return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
+    c.eof = sample_eof; c.off = sample_off; c.end = sample_end; c.rid = rid; c.pos = positions; c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
+    return BVC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                   const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                   const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
+                   uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *sample_status, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    BamCall c;
+    int rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
+                               refseq_len, group_of_sample, n_groups, sample_status);
+    if (rc != BVC_OK) return rc;
+    if ((bam_bytes > 0 && !bam) || (n_samples > 0 && n_positions > 0 && (!counts || !tally))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    c.bam = bam;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ns = (size_t)n_samples, np = (size_t)n_positions;
+    const bool labels = n_groups > 0 && ns > 0;
+    BamPileupScratch S;
+    PinIO io(ctx);
+    if (flags & BVC_PTR_DEVICE) {
+        if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
+        rc = bam_counts_verdict(ctx, io, c, true, sample_status, sample_status, nullptr, S);
+        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, sample_status);
+    }
+    if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
+    if ((rc = io.reserve(ns * 22 + np * 4 + 1024, 64 + ns * 4 + 1024)) != BVC_OK) return rc;
+    // host pointers: the inputs and the two accumulators live in the staging buffer for the length of the call
+    const size_t cwords = ns ? np * (n_groups > 0 ? (size_t)n_groups + 1 : 1) * BVC_NCLASS : 0, trows = ns ? np : 0;
+    uint8_t *u_bam, *u_eof, *u_grp; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos; uint32_t *d_status, *d_counts; bvc_bam_site_tally *d_tally;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        u_bam = L.take<uint8_t>((size_t)bam_bytes);
+        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns); u_grp = L.take<uint8_t>(ns);
+        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
+        d_counts = L.take<uint32_t>(cwords); d_tally = L.take<bvc_bam_site_tally>(trows);
+    });
+    if (rc != BVC_OK) return rc;
+    if (bam_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, bam, (size_t)bam_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
+    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
+    if (labels) BVC_HIP_D(ctx, io.h2d(u_grp, group_of_sample, ns));
+    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
+    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
+    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, nullptr, S);
+    if (rc != BVC_OK || cwords == 0) return rc;
+    // the accumulators go up only now: a call that fails has not touched them
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_counts, counts, cwords * 4, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_tally, tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, d_status)) != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemcpyAsync(counts, d_counts, cwords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tally, d_tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
+{
+    if (!out) return BVC_ERR_ARG;
+    *out = nullptr;
+    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
+    if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BVC_ERR_DEVICE; }
+    bvc_site_acc *acc = new bvc_site_acc;
+    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->budget = byte_budget > 0 ? byte_budget : 0;
+    const size_t cbytes = (size_t)n_positions * acc->row_words() * 4, tbytes = (size_t)n_positions * sizeof(bvc_bam_site_tally);
+    acc->used = (int64_t)(cbytes + tbytes);
+    if (acc->budget > 0 && acc->used > acc->budget) { delete acc; return BVC_ERR_ALLOC; }
+    if (n_positions > 0 &&
+        (hipMalloc(reinterpret_cast<void **>(&acc->d_counts), cbytes) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&acc->d_tally), tbytes) != hipSuccess ||
+         hipMemset(acc->d_counts, 0, cbytes) != hipSuccess || hipMemset(acc->d_tally, 0, tbytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
+        (void)hipGetLastError();
+        bvc_site_acc_destroy(acc);
+        return BVC_ERR_ALLOC;
+    }
+    *out = acc;
+    return BVC_OK;
+}
+
+void bvc_site_acc_destroy(bvc_site_acc *acc)
+{
+    if (!acc) return;
+    (void)hipSetDevice(acc->device);
+    if (acc->d_counts) (void)hipFree(acc->d_counts);
+    if (acc->d_tally) (void)hipFree(acc->d_tally);
+    delete acc;
+}
+
+int bvc_site_acc_bytes(const bvc_site_acc *acc, int64_t *used, int64_t *budget)
+{
+    if (!acc) return BVC_ERR_ARG;
+    if (used) *used = acc->used;
+    if (budget) *budget = acc->budget;
+    return BVC_OK;
+}
+
+int bvc_bam_counts_bgzf_acc(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+                            int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end, const uint8_t *sample_eof, const int32_t *rid,
+                            int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions, const int32_t *positions, int32_t rg_s,
+                            int64_t refseq_len, const uint8_t *group_of_sample, bvc_site_acc *acc, uint32_t *sample_status)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if (n_positions != acc->n_positions) return fail(ctx, BVC_ERR_ARG, "n_positions is not the accumulator's");
+    BamCall c;
+    rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
+                           refseq_len, group_of_sample, acc->n_groups, sample_status);
+    if (rc != BVC_OK) return rc;
+    if (comp_bytes < 0 || n_blocks < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    if (n_blocks > 0 && (!comp || !blocks)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if ((rc = check_blocks(ctx, blocks, n_blocks, comp_bytes, bam_bytes)) != BVC_OK) return rc;
+    if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t ns = (size_t)n_samples, np = (size_t)n_positions, nb = (size_t)n_blocks;
+    const bool labels = acc->n_groups > 0 && ns > 0;
+    PinIO io(ctx);
+    if ((rc = io.reserve(ns * 22 + np * 4 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + nb * 4 + 1024)) != BVC_OK) return rc;
+    uint8_t *u_comp, *u_bam, *u_eof, *u_grp; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
+        u_bam = L.take<uint8_t>((size_t)bam_bytes);
+        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns); u_grp = L.take<uint8_t>(ns);
+        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
+    });
+    if (rc != BVC_OK) return rc;
+    std::vector<uint32_t> block_status(nb);
+    if (nb) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
+        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
+        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
+    }
+    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
+    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
+    if (labels) BVC_HIP_D(ctx, io.h2d(u_grp, group_of_sample, ns));
+    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
+    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
+    BamPileupScratch S;
+    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, &block_status, S);
+    if (rc != BVC_OK) return rc;
+    if ((rc = bam_counts_add(ctx, c, u_grp, acc->n_groups, S, acc->d_counts, acc->d_tally, d_status)) != BVC_OK) return rc;
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n, uint32_t *counts, bvc_bam_site_tally *tally)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
+    if (n > 0 && !tally) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n == 0) return BVC_OK;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t rw = acc->row_words();
+    if (counts) BVC_HIP_D(ctx, hipMemcpyAsync(counts, acc->d_counts + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(tally, acc->d_tally + t0, (size_t)n * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_lrt(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n, const int8_t *ref_base, double min_af,
+                     bvc_site_result *results, bvc_group_result *grp_results)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
+    const int32_t ng = acc->n_groups;
+    if (n > 0 && (!ref_base || !results || (ng > 0 && !grp_results))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n == 0) return BVC_OK;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    // the rows stay where they are: only ref_base goes up and the records come down, through the staging buffer
+    int8_t *d_r; bvc_site_result *d_res; bvc_group_result *d_gres;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
+        d_r = L.take<int8_t>((size_t)n);
+        d_res = L.take<bvc_site_result>((size_t)n);
+        d_gres = L.take<bvc_group_result>((size_t)n * (size_t)ng);
+    });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+    const uint32_t *rows = acc->d_counts + (size_t)t0 * acc->row_words();
+    if (ng > 0) {
+        rc = bvc_lrt_hist_groups(ctx, n, rows, d_r, min_af, ng, d_res, d_gres, BVC_PTR_DEVICE);
+        if (rc == BVC_OK) rc = join_side(ctx);
+    } else
+        rc = bvc_lrt_hist(ctx, n, rows, d_r, min_af, nullptr, nullptr, d_res, BVC_PTR_DEVICE);
+    if (rc != BVC_OK) return drain_on_error(ctx, rc);
+    BVC_HIP_D(ctx, hipMemcpyAsync(results, d_res, (size_t)n * sizeof(bvc_site_result), hipMemcpyDeviceToHost, ctx->stream));
+    if (ng > 0) BVC_HIP_D(ctx, hipMemcpyAsync(grp_results, d_gres, (size_t)n * (size_t)ng * sizeof(bvc_group_result), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+}  // extern "C"

@@ -350,6 +350,24 @@ int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8
                          const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
                          uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink = nullptr);
 
+// bvc_bam.hip, shared with bvc_bam_counts.hip: a call's inputs where the kernels read them (device memory) and its sizes ...
+struct BamCall {
+    int32_t n_samples = 0, n_positions = 0, beg0 = 0, end0 = 0, min_mapq = 0, rg_s = 0;
+    const uint8_t *bam = nullptr, *eof = nullptr, *ref = nullptr;   // ref: the reference's text (the pileup only)
+    const uint8_t *pref = nullptr, *palt = nullptr;                 // the positions' REF and ALT characters (the matrix only)
+    const int64_t *off = nullptr, *end = nullptr;
+    const int32_t *rid = nullptr, *pos = nullptr;
+    int64_t bam_bytes = 0, refseq_len = 0;
+};
+// ... the checks made before anything of the device is touched (strict: the positions ascend strictly; else they may repeat) ...
+int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_positions, int64_t refseq_len, int64_t records_cap);
+int check_host_arrays(bvc_ctx *ctx, int32_t n_samples, const int64_t *sample_off, const int64_t *sample_end, int64_t bam_bytes, int32_t n_positions,
+                      const int32_t *positions, bool strict = true);
+int check_blocks(bvc_ctx *ctx, const bvc_bgzf_block *blocks, int64_t n_blocks, int64_t comp_bytes, int64_t bam_bytes);
+// ... and the verdicts on what the statuses' scan found (head[1..3]: the first sample of status 2, 3, 4) and on the blocks' statuses
+int status_verdict(bvc_ctx *ctx, const int64_t head[4]);
+int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status);
+
 // bvc_vcf.hip: the device copy of bvc_vcf_bp_lut in ctx->d_vcf_lut, made at the context's first use of it
 int vcf_lut_device(bvc_ctx *ctx);
 

@@ -7,6 +7,8 @@
 
 #include "../../include/bvc.h"
 
+struct bvc_bam_site_tally;              // include/bvc_bam_counts.h
+
 namespace bvc {
 
 // Launch policy and one-time kernel setup of ONE context (bvc_ctx owns it; nothing here is process-wide, so
@@ -314,6 +316,14 @@ BamPileupScratch bam_popmatrix_scratch(Layout &L, int64_t bam_bytes, int32_t n_s
 hipError_t launch_bam_popmatrix(hipStream_t stream, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
                                 const int64_t *sample_end, int32_t n_positions, const int32_t *positions, const uint8_t *ref, const uint8_t *alt,
                                 int32_t rg_s, int64_t refseq_len, const BamPileupScratch &s, uint8_t *matrix, int64_t row_stride, uint32_t *sample_status);
+
+// bam_counts_kernel.hip: the same records added into class counts [position][slot][512] and tallies [position] (include/bvc_bam_counts.h,
+// bvc_bam_counts).  launch_bam_index as above, the scratch is bam_popmatrix_scratch; add = false: the dry pass, which only raises status 4
+// (nothing of counts, tally or group_of_sample is read); add = true: the adds.  launch_bam_scan with n_positions = 0 leaves head[1..3].
+hipError_t launch_bam_counts(hipStream_t stream, bool add, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                             const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
+                             const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
+                             ::bvc_bam_site_tally *tally, uint32_t *sample_status);
 
 // store_kernel.hip: temp batches kept on the device (include/bvc_store.h).  A kept batch as the kernels see it: the device addresses of its
 // rec_start row and of its records, and the records' bytes (what every word of the row is clamped with).

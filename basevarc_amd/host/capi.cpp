@@ -82,6 +82,11 @@ int32_t bvchost_parse_store_windows(const char *value, int32_t thread)
     const int k = parse_store_windows(value);
     return k > 0 && store_windows_refused(k, thread) ? -1 : k;
 }
+// the revisit set of --tmp-format counts (counts_revisit): tally = bvc_bam_site_tally [psize], called [psize] -> flags [psize]
+void bvchost_counts_revisit(const void *tally, const uint8_t *called, int64_t psize, int32_t thread, uint8_t *flags)
+{
+    counts_revisit(static_cast<const bvc_bam_site_tally *>(tally), called, (size_t)psize, thread, flags);
+}
 int32_t bvchost_device_of_thread(int32_t ithread, int32_t devices_present, int32_t gpus_option) { return device_of_thread(ithread, devices_present, gpus_option); }
 int32_t bvchost_merge_subfiles(const char *out_prefix, const char *suffix, int32_t thread)
 {

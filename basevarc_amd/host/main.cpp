@@ -72,7 +72,12 @@ static const char *BASETYPE_MESSAGE =
     "                           records, deflated) or raw (binary records, stored: fastest to read back) [text];\n"
     "                           mem: no files at all, the batches stay in the memory of one device (BVC_HOST_STORE_GB\n"
     "                           caps them; not with --load, --keep_tmp or --gpus above 1)\n"
-    "                           (BVC_HOST_STORE_WINDOWS=K|auto: in K windows of positions, one at a time, as -t T*K cuts them)\n";
+    "                           (BVC_HOST_STORE_WINDOWS=K|auto: in K windows of positions, one at a time, as -t T*K cuts them)\n"
+    "                           counts: no files either; every batch is added into per-position class counts on one device\n"
+    "                           (2 KB a position whatever the samples' number), the positions are called from those, and only\n"
+    "                           the called positions and those with indels are piled up a second time, as mem keeps them\n"
+    "                           (BVC_HOST_STORE_GB caps the counts, then those batches; not with --group, --load, --keep_tmp\n"
+    "                           or --gpus above 1)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -137,7 +142,8 @@ static void parse_options(int argc, char **argv, const char *msg)          // sr
         default: die = true;
         }
     }
-    if (opt::tmp_format != "text" && opt::tmp_format != "bin" && opt::tmp_format != "raw" && opt::tmp_format != "mem") die = true;
+    if (opt::tmp_format != "text" && opt::tmp_format != "bin" && opt::tmp_format != "raw" && opt::tmp_format != "mem" && opt::tmp_format != "counts")
+        die = true;
     if (die || opt::input.empty() || opt::output.empty()) {
         std::cerr << msg;
         std::exit(die ? EXIT_FAILURE : EXIT_SUCCESS);
@@ -383,6 +389,8 @@ struct MemRun {
     int windows = 1;
     // the line that ends a run whose batches pass the budget also proposes a K: with K > 1, and with the knob unset
     bool propose_windows = false;
+    // --tmp-format counts, its second pile-up: the names are kept and the warnings printed already
+    bool quiet = false;
 };
 struct MemBatches {
     bvc_store *store = nullptr;                     // (none for a window without positions)
@@ -425,7 +433,8 @@ static void bt_r_mem(const std::vector<std::string> &bams, const std::vector<int
         }
         return rc;
     });
-    if (run.windows == 1) {
+    if (run.quiet) {
+    } else if (run.windows == 1) {
         for (size_t s = 0; s < ns; ++s)
             if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
     } else {
@@ -433,11 +442,44 @@ static void bt_r_mem(const std::vector<std::string> &bams, const std::vector<int
         for (size_t s = 0; s < ns; ++s)
             if (!(batch.rid[s] < 0 || status[s] == 1u)) run.has_reads[b0 + s] = 1;
     }
-    if (iwindow == 0) {
+    if (iwindow == 0 && !run.quiet) {
         run.names[(size_t)ib] = batch.sms;
         for (size_t s = 0; s < ns; ++s) run.sms[b0 + s] = batch.sms[s];
     }
     ++mem.kept;
+    ++g_device_batches;
+}
+
+// ---- phase 1 into class counts (--tmp-format counts): the same gathering and the same retries around bvc_bam_counts_bgzf_acc; the batch
+// is ADDED into the run's one accumulator on device 0 (only a call that succeeds adds anything, so the retry adds once) and nothing is
+// kept of it but the names and the warnings, as --tmp-format mem prints them.
+// What the counts pass leaves for the compute threads: the tallies of every position, which positions are revisited (counts_revisit,
+// pileup.h), those positions as one ascending list -- what the second pile-up's store holds -- and each thread's share of that list.
+struct CountsPass {
+    const std::vector<int32_t> *pv = nullptr;       // the region's positions
+    std::vector<bvc_bam_site_tally> tally;          // [pv->size()]
+    std::vector<uint8_t> flags;                     // [pv->size()]: kRevisit* bits; 0 = the CVG line comes from the tally
+    std::vector<int32_t> pvS;                       // the revisited positions
+    std::vector<size_t> lo, hi;                     // per thread: its window of pv, cut with the set, as indices into pvS
+};
+static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run)
+{
+    static thread_local LoadDevice dev;
+    if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+    const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
+    const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
+    BamBatch batch;
+    batch.open(bams, b0, b1, chr);
+    std::vector<uint32_t> status(ns);
+    device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
+        return bvc_bam_counts_bgzf_acc(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
+                                       batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(),
+                                       pv.data(), rg_s, (int64_t)refseq.size(), nullptr, acc, status.data());
+    });
+    for (size_t s = 0; s < ns; ++s)
+        if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
+    run.names[(size_t)ib] = batch.sms;
     ++g_device_batches;
 }
 
@@ -469,7 +511,7 @@ static Groups read_groups(const std::vector<std::string> &names, int32_t N)
 
 static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32_t> &pv, const std::string &refseq,
                  const std::string &chr, int32_t rg_s, int32_t N, int thread, int ithread, int device, const Knobs &knobs, DeviceSlots &slots,
-                 const MemBatches *mem)
+                 const MemBatches *mem, const CountsPass *cp = nullptr)
 {
     const double t_start = StageClock::now();
     // the outputs are deflated by threads of their writers' own (a VCF line carries a field per SAMPLE, a megabyte at 1e5 samples: up
@@ -517,10 +559,29 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     tr.min_af = min_af;
     tr.fvcf = &fpv;
     tr.fcvg = &fpc;
+    // --tmp-format counts: pv is the revisited positions; the CVG lines of the thread's other positions are written from their tallies, in
+    // front of each revisited position's lines and at the window's end (a position without an entry the parser keeps gets no line)
+    size_t fill_at = 0, fill_hi = 0;
+    if (cp) {
+        thread_window(cp->pv->size(), thread, ithread, fill_at, fill_hi);
+        tr.before_pos = [&, cp](int32_t pos) {
+            for (; fill_at < fill_hi && (*cp->pv)[fill_at] < pos; ++fill_at) {
+                if (cp->flags[fill_at]) continue;
+                const bvc_bam_site_tally &y = cp->tally[fill_at];
+                int32_t cnt[4], fwd[8] = {0, 0, 0, 0, 0, 0, 0, 0}, rev[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (int b = 0; b < 4; ++b) { rev[b] = (int32_t)y.strand_base[b]; fwd[b] = (int32_t)y.strand_base[4 + b]; cnt[b] = rev[b] + fwd[b]; }
+                if (cnt[0] + cnt[1] + cnt[2] + cnt[3] == 0) continue;
+                SiteView v;
+                v.pos = (*cp->pv)[fill_at]; v.cnt = cnt; v.fwd = fwd; v.rev = rev;
+                fpc.write(cvg_line(chr, ref_code(refseq[(size_t)(v.pos - rg_s)]), v, nullptr, 0));
+            }
+        };
+    }
     tr.start();
     Window w = {pv, refseq, rg_s, 0, 0, opt::tile > 0 ? opt::tile : 4096};
     if (!groups.empty()) w.tile = std::max<int64_t>(1, std::min<int64_t>(w.tile, ((int64_t)256 << 20) / std::max(1, N)));
     thread_window(pv.size(), thread, ithread, w.lo, w.hi);
+    if (cp) { w.lo = cp->lo[(size_t)ithread]; w.hi = cp->hi[(size_t)ithread]; }
     reset_parser_carry();
     // The feed.  Tiles of TEXT, or of binary RECORDS when every batch file is binary, for the device parser (the default);
     // BVC_HOST_DEVICE_PARSE=0 keeps the CPU parser (A/B runs, and what the quality-shift test hook and a mix of text and binary files
@@ -555,6 +616,7 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     else if (dev_parse) feed_staged_tiles(tr, w, in, TileForm::Text);
     else feed_cpu_parser(tr, w, in, qual_shift);
     tr.finish();
+    if (cp) tr.before_pos(0x7FFFFFFF);                                  // (the stages are joined: the lines behind the last revisited position)
     const double loop_s = StageClock::now() - t_loop, setup_s = t_loop - t_start;
     if (knobs.profile) {
         // (each line composed first and written at once: the threads end side by side, and a line written piece by piece ends up inside
@@ -713,7 +775,7 @@ static void basetype_in_memory(const std::vector<std::string> &bams, const std::
         std::thread loader;
         if (overlap && w + 1 < K) loader = std::thread([&, w]() { load(w + 1); });
         const double t0 = StageClock::now();
-        compute(w * thread, &wins[(size_t)w], 0);
+        compute(w * thread, &wins[(size_t)w], 0, nullptr);
         const double compute_s = StageClock::now() - t0;
         if (loader.joinable()) loader.join();
         compute_total += compute_s;
@@ -738,20 +800,109 @@ static void basetype_in_memory(const std::vector<std::string> &bams, const std::
     t_loaded = StageClock::now() - compute_total;
 }
 
+// ---- --tmp-format counts: pass 1 adds every batch into one accumulator of class counts and tallies (bvc_bam_counts.h) and calls the
+// positions from it; pass 2 piles the revisited positions -- the called ones, those with indel entries and their predecessors, a fraction of
+// a per cent -- up a second time into a store, as --tmp-format mem does for all of them, and the compute threads run on that store.  The
+// BAMs are gathered exactly twice whatever the cohort's size and the region's length; the accumulator and the store are never alive together.
+template <class Compute>
+static void basetype_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                            int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, const Knobs &knobs, double &t_loaded, Compute compute)
+{
+    if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
+    const int64_t budget = (int64_t)(knobs.store_gb * 1073741824.0);
+    const size_t P = pv.size();
+    const int64_t need = (int64_t)P * (int64_t)(BVC_NCLASS * 4 + sizeof(bvc_bam_site_tally));
+    const std::string what = "the class counts of " + std::to_string(P) + " positions take " + std::to_string(need) + " bytes";
+    if (budget > 0 && need > budget)
+        throw std::runtime_error("ERROR: " + what + " and BVC_HOST_STORE_GB allows " + std::to_string(budget) + "; --tmp-format bin keeps the batches in files");
+    MemRun run;
+    run.names.resize((size_t)nb);
+    run.sms.resize(bams.size());
+    CountsPass cp;
+    cp.pv = &pv;
+    cp.tally.resize(P);
+    cp.flags.assign(P, 0);
+    std::vector<uint8_t> called(P, 0);
+    double min_af = 100.0 / (double)bams.size();                        // src/BaseVarC.cpp:541-543, as bt_s has it
+    if (min_af > 0.001) min_af = 0.001;
+    if (opt::maf < min_af) min_af = opt::maf;
+    int64_t acc_bytes = 0;
+    {
+        struct Acc { bvc_site_acc *p = nullptr; ~Acc() { bvc_site_acc_destroy(p); } } acc;
+        if (bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget) != BVC_OK)
+            throw std::runtime_error("ERROR: the device has no room: " + what + "; --tmp-format bin keeps the batches in files");
+        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run); });
+        LoadDevice dev;
+        if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+        const size_t chunk = 8192;
+        std::vector<int8_t> refs(chunk);
+        std::vector<bvc_site_result> res(chunk);
+        for (size_t t0 = 0; t0 < P; t0 += chunk) {
+            const size_t n = std::min(chunk, P - t0);
+            for (size_t k = 0; k < n; ++k) refs[k] = ref_code(refseq[(size_t)(pv[t0 + k] - rg_s)]);
+            bvc_check(dev.ctx, bvc_site_acc_lrt(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, refs.data(), min_af, res.data(), nullptr));
+            bvc_check(dev.ctx, bvc_site_acc_get(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, nullptr, &cp.tally[t0]));
+            for (size_t k = 0; k < n; ++k) called[t0 + k] = res[k].called != 0;
+        }
+        bvc_site_acc_bytes(acc.p, &acc_bytes, nullptr);
+    }
+    counts_revisit(cp.tally.data(), called.data(), P, thread, cp.flags.data());
+    size_t n_called = 0, n_indel = 0, n_carry = 0;
+    cp.lo.assign((size_t)thread, 0); cp.hi.assign((size_t)thread, 0);
+    for (int i = 0; i < thread; ++i) {
+        size_t lo, hi;
+        thread_window(P, thread, i, lo, hi);
+        cp.lo[(size_t)i] = cp.pvS.size();
+        for (size_t t = lo; t < hi; ++t) {
+            const uint8_t f = cp.flags[t];
+            if (!f) continue;
+            cp.pvS.push_back(pv[t]);
+            if (f & kRevisitCalled) ++n_called;
+            if (f & kRevisitIndel) ++n_indel;
+            if (f == kRevisitCarry) ++n_carry;
+        }
+        cp.hi[(size_t)i] = cp.pvS.size();
+    }
+    MemBatches m;
+    m.run = &run; m.a = 0; m.b = cp.pvS.size(); m.beg0 = std::max(0, rg_s - 1 - 1000); m.end0 = rg_e + 1000;
+    int64_t store_bytes = 0;
+    if (!cp.pvS.empty()) {
+        run.quiet = true;
+        if (bvc_store_create(&m.store, 0, (int32_t)cp.pvS.size(), nb, budget) != BVC_OK)
+            throw std::runtime_error("ERROR: no usable gfx950 device for the store of the batches");
+        run_pool(nb, thread, [&](int t) { bt_r_mem(bams, cp.pvS, refseq, chr, rg_s, nb, bc, t, m, 0); });
+        LoadDevice dev;
+        if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+        bvc_check(dev.ctx, bvc_store_seal(dev.ctx, m.store));
+        bvc_store_bytes(m.store, &store_bytes, nullptr);
+    }
+    if (knobs.profile)
+        std::cerr << "[profile] main: counts pass: " << P << " positions, " << cp.pvS.size() << " revisited (" << n_called << " called, " << n_indel
+                  << " with indel entries, " << n_carry << " for the carry), accumulator " << acc_bytes << " bytes, store " << store_bytes << " bytes" << std::endl;
+    time_t tim1 = time(0);
+    std::cout << "basetype loading done -- " << ctime(&tim1);
+    t_loaded = StageClock::now();
+    compute(0, &m, 0, &cp);
+}
+
 static void run_basetype(int argc, char **argv)                          // src/BaseVarC.cpp:176-314
 {
     parse_options(argc, argv, BASETYPE_MESSAGE);
-    const bool in_memory = opt::tmp_format == "mem";
-    if (in_memory && opt::load) throw std::invalid_argument("ERROR: --tmp-format mem with --load: nothing would be left to compute from");
-    if (in_memory && opt::keep_tmp) throw std::invalid_argument("ERROR: --tmp-format mem with --keep_tmp: there are no temp files to keep");
-    if (in_memory && opt::gpus > 1) throw std::invalid_argument("ERROR: --tmp-format mem with --gpus above 1: the batches stay in the memory of one device");
+    const bool counts = opt::tmp_format == "counts";                    // (no temp files either: everything `mem` refuses, and --group)
+    const bool in_memory = opt::tmp_format == "mem" || counts;
+    const std::string fmt = "--tmp-format " + opt::tmp_format;
+    if (in_memory && opt::load) throw std::invalid_argument("ERROR: " + fmt + " with --load: nothing would be left to compute from");
+    if (in_memory && opt::keep_tmp) throw std::invalid_argument("ERROR: " + fmt + " with --keep_tmp: there are no temp files to keep");
+    if (in_memory && opt::gpus > 1) throw std::invalid_argument("ERROR: " + fmt + " with --gpus above 1: the batches stay in the memory of one device");
+    if (counts && !opt::group.empty())
+        throw std::invalid_argument("ERROR: --tmp-format counts with --group: the program calls the groups from kept batches only, use --tmp-format mem");
     if (in_memory && opt::rerun) {
-        std::cerr << "basetype: --rerun has nothing to reuse with --tmp-format mem, it is ignored" << std::endl;
+        std::cerr << "basetype: --rerun has nothing to reuse with " << fmt << ", it is ignored" << std::endl;
         opt::rerun = false;
     }
     const Knobs knobs(opt::thread);                                      // the environment, read once before any thread starts
     // (BVC_HOST_STORE_WINDOWS acts with --tmp-format mem only; refused before anything is read, made or written)
-    if (in_memory && (knobs.store_windows < 0 || (knobs.store_windows > 0 && store_windows_refused(knobs.store_windows, std::max(1, opt::thread)))))
+    if (in_memory && !counts && (knobs.store_windows < 0 || (knobs.store_windows > 0 && store_windows_refused(knobs.store_windows, std::max(1, opt::thread)))))
         throw std::invalid_argument("ERROR: BVC_HOST_STORE_WINDOWS must be auto or an integer K >= 1 with K x threads <= " +
                                     std::to_string(kStoreWindowsMaxThreads));
     if (opt::reference.empty()) throw std::invalid_argument("reference must be feed");
@@ -804,18 +955,22 @@ static void run_basetype(int argc, char **argv)                          // src/
     // The compute threads of the region, or of one position window: thread i works as thread sub0 + i of n_sub.  Every worker is joined
     // BEFORE anything can throw: unwinding past a joinable std::thread is std::terminate, which would lose the error text and leave the
     // other threads in the middle of their device calls.
-    auto compute = [&](int sub0, const MemBatches *mem, int gpus) {
+    auto compute = [&](int sub0, const MemBatches *mem, int gpus, const CountsPass *cp) {
         std::vector<std::thread> workers;
         for (int i = 0; i < thread; ++i)
             workers.emplace_back([&, i]() {
-                try { bt_s(mem ? std::vector<std::string>() : ftmp_vv[(size_t)i], pv, refseq, chr, rg_s, N, n_sub, sub0 + i,
-                           mem ? 0 : device_of_thread(i, gpus, opt::gpus), knobs, slots, mem); }
+                try { bt_s(mem ? std::vector<std::string>() : ftmp_vv[(size_t)i], cp ? cp->pvS : pv, refseq, chr, rg_s, N, n_sub, sub0 + i,
+                           mem ? 0 : device_of_thread(i, gpus, opt::gpus), knobs, slots, mem, cp); }
                 catch (const std::exception &e) { std::lock_guard<std::mutex> g(mu); if (werr.empty()) werr = e.what(); }
             });
         for (auto &w : workers) w.join();
     };
     double t_loaded = 0, t_joined = 0;
-    if (in_memory) {
+    if (counts) {
+        std::cerr << "begin to extract reads from bam" << std::endl;
+        basetype_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, t_loaded, compute);
+        t_joined = StageClock::now();
+    } else if (in_memory) {
         std::cerr << "begin to extract reads from bam" << std::endl;
         basetype_in_memory(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, n_sub, werr, mu, t_loaded, compute);
         t_joined = StageClock::now();
@@ -843,7 +998,7 @@ static void run_basetype(int argc, char **argv)                          // src/
         if (opt::load) std::exit(EXIT_SUCCESS);
         const int gpus = bvc_device_count();
         if (gpus <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
-        compute(0, nullptr, gpus);
+        compute(0, nullptr, gpus, nullptr);
         t_joined = StageClock::now();
     }
     {

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/bvc.h"
+#include "../../include/bvc_bam_counts.h"
 
 namespace bvchost {
 
@@ -268,6 +269,33 @@ void store_windows(size_t psize, int thread, int windows, size_t *a, size_t *b);
 // in front of that last position.  A window without positions gets an empty range (nothing is fetched for it).
 void store_window_ranges(const int32_t *pv, int windows, const size_t *a, const size_t *b, int32_t beg0, int32_t end0, int32_t *wbeg,
                          int32_t *wend);
+// The positions whose per-sample entries a run that piled phase 1 into class counts (bvc_bam_counts.h) must read after all, from the
+// counts pass's tallies and `called` flags alone.  Per thread window of `thread` threads, position t is in the set when
+//   kRevisitCalled   it is called (VCF sample columns, rank sums);
+//   kRevisitIndel    it has indel entries (the CVG line's indel column, and the strand counts those entries inherit);
+//   kRevisitCarry    it is the nearest earlier position OF THE SAME WINDOW that holds a base token (class 4 counts) in front of a position
+//                    with indel entries: an indel entry shows the fields of the last base token parsed before it (pileup.cpp's g_carry),
+//                    positions in between hold none and cannot change it, and a window that starts without one starts from zeros in
+//                    every run (reset_parser_carry).
+// flags [psize]: the bits above; 0 = the position's CVG line is made from its tally.
+enum : uint8_t { kRevisitCalled = 1, kRevisitIndel = 2, kRevisitCarry = 4 };
+inline void counts_revisit(const bvc_bam_site_tally *tally, const uint8_t *called, size_t psize, int thread, uint8_t *flags)
+{
+    for (int i = 0; i < thread; ++i) {
+        size_t lo, hi;
+        thread_window(psize, thread, i, lo, hi);
+        size_t last_base = psize;                    // the window's latest position so far that holds a base token; psize: none
+        for (size_t t = lo; t < hi; ++t) {
+            const bvc_bam_site_tally &y = tally[t];
+            flags[t] = (uint8_t)((called[t] ? kRevisitCalled : 0) | (y.n_indel > 0 ? kRevisitIndel : 0));
+            if (y.n_indel > 0 && last_base != psize) flags[last_base] |= kRevisitCarry;
+            uint64_t bases = y.n_other;
+            for (int k = 0; k < 8; ++k) bases += y.strand_base[k];
+            if (bases > 0) last_base = t;
+        }
+    }
+}
+
 // Device of a phase-2 thread (additive: the reference has one CPU path): thread i works on device i mod G, G = the devices present,
 // or --gpus when that is given and smaller.  Sites shard by position window, no device ever needs another's data.
 int device_of_thread(int ithread, int devices_present, int gpus_option);

@@ -4,6 +4,7 @@
 #define BVC_HOST_TILE_RUNNER_H
 
 #include <atomic>
+#include <functional>
 #include <future>
 #include <iostream>
 #include <map>
@@ -43,6 +44,9 @@ struct TileRunner {
     std::vector<int32_t> sample0, n_in_batch;         // per temp batch: its first sample and its samples (device-parsed tiles)
     uint8_t carry[5] = {0, 0, 0, 0, 0};               // the parser's long-lived AlleleInfo between tiles (stage 2's thread)
     std::atomic<int64_t> sites_done{0};
+    // --tmp-format counts: the tiles hold the revisited positions alone; called with a position before its lines are written (and by the
+    // caller with the window's end once the tiles are through), it writes the CVG lines of the positions in between from their tallies
+    std::function<void(int32_t)> before_pos;
 
     void fail(const std::string &what)
     {
@@ -314,6 +318,7 @@ struct TileRunner {
         size_t next_called = 0;
         for (size_t t = 0; t < T.n_pos; ++t) {
             const int64_t e0 = T.entry_off[t], e1 = T.entry_off[t + 1];
+            if (before_pos) before_pos(T.pos[t]);
             if (e1 == e0) continue;                      // no entry: the reference skips the position (:443)
             const int32_t *ta = &T.tally[t * 32];
             int32_t cnt[4], fwd[8], rev[8];

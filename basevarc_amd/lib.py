@@ -45,13 +45,14 @@ GROUP_DTYPE = np.dtype(GroupResult)
 STATS_DTYPE = np.dtype([("rank2", "<i8", (3,)), ("n_ref", "<i4"), ("n_alt", "<i4"), ("ref_fwd", "<i4"), ("ref_rev", "<i4"),
                         ("alt_fwd", "<i4"), ("alt_rev", "<i4"), ("valid", "u1"), ("pad", "u1", (15,))])
 ENTRY_DTYPE = np.dtype([("base", "u1"), ("mapq", "u1"), ("qual", "u1"), ("rpr", "u1"), ("strand", "u1"), ("is_indel", "u1"), ("pad", "<u2")])
+TALLY_DTYPE = np.dtype([("strand_base", "<u4", (8,)), ("n_other", "<u4"), ("n_indel", "<u4"), ("pad", "<u4", (2,))])            # bvc_bam_site_tally
 INDEL_DTYPE = np.dtype([("entry", "<i8"), ("text_off", "<i8"), ("len", "<i4"), ("pad", "<i4")])                 # bvc_pileup_indel
 BLOCK_DTYPE = np.dtype([("comp_off", "<i8"), ("out_off", "<i8"), ("comp_len", "<i4"), ("isize", "<i4"), ("crc32", "<u4"),
                         ("check_crc", "<u4")])                                                                   # bvc_bgzf_block
 SITE_STATS_TRIP = 4096      # entries a workgroup of site_stats_kernel takes per trip of its loop (csrc/bvc_internal.h, kSiteStatsTrip)
 VCF_SAMPLES_TILE = 508      # samples a workgroup of vcf_samples_kernel formats per trip of its loop (csrc/bvc_internal.h, kVcfSamplesTile)
 assert SITE_DTYPE.itemsize == C.sizeof(SiteResult) == 120
-assert STATS_DTYPE.itemsize == 64 and ENTRY_DTYPE.itemsize == 8
+assert STATS_DTYPE.itemsize == 64 and ENTRY_DTYPE.itemsize == 8 and TALLY_DTYPE.itemsize == 48
 assert GROUP_DTYPE.itemsize == C.sizeof(GroupResult) == 48
 
 # The C ABI, one row per function: name -> (restype, argtypes), in the order of include/bvc.h (tests/test_binding_abi.py compares
@@ -165,6 +166,18 @@ BAM_DEFLATE_PROTOTYPES = {
     "bvc_bam_pileup_deflate_fetch": (_int, [_vp, _vp, _i64]),
 }
 BAM_DEFLATE_EXPORTS = list(BAM_DEFLATE_PROTOTYPES)
+# The eighth header, include/bvc_bam_counts.h (tests/test_bam_counts_abi.py compares the two), bound by bind() with the others: phase 1 added
+# straight into class counts.  bvc_bam_counts takes bvc_bam_pileup's arguments up to rg_s, bvc_bam_counts_bgzf_acc bvc_bam_pileup_bgzf's.
+BAM_COUNTS_PROTOTYPES = {
+    "bvc_bam_counts": (_int, BAM_PROTOTYPES["bvc_bam_pileup"][1][:14] + [_i64, _vp, _i32, _vp, _vp, _vp, _u32]),
+    "bvc_site_acc_create": (_int, [C.POINTER(_vp), _int, _i32, _i32, _i64]),
+    "bvc_site_acc_destroy": (None, [_vp]),
+    "bvc_site_acc_bytes": (_int, [_vp, _pi64, _pi64]),
+    "bvc_bam_counts_bgzf_acc": (_int, BAM_PROTOTYPES["bvc_bam_pileup_bgzf"][1][:17] + [_i64, _vp, _vp, _vp]),
+    "bvc_site_acc_get": (_int, [_vp, _vp, _i32, _i32, _vp, _vp]),
+    "bvc_site_acc_lrt": (_int, [_vp, _vp, _i32, _i32, _vp, _dbl, _vp, _vp]),
+}
+BAM_COUNTS_EXPORTS = list(BAM_COUNTS_PROTOTYPES)
 STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
@@ -181,11 +194,11 @@ def library_path():
 
 
 def bind(cdll):
-    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES and
-    BAM_DEFLATE_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES,
+    BAM_DEFLATE_PROTOTYPES and BAM_COUNTS_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
                                       list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items()) +
-                                      list(BAM_DEFLATE_PROTOTYPES.items())):
+                                      list(BAM_DEFLATE_PROTOTYPES.items()) + list(BAM_COUNTS_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -1021,6 +1034,57 @@ class Context:
             self._check(rc)
         return rc, matrix[:n, :P], status[:n]
 
+    def bam_counts(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
+                   group_of_sample=None, n_groups=0, sample_status=None):
+        """bvc_bam_counts (include/bvc_bam_counts.h): the inflated BAM records of a batch of samples ADDED into counts ([P, 512], or
+        [P, n_groups + 1, 512] with groups; 4-byte integers) and tally (TALLY_DTYPE [P], or 12 words a position), in place.  numpy arrays
+        (synchronous) or tensors on this context's device (the adds are enqueued when it returns); the sample arrays and positions as
+        bam_pileup takes them, group_of_sample uint8 [n].  Returns (rc, sample_status): rc 0, or BAM_MORE (2) when a sample's status is 2
+        -- nothing is added then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4; nothing is added)."""
+        device = hasattr(bam, "data_ptr")
+        if device:
+            import torch
+            new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=bam.device)
+            u32, size = torch.int32, lambda a: a.numel()
+        else:
+            bam, sample_off, sample_end = _as(bam, np.uint8), _as(sample_off, np.int64), _as(sample_end, np.int64)
+            sample_eof, rid, positions = _as(sample_eof, np.uint8), _as(rid, np.int32), _as(positions, np.int32)
+            group_of_sample = None if group_of_sample is None else _as(group_of_sample, np.uint8)
+            new = lambda n, dt: np.zeros(max(1, n), dtype=dt)
+            u32, size = np.uint32, len
+            if not (isinstance(counts, np.ndarray) and counts.flags.c_contiguous and isinstance(tally, np.ndarray) and tally.flags.c_contiguous):
+                raise ValueError("counts and tally must be contiguous arrays (they are added to in place)")
+        n, P = size(rid), size(positions)
+        if size(sample_off) != n or size(sample_end) != n or size(sample_eof) != n or (group_of_sample is not None and size(group_of_sample) != n):
+            raise ValueError("sample_off, sample_end, sample_eof and group_of_sample must be [n_samples]")
+        sample_status = new(n, u32) if sample_status is None else sample_status
+        ptr = _dev_ptr if device else _np_ptr
+        opt = lambda a: a if a is not None and size(a) else None
+        rc = self._L.bvc_bam_counts(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0),
+                                                           int(end0), int(min_mapq), P, opt(positions), int(rg_s), int(refseq_len),
+                                                           opt(group_of_sample), int(n_groups), counts, tally, sample_status if n else None), ptr),
+                                    BVC_PTR_DEVICE if device else BVC_PTR_HOST)
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        return rc, sample_status
+
+    def bam_counts_bgzf_acc(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len,
+                            acc, group_of_sample=None, sample_status=None):
+        """bvc_bam_counts_bgzf_acc (include/bvc_bam_counts.h): bam_counts from BGZF blocks still compressed (comp / blocks as
+        bam_pileup_bgzf takes them), added into `acc` (a SiteAcc of len(positions) positions) with its n_groups.  Host arrays only.
+        Returns (rc, sample_status): rc 0, or BAM_MORE (2) -- nothing is added then.  Raises BvcError for the errors."""
+        n, _, shared = self._bgzf_inputs(comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s,
+                                         np.zeros(0, dtype=np.uint8))
+        g = None if group_of_sample is None else _as(group_of_sample, np.uint8)
+        if g is not None and len(g) != n:
+            raise ValueError("group_of_sample must be [n_samples]")
+        sample_status = np.zeros(max(1, n), dtype=np.uint32) if sample_status is None else sample_status
+        rc = self._L.bvc_bam_counts_bgzf_acc(self._h, n, *_pointers(shared[:-2], _np_ptr), int(refseq_len), _np_ptr(g) if g is not None and n else None,
+                                             acc._h, _np_ptr(sample_status) if n else None)
+        if rc not in (0, BAM_MORE):
+            self._check(rc)
+        return rc, sample_status
+
     # ---- a cohort in sample chunks: counts that accumulate (include/bvc.h).  `counts` is added to IN PLACE: a uint32 / int32 array of
     # [n_sites, 512] (plain) or [n_sites, n_groups + 1, 512] (groups; slot n_groups = in no group), numpy with the host calls, a tensor
     # on this context's device with the *_device calls (asynchronous on the stream).
@@ -1181,6 +1245,70 @@ class Store:
         used, budget = C.c_int64(0), C.c_int64(0)
         self._L.bvc_store_bytes(self._h, C.byref(used), C.byref(budget))
         return used.value, budget.value
+
+
+class SiteAcc:
+    """One bvc_site_acc (include/bvc_bam_counts.h): class counts [n_positions, slots, 512] and tallies [n_positions] kept in the memory of
+    one device, zeroed.  Added to through any contexts of that device (Context.bam_counts_bgzf_acc; several threads may add at once), read
+    with get, called where it lies with lrt."""
+
+    def __init__(self, device, n_positions, n_groups=0, byte_budget=0):
+        self._L = load_library()
+        h = C.c_void_p()
+        rc = self._L.bvc_site_acc_create(C.byref(h), int(device), int(n_positions), int(n_groups), int(byte_budget))
+        if rc != 0:
+            err = BvcError(f"bvc_site_acc_create(device={device}, n_positions={n_positions}, n_groups={n_groups}) failed with code {rc}")
+            err.status = rc
+            raise err
+        self._h = h
+        self.device, self.n_positions, self.n_groups = int(device), int(n_positions), int(n_groups)
+        self.slots = self.n_groups + 1 if self.n_groups else 1
+
+    create = classmethod(lambda cls, *a, **kw: cls(*a, **kw))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.bvc_site_acc_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def bytes(self):
+        """bvc_site_acc_bytes: (used, budget)."""
+        used, budget = C.c_int64(0), C.c_int64(0)
+        self._L.bvc_site_acc_bytes(self._h, C.byref(used), C.byref(budget))
+        return used.value, budget.value
+
+    def get(self, ctx, t0=0, n=None, counts=True):
+        """bvc_site_acc_get: (counts uint32 [n, 512] or [n, n_groups + 1, 512] -- None with counts=False --, tally TALLY_DTYPE [n]) of rows
+        [t0, t0 + n)."""
+        n = self.n_positions - int(t0) if n is None else int(n)
+        shape = (max(n, 0), NCLASS) if not self.n_groups else (max(n, 0), self.slots, NCLASS)
+        c = np.zeros(shape, dtype=np.uint32) if counts else None
+        t = np.zeros(max(n, 0), dtype=TALLY_DTYPE)
+        ctx._check(self._L.bvc_site_acc_get(ctx._h, self._h, int(t0), n, _np_ptr(c) if counts and n > 0 else None, _np_ptr(t) if n > 0 else None))
+        return c, t
+
+    def lrt(self, ctx, ref_base, min_af, t0=0):
+        """bvc_site_acc_lrt: stage 2 on rows [t0, t0 + len(ref_base)) where they lie.  Returns the site records (SITE_DTYPE), or with
+        groups (site records, group records [n, n_groups])."""
+        r = _as(ref_base, np.int8)
+        n = len(r)
+        res = np.zeros(n, dtype=SITE_DTYPE)
+        gres = np.zeros((n, self.n_groups), dtype=GROUP_DTYPE) if self.n_groups else None
+        ctx._check(self._L.bvc_site_acc_lrt(ctx._h, self._h, int(t0), n, _np_ptr(r) if n else None, float(min_af), _np_ptr(res) if n else None,
+                                            _np_ptr(gres) if gres is not None and n else None))
+        return (res, gres) if self.n_groups else res
 
 
 def results_from_tensor(results_t):

@@ -715,6 +715,8 @@ int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64
  * gathered from all kept batches -- are declared in bvc_store.h beside this header. */
 /* Phase 1's temp batches deflated where they are made -- bvc_bam_pileup_bgzf_deflate, bvc_bam_pileup_text_bgzf_deflate: BAM blocks in, the
  * batch's finished BGZF blocks out -- are declared in bvc_bam_deflate.h beside this header. */
+/* Phase 1 straight into class counts -- bvc_bam_counts: the same BAM records added into per-position class counts and tallies, bvc_site_acc_*:
+ * such counts kept on the device and called from there -- are declared in bvc_bam_counts.h beside this header. */
 
 #ifdef __cplusplus
 }

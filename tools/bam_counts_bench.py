@@ -1,0 +1,153 @@
+#!/usr/bin/env python3
+"""bvc_bam_counts alone (needs a gfx950 device) on the inflated records of the 100 test BAMs in device memory, for bvc_bam_pileup's
+position list of the test region, next to bvc_bam_pileup and bvc_bam_popmatrix on the same records in the same run; with n_groups 0 and 5.
+
+  python tools/bam_counts_bench.py [--repeats 5] [--out FILE]                # (a) the call alone
+  python tools/bam_counts_bench.py --process [--copies 50] [--repeats 3] [--out FILE]
+                                                     # (b) the whole `BaseVarC basetype` process with --tmp-format counts next to mem and bin
+                                                     # (bin with BVC_HOST_DEVICE_PILEUP=1: its phase 1 on the device like the other two), at
+                                                     # 100 samples and at 100 x copies, 1 / 4 / 8 threads, best of --repeats wall-clock runs;
+                                                     # and from one more run of each with BVC_HOST_PROFILE=1 the accumulator's, the second
+                                                     # pile-up's store's and mem's store's bytes
+
+Every time it prints is the best wall-clock time of a device-pointer call with the context synchronised before and after (as
+tools/popmatrix_bench.py and tools/bam_pileup_bench.py take theirs).  At 100 samples that is launch and wait latency, not kernel time: a
+counts call is index + dry pass + scan + one wait + add pass.  The kernels' own times come from the same run under the profiler's kernel
+trace (HIP's timestamps of every dispatch):
+
+  rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bam_counts_bench.py
+
+The adds are counted by the model (tests/bam_counts_model.py): one per tallied entry and one more per counted observation."""
+import argparse
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from tools.bam_pileup_bench import Lines  # noqa: E402
+
+
+def best_of(ctx, repeats, call):
+    best = None
+    for _ in range(repeats + 2):
+        ctx.synchronize()
+        t = time.perf_counter()
+        call()
+        ctx.synchronize()
+        dt = time.perf_counter() - t
+        best = dt if best is None else min(best, dt)
+    return best
+
+
+def process(a):
+    import re
+    import subprocess
+    import tempfile
+    from basevarc_amd import build as b
+    from tests import hostref
+    from tools.store_bench import run_seconds
+    exe, _ = b.build_host()
+    forms = (("bin, BVC_HOST_DEVICE_PILEUP=1", ["--tmp-format", "bin"], {"BVC_HOST_DEVICE_PILEUP": "1"}), ("mem", ["--tmp-format", "mem"], {}),
+             ("counts", ["--tmp-format", "counts"], {}))
+    lines = Lines()
+    lines.append(f"# `BaseVarC basetype`, whole process: tools/bam_counts_bench.py --process, best of {a.repeats} runs, seconds")
+    with tempfile.TemporaryDirectory() as d:
+        fa = hostref.write_fasta(os.path.join(d, "chr17.fa"))
+        lst = hostref.write_bam_list(os.path.join(d, "bam.list"))
+        big = os.path.join(d, "big.list")
+        with open(big, "w") as f:
+            f.write(open(lst).read() * a.copies)
+        for name, path in (("100 samples (the test BAMs)", lst), (f"{100 * a.copies} samples (each test BAM {a.copies} times)", big)):
+            lines.append(f"{name}, batches of 100, {hostref.REGION}, -q 20")
+            lines.append(f"  {'threads':>7s} " + " ".join(f"{n:>30s}" for n, _, _ in forms))
+            for threads in (1, 4, 8):
+                ts = [run_seconds(exe, path, fa, hostref.REGION, os.path.join(d, f"o{i}"), threads, 100, extra, env, a.repeats)
+                      for i, (_, extra, env) in enumerate(forms)]
+                lines.append(f"  {threads:7d} " + " ".join(f"{t:30.2f}" for t in ts))
+            for fmt, pattern in (("counts", r"counts pass: .*"), ("mem", r"batches kept there \(bvc_bam_pileup_bgzf_store\), \d+ bytes")):
+                r = subprocess.run([exe, "basetype", "-q", "20", "-t", "4", "-b", "100", "-i", path, "-s", hostref.REGION, "-r", fa, "-o", os.path.join(d, "p"),
+                                    "--tmp-format", fmt], capture_output=True, text=True, env=dict(os.environ, BVC_HOST_PROFILE="1"))
+                if r.returncode != 0:
+                    raise RuntimeError(r.stderr[-2000:])
+                lines.append(f"  {fmt}, 4 threads: " + re.search(pattern, r.stderr).group(0))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=None)
+    ap.add_argument("--copies", type=int, default=50)
+    ap.add_argument("--process", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.process:
+        a.repeats = 3 if a.repeats is None else a.repeats
+        return process(a)
+    a.repeats = 5 if a.repeats is None else a.repeats
+    import numpy as np
+    import torch
+    from basevarc_amd import Context
+    from tests import bam_counts_model as cm
+    from tests import bam_pileup_model as bm
+    from tests import popmatrix_model as pm
+    from tests.test_bam_pileup_abi import bam_data_bytes, bam_data_call
+    contig, beg0, end0, mapq, pv, rg_s, refseq = bam_data_call()
+    data = bam_data_bytes()
+    bam = b"".join(d for d, _, _ in data)
+    off, end, at = [], [], 0
+    for d, first, _ in data:
+        off.append(at + first)
+        at += len(d)
+        end.append(at)
+    rid = [refs.index(contig) for _, _, refs in data]
+    n, P = len(data), len(pv)
+    exp = bm.expected([(d[first:], True, r) for (d, first, _), r in zip(data, rid)], beg0, end0, mapq, pv, rg_s, refseq)
+    assert exp["rc"] == 0
+    dev = lambda x: torch.from_numpy(x).cuda()
+    ctx = Context(0)
+    head = (dev(np.frombuffer(bam, dtype=np.uint8).copy()), dev(np.array(off, dtype=np.int64)), dev(np.array(end, dtype=np.int64)),
+            torch.ones(n, dtype=torch.uint8, device="cuda"), dev(np.array(rid, dtype=np.int32)), beg0, end0, mapq)
+    d_pos = dev(np.array(pv, dtype=np.int32))
+    lines = Lines()
+    lines.append(f"# bvc_bam_counts alone: tools/bam_counts_bench.py, best of {a.repeats + 2} device-pointer calls, wall clock around a synchronised context")
+    lines.append(f"{n} samples, {len(bam)} inflated bytes, {P} positions, -q {mapq}")
+    # the two calls it stands between
+    d_ref = dev(np.frombuffer(refseq.encode(), dtype=np.uint8).copy())
+    rc, rec, rs, st, need = ctx.bam_pileup(*head, d_pos, rg_s, d_ref)
+    assert rc == 0
+    t_pileup = best_of(ctx, a.repeats, lambda: ctx.bam_pileup(*head, d_pos, rg_s, d_ref, records=rec, rec_start=rs, sample_status=st))
+    lines.append(f"  bvc_bam_pileup     {t_pileup * 1e3:8.2f} ms a call ({need} bytes of records)")
+    ra = pm.refalt(pv, rg_s, refseq)
+    m_args = head + (d_pos, dev(np.array([ord(r) for _, r, _ in ra], dtype=np.uint8)), dev(np.array([ord(x) for _, _, x in ra], dtype=np.uint8)), rg_s, len(refseq))
+    rc, mat, st2 = ctx.bam_popmatrix(*m_args)
+    assert rc == 0
+    t_matrix = best_of(ctx, a.repeats, lambda: ctx.bam_popmatrix(*m_args, matrix=mat, sample_status=st2))
+    lines.append(f"  bvc_bam_popmatrix  {t_matrix * 1e3:8.2f} ms a call")
+    for n_groups in (0, 5):
+        labels = (np.arange(n) % 7).astype(np.uint8) if n_groups else None
+        want_c, want_t = cm.fold(exp["maps"], pv, labels, n_groups)
+        adds = int(want_c.sum()) + int(want_t["strand_base"].sum()) + int(want_t["n_other"].sum()) + int(want_t["n_indel"].sum())
+        d_counts = torch.zeros(P * cm.slots_of(n_groups) * 512, dtype=torch.int32, device="cuda")
+        d_tally = torch.zeros(P * 12, dtype=torch.int32, device="cuda")
+        kw = dict(group_of_sample=dev(labels) if n_groups else None, n_groups=n_groups, sample_status=st2)
+        assert ctx.bam_counts(*head, d_pos, rg_s, len(refseq), d_counts, d_tally, **kw)[0] == 0
+        ctx.synchronize()
+        assert (d_counts.cpu().numpy().view(np.uint32) == want_c.reshape(-1)).all() and d_tally.cpu().numpy().tobytes() == want_t.tobytes()
+        t = best_of(ctx, a.repeats, lambda: ctx.bam_counts(*head, d_pos, rg_s, len(refseq), d_counts, d_tally, **kw))
+        lines.append(f"  bvc_bam_counts, n_groups {n_groups}: {t * 1e3:8.2f} ms a call, {adds} atomic adds into {d_counts.numel() * 4 + d_tally.numel() * 4} bytes "
+                     f"of accumulators ({adds / t / 1e6:.1f} M adds/s over the whole call)")
+    ctx.close()
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write(text)
+
+
+if __name__ == "__main__":
+    main()
