@@ -379,8 +379,11 @@ static void bt_r_device(const std::vector<std::string> &bams, const std::vector<
 // batch's records stay on device 0 as batch `ib` of the process's one store, and nothing is written.  The batch's sample names are kept
 // here for the VCF header.
 // With BVC_HOST_STORE_WINDOWS=K the region's positions are cut into K windows (store_windows, pileup.h) and a MemBatches is ONE window's
-// store: positions pv[a .. b) piled up from the fetch range [beg0, end0) (store_window_ranges), filled, computed from and dropped before
-// the next one's (beside it with BVC_HOST_STORE_OVERLAP).  What outlives a window -- the sample names, which window 0 keeps, and the
+// store: positions pv[a .. b) piled up from the blocks gathered for [beg0, end0) (store_window_ranges), filled, computed from and dropped
+// before the next one's (beside it with BVC_HOST_STORE_OVERLAP).  The reads of those blocks are filtered by the REGION's start, not the
+// window's (keep_from): a read that ended in front of the window's cut stays in the list, because the rule steps from a first covering read
+// whose position is deleted or skipped to the NEXT read of the list, covering or not -- without it the step would land on another read
+// than the whole-region fetch's.  What outlives a window -- the sample names, which window 0 keeps, and the
 // samples that had reads in some window -- is the run's (MemRun).
 struct MemRun {
     std::vector<std::vector<std::string>> names;    // per batch, filled by the thread that extracts it (window 0)
@@ -395,7 +398,8 @@ struct MemRun {
 struct MemBatches {
     bvc_store *store = nullptr;                     // (none for a window without positions)
     size_t a = 0, b = 0;                            // the window's positions: pv[a .. b); the store's position 0 is pv[a]
-    int32_t beg0 = 0, end0 = 0;                     // its fetch range
+    int32_t beg0 = 0, end0 = 0;                     // the range its blocks are gathered for
+    int32_t keep_from = 0;                          // the region's padded start: reads that end behind it are kept, as the whole-region fetch keeps them
     std::atomic<int> kept{0};                       // batches put so far
     double load_s = 0;
     MemRun *run = nullptr;
@@ -420,8 +424,8 @@ static void bt_r_mem(const std::vector<std::string> &bams, const std::vector<int
         int64_t bytes = 0;
         // (rg_s and refseq stay the region's: deletion text is cut from them)
         const int rc = bvc_bam_pileup_bgzf_store(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(),
-                                                 batch.out_bytes, batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq,
-                                                 (int32_t)(mem.b - mem.a), pv.data() + mem.a, rg_s, refseq.data(), (int64_t)refseq.size(), mem.store, ib,
+                                                 batch.out_bytes, batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), mem.keep_from, end0,
+                                                 opt::mapq, (int32_t)(mem.b - mem.a), pv.data() + mem.a, rg_s, refseq.data(), (int64_t)refseq.size(), mem.store, ib,
                                                  &bytes, status.data());
         if (rc == BVC_ERR_ALLOC && run.propose_windows) {
             // the windows that would fit, going by the share of the batches that did: K x (batches in all / batches kept), rounded up
@@ -732,7 +736,7 @@ static void basetype_in_memory(const std::vector<std::string> &bams, const std::
     for (int w = 0; w < K; ++w) {
         wins.emplace_back();
         MemBatches &m = wins.back();
-        m.a = wa[(size_t)w]; m.b = wb[(size_t)w]; m.beg0 = wbeg[(size_t)w]; m.end0 = wend[(size_t)w]; m.run = &run;
+        m.a = wa[(size_t)w]; m.b = wb[(size_t)w]; m.beg0 = wbeg[(size_t)w]; m.end0 = wend[(size_t)w]; m.keep_from = wbeg[0]; m.run = &run;
     }
     auto failed = [&]() { std::lock_guard<std::mutex> g(mu); return !werr.empty(); };
     // a window's load: its store made, every batch piled up into it, the store sealed.  An error is kept as the compute threads' are
@@ -864,7 +868,7 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
         cp.hi[(size_t)i] = cp.pvS.size();
     }
     MemBatches m;
-    m.run = &run; m.a = 0; m.b = cp.pvS.size(); m.beg0 = std::max(0, rg_s - 1 - 1000); m.end0 = rg_e + 1000;
+    m.run = &run; m.a = 0; m.b = cp.pvS.size(); m.beg0 = m.keep_from = std::max(0, rg_s - 1 - 1000); m.end0 = rg_e + 1000;
     int64_t store_bytes = 0;
     if (!cp.pvS.empty()) {
         run.quiet = true;

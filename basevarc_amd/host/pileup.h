@@ -262,11 +262,14 @@ void thread_window(size_t psize, int thread, int ithread, size_t &lo, size_t &hi
 // w * thread + thread - 1 of n taken together: [a[w], b[w]).  Contiguous, ascending, disjoint, covering [0, psize); empty windows come
 // last only.  Compute thread i of window w then works as thread w * thread + i of n, so the outputs are those of a -t n run.
 void store_windows(size_t psize, int thread, int windows, size_t *a, size_t *b);
-// The windows' fetch ranges [wbeg[w], wend[w]) (0-based, as BamFile::fetch takes them): they tile the region's [beg0, end0).  Window 0
-// begins at beg0, the last window that has positions ends at end0, and the cut between a window and the next one that has positions is
-// the coordinate just behind the earlier window's last position (pv holds 1-based positions, so that coordinate is pv[b[w] - 1]): a
-// read that starts there or later covers nothing of the earlier window, and the later window keeps every read that has not ended at or
-// in front of that last position.  A window without positions gets an empty range (nothing is fetched for it).
+// The ranges [wbeg[w], wend[w]) the windows' blocks are gathered for (0-based, as BamFile::fetch takes them): they tile the region's
+// [beg0, end0).  Window 0 begins at beg0, the last window that has positions ends at end0, and the cut between a window and the next one
+// that has positions is the coordinate just behind the earlier window's last position (pv holds 1-based positions, so that coordinate is
+// pv[b[w] - 1]): a read that starts there or later covers nothing of the earlier window.  wbeg[w] says where the index is asked for the
+// window's first block and nothing else: the reads of the gathered blocks are filtered by the REGION's beg0 (main.cpp, MemBatches::
+// keep_from), so the window's list is the whole-region fetch's list from some read at or in front of the first one that covers a
+// position of the window -- the rule never looks in front of that read, and behind it the two lists are the same read for read.  A
+// window without positions gets an empty range (nothing is gathered for it).
 void store_window_ranges(const int32_t *pv, int windows, const size_t *a, const size_t *b, int32_t beg0, int32_t end0, int32_t *wbeg,
                          int32_t *wend);
 // The positions whose per-sample entries a run that piled phase 1 into class counts (bvc_bam_counts.h) must read after all, from the

@@ -41,7 +41,8 @@ int main(int argc, char **argv)
                     thread_window(psize, T * K, w * T + T - 1, lo2, hi2);
                     ok = ok && a[w] == lo && b[w] == hi2 && a[w] <= b[w] && (w == 0 || a[w] == b[w - 1]);
                     ok = ok && wbeg[w] == reach && wend[w] >= wbeg[w];
-                    // a window's positions lie inside its fetch range
+                    // a window's positions lie inside the range its blocks are gathered for (the reads' filter is the region's beg0: the
+                    // ranges say where gathering starts and stops, not which reads are kept)
                     if (a[w] < b[w]) ok = ok && wbeg[w] <= pv[a[w]] - 1 && pv[b[w] - 1] - 1 < wend[w];
                     reach = wend[w];
                 }

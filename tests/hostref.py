@@ -10,16 +10,43 @@ from tests.golden import make_testdata_pileup as tp
 HERE = os.path.dirname(os.path.abspath(__file__))
 DATA = os.path.join(HERE, "golden", "testdata")
 REGION = "chr17:41197700-41276155"
+BUF = 1000                                  # the reference is fetched this far behind the region, and the reads this far around it
 
 
-def region_fixture():
+class Cohort:
+    """What a run reads, for cohorts other than the 100 test BAMs (tests/cohort_cases.py writes them): the directory, the BAM paths in list
+    order, the region as the command line takes it, the contig table [(name, length)] and the contigs' sequences {name: text}."""
+
+    def __init__(self, directory, bams, region, contigs, sequences):
+        self.dir, self.bams, self.region, self.contigs, self.sequences = str(directory), list(bams), region, list(contigs), dict(sequences)
+
+    def split_region(self):
+        """(contig, start, end) as splitrg reads the text, before its end - 1"""
+        chrom, rest = self.region.split(":")
+        s, e = rest.split("-")
+        return chrom, int(s), int(e)
+
+    def fetched(self):
+        """the string fetch_reference gives for [start, end - 1 + BUF], clamped to the contig"""
+        chrom, s, e = self.split_region()
+        return self.sequences[chrom][s - 1:e - 1 + BUF]
+
+
+def region_fixture(cohort=None):
+    if cohort is not None:
+        chrom, s, _ = cohort.split_region()
+        return chrom, s, dict(cohort.contigs)[chrom], cohort.fetched()
     head, seq = open(os.path.join(DATA, "chr17_41197700_region.txt")).read().split("\n")[:2]
     contig, start, length = head.split()
     return contig, int(start), int(length), seq
 
 
-def write_fasta(path):
-    """A full-length single-contig FASTA (N outside the fixture region) + .fai, so that chr17 coordinates work."""
+def write_fasta(path, cohort=None):
+    """A full-length single-contig FASTA (N outside the fixture region) + .fai, so that chr17 coordinates work.  A cohort's: every
+    contig on one line."""
+    if cohort is not None:
+        from tests import bam_files
+        return bam_files.write_reference(path, [(n, cohort.sequences[n]) for n, _ in cohort.contigs])
     contig, start, length, seq = region_fixture()
     with open(path, "w") as f:
         f.write(f">{contig}\n")
@@ -32,8 +59,11 @@ def write_fasta(path):
     return path
 
 
-def write_bam_list(path):
+def write_bam_list(path, cohort=None):
     with open(path, "w") as f:
+        if cohort is not None:
+            f.write("".join(b + "\n" for b in cohort.bams))
+            return path
         for l in open(os.path.join(DATA, "bam.list")):
             if l.strip():
                 f.write(os.path.join(DATA, l.strip().replace("data/", "", 1)) + "\n")
@@ -48,15 +78,20 @@ def thread_window(psize, thread, ithread):
 
 
 class Pipeline:
-    def __init__(self, mapq=20, batch=10, thread=1, maf=0.001):
-        self.batch, self.thread = batch, thread
-        contig, start, _, refseq = region_fixture()
+    def __init__(self, mapq=20, batch=10, thread=1, maf=0.001, cohort=None):
+        self.batch, self.thread, self.cohort = batch, thread, cohort
+        contig, start, _, refseq = region_fixture(cohort)
         self.chr, self.refseq = contig, refseq
-        chrom, s, e = tp.REGION
+        chrom, s, e = tp.REGION if cohort is None else cohort.split_region()
         self.rg_s, self.rg_e = s, e - 1
-        self.pv = [self.rg_s + i for i in range(len(refseq) - 1000) if refseq[i] in "ACGT"]
-        lst = os.path.join(DATA, "bam.list")
-        names, rvs, _ = tp.load_samples(DATA, self._list_for_loader(lst), mapq=mapq)
+        self.pv = [self.rg_s + i for i in range(len(refseq) - BUF) if refseq[i] in "ACGT"]
+        if cohort is None:
+            lst = os.path.join(DATA, "bam.list")
+            names, rvs, _ = tp.load_samples(DATA, self._list_for_loader(lst), mapq=mapq)
+        else:
+            lst = write_bam_list(os.path.join(cohort.dir, "pipeline.list"), cohort)
+            names, rvs, _ = tp.load_samples(cohort.dir, lst, region=(chrom, s, e), mapq=mapq)
+        self.empty = [n for n, rv in zip(names, rvs) if not rv]     # the samples bt_r reports as empty, in list order
         self.names = names
         self.maps = [tp.find_snp_at_pos(rv, self.pv, refseq, self.rg_s) for rv in rvs]
         self.n = len(names)
@@ -99,7 +134,6 @@ class Pipeline:
         files = self.batch_files()
         nb = 1 + (self.n - 1) // self.batch
         vcf, cvg = [], []
-        contig, _, length, _ = region_fixture()
         for t in range(self.thread):
             P = eo.Parser()
             per_batch = [files[(t, ib)].split("\n")[1:] for ib in range(nb)]
@@ -133,14 +167,62 @@ class Pipeline:
         return "".join(vcf), "".join(cvg)
 
 
-def headers(reference_path, names, group_names=()):
-    contig, _, length, _ = region_fixture()
+def headers(reference_path, names, group_names=(), cohort=None):
+    contig, _, length, _ = region_fixture(cohort)
+    contigs = [(contig, length)] if cohort is None else cohort.contigs
     # CVG_HEADER / VCF_HEADER, src/BaseVarC.cpp:65-88; assembled as bt_s does (:364-382)
     from tests.hostref_headers import CVG_HEADER, VCF_HEADER
     vh = VCF_HEADER
     for g in group_names:
         vh += (f"##INFO=<ID={g}_AF,Number=A,Type=Float,Description=\"Allele frequency in the {g} populations "
                "calculated based on LRT.[0,1]\">\n")
-    vh += f"##contig=<ID={contig},length={length}>\n" + f"##reference=file://{reference_path}\n"
+    vh += "".join(f"##contig=<ID={c},length={l}>\n" for c, l in contigs) + f"##reference=file://{reference_path}\n"
     vh += "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\tFORMAT\t" + "\t".join(names) + "\n"
     return vh, CVG_HEADER + "".join("\t" + g for g in group_names) + "\n"
+
+
+# ---- comparing a VCF with the pipeline's ---------------------------------------------------------------------------------------------
+# The bars per key.  QUAL is printed {:.2f}: one unit of the last place and a tenth.  The keys printed {:.3f} likewise.  The allele
+# frequencies are printed {:.6f} and computed by the device's EM: AF_ATOL of tests/test_gpu_lrt_sites.py (1e-6) plus one unit of the last
+# printed place.  Everything else -- counts, depths, the sample columns -- is text and must be equal.
+QUAL_BAR = 0.011
+FIXED3_KEYS = ("QD", "MQRankSum", "ReadPosRankSum", "BaseQRankSum", "FS", "SOR")
+FIXED3_BAR = 1.1e-3
+AF_BAR = 2e-6
+
+
+def info_bar(key):
+    if key in ("CM_AF", "CM_CAF") or key.endswith("_AF"):
+        return AF_BAR
+    return FIXED3_BAR if key in FIXED3_KEYS else 0.0
+
+
+def compare_vcf(got, want, say=True):
+    """Line for line: equal text, apart from float fields within the bars above.  Returns {key: the worst difference seen} (and prints it,
+    so that a run kept with its output shows how near the bars the fields came)."""
+    worst = {}
+
+    def near(key, x, y, bar):
+        if x == y:
+            return
+        d = abs(float(x) - float(y))
+        worst[key] = max(worst.get(key, 0.0), d)
+        assert d <= bar, (key, x, y, bar)             # (a nan on one side only is no number <= bar: it fails here)
+    gl, wl = got.split("\n"), want.split("\n")
+    assert len(gl) == len(wl), (len(gl), len(wl))
+    for g, w in zip(gl, wl):
+        if g == w:
+            continue
+        gf, wf = g.split("\t"), w.split("\t")
+        assert len(gf) == len(wf) > 8 and gf[:5] == wf[:5] and gf[6] == wf[6] and gf[8:] == wf[8:], (g[:300], w[:300])
+        near("QUAL", gf[5], wf[5], QUAL_BAR)
+        ga, wa = gf[7].split(";"), wf[7].split(";")
+        assert len(ga) == len(wa), (gf[7], wf[7])
+        for a, c in zip(ga, wa):
+            (ka, va), (kc, vc) = a.split("="), c.split("=")
+            assert ka == kc and va.count(",") == vc.count(","), (a, c)
+            for x, y in zip(va.split(","), vc.split(",")):
+                near(ka, x, y, info_bar(ka))
+    if say and worst:
+        print("vcf worst differences: " + " ".join(f"{k}={v:.3g}" for k, v in sorted(worst.items())))
+    return worst

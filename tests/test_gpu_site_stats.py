@@ -148,6 +148,39 @@ def test_every_field_equals_the_integer_model(ctx, cases, parity, pointers):
     assert stats["valid"][called].all() and (stats["n_ref"][called] > 0).any() and (stats["n_alt"][called] > 0).any()
 
 
+STATS_COPIES_DEFAULT = 2                            # tuning key "stats_copies_log2" (include/bvc.h): 2^n copies of a workgroup's counters
+
+
+class copies:
+    """The shared context with stats_copies_log2 = n, and the default again afterwards.  3 and 4 take more than 48 KB of LDS a workgroup
+    (site_stats_lds_bytes: 6,416 bytes + 6,144 x 2^n), the branch of launch_site_stats that raises the kernel's limit first."""
+
+    def __init__(self, ctx, n):
+        self.ctx, self.n = ctx, n
+
+    def __enter__(self):
+        self.ctx.set_tuning("stats_copies_log2", self.n)
+
+    def __exit__(self, *exc):
+        self.ctx.set_tuning("stats_copies_log2", STATS_COPIES_DEFAULT)
+
+
+@pytest.mark.parametrize("log2c", [0, 1, 3, 4])
+@pytest.mark.parametrize("parity", [0, 1])
+def test_every_field_equals_the_integer_model_with_other_numbers_of_counter_copies(ctx, cases, parity, log2c):
+    """test_every_field_equals_the_integer_model (host pointers) with 1, 2, 8 and 16 copies of the counters: the records are integers and
+    do not depend on how many copies the votes were spread over."""
+    with copies(ctx, log2c):
+        test_every_field_equals_the_integer_model(ctx, cases, parity, "host")
+
+
+@pytest.mark.parametrize("log2c", [0, 4])
+def test_more_called_sites_than_workgroups_with_one_and_sixteen_counter_copies(ctx, log2c):
+    """The fold leaves every copy zero for the workgroup's next site: with one copy and with sixteen"""
+    with copies(ctx, log2c):
+        test_more_called_sites_than_workgroups(ctx)
+
+
 def device_call(ctx, offsets, entries, refs, results, shift):
     """bvc_site_stats_csr with BVC_PTR_DEVICE on torch memory (the binding's site_stats_csr_device takes typed tensors: int64 offsets)."""
     import torch

@@ -17,7 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # key: (lowest value, highest value) of include/bvc.h; "em_wpb" takes its two ends only
 KNOBS = {"em_waves_per_cu": (0, 32), "em_wpb": (1, 4), "hist_split": (0, 64), "group_pipe": (0, 1), "group_copies_log2": (-1, 5),
          "group_big_lds": (0, 1), "group_h16": (0, 1), "em_streams": (0, 3), "em_engine": (0, 1), "em_tiny_regions": (0, 1),
-         "em_prune": (0, 1), "host_chunk_kib": (1, 1 << 21)}
+         "em_prune": (0, 1), "bgzf_codes": (0, 1), "bgzf_parse": (0, 1), "bgzf_cuts": (0, 1), "csr_scatter_max": (0, 1 << 30),
+         "stats_copies_log2": (0, 4), "host_chunk_kib": (1, 1 << 21)}
 
 CHILD = """
 import sys

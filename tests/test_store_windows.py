@@ -1,8 +1,10 @@
 """Position windows of `--tmp-format mem` (BVC_HOST_STORE_WINDOWS), the parts that need no device: the window arithmetic the host program
 uses (bvchost_store_windows, bvchost_store_window_ranges) against a plain restatement of thread_window; the knob's refusals, which end the
 program before it touches a device; and, with the model of bvc_bam_pileup (tests/bam_pileup_model.py) on the 100 test BAMs, the two facts
-the windows rest on: a window's records are the whole-region call's records for its positions but for the mapq an indel entry inherits,
-and a sample is empty in the region exactly when it is empty in every window."""
+the windows rest on: a window's records -- piled up from the records behind the index's offset for the window's start, filtered by the
+REGION's start -- are the whole-region call's records for its positions but for the mapq an indel entry inherits, and a sample is empty
+in the region exactly when it is empty in every window.  (tests/test_cohort_cases.py has the reads that tell the region's start from the
+window's as the filter; the 100 test BAMs hold none.)"""
 import ctypes as C
 import glob
 import os
@@ -36,6 +38,23 @@ def thread_window(psize, thread, ithread):
     lo = min(psize, ithread * window)
     hi = psize if ithread == thread - 1 else min(psize, (ithread + 1) * window)
     return lo, hi
+
+
+def store_windows(psize, T, K):
+    """host/pileup.cpp's store_windows, restated: window w is the ranges of threads wT .. wT+T-1 of a run with T*K threads"""
+    ranges = [thread_window(psize, T * K, j) for j in range(T * K)]
+    return [ranges[w * T][0] for w in range(K)], [ranges[w * T + T - 1][1] for w in range(K)]
+
+
+def store_window_ranges(pv, a, b, beg0, end0):
+    """host/pileup.cpp's store_window_ranges, restated: the windows' gather ranges [wbeg, wend), 0-based, tiling [beg0, end0)"""
+    wbeg, wend, at = [], [], beg0
+    for w in range(len(a)):
+        last = w + 1 == len(a) or a[w + 1] == b[w + 1]
+        wbeg.append(at)
+        at = at if a[w] == b[w] and w > 0 else end0 if last else min(end0, max(at, pv[b[w] - 1]))
+        wend.append(at)
+    return wbeg, wend
 
 
 def windows_of(H, psize, T, K):
@@ -117,6 +136,25 @@ def region():
     return call, samples, status, {p: {batch: records_of(e, batch) for batch in BATCHES} for p, e in whole.items()}
 
 
+@pytest.fixture(scope="module")
+def gathered():
+    """What bam_region_blocks starts a window's gathering from, per test BAM: (inflated bytes, the region's reference, its linear index
+    from the .bam.bai, {virtual offset: offset in the inflated bytes} of the records)."""
+    from tests import bam_files as bf
+    from tests import hostref
+    out = []
+    for (d, _, refs), line in zip(bam_data_bytes(), (l for l in open(os.path.join(hostref.DATA, "bam.list")) if l.strip())):
+        path = os.path.join(hostref.DATA, line.strip().replace("data/", "", 1))
+        rid = refs.index(bam_data_call()[0])
+        out.append((d, rid, bf.read_bai_linear(path + ".bai")[rid], {r[4]: r[6] for r in bf.walk_bam(path)[1]}))
+    return out
+
+
+def window_samples(gathered, wbeg):
+    """The samples' bytes from the record the index names for the 16 kbp window of wbeg (clamped to its last window, as bai_linear_offset)"""
+    return [(d[at[lin[min(wbeg >> 14, len(lin) - 1)]]:], rid) for d, rid, lin, at in gathered]
+
+
 def per_sample(samples, beg0, end0, mapq, positions, rg_s, refseq):
     """bam_pileup_model.expected's first half, sample by sample (the batches below share it)"""
     status, maps = [], []
@@ -156,11 +194,12 @@ def records_of(entries, batch):
 
 
 @pytest.mark.parametrize("T, K", [(1, 2), (2, 3), (4, 7)])
-def test_a_windows_records_are_the_regions_but_for_the_mapq_an_indel_entry_inherits(host, region, T, K):
+def test_a_windows_records_are_the_regions_but_for_the_mapq_an_indel_entry_inherits(host, region, gathered, T, K):
     _, H = host
     (contig, beg0, end0, mapq, pv, rg_s, refseq), samples, status, whole = region
     a, b = windows_of(H, len(pv), T, K)
     wbeg, wend = fetch_ranges_of(H, pv, a, b, beg0, end0)
+    assert (a, b) == store_windows(len(pv), T, K) and (wbeg, wend) == store_window_ranges(pv, a, b, beg0, end0)
     # the fetch ranges tile the region's; the cut lies between the last position of a window and the first of the next (0-based
     # coordinates: position p is coordinate p - 1)
     assert wbeg[0] == beg0 and wend[-1] == end0 and all(wend[w] == wbeg[w + 1] for w in range(K - 1))
@@ -169,7 +208,8 @@ def test_a_windows_records_are_the_regions_but_for_the_mapq_an_indel_entry_inher
     empty_everywhere = [True] * len(samples)
     compared = 0
     for w in range(K):
-        st_w, maps_w = per_sample(samples, wbeg[w], wend[w], mapq, pv[a[w]:b[w]], rg_s, refseq)
+        # (gathered from the window's start, filtered by the region's: host/main.cpp, MemBatches::keep_from)
+        st_w, maps_w = per_sample(window_samples(gathered, wbeg[w]), beg0, wend[w], mapq, pv[a[w]:b[w]], rg_s, refseq)
         for s, st in enumerate(st_w):
             empty_everywhere[s] = empty_everywhere[s] and st == 1
         mine = entries_by_position(maps_w)
