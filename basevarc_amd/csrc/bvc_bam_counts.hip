@@ -1,17 +1,21 @@
 // bvc_bam_counts.hip -- bvc_bam_counts, bvc_bam_counts_bgzf_acc and the accumulator bvc_site_acc (include/bvc_bam_counts.h): the inflated BAM
 // records of a batch of samples added into per-position class counts and tallies (bam_counts_kernel.hip).  The call's inputs (BamCall), their
 // checks and the verdicts on the statuses and the blocks are bvc_bam.hip's.  Order of work: index -> dry pass -> scan -> first wait ->
-// verdict -> add pass (-> second wait in the host forms): nothing is added unless the call returns BVC_OK.
+// verdict -> add pass (-> second wait in the host forms): nothing is added unless the call returns BVC_OK.  The ninth header's calls
+// (include/bvc_bam_group_depth.h: bvc_bam_counts_depth, the accumulator's second kind) live here too: they are the same calls with one slot
+// of counts, the groups' depths beside it and bam_group_depth_kernel.hip as their add pass.
 #include "bvc_ctx.h"
-#include "../../include/bvc_bam_counts.h"
+#include "../../include/bvc_bam_group_depth.h"
 
 // An accumulator is no part of a context: its device memory is its own, and its bookkeeping is fixed when it is made (the adds are atomic).
 struct bvc_site_acc {
     int device = -1;
     int32_t n_positions = 0, n_groups = 0;
     int64_t budget = 0, used = 0;
+    int32_t depth_groups = 0;                        // the second kind (bvc_site_acc_create_depth): n_groups stays 0, one slot
     uint32_t *d_counts = nullptr;                    // [n_positions][slots][512]
     bvc_bam_site_tally *d_tally = nullptr;           // [n_positions]
+    uint32_t *d_depth = nullptr;                     // [n_positions][depth_groups][4], the second kind only
     size_t slots() const { return n_groups > 0 ? (size_t)n_groups + 1 : 1; }
     size_t row_words() const { return slots() * BVC_NCLASS; }
 };
@@ -60,12 +64,24 @@ int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_devic
     return status_verdict(ctx, head);
 }
 
-// The add pass, enqueued on the context's stream.
+// The add pass, enqueued on the context's stream.  d_depth: the depth form's array (one slot of counts, n_groups depth rows), else null.
 int bam_counts_add(bvc_ctx *ctx, const BamCall &c, const uint8_t *d_group, int32_t n_groups, const BamPileupScratch &S, uint32_t *d_counts,
-                   bvc_bam_site_tally *d_tally, uint32_t *d_status)
+                   bvc_bam_site_tally *d_tally, uint32_t *d_depth, uint32_t *d_status)
 {
-    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
-                                     d_group, n_groups, S, d_counts, d_tally, d_status));
+    if (d_depth)
+        BVC_HIP_D(ctx, launch_bam_counts_depth(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
+                                               d_group, n_groups, S, d_counts, d_tally, d_depth));
+    else
+        BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
+                                         d_group, n_groups, S, d_counts, d_tally, d_status));
+    return BVC_OK;
+}
+
+// The depth forms' own check of the labels: there is no form without groups
+int check_depth_groups(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of_sample, int32_t n_groups)
+{
+    if (n_groups < 1 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 1..32");
+    if (n_samples > 0 && !group_of_sample) return fail(ctx, BVC_ERR_ARG, "null group_of_sample with samples present");
     return BVC_OK;
 }
 
@@ -85,21 +101,21 @@ int check_counts_call(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_b
     return BVC_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
-                   const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
-                   const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
-                   uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *sample_status, uint32_t flags)
+// bvc_bam_counts (depth = false: counts [P][slots][512], group_depth unused) and bvc_bam_counts_depth (depth = true: counts [P][512] and
+// group_depth [P][n_groups][4]) are one call.
+int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                    const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                    const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups, bool depth,
+                    uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
 {
     if (!ctx) return BVC_ERR_ARG;
     BamCall c;
     int rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                               refseq_len, group_of_sample, n_groups, sample_status);
+                               refseq_len, group_of_sample, depth ? 0 : n_groups, sample_status);
     if (rc != BVC_OK) return rc;
-    if ((bam_bytes > 0 && !bam) || (n_samples > 0 && n_positions > 0 && (!counts || !tally))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (depth && (rc = check_depth_groups(ctx, n_samples, group_of_sample, n_groups)) != BVC_OK) return rc;
+    if ((bam_bytes > 0 && !bam) || (n_samples > 0 && n_positions > 0 && (!counts || !tally || (depth && !group_depth))))
+        return fail(ctx, BVC_ERR_ARG, "null data pointer");
     c.bam = bam;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ns = (size_t)n_samples, np = (size_t)n_positions;
@@ -109,18 +125,19 @@ int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t 
     if (flags & BVC_PTR_DEVICE) {
         if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
         rc = bam_counts_verdict(ctx, io, c, true, sample_status, sample_status, nullptr, S);
-        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, sample_status);
+        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, depth ? group_depth : nullptr, sample_status);
     }
     if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
     if ((rc = io.reserve(ns * 22 + np * 4 + 1024, 64 + ns * 4 + 1024)) != BVC_OK) return rc;
-    // host pointers: the inputs and the two accumulators live in the staging buffer for the length of the call
-    const size_t cwords = ns ? np * (n_groups > 0 ? (size_t)n_groups + 1 : 1) * BVC_NCLASS : 0, trows = ns ? np : 0;
-    uint8_t *u_bam, *u_eof, *u_grp; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos; uint32_t *d_status, *d_counts; bvc_bam_site_tally *d_tally;
+    // host pointers: the inputs and the accumulators live in the staging buffer for the length of the call
+    const size_t cwords = ns ? np * (n_groups > 0 && !depth ? (size_t)n_groups + 1 : 1) * BVC_NCLASS : 0, trows = ns ? np : 0;
+    const size_t dwords = depth && ns ? np * (size_t)n_groups * 4 : 0;
+    uint8_t *u_bam, *u_eof, *u_grp; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos; uint32_t *d_status, *d_counts, *d_depth; bvc_bam_site_tally *d_tally;
     rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
         u_bam = L.take<uint8_t>((size_t)bam_bytes);
         u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns); u_grp = L.take<uint8_t>(ns);
         u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
-        d_counts = L.take<uint32_t>(cwords); d_tally = L.take<bvc_bam_site_tally>(trows);
+        d_counts = L.take<uint32_t>(cwords); d_tally = L.take<bvc_bam_site_tally>(trows); d_depth = L.take<uint32_t>(dwords);
     });
     if (rc != BVC_OK) return rc;
     if (bam_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, bam, (size_t)bam_bytes, hipMemcpyHostToDevice, ctx->stream));
@@ -136,27 +153,31 @@ int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t 
     // the accumulators go up only now: a call that fails has not touched them
     BVC_HIP_D(ctx, hipMemcpyAsync(d_counts, counts, cwords * 4, hipMemcpyHostToDevice, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(d_tally, tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, d_status)) != BVC_OK) return rc;
+    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(d_depth, group_depth, dwords * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, depth ? d_depth : nullptr, d_status)) != BVC_OK) return rc;
     BVC_HIP_D(ctx, hipMemcpyAsync(counts, d_counts, cwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(tally, d_tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
+    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(group_depth, d_depth, dwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }
 
-int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
+// Both kinds of accumulator are made here: depth_groups > 0 is the second kind (n_groups is then 0)
+int site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t depth_groups, int64_t byte_budget)
 {
-    if (!out) return BVC_ERR_ARG;
-    *out = nullptr;
-    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BVC_ERR_DEVICE; }
     bvc_site_acc *acc = new bvc_site_acc;
-    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->budget = byte_budget > 0 ? byte_budget : 0;
+    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->depth_groups = depth_groups;
+    acc->budget = byte_budget > 0 ? byte_budget : 0;
     const size_t cbytes = (size_t)n_positions * acc->row_words() * 4, tbytes = (size_t)n_positions * sizeof(bvc_bam_site_tally);
-    acc->used = (int64_t)(cbytes + tbytes);
+    const size_t dbytes = (size_t)n_positions * (size_t)depth_groups * 16;
+    acc->used = (int64_t)(cbytes + tbytes + dbytes);
     if (acc->budget > 0 && acc->used > acc->budget) { delete acc; return BVC_ERR_ALLOC; }
     if (n_positions > 0 &&
         (hipMalloc(reinterpret_cast<void **>(&acc->d_counts), cbytes) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&acc->d_tally), tbytes) != hipSuccess ||
-         hipMemset(acc->d_counts, 0, cbytes) != hipSuccess || hipMemset(acc->d_tally, 0, tbytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess)) {
+         (dbytes && hipMalloc(reinterpret_cast<void **>(&acc->d_depth), dbytes) != hipSuccess) ||
+         hipMemset(acc->d_counts, 0, cbytes) != hipSuccess || hipMemset(acc->d_tally, 0, tbytes) != hipSuccess ||
+         (dbytes && hipMemset(acc->d_depth, 0, dbytes) != hipSuccess) || hipDeviceSynchronize() != hipSuccess)) {
         (void)hipGetLastError();
         bvc_site_acc_destroy(acc);
         return BVC_ERR_ALLOC;
@@ -165,12 +186,51 @@ int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int
     return BVC_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                   const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                   const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
+                   uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *sample_status, uint32_t flags)
+{
+    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
+                           refseq_len, group_of_sample, n_groups, false, counts, tally, nullptr, sample_status, flags);
+}
+
+int bvc_bam_counts_depth(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                         const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                         const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
+                         uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
+{
+    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
+                           refseq_len, group_of_sample, n_groups, true, counts, tally, group_depth, sample_status, flags);
+}
+
+int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
+{
+    if (!out) return BVC_ERR_ARG;
+    *out = nullptr;
+    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
+    return site_acc_create(out, device, n_positions, n_groups, 0, byte_budget);
+}
+
+int bvc_site_acc_create_depth(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
+{
+    if (!out) return BVC_ERR_ARG;
+    *out = nullptr;
+    if (n_positions < 0 || n_groups < 1 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
+    return site_acc_create(out, device, n_positions, 0, n_groups, byte_budget);
+}
+
 void bvc_site_acc_destroy(bvc_site_acc *acc)
 {
     if (!acc) return;
     (void)hipSetDevice(acc->device);
     if (acc->d_counts) (void)hipFree(acc->d_counts);
     if (acc->d_tally) (void)hipFree(acc->d_tally);
+    if (acc->d_depth) (void)hipFree(acc->d_depth);
     delete acc;
 }
 
@@ -195,13 +255,15 @@ int bvc_bam_counts_bgzf_acc(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp
     rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
                            refseq_len, group_of_sample, acc->n_groups, sample_status);
     if (rc != BVC_OK) return rc;
+    const int32_t dg = acc->depth_groups;                               // (> 0: the second kind, whose n_groups is 0)
+    if (dg > 0 && (rc = check_depth_groups(ctx, n_samples, group_of_sample, dg)) != BVC_OK) return rc;
     if (comp_bytes < 0 || n_blocks < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
     if (n_blocks > 0 && (!comp || !blocks)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if ((rc = check_blocks(ctx, blocks, n_blocks, comp_bytes, bam_bytes)) != BVC_OK) return rc;
     if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ns = (size_t)n_samples, np = (size_t)n_positions, nb = (size_t)n_blocks;
-    const bool labels = acc->n_groups > 0 && ns > 0;
+    const bool labels = (acc->n_groups > 0 || dg > 0) && ns > 0;
     PinIO io(ctx);
     if ((rc = io.reserve(ns * 22 + np * 4 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + nb * 4 + 1024)) != BVC_OK) return rc;
     uint8_t *u_comp, *u_bam, *u_eof, *u_grp; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
@@ -229,7 +291,8 @@ int bvc_bam_counts_bgzf_acc(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp
     BamPileupScratch S;
     rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, &block_status, S);
     if (rc != BVC_OK) return rc;
-    if ((rc = bam_counts_add(ctx, c, u_grp, acc->n_groups, S, acc->d_counts, acc->d_tally, d_status)) != BVC_OK) return rc;
+    if ((rc = bam_counts_add(ctx, c, u_grp, dg > 0 ? dg : acc->n_groups, S, acc->d_counts, acc->d_tally, dg > 0 ? acc->d_depth : nullptr, d_status)) != BVC_OK)
+        return rc;
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }
@@ -246,6 +309,22 @@ int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     const size_t rw = acc->row_words();
     if (counts) BVC_HIP_D(ctx, hipMemcpyAsync(counts, acc->d_counts + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(tally, acc->d_tally + t0, (size_t)n * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_get_depth(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n, uint32_t *group_depth)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if (acc->depth_groups <= 0) return fail(ctx, BVC_ERR_ARG, "the accumulator keeps no group depths (bvc_site_acc_create_depth makes one that does)");
+    if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
+    if (n > 0 && !group_depth) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n == 0) return BVC_OK;
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t rw = (size_t)acc->depth_groups * 4;
+    BVC_HIP_D(ctx, hipMemcpyAsync(group_depth, acc->d_depth + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }

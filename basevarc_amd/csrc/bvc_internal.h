@@ -324,6 +324,13 @@ hipError_t launch_bam_counts(hipStream_t stream, bool add, int32_t n_samples, co
                              const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
                              const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
                              ::bvc_bam_site_tally *tally, uint32_t *sample_status);
+// bam_group_depth_kernel.hip: the add pass with ONE slot of counts [position][512] and the groups' depths [position][n_groups][4] beside it
+// (include/bvc_bam_group_depth.h, bvc_bam_counts_depth); n_groups 1..32, a label >= n_groups adds no depth.  Its dry pass is
+// launch_bam_counts(add = false).
+hipError_t launch_bam_counts_depth(hipStream_t stream, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                                   const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
+                                   const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
+                                   ::bvc_bam_site_tally *tally, uint32_t *group_depth);
 
 // store_kernel.hip: temp batches kept on the device (include/bvc_store.h).  A kept batch as the kernels see it: the device addresses of its
 // rec_start row and of its records, and the records' bytes (what every word of the row is clamped with).

@@ -87,6 +87,24 @@ void bvchost_counts_revisit(const void *tally, const uint8_t *called, int64_t ps
 {
     counts_revisit(static_cast<const bvc_bam_site_tally *>(tally), called, (size_t)psize, thread, flags);
 }
+// the labels and columns of --tmp-format counts with --group (counts_group_map): file_text = the group file's bytes, samples = the sample
+// names, one a line.  label [n of those names]; column_file_index [up to cap]; *n_columns = the groups that have a sample.  Returns the
+// number of distinct group names of the file.
+int32_t bvchost_counts_group_map(const char *file_text, const char *samples, uint8_t *label, int32_t *column_file_index, int32_t cap, int32_t *n_columns)
+{
+    std::vector<std::string> ids, groups, sv, names;
+    std::istringstream f(file_text), ss(samples);
+    std::string id, grp;
+    while (f >> id >> grp) { ids.push_back(id); groups.push_back(grp); }
+    while (std::getline(ss, id)) sv.push_back(id);
+    std::vector<uint8_t> lab;
+    std::vector<int32_t> cols;
+    counts_group_map(ids, groups, sv, names, lab, cols);
+    std::copy(lab.begin(), lab.end(), label);
+    for (size_t c = 0; c < cols.size() && (int32_t)c < cap; ++c) column_file_index[c] = cols[c];
+    *n_columns = (int32_t)cols.size();
+    return (int32_t)names.size();
+}
 int32_t bvchost_device_of_thread(int32_t ithread, int32_t devices_present, int32_t gpus_option) { return device_of_thread(ithread, devices_present, gpus_option); }
 int32_t bvchost_merge_subfiles(const char *out_prefix, const char *suffix, int32_t thread)
 {

@@ -150,6 +150,13 @@ struct Knobs {
     // 1, with K > 1 only: window w+1 is loaded while window w is computed, in lock-step (both are joined before the next pair starts); two
     // stores are alive at a time, each with half of BVC_HOST_STORE_GB.  The outputs are those of 0.  Default 0
     const bool store_overlap = num("BVC_HOST_STORE_OVERLAP", 0) != 0;
+    // 1: --tmp-format counts takes --group -- the counts pass keeps the groups' depths per base beside ONE slot of class counts
+    // (bvc_site_acc_create_depth, include/bvc_bam_group_depth.h: 16 bytes a group and position more) for the CVG lines' group columns, and
+    // the "<group>_AF" values come from the second pile-up's store as with mem; more than 32 distinct group names in the file end the run.
+    // The outputs inflate to the bytes of --tmp-format bin --group.  0: counts refuses --group.  Without --group it changes nothing.  Default 0
+    // (run_basetype asks counts_groups_on() where its refusals stand, before this object is made: the refusal opens nothing)
+    static bool counts_groups_on() { return num("BVC_HOST_COUNTS_GROUPS", 0) != 0; }
+    const bool counts_groups = counts_groups_on();
     const bool two_byte_tiles =set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

@@ -77,7 +77,8 @@ static const char *BASETYPE_MESSAGE =
     "                           (2 KB a position whatever the samples' number), the positions are called from those, and only\n"
     "                           the called positions and those with indels are piled up a second time, as mem keeps them\n"
     "                           (BVC_HOST_STORE_GB caps the counts, then those batches; not with --group, --load, --keep_tmp\n"
-    "                           or --gpus above 1)\n";
+    "                           or --gpus above 1; BVC_HOST_COUNTS_GROUPS=1 takes --group: 16 bytes a group and position more,\n"
+    "                           32 distinct group names in the file at the most)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -465,9 +466,18 @@ struct CountsPass {
     std::vector<uint8_t> flags;                     // [pv->size()]: kRevisit* bits; 0 = the CVG line comes from the tally
     std::vector<int32_t> pvS;                       // the revisited positions
     std::vector<size_t> lo, hi;                     // per thread: its window of pv, cut with the set, as indices into pvS
+    // BVC_HOST_COUNTS_GROUPS with --group: the groups' depths of every position, one row a distinct group name of the file (counts_group_map,
+    // pileup.h), and per group that has a sample -- Groups' order -- its row
+    int n_file_groups = 0;                          // 0: no --group
+    std::vector<uint32_t> depth;                    // [pv->size()][n_file_groups][4]
+    std::vector<int32_t> column_file_index;
+};
+// The group file as the counts pass reads it, once, before anything is piled up
+struct GroupFile {
+    std::vector<std::string> ids, groups, names;    // the lines in order; the distinct group names, sorted
 };
 static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
-                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run)
+                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run, const GroupFile *gf)
 {
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
@@ -476,10 +486,17 @@ static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<
     BamBatch batch;
     batch.open(bams, b0, b1, chr);
     std::vector<uint32_t> status(ns);
+    // (the labels of the groups' depths go by the group file alone: the other batches' names are not known yet)
+    std::vector<uint8_t> label;
+    if (gf) {
+        std::vector<std::string> names;
+        std::vector<int32_t> columns;
+        counts_group_map(gf->ids, gf->groups, batch.sms, names, label, columns);
+    }
     device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
         return bvc_bam_counts_bgzf_acc(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
                                        batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(),
-                                       pv.data(), rg_s, (int64_t)refseq.size(), nullptr, acc, status.data());
+                                       pv.data(), rg_s, (int64_t)refseq.size(), gf ? label.data() : nullptr, acc, status.data());
     });
     for (size_t s = 0; s < ns; ++s)
         if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
@@ -566,8 +583,14 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
     // --tmp-format counts: pv is the revisited positions; the CVG lines of the thread's other positions are written from their tallies, in
     // front of each revisited position's lines and at the window's end (a position without an entry the parser keeps gets no line)
     size_t fill_at = 0, fill_hi = 0;
+    // (with groups: one record a group that has a sample, its depth from the counts pass's row of that group)
+    std::vector<bvc_group_result> fill_grp;
     if (cp) {
         thread_window(cp->pv->size(), thread, ithread, fill_at, fill_hi);
+        if (cp->n_file_groups > 0) {
+            if (cp->column_file_index.size() != groups.names.size()) throw std::runtime_error("ERROR: the counts pass's groups are not the group file's");
+            fill_grp.assign(groups.names.size(), bvc_group_result());
+        }
         tr.before_pos = [&, cp](int32_t pos) {
             for (; fill_at < fill_hi && (*cp->pv)[fill_at] < pos; ++fill_at) {
                 if (cp->flags[fill_at]) continue;
@@ -577,7 +600,10 @@ static void bt_s(const std::vector<std::string> &ftmp_v, const std::vector<int32
                 if (cnt[0] + cnt[1] + cnt[2] + cnt[3] == 0) continue;
                 SiteView v;
                 v.pos = (*cp->pv)[fill_at]; v.cnt = cnt; v.fwd = fwd; v.rev = rev;
-                fpc.write(cvg_line(chr, ref_code(refseq[(size_t)(v.pos - rg_s)]), v, nullptr, 0));
+                const uint32_t *row = fill_grp.empty() ? nullptr : cp->depth.data() + fill_at * (size_t)cp->n_file_groups * 4;
+                for (size_t c = 0; c < fill_grp.size(); ++c)
+                    for (int b = 0; b < 4; ++b) fill_grp[c].depth[b] = (int32_t)row[(size_t)cp->column_file_index[c] * 4 + (size_t)b];
+                fpc.write(cvg_line(chr, ref_code(refseq[(size_t)(v.pos - rg_s)]), v, fill_grp.empty() ? nullptr : fill_grp.data(), (int)fill_grp.size()));
             }
         };
     }
@@ -810,13 +836,16 @@ static void basetype_in_memory(const std::vector<std::string> &bams, const std::
 // BAMs are gathered exactly twice whatever the cohort's size and the region's length; the accumulator and the store are never alive together.
 template <class Compute>
 static void basetype_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
-                            int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, const Knobs &knobs, double &t_loaded, Compute compute)
+                            int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, const Knobs &knobs, const GroupFile *gf, double &t_loaded,
+                            Compute compute)
 {
     if (bvc_device_count() <= 0) throw std::runtime_error("ERROR: no gfx950 device (libbvc has no CPU fallback)");
     const int64_t budget = (int64_t)(knobs.store_gb * 1073741824.0);
     const size_t P = pv.size();
-    const int64_t need = (int64_t)P * (int64_t)(BVC_NCLASS * 4 + sizeof(bvc_bam_site_tally));
-    const std::string what = "the class counts of " + std::to_string(P) + " positions take " + std::to_string(need) + " bytes";
+    const size_t G = gf ? gf->names.size() : 0;                         // (depth rows: 16 bytes a group and position)
+    const int64_t need = (int64_t)P * (int64_t)(BVC_NCLASS * 4 + sizeof(bvc_bam_site_tally) + 16 * G);
+    const std::string what = "the class counts" + std::string(G ? " and the groups' depths" : "") + " of " + std::to_string(P) + " positions take " +
+                             std::to_string(need) + " bytes";
     if (budget > 0 && need > budget)
         throw std::runtime_error("ERROR: " + what + " and BVC_HOST_STORE_GB allows " + std::to_string(budget) + "; --tmp-format bin keeps the batches in files");
     MemRun run;
@@ -826,6 +855,8 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     cp.pv = &pv;
     cp.tally.resize(P);
     cp.flags.assign(P, 0);
+    cp.n_file_groups = (int)G;
+    cp.depth.resize(P * G * 4);
     std::vector<uint8_t> called(P, 0);
     double min_af = 100.0 / (double)bams.size();                        // src/BaseVarC.cpp:541-543, as bt_s has it
     if (min_af > 0.001) min_af = 0.001;
@@ -833,9 +864,9 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     int64_t acc_bytes = 0;
     {
         struct Acc { bvc_site_acc *p = nullptr; ~Acc() { bvc_site_acc_destroy(p); } } acc;
-        if (bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget) != BVC_OK)
+        if ((G ? bvc_site_acc_create_depth(&acc.p, 0, (int32_t)P, (int32_t)G, budget) : bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget)) != BVC_OK)
             throw std::runtime_error("ERROR: the device has no room: " + what + "; --tmp-format bin keeps the batches in files");
-        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run); });
+        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run, gf); });
         LoadDevice dev;
         if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
         const size_t chunk = 8192;
@@ -846,9 +877,17 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
             for (size_t k = 0; k < n; ++k) refs[k] = ref_code(refseq[(size_t)(pv[t0 + k] - rg_s)]);
             bvc_check(dev.ctx, bvc_site_acc_lrt(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, refs.data(), min_af, res.data(), nullptr));
             bvc_check(dev.ctx, bvc_site_acc_get(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, nullptr, &cp.tally[t0]));
+            if (G) bvc_check(dev.ctx, bvc_site_acc_get_depth(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, &cp.depth[t0 * G * 4]));
             for (size_t k = 0; k < n; ++k) called[t0 + k] = res[k].called != 0;
         }
         bvc_site_acc_bytes(acc.p, &acc_bytes, nullptr);
+    }
+    if (gf) {
+        // the names are known now: the groups that have a sample (read_groups' set, in its order) and each one's depth row
+        std::vector<std::string> all, names;
+        std::vector<uint8_t> label;
+        for (auto const &of_batch : run.names) all.insert(all.end(), of_batch.begin(), of_batch.end());
+        counts_group_map(gf->ids, gf->groups, all, names, label, cp.column_file_index);
     }
     counts_revisit(cp.tally.data(), called.data(), P, thread, cp.flags.data());
     size_t n_called = 0, n_indel = 0, n_carry = 0;
@@ -892,14 +931,29 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
 static void run_basetype(int argc, char **argv)                          // src/BaseVarC.cpp:176-314
 {
     parse_options(argc, argv, BASETYPE_MESSAGE);
-    const bool counts = opt::tmp_format == "counts";                    // (no temp files either: everything `mem` refuses, and --group)
+    const bool counts = opt::tmp_format == "counts";                    // (no temp files either: everything `mem` refuses, and --group without its knob)
     const bool in_memory = opt::tmp_format == "mem" || counts;
     const std::string fmt = "--tmp-format " + opt::tmp_format;
     if (in_memory && opt::load) throw std::invalid_argument("ERROR: " + fmt + " with --load: nothing would be left to compute from");
     if (in_memory && opt::keep_tmp) throw std::invalid_argument("ERROR: " + fmt + " with --keep_tmp: there are no temp files to keep");
     if (in_memory && opt::gpus > 1) throw std::invalid_argument("ERROR: " + fmt + " with --gpus above 1: the batches stay in the memory of one device");
-    if (counts && !opt::group.empty())
-        throw std::invalid_argument("ERROR: --tmp-format counts with --group: the program calls the groups from kept batches only, use --tmp-format mem");
+    // (BVC_HOST_COUNTS_GROUPS=1 takes --group with counts; read here, where the refusal stands, in front of everything else the run reads)
+    const bool counts_groups = counts && !opt::group.empty() && Knobs::counts_groups_on();
+    if (counts && !opt::group.empty() && !counts_groups)
+        throw std::invalid_argument("ERROR: --tmp-format counts with --group: the program calls the groups from kept batches only, use --tmp-format mem "
+                                    "(or set BVC_HOST_COUNTS_GROUPS=1)");
+    GroupFile group_file;
+    if (counts_groups) {
+        std::ifstream ifg(opt::group);
+        std::string id, grp;
+        while (ifg >> id >> grp) { group_file.ids.push_back(id); group_file.groups.push_back(grp); }
+        std::vector<uint8_t> label;
+        std::vector<int32_t> columns;
+        counts_group_map(group_file.ids, group_file.groups, std::vector<std::string>(), group_file.names, label, columns);
+        if (group_file.names.size() > BVC_MAX_GROUPS)
+            throw std::invalid_argument("ERROR: --tmp-format counts with --group: " + std::to_string(group_file.names.size()) + " group names in " + opt::group +
+                                        ", the counts pass keeps the depths of 32 at the most, use --tmp-format mem");
+    }
     if (in_memory && opt::rerun) {
         std::cerr << "basetype: --rerun has nothing to reuse with " << fmt << ", it is ignored" << std::endl;
         opt::rerun = false;
@@ -972,7 +1026,8 @@ static void run_basetype(int argc, char **argv)                          // src/
     double t_loaded = 0, t_joined = 0;
     if (counts) {
         std::cerr << "begin to extract reads from bam" << std::endl;
-        basetype_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, t_loaded, compute);
+        basetype_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, counts_groups && !group_file.names.empty() ? &group_file : nullptr, t_loaded,
+                        compute);
         t_joined = StageClock::now();
     } else if (in_memory) {
         std::cerr << "begin to extract reads from bam" << std::endl;

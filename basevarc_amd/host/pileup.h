@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "../../include/bvc.h"
-#include "../../include/bvc_bam_counts.h"
+#include "../../include/bvc_bam_group_depth.h"
 
 namespace bvchost {
 
@@ -297,6 +297,35 @@ inline void counts_revisit(const bvc_bam_site_tally *tally, const uint8_t *calle
             if (bases > 0) last_base = t;
         }
     }
+}
+
+// --tmp-format counts with --group (BVC_HOST_COUNTS_GROUPS): the counts pass labels a sample for the groups' depths (bvc_bam_group_depth.h)
+// before the cohort's sample names are all known, which is what Groups' indices go by (read_groups: only groups that HAVE a sample count,
+// name-sorted).  So the pass labels by the group file alone: the file's distinct group names, sorted, are `names`, and a sample's label is
+// the index of its group among them, 255 when the file does not list it (or the index does not fit a label; more than BVC_MAX_GROUPS names
+// are refused before anything is labelled).  The groups that have a sample among `samples` are a subsequence of `names` in the same order:
+// column_file_index[c] is the index in `names` of the c-th of them -- column c of the CVG line reads depth row column_file_index[c].
+// ids[i], groups[i]: the file's lines in order; a sample listed twice keeps its first line (read_groups' insert).
+inline void counts_group_map(const std::vector<std::string> &ids, const std::vector<std::string> &groups, const std::vector<std::string> &samples,
+                             std::vector<std::string> &names, std::vector<uint8_t> &label, std::vector<int32_t> &column_file_index)
+{
+    names = groups;
+    std::sort(names.begin(), names.end());
+    names.erase(std::unique(names.begin(), names.end()), names.end());
+    std::map<std::string, size_t> group_of_id;
+    for (size_t i = 0; i < ids.size() && i < groups.size(); ++i)
+        group_of_id.insert({ids[i], (size_t)(std::lower_bound(names.begin(), names.end(), groups[i]) - names.begin())});
+    label.assign(samples.size(), 255);
+    std::vector<char> present(names.size(), 0);
+    for (size_t s = 0; s < samples.size(); ++s) {
+        auto it = group_of_id.find(samples[s]);
+        if (it == group_of_id.end()) continue;
+        present[it->second] = 1;
+        if (it->second < 255) label[s] = (uint8_t)it->second;
+    }
+    column_file_index.clear();
+    for (size_t g = 0; g < names.size(); ++g)
+        if (present[g]) column_file_index.push_back((int32_t)g);
 }
 
 // Device of a phase-2 thread (additive: the reference has one CPU path): thread i works on device i mod G, G = the devices present,

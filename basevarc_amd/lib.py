@@ -178,6 +178,15 @@ BAM_COUNTS_PROTOTYPES = {
     "bvc_site_acc_lrt": (_int, [_vp, _vp, _i32, _i32, _vp, _dbl, _vp, _vp]),
 }
 BAM_COUNTS_EXPORTS = list(BAM_COUNTS_PROTOTYPES)
+# The ninth header, include/bvc_bam_group_depth.h (tests/test_bam_group_depth_abi.py compares the two), bound by bind() with the others: phase 1
+# added into one slot of class counts with the groups' depths beside it.  bvc_bam_counts_depth takes bvc_bam_counts's arguments up to tally,
+# then group_depth.
+BAM_GROUP_DEPTH_PROTOTYPES = {
+    "bvc_bam_counts_depth": (_int, BAM_COUNTS_PROTOTYPES["bvc_bam_counts"][1][:19] + [_vp, _vp, _u32]),
+    "bvc_site_acc_create_depth": (_int, [C.POINTER(_vp), _int, _i32, _i32, _i64]),
+    "bvc_site_acc_get_depth": (_int, [_vp, _vp, _i32, _i32, _vp]),
+}
+BAM_GROUP_DEPTH_EXPORTS = list(BAM_GROUP_DEPTH_PROTOTYPES)
 STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
@@ -195,10 +204,11 @@ def library_path():
 
 def bind(cdll):
     """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES,
-    BAM_DEFLATE_PROTOTYPES and BAM_COUNTS_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    BAM_DEFLATE_PROTOTYPES, BAM_COUNTS_PROTOTYPES and BAM_GROUP_DEPTH_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
                                       list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items()) +
-                                      list(BAM_DEFLATE_PROTOTYPES.items()) + list(BAM_COUNTS_PROTOTYPES.items())):
+                                      list(BAM_DEFLATE_PROTOTYPES.items()) + list(BAM_COUNTS_PROTOTYPES.items()) +
+                                      list(BAM_GROUP_DEPTH_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -1035,13 +1045,15 @@ class Context:
         return rc, matrix[:n, :P], status[:n]
 
     def bam_counts(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
-                   group_of_sample=None, n_groups=0, sample_status=None):
+                   group_of_sample=None, n_groups=0, sample_status=None, group_depth=None):
         """bvc_bam_counts (include/bvc_bam_counts.h): the inflated BAM records of a batch of samples ADDED into counts ([P, 512], or
         [P, n_groups + 1, 512] with groups; 4-byte integers) and tally (TALLY_DTYPE [P], or 12 words a position), in place.  numpy arrays
         (synchronous) or tensors on this context's device (the adds are enqueued when it returns); the sample arrays and positions as
         bam_pileup takes them, group_of_sample uint8 [n].  Returns (rc, sample_status): rc 0, or BAM_MORE (2) when a sample's status is 2
-        -- nothing is added then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4; nothing is added)."""
+        -- nothing is added then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4; nothing is added).
+        group_depth: bam_counts_depth's third array -- the call is then bvc_bam_counts_depth."""
         device = hasattr(bam, "data_ptr")
+        outs = (counts, tally) if group_depth is None else (counts, tally, group_depth)
         if device:
             import torch
             new = lambda n, dt: torch.zeros(max(1, n), dtype=dt, device=bam.device)
@@ -1052,21 +1064,32 @@ class Context:
             group_of_sample = None if group_of_sample is None else _as(group_of_sample, np.uint8)
             new = lambda n, dt: np.zeros(max(1, n), dtype=dt)
             u32, size = np.uint32, len
-            if not (isinstance(counts, np.ndarray) and counts.flags.c_contiguous and isinstance(tally, np.ndarray) and tally.flags.c_contiguous):
-                raise ValueError("counts and tally must be contiguous arrays (they are added to in place)")
+            if not all(isinstance(a, np.ndarray) and a.flags.c_contiguous for a in outs):
+                raise ValueError("counts and tally" + (" and group_depth" if group_depth is not None else "") +
+                                 " must be contiguous arrays (they are added to in place)")
         n, P = size(rid), size(positions)
         if size(sample_off) != n or size(sample_end) != n or size(sample_eof) != n or (group_of_sample is not None and size(group_of_sample) != n):
             raise ValueError("sample_off, sample_end, sample_eof and group_of_sample must be [n_samples]")
         sample_status = new(n, u32) if sample_status is None else sample_status
         ptr = _dev_ptr if device else _np_ptr
         opt = lambda a: a if a is not None and size(a) else None
-        rc = self._L.bvc_bam_counts(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0),
-                                                           int(end0), int(min_mapq), P, opt(positions), int(rg_s), int(refseq_len),
-                                                           opt(group_of_sample), int(n_groups), counts, tally, sample_status if n else None), ptr),
-                                    BVC_PTR_DEVICE if device else BVC_PTR_HOST)
+        fn = self._L.bvc_bam_counts if group_depth is None else self._L.bvc_bam_counts_depth
+        rc = fn(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0), int(end0), int(min_mapq), P,
+                                        opt(positions), int(rg_s), int(refseq_len), opt(group_of_sample), int(n_groups), *outs, sample_status if n else None), ptr),
+                BVC_PTR_DEVICE if device else BVC_PTR_HOST)
         if rc not in (0, BAM_MORE):
             self._check(rc)
         return rc, sample_status
+
+    def bam_counts_depth(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
+                         group_depth, group_of_sample, n_groups, sample_status=None):
+        """bvc_bam_counts_depth (include/bvc_bam_group_depth.h): bam_counts into ONE slot of counts ([P, 512]) and tally, and the covered
+        observations of each group per base ADDED into group_depth ([P, n_groups, 4]; 4-byte integers), in place.  n_groups 1..32; a label
+        >= n_groups adds no depth.  Arrays, return value and errors as bam_counts."""
+        if group_depth is None:
+            raise ValueError("group_depth must be an array (bam_counts is the call without one)")
+        return self.bam_counts(bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
+                               group_of_sample, n_groups, sample_status, group_depth)
 
     def bam_counts_bgzf_acc(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len,
                             acc, group_of_sample=None, sample_status=None):
@@ -1252,19 +1275,29 @@ class SiteAcc:
     one device, zeroed.  Added to through any contexts of that device (Context.bam_counts_bgzf_acc; several threads may add at once), read
     with get, called where it lies with lrt."""
 
-    def __init__(self, device, n_positions, n_groups=0, byte_budget=0):
+    def __init__(self, device, n_positions, n_groups=0, byte_budget=0, depth_groups=0):
+        """depth_groups > 0: the second kind (bvc_site_acc_create_depth, include/bvc_bam_group_depth.h) -- one slot of counts, the tallies
+        and the depths [n_positions, depth_groups, 4] of that many groups; n_groups must then be 0."""
         self._L = load_library()
         h = C.c_void_p()
-        rc = self._L.bvc_site_acc_create(C.byref(h), int(device), int(n_positions), int(n_groups), int(byte_budget))
+        if depth_groups and n_groups:
+            raise ValueError("an accumulator keeps a slot per group (n_groups) or the groups' depths (depth_groups), not both")
+        if depth_groups:
+            what = f"bvc_site_acc_create_depth(device={device}, n_positions={n_positions}, n_groups={depth_groups})"
+            rc = self._L.bvc_site_acc_create_depth(C.byref(h), int(device), int(n_positions), int(depth_groups), int(byte_budget))
+        else:
+            what = f"bvc_site_acc_create(device={device}, n_positions={n_positions}, n_groups={n_groups})"
+            rc = self._L.bvc_site_acc_create(C.byref(h), int(device), int(n_positions), int(n_groups), int(byte_budget))
         if rc != 0:
-            err = BvcError(f"bvc_site_acc_create(device={device}, n_positions={n_positions}, n_groups={n_groups}) failed with code {rc}")
+            err = BvcError(f"{what} failed with code {rc}")
             err.status = rc
             raise err
         self._h = h
-        self.device, self.n_positions, self.n_groups = int(device), int(n_positions), int(n_groups)
+        self.device, self.n_positions, self.n_groups, self.depth_groups = int(device), int(n_positions), int(n_groups), int(depth_groups)
         self.slots = self.n_groups + 1 if self.n_groups else 1
 
     create = classmethod(lambda cls, *a, **kw: cls(*a, **kw))
+    create_depth = classmethod(lambda cls, device, n_positions, n_groups, byte_budget=0: cls(device, n_positions, 0, byte_budget, depth_groups=n_groups))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -1298,6 +1331,14 @@ class SiteAcc:
         t = np.zeros(max(n, 0), dtype=TALLY_DTYPE)
         ctx._check(self._L.bvc_site_acc_get(ctx._h, self._h, int(t0), n, _np_ptr(c) if counts and n > 0 else None, _np_ptr(t) if n > 0 else None))
         return c, t
+
+    def get_depth(self, ctx, t0=0, n=None):
+        """bvc_site_acc_get_depth: the groups' depths uint32 [n, depth_groups, 4] of rows [t0, t0 + n); an accumulator of the first kind is
+        refused (BVC_ERR_ARG)."""
+        n = self.n_positions - int(t0) if n is None else int(n)
+        d = np.zeros((max(n, 0), max(self.depth_groups, 1), 4), dtype=np.uint32)
+        ctx._check(self._L.bvc_site_acc_get_depth(ctx._h, self._h, int(t0), n, _np_ptr(d) if n > 0 else None))
+        return d
 
     def lrt(self, ctx, ref_base, min_af, t0=0):
         """bvc_site_acc_lrt: stage 2 on rows [t0, t0 + len(ref_base)) where they lie.  Returns the site records (SITE_DTYPE), or with

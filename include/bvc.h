@@ -717,6 +717,9 @@ int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64
  * batch's finished BGZF blocks out -- are declared in bvc_bam_deflate.h beside this header. */
 /* Phase 1 straight into class counts -- bvc_bam_counts: the same BAM records added into per-position class counts and tallies, bvc_site_acc_*:
  * such counts kept on the device and called from there -- are declared in bvc_bam_counts.h beside this header. */
+/* The same into ONE slot of class counts with the groups' depths per base beside it -- bvc_bam_counts_depth, bvc_site_acc_create_depth,
+ * bvc_site_acc_get_depth: 16 bytes a group and position where bvc_bam_counts takes 2 KB -- is declared in bvc_bam_group_depth.h beside this
+ * header. */
 
 #ifdef __cplusplus
 }

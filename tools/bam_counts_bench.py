@@ -2,7 +2,8 @@
 """bvc_bam_counts alone (needs a gfx950 device) on the inflated records of the 100 test BAMs in device memory, for bvc_bam_pileup's
 position list of the test region, next to bvc_bam_pileup and bvc_bam_popmatrix on the same records in the same run; with n_groups 0 and 5.
 
-  python tools/bam_counts_bench.py [--repeats 5] [--out FILE]                # (a) the call alone
+  python tools/bam_counts_bench.py [--repeats 5] [--depth G ...] [--out FILE]  # (a) the call alone; --depth G: and bvc_bam_counts_depth
+                                                     # (include/bvc_bam_group_depth.h: one slot of counts and the depths of G groups) behind it
   python tools/bam_counts_bench.py --process [--copies 50] [--repeats 3] [--out FILE]
                                                      # (b) the whole `BaseVarC basetype` process with --tmp-format counts next to mem and bin
                                                      # (bin with BVC_HOST_DEVICE_PILEUP=1: its phase 1 on the device like the other two), at
@@ -17,7 +18,11 @@ trace (HIP's timestamps of every dispatch):
 
   rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bam_counts_bench.py
 
-The adds are counted by the model (tests/bam_counts_model.py): one per tallied entry and one more per counted observation."""
+and --kernel-trace DIR, given the same --repeats and --depth, reads that run's kernel trace back: the add passes' dispatches in the order
+the forms ran, each form's fastest, median and slowest dispatch.
+
+The adds are counted by the model (tests/bam_counts_model.py): one per tallied entry and one more per counted observation; the depth form
+adds one more per counted observation of a sample that is in a group."""
 import argparse
 import os
 import sys
@@ -39,6 +44,31 @@ def best_of(ctx, repeats, call):
         dt = time.perf_counter() - t
         best = dt if best is None else min(best, dt)
     return best
+
+
+def trace_report(a):
+    """The add passes of one profiled run, form by form: every form made 1 + (repeats + 2) calls, in the order main() makes them."""
+    import csv
+    import glob
+    import statistics
+    files = glob.glob(os.path.join(a.kernel_trace, "**", "*kernel_trace.csv"), recursive=True)
+    if len(files) != 1:
+        raise SystemExit(f"one kernel trace expected under {a.kernel_trace}, found {len(files)}")
+    rows = list(csv.DictReader(open(files[0])))
+    calls = a.repeats + 3
+    lines = Lines()
+    lines.append(f"# the add passes' kernel times of one profiled run (rocprofv3 --kernel-trace), {calls} dispatches a form: min / median / max, microseconds")
+    for kernel, forms in (("bam_counts_kernel<true>", ["bvc_bam_counts, n_groups 0", "bvc_bam_counts, n_groups 5"]),
+                          ("bam_counts_depth_kernel", [f"bvc_bam_counts_depth, n_groups {g}" for g in a.depth])):
+        mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if kernel in r["Kernel_Name"])
+        if len(mine) != calls * len(forms):
+            raise SystemExit(f"{kernel}: {len(mine)} dispatches in the trace, {calls * len(forms)} expected")
+        for i, form in enumerate(forms):
+            us = [(e - b) / 1e3 for b, e in mine[i * calls:(i + 1) * calls]]
+            lines.append(f"  {kernel:26s} {form:36s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
 
 
 def process(a):
@@ -84,7 +114,12 @@ def main():
     ap.add_argument("--copies", type=int, default=50)
     ap.add_argument("--process", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--depth", type=int, action="append", default=[], help="also bvc_bam_counts_depth with this many groups (may be given more than once)")
+    ap.add_argument("--kernel-trace", default=None, help="the directory of a rocprofv3 --kernel-trace run of this tool with the same --repeats and --depth")
     a = ap.parse_args()
+    if a.kernel_trace:
+        a.repeats = 5 if a.repeats is None else a.repeats
+        return trace_report(a)
     if a.process:
         a.repeats = 3 if a.repeats is None else a.repeats
         return process(a)
@@ -141,6 +176,24 @@ def main():
         t = best_of(ctx, a.repeats, lambda: ctx.bam_counts(*head, d_pos, rg_s, len(refseq), d_counts, d_tally, **kw))
         lines.append(f"  bvc_bam_counts, n_groups {n_groups}: {t * 1e3:8.2f} ms a call, {adds} atomic adds into {d_counts.numel() * 4 + d_tally.numel() * 4} bytes "
                      f"of accumulators ({adds / t / 1e6:.1f} M adds/s over the whole call)")
+    for n_groups in a.depth:
+        from tests import bam_group_depth_model as gm
+        labels = (np.arange(n) % 7).astype(np.uint8)                  # (the labels of the grouped form above: with 5 groups two of seven are in none)
+        want_c, want_t, want_d = gm.fold_maps(exp["maps"], pv, labels, n_groups)
+        adds = int(want_c.sum()) + int(want_d.sum()) + int(want_t["strand_base"].sum()) + int(want_t["n_other"].sum()) + int(want_t["n_indel"].sum())
+        d_counts = torch.zeros(P * 512, dtype=torch.int32, device="cuda")
+        d_tally = torch.zeros(P * 12, dtype=torch.int32, device="cuda")
+        d_depth = torch.zeros(P * n_groups * 4, dtype=torch.int32, device="cuda")
+        kw = dict(group_of_sample=dev(labels), n_groups=n_groups, sample_status=st2)
+        assert ctx.bam_counts_depth(*head, d_pos, rg_s, len(refseq), d_counts, d_tally, d_depth, **kw)[0] == 0
+        ctx.synchronize()
+        assert (d_counts.cpu().numpy().view(np.uint32) == want_c.reshape(-1)).all() and d_tally.cpu().numpy().tobytes() == want_t.tobytes()
+        assert (d_depth.cpu().numpy().view(np.uint32) == want_d.reshape(-1)).all()
+        t = best_of(ctx, a.repeats, lambda: ctx.bam_counts_depth(*head, d_pos, rg_s, len(refseq), d_counts, d_tally, d_depth, **kw))
+        hot = int(want_d.max())
+        lines.append(f"  bvc_bam_counts_depth, n_groups {n_groups}: {t * 1e3:8.2f} ms a call, {adds} atomic adds into "
+                     f"{(d_counts.numel() + d_tally.numel() + d_depth.numel()) * 4} bytes of accumulators ({adds / t / 1e6:.1f} M adds/s over the whole call); "
+                     f"the most adds of one call into one depth word: {hot}")
     ctx.close()
     text = "\n".join(lines) + "\n"
     if a.out:
