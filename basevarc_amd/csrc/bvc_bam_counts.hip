@@ -3,9 +3,12 @@
 // checks and the verdicts on the statuses and the blocks are bvc_bam.hip's.  Order of work: index -> dry pass -> scan -> first wait ->
 // verdict -> add pass (-> second wait in the host forms): nothing is added unless the call returns BVC_OK.  The ninth header's calls
 // (include/bvc_bam_group_depth.h: bvc_bam_counts_depth, the accumulator's second kind) live here too: they are the same calls with one slot
-// of counts, the groups' depths beside it and bam_group_depth_kernel.hip as their add pass.
+// of counts, the groups' depths beside it and bam_group_depth_kernel.hip as their add pass.  And the tenth header's
+// (include/bvc_site_acc_quals.h: bvc_bam_counts_quals, the accumulator's third kind): the same calls again with narrow rows of counts
+// [position][4][n_quals], bam_counts_quals_kernel.hip as both passes, one more verdict (status 5) behind the existing one, and
+// acc_expand_kernel between narrow rows and the callers of bvc_site_acc_get / bvc_site_acc_lrt.
 #include "bvc_ctx.h"
-#include "../../include/bvc_bam_group_depth.h"
+#include "../../include/bvc_site_acc_quals.h"
 
 // An accumulator is no part of a context: its device memory is its own, and its bookkeeping is fixed when it is made (the adds are atomic).
 struct bvc_site_acc {
@@ -15,10 +18,16 @@ struct bvc_site_acc {
     int32_t depth_groups = 0;                        // the second kind (bvc_site_acc_create_depth): n_groups stays 0, one slot
     uint32_t *d_counts = nullptr;                    // [n_positions][slots][512]
     bvc_bam_site_tally *d_tally = nullptr;           // [n_positions]
-    uint32_t *d_depth = nullptr;                     // [n_positions][depth_groups][4], the second kind only
+    uint32_t *d_depth = nullptr;                     // [n_positions][depth_groups][4], the second and third kind
+    int32_t n_quals = 0;                             // > 0: the third kind (bvc_site_acc_create_quals) -- n_groups stays 0, one slot of
+                                                     // [4][n_quals] words, depth_groups 0..32
     size_t slots() const { return n_groups > 0 ? (size_t)n_groups + 1 : 1; }
-    size_t row_words() const { return slots() * BVC_NCLASS; }
+    size_t row_words() const { return n_quals > 0 ? (size_t)n_quals * 4 : slots() * BVC_NCLASS; }
+    bool expanded() const { return n_quals > 0 && n_quals < 128; }   // its rows are not the [512] layout: acc_expand_kernel makes it
 };
+
+// Rows a call expands at a time into the context's scratch (bvc_site_acc_get, bvc_site_acc_lrt on narrow rows): 64 MiB of [512] rows
+constexpr int32_t kExpandRows = 32768;
 
 namespace {
 
@@ -44,31 +53,53 @@ int check_counts_groups(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of
 
 // Index, dry pass, scan and the call's first wait, on inputs in device memory: the statuses (to sample_status on the host unless
 // out_device) and the verdict -- the blocks' first (blocks: their statuses come down with the same wait; may be null), then the samples'.
+// n_quals > 0: the narrow forms -- their dry pass also raises status 5, whose first sample comes down with the same wait and is judged
+// behind the existing verdict.
 int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, uint32_t *d_status, uint32_t *sample_status,
-                       const std::vector<uint32_t> *blocks, BamPileupScratch &S)
+                       const std::vector<uint32_t> *blocks, BamPileupScratch &S, int32_t n_quals = 0)
 {
     const size_t ns = (size_t)c.n_samples;
-    const int rc = carve(ctx, ctx->d_bam, 256, [&](Layout &L) { S = bam_popmatrix_scratch(L, c.bam_bytes, c.n_samples); });
+    int64_t *d_first5 = nullptr;
+    int rc = carve(ctx, ctx->d_bam, 256, [&](Layout &L) {
+        S = bam_popmatrix_scratch(L, c.bam_bytes, c.n_samples);
+        if (n_quals > 0) d_first5 = L.take<int64_t>(1);
+    });
     if (rc != BVC_OK) return rc;
     BVC_HIP_D(ctx, launch_bam_index(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.eof, c.rid, c.beg0, c.end0, c.min_mapq, S, d_status));
-    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
-                                     nullptr, 0, S, nullptr, nullptr, d_status));
+    if (n_quals > 0)
+        BVC_HIP_D(ctx, launch_bam_counts_quals(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s,
+                                               c.refseq_len, nullptr, 0, n_quals, S, nullptr, nullptr, nullptr, d_status));
+    else
+        BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
+                                         nullptr, 0, S, nullptr, nullptr, d_status));
     BVC_HIP_D(ctx, launch_bam_scan(ctx->stream, 0, c.n_samples, S, d_status));
-    int64_t head[4] = {0, 0, 0, 0};
+    int64_t head[4] = {0, 0, 0, 0}, first5 = 0x7FFFFFFF;
     BVC_HIP_D(ctx, io.d2h(head, S.head, sizeof head));
+    if (n_quals > 0) {
+        BVC_HIP_D(ctx, launch_first_status(ctx->stream, c.n_samples, d_status, 5u, d_first5));
+        BVC_HIP_D(ctx, io.d2h(&first5, d_first5, sizeof first5));
+    }
     if (!out_device && ns) BVC_HIP_D(ctx, io.d2h(sample_status, d_status, ns * 4));
     BVC_HIP_D(ctx, wait_stream(ctx));               // the statuses decide whether anything is added
     io.deliver();
     // a block that did not inflate (or failed its CRC32) outranks what the kernels made of its bytes
     if (blocks && block_verdict(ctx, *blocks) != BVC_OK) return BVC_ERR_DATA;
-    return status_verdict(ctx, head);
+    if ((rc = status_verdict(ctx, head)) != BVC_OK || first5 == 0x7FFFFFFF) return rc;
+    char msg[160];
+    std::snprintf(msg, sizeof msg, "sample %lld: a base quality of %d or more, and the counts keep n_quals = %d quality columns", (long long)first5,
+                  (int)n_quals, (int)n_quals);
+    return fail(ctx, BVC_ERR_DATA, msg);
 }
 
 // The add pass, enqueued on the context's stream.  d_depth: the depth form's array (one slot of counts, n_groups depth rows), else null.
+// n_quals > 0: the narrow forms (d_counts [P][4][n_quals]; d_depth null with n_groups 0).
 int bam_counts_add(bvc_ctx *ctx, const BamCall &c, const uint8_t *d_group, int32_t n_groups, const BamPileupScratch &S, uint32_t *d_counts,
-                   bvc_bam_site_tally *d_tally, uint32_t *d_depth, uint32_t *d_status)
+                   bvc_bam_site_tally *d_tally, uint32_t *d_depth, uint32_t *d_status, int32_t n_quals = 0)
 {
-    if (d_depth)
+    if (n_quals > 0)
+        BVC_HIP_D(ctx, launch_bam_counts_quals(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s,
+                                               c.refseq_len, d_group, n_groups, n_quals, S, d_counts, d_tally, d_depth, d_status));
+    else if (d_depth)
         BVC_HIP_D(ctx, launch_bam_counts_depth(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
                                                d_group, n_groups, S, d_counts, d_tally, d_depth));
     else
@@ -102,11 +133,12 @@ int check_counts_call(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_b
 }
 
 // bvc_bam_counts (depth = false: counts [P][slots][512], group_depth unused) and bvc_bam_counts_depth (depth = true: counts [P][512] and
-// group_depth [P][n_groups][4]) are one call.
+// group_depth [P][n_groups][4]) are one call; so is bvc_bam_counts_quals (n_quals > 0: counts [P][4][n_quals]; depth says whether it has
+// groups, n_groups 0 is allowed).
 int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
                     const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
                     const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups, bool depth,
-                    uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
+                    uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags, int32_t n_quals = 0)
 {
     if (!ctx) return BVC_ERR_ARG;
     BamCall c;
@@ -124,13 +156,14 @@ int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t
     PinIO io(ctx);
     if (flags & BVC_PTR_DEVICE) {
         if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
-        rc = bam_counts_verdict(ctx, io, c, true, sample_status, sample_status, nullptr, S);
-        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, depth ? group_depth : nullptr, sample_status);
+        rc = bam_counts_verdict(ctx, io, c, true, sample_status, sample_status, nullptr, S, n_quals);
+        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, depth ? group_depth : nullptr, sample_status, n_quals);
     }
     if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
     if ((rc = io.reserve(ns * 22 + np * 4 + 1024, 64 + ns * 4 + 1024)) != BVC_OK) return rc;
     // host pointers: the inputs and the accumulators live in the staging buffer for the length of the call
-    const size_t cwords = ns ? np * (n_groups > 0 && !depth ? (size_t)n_groups + 1 : 1) * BVC_NCLASS : 0, trows = ns ? np : 0;
+    const size_t row = n_quals > 0 ? (size_t)n_quals * 4 : (n_groups > 0 && !depth ? (size_t)n_groups + 1 : 1) * BVC_NCLASS;
+    const size_t cwords = ns ? np * row : 0, trows = ns ? np : 0;
     const size_t dwords = depth && ns ? np * (size_t)n_groups * 4 : 0;
     uint8_t *u_bam, *u_eof, *u_grp; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos; uint32_t *d_status, *d_counts, *d_depth; bvc_bam_site_tally *d_tally;
     rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
@@ -148,13 +181,13 @@ int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t
     if (labels) BVC_HIP_D(ctx, io.h2d(u_grp, group_of_sample, ns));
     BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
     c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
-    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, nullptr, S);
+    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, nullptr, S, n_quals);
     if (rc != BVC_OK || cwords == 0) return rc;
     // the accumulators go up only now: a call that fails has not touched them
     BVC_HIP_D(ctx, hipMemcpyAsync(d_counts, counts, cwords * 4, hipMemcpyHostToDevice, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(d_tally, tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyHostToDevice, ctx->stream));
     if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(d_depth, group_depth, dwords * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, depth ? d_depth : nullptr, d_status)) != BVC_OK) return rc;
+    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, depth ? d_depth : nullptr, d_status, n_quals)) != BVC_OK) return rc;
     BVC_HIP_D(ctx, hipMemcpyAsync(counts, d_counts, cwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(tally, d_tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
     if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(group_depth, d_depth, dwords * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -162,12 +195,13 @@ int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t
     return BVC_OK;
 }
 
-// Both kinds of accumulator are made here: depth_groups > 0 is the second kind (n_groups is then 0)
-int site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t depth_groups, int64_t byte_budget)
+// Every kind of accumulator is made here: depth_groups > 0 is the second kind (n_groups is then 0), n_quals > 0 the third (n_groups 0,
+// depth_groups 0..32)
+int site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t depth_groups, int64_t byte_budget, int32_t n_quals = 0)
 {
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BVC_ERR_DEVICE; }
     bvc_site_acc *acc = new bvc_site_acc;
-    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->depth_groups = depth_groups;
+    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->depth_groups = depth_groups; acc->n_quals = n_quals;
     acc->budget = byte_budget > 0 ? byte_budget : 0;
     const size_t cbytes = (size_t)n_positions * acc->row_words() * 4, tbytes = (size_t)n_positions * sizeof(bvc_bam_site_tally);
     const size_t dbytes = (size_t)n_positions * (size_t)depth_groups * 16;
@@ -208,6 +242,19 @@ int bvc_bam_counts_depth(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, in
                            refseq_len, group_of_sample, n_groups, true, counts, tally, group_depth, sample_status, flags);
 }
 
+int bvc_bam_counts_quals(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                         const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                         const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups, int32_t n_quals,
+                         uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    if (!quals_ok(n_quals)) return fail(ctx, BVC_ERR_ARG, "n_quals must be a multiple of 4 in 4..128");
+    if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
+    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
+                           refseq_len, n_groups > 0 ? group_of_sample : nullptr, n_groups, n_groups > 0, counts, tally, group_depth, sample_status, flags,
+                           n_quals);
+}
+
 int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
 {
     if (!out) return BVC_ERR_ARG;
@@ -222,6 +269,21 @@ int bvc_site_acc_create_depth(bvc_site_acc **out, int device, int32_t n_position
     *out = nullptr;
     if (n_positions < 0 || n_groups < 1 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
     return site_acc_create(out, device, n_positions, 0, n_groups, byte_budget);
+}
+
+int bvc_site_acc_create_quals(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t n_quals, int64_t byte_budget)
+{
+    if (!out) return BVC_ERR_ARG;
+    *out = nullptr;
+    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS || !quals_ok(n_quals)) return BVC_ERR_ARG;
+    return site_acc_create(out, device, n_positions, 0, n_groups, byte_budget, n_quals);
+}
+
+int bvc_site_acc_quals(const bvc_site_acc *acc, int32_t *n_quals)
+{
+    if (!acc || !n_quals) return BVC_ERR_ARG;
+    *n_quals = acc->n_quals > 0 ? acc->n_quals : 128;
+    return BVC_OK;
 }
 
 void bvc_site_acc_destroy(bvc_site_acc *acc)
@@ -289,9 +351,10 @@ int bvc_bam_counts_bgzf_acc(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp
     BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
     c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
     BamPileupScratch S;
-    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, &block_status, S);
+    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, &block_status, S, acc->n_quals);
     if (rc != BVC_OK) return rc;
-    if ((rc = bam_counts_add(ctx, c, u_grp, dg > 0 ? dg : acc->n_groups, S, acc->d_counts, acc->d_tally, dg > 0 ? acc->d_depth : nullptr, d_status)) != BVC_OK)
+    if ((rc = bam_counts_add(ctx, c, u_grp, dg > 0 ? dg : acc->n_groups, S, acc->d_counts, acc->d_tally, dg > 0 ? acc->d_depth : nullptr, d_status,
+                             acc->n_quals)) != BVC_OK)
         return rc;
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
@@ -307,7 +370,18 @@ int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     if (n == 0) return BVC_OK;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t rw = acc->row_words();
-    if (counts) BVC_HIP_D(ctx, hipMemcpyAsync(counts, acc->d_counts + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (counts && acc->expanded()) {
+        // narrow rows: a bounded piece at a time is expanded into the context's scratch and comes down from there
+        const int32_t piece = n < kExpandRows ? n : kExpandRows;
+        uint32_t *d_wide;
+        if ((rc = carve(ctx, ctx->d_acc, 256, [&](Layout &L) { d_wide = L.take<uint32_t>((size_t)piece * BVC_NCLASS); })) != BVC_OK) return rc;
+        for (int32_t k = 0; k < n; k += piece) {
+            const int32_t m = n - k < piece ? n - k : piece;
+            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, acc->n_quals, acc->d_counts + ((size_t)t0 + (size_t)k) * rw, d_wide));
+            BVC_HIP_D(ctx, hipMemcpyAsync(counts + (size_t)k * BVC_NCLASS, d_wide, (size_t)m * BVC_NCLASS * 4, hipMemcpyDeviceToHost, ctx->stream));
+        }
+    } else if (counts)
+        BVC_HIP_D(ctx, hipMemcpyAsync(counts, acc->d_counts + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(tally, acc->d_tally + t0, (size_t)n * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
@@ -341,16 +415,25 @@ int bvc_site_acc_lrt(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     if (n == 0) return BVC_OK;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     // the rows stay where they are: only ref_base goes up and the records come down, through the staging buffer
-    int8_t *d_r; bvc_site_result *d_res; bvc_group_result *d_gres;
+    int8_t *d_r; bvc_site_result *d_res; bvc_group_result *d_gres; uint32_t *d_wide;
+    const int32_t piece = !acc->expanded() ? 0 : n < kExpandRows ? n : kExpandRows;      // narrow rows: expanded a piece at a time
     rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
         d_r = L.take<int8_t>((size_t)n);
         d_res = L.take<bvc_site_result>((size_t)n);
         d_gres = L.take<bvc_group_result>((size_t)n * (size_t)ng);
+        d_wide = L.take<uint32_t>((size_t)piece * BVC_NCLASS);
     });
     if (rc != BVC_OK) return rc;
     BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
     const uint32_t *rows = acc->d_counts + (size_t)t0 * acc->row_words();
-    if (ng > 0) {
+    if (piece > 0) {
+        // (the stream orders a piece's stage 2 in front of the next piece's expansion into the same scratch)
+        for (int32_t k = 0; k < n && rc == BVC_OK; k += piece) {
+            const int32_t m = n - k < piece ? n - k : piece;
+            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, acc->n_quals, rows + (size_t)k * acc->row_words(), d_wide));
+            rc = bvc_lrt_hist(ctx, m, d_wide, d_r + k, min_af, nullptr, nullptr, d_res + k, BVC_PTR_DEVICE);
+        }
+    } else if (ng > 0) {
         rc = bvc_lrt_hist_groups(ctx, n, rows, d_r, min_af, ng, d_res, d_gres, BVC_PTR_DEVICE);
         if (rc == BVC_OK) rc = join_side(ctx);
     } else

@@ -331,6 +331,18 @@ hipError_t launch_bam_counts_depth(hipStream_t stream, int32_t n_samples, const 
                                    const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
                                    const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
                                    ::bvc_bam_site_tally *tally, uint32_t *group_depth);
+// bam_counts_quals_kernel.hip: both passes with NARROW rows of counts [position][4][n_quals] (include/bvc_site_acc_quals.h,
+// bvc_bam_counts_quals); n_quals a multiple of 4 in 4..128, n_groups 0..32 (0: group_of_sample and group_depth are not read).  add = false:
+// the dry pass, which raises status 4 and status 5 (4 where both hold) and reads nothing of the three arrays; add = true: the adds, none
+// for a quality >= n_quals.  launch_first_status leaves in out[0] the first sample of status `which` (0x7FFFFFFF: none);
+// launch_acc_expand turns rows [n_rows][4][n_quals] into [n_rows][512] with zeros in the columns >= n_quals (both 16-byte aligned).
+inline bool quals_ok(int32_t n_quals) { return n_quals >= 4 && n_quals <= 128 && n_quals % 4 == 0; }
+hipError_t launch_bam_counts_quals(hipStream_t stream, bool add, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
+                                   const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
+                                   const uint8_t *group_of_sample, int32_t n_groups, int32_t n_quals, const BamPileupScratch &s, uint32_t *counts,
+                                   ::bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status);
+hipError_t launch_first_status(hipStream_t stream, int32_t n_samples, const uint32_t *sample_status, uint32_t which, int64_t *out);
+hipError_t launch_acc_expand(hipStream_t stream, int64_t n_rows, int32_t n_quals, const uint32_t *narrow, uint32_t *wide);
 
 // store_kernel.hip: temp batches kept on the device (include/bvc_store.h).  A kept batch as the kernels see it: the device addresses of its
 // rec_start row and of its records, and the records' bytes (what every word of the row is clamped with).

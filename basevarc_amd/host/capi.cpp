@@ -82,6 +82,8 @@ int32_t bvchost_parse_store_windows(const char *value, int32_t thread)
     const int k = parse_store_windows(value);
     return k > 0 && store_windows_refused(k, thread) ? -1 : k;
 }
+// BVC_HOST_COUNTS_QUALS as the host program reads it: a multiple of 4 in 4..128, 128 for a null pointer (unset), -1 for a value it refuses
+int32_t bvchost_parse_counts_quals(const char *value) { return parse_counts_quals(value); }
 // the revisit set of --tmp-format counts (counts_revisit): tally = bvc_bam_site_tally [psize], called [psize] -> flags [psize]
 void bvchost_counts_revisit(const void *tally, const uint8_t *called, int64_t psize, int32_t thread, uint8_t *flags)
 {

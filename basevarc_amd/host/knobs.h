@@ -72,6 +72,18 @@ inline int auto_store_windows(const uint32_t *rec_start, size_t psize, int threa
     return k;
 }
 
+// BVC_HOST_COUNTS_QUALS as text: the quality columns --tmp-format counts keeps for each base, a multiple of 4 in 4..128 in plain digits.
+// nullptr (unset) is 128.  -1: none of these.
+inline int parse_counts_quals(const char *v)
+{
+    if (!v) return 128;
+    const std::string s(v);
+    if (s.empty() || s.size() > 3) return -1;
+    for (char c : s) if (c < '0' || c > '9') return -1;
+    const int q = atoi(s.c_str());
+    return q >= 4 && q <= 128 && q % 4 == 0 ? q : -1;
+}
+
 struct Knobs {
     static bool set(const char *name) { return getenv(name) != nullptr; }
     static int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
@@ -157,6 +169,13 @@ struct Knobs {
     // (run_basetype asks counts_groups_on() where its refusals stand, before this object is made: the refusal opens nothing)
     static bool counts_groups_on() { return num("BVC_HOST_COUNTS_GROUPS", 0) != 0; }
     const bool counts_groups = counts_groups_on();
+    // --tmp-format counts only (every other format ignores it): the quality columns the counts pass keeps for each base, a multiple of 4 in
+    // 4..128 (bvc_site_acc_create_quals, include/bvc_site_acc_quals.h).  A position then takes 16 x Q + 48 bytes (and 16 a group) where it
+    // takes 2 KB + 48 at 128, so a region 2048 / (16 x Q) times as long fits the device; a batch that holds a counted base quality of Q or
+    // more ends the run with a line that names the BAM and BVC_HOST_COUNTS_QUALS=128.  The outputs are those of 128.  Any other value ends
+    // the run before anything is opened (run_basetype asks parse_counts_quals where its refusals stand; -1 here).  Default 128: the
+    // accumulators of bvc_site_acc_create / _create_depth, as before the knob
+    const int counts_quals = parse_counts_quals(getenv("BVC_HOST_COUNTS_QUALS"));
     const bool two_byte_tiles =set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

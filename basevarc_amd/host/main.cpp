@@ -78,7 +78,8 @@ static const char *BASETYPE_MESSAGE =
     "                           the called positions and those with indels are piled up a second time, as mem keeps them\n"
     "                           (BVC_HOST_STORE_GB caps the counts, then those batches; not with --group, --load, --keep_tmp\n"
     "                           or --gpus above 1; BVC_HOST_COUNTS_GROUPS=1 takes --group: 16 bytes a group and position more,\n"
-    "                           32 distinct group names in the file at the most)\n";
+    "                           32 distinct group names in the file at the most; BVC_HOST_COUNTS_QUALS=Q, a multiple of 4 in\n"
+    "                           4..128 [128]: 16 x Q bytes a position, and a base quality of Q or more ends the run)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -477,7 +478,7 @@ struct GroupFile {
     std::vector<std::string> ids, groups, names;    // the lines in order; the distinct group names, sorted
 };
 static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
-                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run, const GroupFile *gf)
+                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run, const GroupFile *gf, int quals)
 {
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
@@ -494,9 +495,17 @@ static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<
         counts_group_map(gf->ids, gf->groups, batch.sms, names, label, columns);
     }
     device_batch_loop(batch, dev, bams, b0, beg0, end0, status, [&]() {
-        return bvc_bam_counts_bgzf_acc(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(), batch.out_bytes,
-                                       batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq, (int32_t)pv.size(),
-                                       pv.data(), rg_s, (int64_t)refseq.size(), gf ? label.data() : nullptr, acc, status.data());
+        const int rc = bvc_bam_counts_bgzf_acc(dev.ctx, (int32_t)ns, dev.pin, batch.comp_bytes, batch.table.data(), (int64_t)batch.table.size(),
+                                               batch.out_bytes, batch.off.data(), batch.end.data(), batch.eof.data(), batch.rid.data(), beg0, end0, opt::mapq,
+                                               (int32_t)pv.size(), pv.data(), rg_s, (int64_t)refseq.size(), gf ? label.data() : nullptr, acc, status.data());
+        // narrow rows (BVC_HOST_COUNTS_QUALS): a batch refused for a quality the rows have no column for ends the run (statuses 3 and 4 of
+        // the same batch go first, with the loop's own messages)
+        if (rc == BVC_ERR_DATA && std::none_of(status.begin(), status.end(), [](uint32_t s) { return s == 3u || s == 4u; }))
+            for (size_t s = 0; s < ns; ++s)
+                if (status[s] == 5u)
+                    throw std::runtime_error("ERROR: a base quality of " + std::to_string(quals) + " or more in " + bams[b0 + s] + ": the counts keep " +
+                                             std::to_string(quals) + " quality columns, run with BVC_HOST_COUNTS_QUALS=128");
+        return rc;
     });
     for (size_t s = 0; s < ns; ++s)
         if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
@@ -843,7 +852,8 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     const int64_t budget = (int64_t)(knobs.store_gb * 1073741824.0);
     const size_t P = pv.size();
     const size_t G = gf ? gf->names.size() : 0;                         // (depth rows: 16 bytes a group and position)
-    const int64_t need = (int64_t)P * (int64_t)(BVC_NCLASS * 4 + sizeof(bvc_bam_site_tally) + 16 * G);
+    const int Q = knobs.counts_quals;                                   // (BVC_HOST_COUNTS_QUALS: 128 unless set; checked in run_basetype)
+    const int64_t need = (int64_t)P * (int64_t)(16 * (size_t)Q + sizeof(bvc_bam_site_tally) + 16 * G);
     const std::string what = "the class counts" + std::string(G ? " and the groups' depths" : "") + " of " + std::to_string(P) + " positions take " +
                              std::to_string(need) + " bytes";
     if (budget > 0 && need > budget)
@@ -864,9 +874,11 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     int64_t acc_bytes = 0;
     {
         struct Acc { bvc_site_acc *p = nullptr; ~Acc() { bvc_site_acc_destroy(p); } } acc;
-        if ((G ? bvc_site_acc_create_depth(&acc.p, 0, (int32_t)P, (int32_t)G, budget) : bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget)) != BVC_OK)
+        if ((Q < 128 ? bvc_site_acc_create_quals(&acc.p, 0, (int32_t)P, (int32_t)G, Q, budget)
+             : G     ? bvc_site_acc_create_depth(&acc.p, 0, (int32_t)P, (int32_t)G, budget)
+                     : bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget)) != BVC_OK)
             throw std::runtime_error("ERROR: the device has no room: " + what + "; --tmp-format bin keeps the batches in files");
-        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run, gf); });
+        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run, gf, Q); });
         LoadDevice dev;
         if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
         const size_t chunk = 8192;
@@ -942,6 +954,9 @@ static void run_basetype(int argc, char **argv)                          // src/
     if (counts && !opt::group.empty() && !counts_groups)
         throw std::invalid_argument("ERROR: --tmp-format counts with --group: the program calls the groups from kept batches only, use --tmp-format mem "
                                     "(or set BVC_HOST_COUNTS_GROUPS=1)");
+    // (BVC_HOST_COUNTS_QUALS acts with counts only; a value that is no multiple of 4 in 4..128 is refused here, before anything is opened)
+    if (counts && parse_counts_quals(getenv("BVC_HOST_COUNTS_QUALS")) < 0)
+        throw std::invalid_argument("ERROR: BVC_HOST_COUNTS_QUALS must be a multiple of 4 in 4..128");
     GroupFile group_file;
     if (counts_groups) {
         std::ifstream ifg(opt::group);

@@ -20,7 +20,7 @@
 #include <vector>
 
 #include "../../include/bvc.h"
-#include "../../include/bvc_bam_group_depth.h"
+#include "../../include/bvc_site_acc_quals.h"
 
 namespace bvchost {
 

@@ -187,6 +187,15 @@ BAM_GROUP_DEPTH_PROTOTYPES = {
     "bvc_site_acc_get_depth": (_int, [_vp, _vp, _i32, _i32, _vp]),
 }
 BAM_GROUP_DEPTH_EXPORTS = list(BAM_GROUP_DEPTH_PROTOTYPES)
+# The tenth header, include/bvc_site_acc_quals.h (tests/test_bam_counts_quals_abi.py compares the two), bound by bind() with the others: phase 1
+# added into narrow rows of class counts [position][4][n_quals].  bvc_bam_counts_quals takes bvc_bam_counts_depth's arguments with n_quals
+# behind n_groups.
+SITE_ACC_QUALS_PROTOTYPES = {
+    "bvc_bam_counts_quals": (_int, BAM_COUNTS_PROTOTYPES["bvc_bam_counts"][1][:17] + [_i32, _vp, _vp, _vp, _vp, _u32]),
+    "bvc_site_acc_create_quals": (_int, [C.POINTER(_vp), _int, _i32, _i32, _i32, _i64]),
+    "bvc_site_acc_quals": (_int, [_vp, C.POINTER(_i32)]),
+}
+SITE_ACC_QUALS_EXPORTS = list(SITE_ACC_QUALS_PROTOTYPES)
 STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
@@ -204,11 +213,11 @@ def library_path():
 
 def bind(cdll):
     """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES,
-    BAM_DEFLATE_PROTOTYPES, BAM_COUNTS_PROTOTYPES and BAM_GROUP_DEPTH_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    BAM_DEFLATE_PROTOTYPES, BAM_COUNTS_PROTOTYPES, BAM_GROUP_DEPTH_PROTOTYPES and SITE_ACC_QUALS_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
                                       list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items()) +
                                       list(BAM_DEFLATE_PROTOTYPES.items()) + list(BAM_COUNTS_PROTOTYPES.items()) +
-                                      list(BAM_GROUP_DEPTH_PROTOTYPES.items())):
+                                      list(BAM_GROUP_DEPTH_PROTOTYPES.items()) + list(SITE_ACC_QUALS_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -1045,13 +1054,14 @@ class Context:
         return rc, matrix[:n, :P], status[:n]
 
     def bam_counts(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
-                   group_of_sample=None, n_groups=0, sample_status=None, group_depth=None):
+                   group_of_sample=None, n_groups=0, sample_status=None, group_depth=None, n_quals=None):
         """bvc_bam_counts (include/bvc_bam_counts.h): the inflated BAM records of a batch of samples ADDED into counts ([P, 512], or
         [P, n_groups + 1, 512] with groups; 4-byte integers) and tally (TALLY_DTYPE [P], or 12 words a position), in place.  numpy arrays
         (synchronous) or tensors on this context's device (the adds are enqueued when it returns); the sample arrays and positions as
         bam_pileup takes them, group_of_sample uint8 [n].  Returns (rc, sample_status): rc 0, or BAM_MORE (2) when a sample's status is 2
         -- nothing is added then.  Raises BvcError for the errors (status BVC_ERR_DATA = -5: a sample of status 3 or 4; nothing is added).
-        group_depth: bam_counts_depth's third array -- the call is then bvc_bam_counts_depth."""
+        group_depth: bam_counts_depth's third array -- the call is then bvc_bam_counts_depth.  n_quals: the call is bvc_bam_counts_quals
+        (bam_counts_quals below), whose group_depth may be None without groups."""
         device = hasattr(bam, "data_ptr")
         outs = (counts, tally) if group_depth is None else (counts, tally, group_depth)
         if device:
@@ -1074,8 +1084,12 @@ class Context:
         ptr = _dev_ptr if device else _np_ptr
         opt = lambda a: a if a is not None and size(a) else None
         fn = self._L.bvc_bam_counts if group_depth is None else self._L.bvc_bam_counts_depth
+        quals = ()
+        if n_quals is not None:
+            fn, quals, outs = self._L.bvc_bam_counts_quals, (int(n_quals),), (counts, tally, group_depth)
         rc = fn(self._h, n, *_pointers((opt(bam), size(bam), opt(sample_off), opt(sample_end), opt(sample_eof), opt(rid), int(beg0), int(end0), int(min_mapq), P,
-                                        opt(positions), int(rg_s), int(refseq_len), opt(group_of_sample), int(n_groups), *outs, sample_status if n else None), ptr),
+                                        opt(positions), int(rg_s), int(refseq_len), opt(group_of_sample), int(n_groups), *quals, *outs,
+                                        sample_status if n else None), ptr),
                 BVC_PTR_DEVICE if device else BVC_PTR_HOST)
         if rc not in (0, BAM_MORE):
             self._check(rc)
@@ -1090,6 +1104,20 @@ class Context:
             raise ValueError("group_depth must be an array (bam_counts is the call without one)")
         return self.bam_counts(bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
                                group_of_sample, n_groups, sample_status, group_depth)
+
+    def bam_counts_quals(self, bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, n_quals, counts, tally,
+                         group_depth=None, group_of_sample=None, n_groups=0, sample_status=None):
+        """bvc_bam_counts_quals (include/bvc_site_acc_quals.h): bam_counts into NARROW rows of counts ([P, 4, n_quals]; n_quals a multiple
+        of 4 in 4..128) and tally, and with n_groups 1..32 the groups' depths into group_depth ([P, n_groups, 4]), in place.  A batch with a
+        counted observation of quality n_quals..127 is refused (BvcError of status BVC_ERR_DATA = -5, that sample's status 5) and adds
+        nothing.  Arrays, return value and the other errors as bam_counts."""
+        if (group_depth is None) != (not n_groups):
+            raise ValueError("group_depth goes with n_groups 1..32")
+        outs = (counts, tally) if group_depth is None else (counts, tally, group_depth)
+        if not hasattr(bam, "data_ptr") and not all(isinstance(a, np.ndarray) and a.flags.c_contiguous for a in outs):
+            raise ValueError("counts, tally and group_depth must be contiguous arrays (they are added to in place)")
+        return self.bam_counts(bam, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len, counts, tally,
+                               group_of_sample, n_groups, sample_status, group_depth, n_quals=n_quals)
 
     def bam_counts_bgzf_acc(self, comp, blocks, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, positions, rg_s, refseq_len,
                             acc, group_of_sample=None, sample_status=None):
@@ -1275,14 +1303,19 @@ class SiteAcc:
     one device, zeroed.  Added to through any contexts of that device (Context.bam_counts_bgzf_acc; several threads may add at once), read
     with get, called where it lies with lrt."""
 
-    def __init__(self, device, n_positions, n_groups=0, byte_budget=0, depth_groups=0):
+    def __init__(self, device, n_positions, n_groups=0, byte_budget=0, depth_groups=0, n_quals=None):
         """depth_groups > 0: the second kind (bvc_site_acc_create_depth, include/bvc_bam_group_depth.h) -- one slot of counts, the tallies
-        and the depths [n_positions, depth_groups, 4] of that many groups; n_groups must then be 0."""
+        and the depths [n_positions, depth_groups, 4] of that many groups; n_groups must then be 0.  n_quals: the third kind
+        (bvc_site_acc_create_quals, include/bvc_site_acc_quals.h) -- one slot of narrow rows [4, n_quals], the tallies and the depths of
+        depth_groups groups (0: none); n_groups must be 0."""
         self._L = load_library()
         h = C.c_void_p()
-        if depth_groups and n_groups:
+        if (depth_groups or n_quals is not None) and n_groups:
             raise ValueError("an accumulator keeps a slot per group (n_groups) or the groups' depths (depth_groups), not both")
-        if depth_groups:
+        if n_quals is not None:
+            what = f"bvc_site_acc_create_quals(device={device}, n_positions={n_positions}, n_groups={depth_groups}, n_quals={n_quals})"
+            rc = self._L.bvc_site_acc_create_quals(C.byref(h), int(device), int(n_positions), int(depth_groups), int(n_quals), int(byte_budget))
+        elif depth_groups:
             what = f"bvc_site_acc_create_depth(device={device}, n_positions={n_positions}, n_groups={depth_groups})"
             rc = self._L.bvc_site_acc_create_depth(C.byref(h), int(device), int(n_positions), int(depth_groups), int(byte_budget))
         else:
@@ -1295,9 +1328,14 @@ class SiteAcc:
         self._h = h
         self.device, self.n_positions, self.n_groups, self.depth_groups = int(device), int(n_positions), int(n_groups), int(depth_groups)
         self.slots = self.n_groups + 1 if self.n_groups else 1
+        q = C.c_int32(0)
+        self._L.bvc_site_acc_quals(self._h, C.byref(q))
+        self.n_quals = q.value                       # the quality columns stored for each base: 128 unless made by create_quals
 
     create = classmethod(lambda cls, *a, **kw: cls(*a, **kw))
     create_depth = classmethod(lambda cls, device, n_positions, n_groups, byte_budget=0: cls(device, n_positions, 0, byte_budget, depth_groups=n_groups))
+    create_quals = classmethod(lambda cls, device, n_positions, n_quals, n_groups=0, byte_budget=0:
+                               cls(device, n_positions, 0, byte_budget, depth_groups=n_groups, n_quals=n_quals))
 
     def close(self):
         if getattr(self, "_h", None):

@@ -720,6 +720,9 @@ int bvc_pileup_sample_bgzf(bvc_ctx *ctx, int64_t n_samples, uint8_t *comp, int64
 /* The same into ONE slot of class counts with the groups' depths per base beside it -- bvc_bam_counts_depth, bvc_site_acc_create_depth,
  * bvc_site_acc_get_depth: 16 bytes a group and position where bvc_bam_counts takes 2 KB -- is declared in bvc_bam_group_depth.h beside this
  * header. */
+/* Such counts in narrow quality rows -- bvc_bam_counts_quals, bvc_site_acc_create_quals, bvc_site_acc_quals: 16 x n_quals bytes a position
+ * where a row of 128 quality columns takes 2 KB, and a batch that needs a higher quality is refused -- are declared in bvc_site_acc_quals.h
+ * beside this header. */
 
 #ifdef __cplusplus
 }

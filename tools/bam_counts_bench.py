@@ -4,6 +4,9 @@ position list of the test region, next to bvc_bam_pileup and bvc_bam_popmatrix o
 
   python tools/bam_counts_bench.py [--repeats 5] [--depth G ...] [--out FILE]  # (a) the call alone; --depth G: and bvc_bam_counts_depth
                                                      # (include/bvc_bam_group_depth.h: one slot of counts and the depths of G groups) behind it
+  python tools/bam_counts_bench.py --quals Q ...     # and bvc_bam_counts_quals (include/bvc_site_acc_quals.h: narrow rows of Q quality columns) with
+                                                     # 0 and 5 groups behind those, 8 fetches of 8,192 rows of an accumulator of Q columns
+                                                     # (acc_expand_kernel) and the time to make a wide and a narrow accumulator of the region
   python tools/bam_counts_bench.py --process [--copies 50] [--repeats 3] [--out FILE]
                                                      # (b) the whole `BaseVarC basetype` process with --tmp-format counts next to mem and bin
                                                      # (bin with BVC_HOST_DEVICE_PILEUP=1: its phase 1 on the device like the other two), at
@@ -18,7 +21,7 @@ trace (HIP's timestamps of every dispatch):
 
   rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -- python tools/bam_counts_bench.py
 
-and --kernel-trace DIR, given the same --repeats and --depth, reads that run's kernel trace back: the add passes' dispatches in the order
+and --kernel-trace DIR, given the same --repeats, --depth and --quals, reads that run's kernel trace back: the add passes' dispatches in the order
 the forms ran, each form's fastest, median and slowest dispatch.
 
 The adds are counted by the model (tests/bam_counts_model.py): one per tallied entry and one more per counted observation; the depth form
@@ -58,14 +61,29 @@ def trace_report(a):
     calls = a.repeats + 3
     lines = Lines()
     lines.append(f"# the add passes' kernel times of one profiled run (rocprofv3 --kernel-trace), {calls} dispatches a form: min / median / max, microseconds")
+    narrow = [f"bvc_bam_counts_quals, n_quals {q}, n_groups {g}" for q in a.quals for g in (0, 5)]
     for kernel, forms in (("bam_counts_kernel<true>", ["bvc_bam_counts, n_groups 0", "bvc_bam_counts, n_groups 5"]),
-                          ("bam_counts_depth_kernel", [f"bvc_bam_counts_depth, n_groups {g}" for g in a.depth])):
+                          ("bam_counts_depth_kernel", [f"bvc_bam_counts_depth, n_groups {g}" for g in a.depth]),
+                          ("bam_counts_quals_kernel<true>", narrow),
+                          # the dry passes, every form's pooled: the wide one serves bvc_bam_counts and bvc_bam_counts_depth
+                          ("bam_counts_kernel<false>", ["the dry pass of the wide forms"] * (2 + len(a.depth))),
+                          ("bam_counts_quals_kernel<false>", ["the dry pass of the narrow forms"] * len(narrow))):
         mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if kernel in r["Kernel_Name"])
         if len(mine) != calls * len(forms):
             raise SystemExit(f"{kernel}: {len(mine)} dispatches in the trace, {calls * len(forms)} expected")
+        if len(set(forms)) == 1 and len(forms) > 1:                # (pooled: one line for all of them)
+            us = [(e - b) / 1e3 for b, e in mine]
+            lines.append(f"  {kernel:30s} {forms[0]:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}  ({len(us)} dispatches)")
+            continue
         for i, form in enumerate(forms):
             us = [(e - b) / 1e3 for b, e in mine[i * calls:(i + 1) * calls]]
-            lines.append(f"  {kernel:26s} {form:36s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}")
+            lines.append(f"  {kernel:30s} {form:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}")
+    mine = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "acc_expand_kernel" in r["Kernel_Name"]]
+    if mine:
+        q = a.quals[0]
+        gbs = 8192 * (16 * q + 2048) / (statistics.median(mine) * 1e-6) / 1e9
+        lines.append(f"  {'acc_expand_kernel':30s} {f'8,192 rows of {q} columns, {len(mine)} dispatches':44s} {min(mine):8.1f} {statistics.median(mine):8.1f} {max(mine):8.1f}"
+                     f"  ({8192 * (16 * q + 2048)} bytes read and written: {gbs:.0f} GB/s at the median)")
     if a.out:
         with open(a.out, "w") as f:
             f.write("\n".join(lines) + "\n")
@@ -115,7 +133,8 @@ def main():
     ap.add_argument("--process", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--depth", type=int, action="append", default=[], help="also bvc_bam_counts_depth with this many groups (may be given more than once)")
-    ap.add_argument("--kernel-trace", default=None, help="the directory of a rocprofv3 --kernel-trace run of this tool with the same --repeats and --depth")
+    ap.add_argument("--quals", type=int, action="append", default=[], help="also bvc_bam_counts_quals with this many quality columns, 0 and 5 groups (may be given more than once)")
+    ap.add_argument("--kernel-trace", default=None, help="the directory of a rocprofv3 --kernel-trace run of this tool with the same --repeats, --depth and --quals")
     a = ap.parse_args()
     if a.kernel_trace:
         a.repeats = 5 if a.repeats is None else a.repeats
@@ -194,6 +213,45 @@ def main():
         lines.append(f"  bvc_bam_counts_depth, n_groups {n_groups}: {t * 1e3:8.2f} ms a call, {adds} atomic adds into "
                      f"{(d_counts.numel() + d_tally.numel() + d_depth.numel()) * 4} bytes of accumulators ({adds / t / 1e6:.1f} M adds/s over the whole call); "
                      f"the most adds of one call into one depth word: {hot}")
+    for n_quals in a.quals:
+        from basevarc_amd import SiteAcc
+        from tests import bam_counts_quals_model as qm
+        want = qm.expected(None, None, None, None, pv, None, None, n_quals, exp=exp)
+        if want["rc"] != 0:
+            raise SystemExit(f"--quals {n_quals}: the records hold a counted quality of {n_quals} or more")
+        for n_groups in (0, 5):
+            labels = (np.arange(n) % 7).astype(np.uint8)
+            want = qm.expected(None, None, None, None, pv, None, None, n_quals, labels, n_groups, exp=exp)
+            adds = int(want["counts"].sum()) + (int(want["depth"].sum()) if n_groups else 0) + int(want["tally"]["strand_base"].sum()) + \
+                int(want["tally"]["n_other"].sum()) + int(want["tally"]["n_indel"].sum())
+            d_counts = torch.zeros(P * 4 * n_quals, dtype=torch.int32, device="cuda")
+            d_tally = torch.zeros(P * 12, dtype=torch.int32, device="cuda")
+            d_depth = torch.zeros(P * n_groups * 4, dtype=torch.int32, device="cuda") if n_groups else None
+            kw = dict(group_depth=d_depth, group_of_sample=dev(labels) if n_groups else None, n_groups=n_groups, sample_status=st2)
+            assert ctx.bam_counts_quals(*head, d_pos, rg_s, len(refseq), n_quals, d_counts, d_tally, **kw)[0] == 0
+            ctx.synchronize()
+            assert (d_counts.cpu().numpy().view(np.uint32) == want["counts"].reshape(-1)).all() and d_tally.cpu().numpy().tobytes() == want["tally"].tobytes()
+            assert not n_groups or (d_depth.cpu().numpy().view(np.uint32) == want["depth"].reshape(-1)).all()
+            t = best_of(ctx, a.repeats, lambda: ctx.bam_counts_quals(*head, d_pos, rg_s, len(refseq), n_quals, d_counts, d_tally, **kw))
+            nbytes = (d_counts.numel() + d_tally.numel() + (d_depth.numel() if n_groups else 0)) * 4
+            lines.append(f"  bvc_bam_counts_quals, n_quals {n_quals}, n_groups {n_groups}: {t * 1e3:8.2f} ms a call, {adds} atomic adds into {nbytes} bytes "
+                         f"of accumulators ({adds / t / 1e6:.1f} M adds/s over the whole call)")
+        # the accumulators: the time to make (and zero) one of each kind for the region, and fetches of 8,192 expanded rows
+        made = {}
+        for kind, make in (("wide (bvc_site_acc_create)", lambda: SiteAcc(0, P)), (f"{n_quals} columns (bvc_site_acc_create_quals)", lambda: SiteAcc.create_quals(0, P, n_quals))):
+            best = None
+            for _ in range(a.repeats + 2):
+                t = time.perf_counter()
+                acc = make()
+                dt = time.perf_counter() - t
+                used = acc.bytes()[0]
+                acc.close()
+                best = dt if best is None else min(best, dt)
+            made[kind] = (best, used)
+            lines.append(f"  an accumulator of {P} positions, {kind}: {best * 1e3:8.2f} ms to make and zero, {used} bytes")
+        with SiteAcc.create_quals(0, P, n_quals) as acc:
+            t = best_of(ctx, 6, lambda: acc.get(ctx, 1000, 8192))
+            lines.append(f"  bvc_site_acc_get, 8,192 rows of {n_quals} columns expanded and brought to the host: {t * 1e3:8.2f} ms a call")
     ctx.close()
     text = "\n".join(lines) + "\n"
     if a.out:
