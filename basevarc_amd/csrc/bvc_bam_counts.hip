@@ -6,9 +6,12 @@
 // of counts, the groups' depths beside it and bam_group_depth_kernel.hip as their add pass.  And the tenth header's
 // (include/bvc_site_acc_quals.h: bvc_bam_counts_quals, the accumulator's third kind): the same calls again with narrow rows of counts
 // [position][4][n_quals], bam_counts_quals_kernel.hip as both passes, one more verdict (status 5) behind the existing one, and
-// acc_expand_kernel between narrow rows and the callers of bvc_site_acc_get / bvc_site_acc_lrt.
+// acc_expand_kernel between narrow rows and the callers of bvc_site_acc_get / bvc_site_acc_lrt.  And the eleventh header's
+// (include/bvc_site_acc_pack.h: bvc_site_acc_pack and bvc_site_acc_add_packed, beside bvc_site_acc_get): an accumulator's rows as the
+// entries of their non-zero words and back, acc_pack_kernel.hip -- size pass -> scan -> the wait for the total -> place pass, and dry pass
+// -> first fault -> the wait for the verdict -> add pass.
 #include "bvc_ctx.h"
-#include "../../include/bvc_site_acc_quals.h"
+#include "../../include/bvc_site_acc_pack.h"
 
 // An accumulator is no part of a context: its device memory is its own, and its bookkeeping is fixed when it is made (the adds are atomic).
 struct bvc_site_acc {
@@ -24,6 +27,13 @@ struct bvc_site_acc {
     size_t slots() const { return n_groups > 0 ? (size_t)n_groups + 1 : 1; }
     size_t row_words() const { return n_quals > 0 ? (size_t)n_quals * 4 : slots() * BVC_NCLASS; }
     bool expanded() const { return n_quals > 0 && n_quals < 128; }   // its rows are not the [512] layout: acc_expand_kernel makes it
+    size_t logical_words() const { return slots() * BVC_NCLASS + 10 + (size_t)depth_groups * 4; }   // W of bvc_site_acc_pack.h
+    // rows from t0 on as acc_pack_kernel.hip's kernels see them (128 columns are stored as the wide layout stores them)
+    AccRowShape shape(int32_t t0) const
+    {
+        return AccRowShape{(int64_t)t0, (uint32_t)(row_words() / 4), expanded() ? (uint32_t)n_quals / 4u : 0u, (uint32_t)(slots() * BVC_NCLASS),
+                           (uint32_t)depth_groups};
+    }
 };
 
 // Rows a call expands at a time into the context's scratch (bvc_site_acc_get, bvc_site_acc_lrt on narrow rows): 64 MiB of [512] rows
@@ -384,6 +394,132 @@ int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
         BVC_HIP_D(ctx, hipMemcpyAsync(counts, acc->d_counts + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, hipMemcpyAsync(tally, acc->d_tally + t0, (size_t)n * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_row_words(const bvc_site_acc *acc, int32_t *row_words, int32_t *slots, int32_t *depth_groups)
+{
+    if (!acc) return BVC_ERR_ARG;
+    if (row_words) *row_words = (int32_t)acc->logical_words();
+    if (slots) *slots = (int32_t)acc->slots();
+    if (depth_groups) *depth_groups = acc->depth_groups;
+    return BVC_OK;
+}
+
+int bvc_site_acc_pack(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n, int64_t *row_start, uint16_t *cell, uint32_t *count,
+                      int64_t entries_cap, int64_t *n_entries, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
+    if (!row_start || !n_entries) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (entries_cap < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const bool dev = (flags & BVC_PTR_DEVICE) != 0;
+    const size_t nr = (size_t)n;
+    if (n == 0) {
+        *n_entries = 0;
+        if (!dev) { row_start[0] = 0; return BVC_OK; }
+        BVC_HIP_D(ctx, hipMemsetAsync(row_start, 0, 8, ctx->stream));
+        return BVC_OK;
+    }
+    // size pass -> scan -> the one wait, for the total (in the host form row_start comes down with it)
+    uint32_t *d_row_n; int64_t *d_row_start = row_start;
+    rc = carve(ctx, ctx->d_acc, 256, [&](Layout &L) {
+        d_row_n = L.take<uint32_t>(nr);
+        if (!dev) d_row_start = L.take<int64_t>(nr + 1);
+    });
+    if (rc != BVC_OK) return rc;
+    const AccRowShape s = acc->shape(t0);
+    PinIO io(ctx);
+    if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
+    BVC_HIP_D(ctx, launch_acc_pack(ctx->stream, false, n, s, acc->d_counts, acc->d_tally, acc->d_depth, d_row_n, nullptr, nullptr, nullptr));
+    BVC_HIP_D(ctx, launch_acc_pack_scan(ctx->stream, n, d_row_n, d_row_start));
+    int64_t total = 0;
+    BVC_HIP_D(ctx, io.d2h(&total, d_row_start + nr, 8));
+    if (!dev) BVC_HIP_D(ctx, hipMemcpyAsync(row_start, d_row_start, (nr + 1) * 8, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    *n_entries = total;
+    if (total > entries_cap) return BVC_ACC_MORE;
+    if (total == 0) return BVC_OK;
+    if (!cell || !count) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (dev) {
+        BVC_HIP_D(ctx, launch_acc_pack(ctx->stream, true, n, s, acc->d_counts, acc->d_tally, acc->d_depth, nullptr, d_row_start, cell, count));
+        return BVC_OK;
+    }
+    // host pointers: the entries are placed in the staging buffer and come down from there (d_row_start stays where it is, in d_acc)
+    uint16_t *d_cell; uint32_t *d_count;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { d_cell = L.take<uint16_t>((size_t)total); d_count = L.take<uint32_t>((size_t)total); });
+    if (rc != BVC_OK) return rc;
+    BVC_HIP_D(ctx, launch_acc_pack(ctx->stream, true, n, s, acc->d_counts, acc->d_tally, acc->d_depth, nullptr, d_row_start, d_cell, d_count));
+    BVC_HIP_D(ctx, hipMemcpyAsync(cell, d_cell, (size_t)total * 2, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(count, d_count, (size_t)total * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    return BVC_OK;
+}
+
+int bvc_site_acc_add_packed(bvc_ctx *ctx, bvc_site_acc *acc, int32_t t0, int32_t n, const int64_t *row_start, const uint16_t *cell,
+                            const uint32_t *count, int64_t n_entries, uint32_t flags)
+{
+    if (!ctx) return BVC_ERR_ARG;
+    int rc = check_acc(ctx, acc);
+    if (rc != BVC_OK) return rc;
+    if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
+    if (n_entries < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
+    if (!row_start || (n_entries > 0 && (!cell || !count))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    if (n == 0) return n_entries == 0 ? BVC_OK : fail(ctx, BVC_ERR_DATA, "row 0: row_start does not end at n_entries (no rows, yet entries)");
+    BVC_HIP(ctx, hipSetDevice(ctx->device));
+    const bool dev = (flags & BVC_PTR_DEVICE) != 0;
+    const size_t nr = (size_t)n, ne = (size_t)n_entries;
+    uint32_t *d_fault; int64_t *d_first;
+    if ((rc = carve(ctx, ctx->d_acc, 256, [&](Layout &L) { d_fault = L.take<uint32_t>(nr); d_first = L.take<int64_t>(2); })) != BVC_OK) return rc;
+    const int64_t *d_row_start = row_start; const uint16_t *d_cell = cell; const uint32_t *d_count = count;
+    if (!dev) {
+        // host pointers: the piece lives in the staging buffer for the length of the call
+        int64_t *u_rs; uint16_t *u_cell; uint32_t *u_count;
+        rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { u_rs = L.take<int64_t>(nr + 1); u_cell = L.take<uint16_t>(ne); u_count = L.take<uint32_t>(ne); });
+        if (rc != BVC_OK) return rc;
+        BVC_HIP_D(ctx, hipMemcpyAsync(u_rs, row_start, (nr + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+        if (ne) {
+            BVC_HIP_D(ctx, hipMemcpyAsync(u_cell, cell, ne * 2, hipMemcpyHostToDevice, ctx->stream));
+            BVC_HIP_D(ctx, hipMemcpyAsync(u_count, count, ne * 4, hipMemcpyHostToDevice, ctx->stream));
+        }
+        d_row_start = u_rs; d_cell = u_cell; d_count = u_count;
+    }
+    const AccRowShape s = acc->shape(t0);
+    const int32_t nq = acc->expanded() ? acc->n_quals : 128;
+    PinIO io(ctx);
+    if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
+    // dry pass -> first fault -> the one wait, for the verdict: nothing is added unless the whole piece is sound
+    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, false, n, s, nq, d_row_start, d_cell, d_count, n_entries, nullptr, nullptr, acc->d_depth, d_fault));
+    BVC_HIP_D(ctx, launch_acc_first_fault(ctx->stream, n, d_fault, d_first));
+    int64_t first[2] = {0, 0};
+    BVC_HIP_D(ctx, io.d2h(first, d_first, sizeof first));
+    BVC_HIP_D(ctx, wait_stream(ctx));
+    io.deliver();
+    if (first[1] != 0) {
+        char msg[200];
+        const long long t = (long long)first[0];
+        switch ((uint32_t)first[1]) {
+        case kAccFaultRowStart:
+            std::snprintf(msg, sizeof msg, "row %lld: row_start must start at 0, never decrease and end at n_entries = %lld", t, (long long)n_entries);
+            break;
+        case kAccFaultCell:
+            std::snprintf(msg, sizeof msg, "row %lld: a cell of %d or more, and the accumulator's row has %d words", t, (int)acc->logical_words(),
+                          (int)acc->logical_words());
+            break;
+        case kAccFaultOrder: std::snprintf(msg, sizeof msg, "row %lld: the cells of a row must ascend strictly", t); break;
+        default:
+            std::snprintf(msg, sizeof msg, "row %lld: a count of a base quality of %d or more, and the counts keep n_quals = %d quality columns", t, (int)nq,
+                          (int)nq);
+        }
+        return fail(ctx, BVC_ERR_DATA, msg);
+    }
+    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, true, n, s, nq, d_row_start, d_cell, d_count, n_entries, acc->d_counts, acc->d_tally, acc->d_depth,
+                                         nullptr));
+    if (!dev) BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }
 

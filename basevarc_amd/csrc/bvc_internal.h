@@ -344,6 +344,23 @@ hipError_t launch_bam_counts_quals(hipStream_t stream, bool add, int32_t n_sampl
 hipError_t launch_first_status(hipStream_t stream, int32_t n_samples, const uint32_t *sample_status, uint32_t which, int64_t *out);
 hipError_t launch_acc_expand(hipStream_t stream, int64_t n_rows, int32_t n_quals, const uint32_t *narrow, uint32_t *wide);
 
+// acc_pack_kernel.hip: an accumulator's rows <-> (row_start, cell, count) entries of their logical rows (include/bvc_site_acc_pack.h).  The
+// rows a launch works on as the kernels see them: row0 is the first of them in the accumulator's arrays, count_pieces the 16-byte pieces of
+// a position's counts as they are STORED (slots x 128, or n_quals for narrow rows, whose q4 = n_quals / 4; q4 = 0: the wide layout),
+// count_cells the LOGICAL count cells (slots x 512).
+struct AccRowShape { int64_t row0; uint32_t count_pieces, q4, count_cells, depth_groups; };
+enum : uint32_t { kAccFaultRowStart = 1, kAccFaultCell = 2, kAccFaultOrder = 3, kAccFaultQual = 4 };   // a row's fault in row_fault
+// place = false: row_n [n_rows] (nothing of row_start, cell or count is touched); place = true: cell and count through row_start [n_rows + 1]
+hipError_t launch_acc_pack(hipStream_t stream, bool place, int64_t n_rows, const AccRowShape &s, const uint32_t *counts, const ::bvc_bam_site_tally *tally,
+                           const uint32_t *depth, uint32_t *row_n, const int64_t *row_start, uint16_t *cell, uint32_t *count);
+hipError_t launch_acc_pack_scan(hipStream_t stream, int64_t n_rows, const uint32_t *row_n, int64_t *row_start);
+// add = false: row_fault [n_rows] (nothing is added); add = true: the adds (row_fault unused).  n_quals: the columns stored, 128 for wide rows
+hipError_t launch_acc_add_packed(hipStream_t stream, bool add, int64_t n_rows, const AccRowShape &s, int32_t n_quals, const int64_t *row_start,
+                                 const uint16_t *cell, const uint32_t *count, int64_t n_entries, uint32_t *counts, ::bvc_bam_site_tally *tally,
+                                 uint32_t *depth, uint32_t *row_fault);
+// out[0] = the first row whose fault is not 0 (0x7FFFFFFFFFFFFFFF: none), out[1] = that fault
+hipError_t launch_acc_first_fault(hipStream_t stream, int64_t n_rows, const uint32_t *row_fault, int64_t *out);
+
 // store_kernel.hip: temp batches kept on the device (include/bvc_store.h).  A kept batch as the kernels see it: the device addresses of its
 // rec_start row and of its records, and the records' bytes (what every word of the row is clamped with).
 constexpr int kStoreGrid = 1024;         // workgroups of store_gather_kernel at most: a tile of more items sends each round its loop again

@@ -14,6 +14,7 @@
 #include "../../include/bvc_store.h"
 #include "bam.h"
 #include "bgzf.h"
+#include "counts_file.h"
 #include "inflate.h"
 #include "knobs.h"
 #include "pileup.h"
@@ -106,6 +107,84 @@ int32_t bvchost_counts_group_map(const char *file_text, const char *samples, uin
     for (size_t c = 0; c < cols.size() && (int32_t)c < cap; ++c) column_file_index[c] = cols[c];
     *n_columns = (int32_t)cols.size();
     return (int32_t)names.size();
+}
+// BVC_HOST_COUNTS_LOAD as the host program reads it (parse_counts_load): the number of files, their names one a line in out (truncated to
+// cap); 0 for a null pointer (unset), -1 for a value it refuses.  BVC_HOST_COUNTS_SAVE (parse_counts_save): 0 unset, 1 a name, -1 refused
+int32_t bvchost_parse_counts_load(const char *value, char *out, size_t cap)
+{
+    std::vector<std::string> files;
+    if (!parse_counts_load(value, files)) return -1;
+    std::string text;
+    for (auto const &f : files) text += f + "\n";
+    copy_out(text, out, cap);
+    return (int32_t)files.size();
+}
+int32_t bvchost_parse_counts_save(const char *value) { return parse_counts_save(value); }
+uint64_t bvchost_counts_fnv1a64(const void *data, int64_t n) { return counts_fnv1a64(data, (size_t)n); }
+// The counts file over plain arrays (counts_file.h).  ints: rg_s, rg_e, n_positions, mapq, slots, depth_groups, n_quals; text: the
+// chromosome's line, then "G\t<group name>" and "B\t<path>\t<sample>" lines; the pieces' t0 and n [n_pieces], their row_start arrays
+// ([n + 1] each), cells and counts one behind the other.  Returns 0, or 1 with the writer's line in err.
+int32_t bvchost_counts_file_write(const char *path, const int32_t *ints, uint64_t pos_hash, const char *text, int32_t n_pieces, const int32_t *t0,
+                                  const int32_t *n, const int64_t *row_start, const uint16_t *cell, const uint32_t *count, char *err, size_t err_cap)
+{
+    CountsFileMeta m;
+    m.rg_s = ints[0]; m.rg_e = ints[1]; m.n_positions = ints[2]; m.mapq = ints[3];
+    m.slots = (uint32_t)ints[4]; m.depth_groups = (uint32_t)ints[5]; m.n_quals = (uint32_t)ints[6];
+    m.pos_hash = pos_hash;
+    std::istringstream in(text);
+    std::string line, e;
+    std::getline(in, m.chrom);
+    while (std::getline(in, line)) {
+        if (line.compare(0, 2, "G\t") == 0) m.groups.push_back(line.substr(2));
+        else if (line.compare(0, 2, "B\t") == 0) {
+            const size_t tab = line.find('\t', 2);
+            m.bam_paths.push_back(line.substr(2, tab - 2));
+            m.bam_samples.push_back(tab == std::string::npos ? std::string() : line.substr(tab + 1));
+        }
+    }
+    CountsFileWriter w;
+    bool ok = w.open(path, m, e);
+    for (int32_t i = 0; i < n_pieces && ok; ++i) {
+        ok = w.piece(t0[i], n[i], row_start, cell, count, e);
+        cell += row_start[n[i]]; count += row_start[n[i]]; row_start += n[i] + 1;
+    }
+    ok = ok && w.close(e);
+    if (!ok) copy_out(e, err, err_cap);
+    return ok ? 0 : 1;
+}
+// The way back.  totals [3]: the pieces, the row_start words and the entries the file holds, always written when the file is sound.
+// Returns 0 with everything delivered, 2 where a cap is too small (totals and the header are delivered), 1 with the reader's line in err.
+int32_t bvchost_counts_file_read(const char *path, int32_t *ints, uint64_t *pos_hash, char *text, size_t text_cap, int32_t pieces_cap, int32_t *t0,
+                                 int32_t *n, int64_t rs_cap, int64_t *row_start, int64_t entries_cap, uint16_t *cell, uint32_t *count, int64_t *totals,
+                                 char *err, size_t err_cap)
+{
+    CountsFileMeta m;
+    CountsFileReader r;
+    std::string e;
+    if (!r.open(path, m, e)) { copy_out(e, err, err_cap); return 1; }
+    ints[0] = m.rg_s; ints[1] = m.rg_e; ints[2] = m.n_positions; ints[3] = m.mapq;
+    ints[4] = (int32_t)m.slots; ints[5] = (int32_t)m.depth_groups; ints[6] = (int32_t)m.n_quals;
+    *pos_hash = m.pos_hash;
+    std::string t = m.chrom + "\n";
+    for (auto const &g : m.groups) t += "G\t" + g + "\n";
+    for (size_t i = 0; i < m.bam_paths.size(); ++i) t += "B\t" + m.bam_paths[i] + "\t" + m.bam_samples[i] + "\n";
+    const bool text_fits = copy_out(t, text, text_cap) <= text_cap;
+    int64_t pieces = 0, words = 0, entries = 0;
+    CountsPiece p;
+    int rc;
+    while ((rc = r.next(p, e)) == 1) {
+        const int64_t ne = (int64_t)p.cell.size();
+        if (pieces < pieces_cap && words + p.n + 1 <= rs_cap && entries + ne <= entries_cap) {
+            t0[pieces] = p.t0; n[pieces] = p.n;
+            std::copy(p.row_start.begin(), p.row_start.end(), row_start + words);
+            std::copy(p.cell.begin(), p.cell.end(), cell + entries);
+            std::copy(p.count.begin(), p.count.end(), count + entries);
+        }
+        ++pieces; words += p.n + 1; entries += ne;
+    }
+    if (rc < 0) { copy_out(e, err, err_cap); return 1; }
+    totals[0] = pieces; totals[1] = words; totals[2] = entries;
+    return text_fits && pieces <= pieces_cap && words <= rs_cap && entries <= entries_cap ? 0 : 2;
 }
 int32_t bvchost_device_of_thread(int32_t ithread, int32_t devices_present, int32_t gpus_option) { return device_of_thread(ithread, devices_present, gpus_option); }
 int32_t bvchost_merge_subfiles(const char *out_prefix, const char *suffix, int32_t thread)

@@ -84,6 +84,26 @@ inline int parse_counts_quals(const char *v)
     return q >= 4 && q <= 128 && q % 4 == 0 ? q : -1;
 }
 
+// BVC_HOST_COUNTS_LOAD as text: FILE[:FILE...], the counts files (counts_file.h) a --tmp-format counts run adds into its accumulator before
+// pass 1.  nullptr (unset): no file, true.  false: an empty value or an empty name between, in front of or behind the colons.
+inline bool parse_counts_load(const char *v, std::vector<std::string> &files)
+{
+    files.clear();
+    if (!v) return true;
+    const std::string s(v);
+    for (size_t a = 0;;) {
+        const size_t e = s.find(':', a);
+        const std::string f = s.substr(a, e == std::string::npos ? std::string::npos : e - a);
+        if (f.empty()) { files.clear(); return false; }
+        files.push_back(f);
+        if (e == std::string::npos) return true;
+        a = e + 1;
+    }
+}
+// BVC_HOST_COUNTS_SAVE as text: the one counts file the run writes after pass 1 (a colon is part of the name).  0: unset; 1: a name;
+// -1: an empty value
+inline int parse_counts_save(const char *v) { return !v ? 0 : *v ? 1 : -1; }
+
 struct Knobs {
     static bool set(const char *name) { return getenv(name) != nullptr; }
     static int num(const char *name, int dflt) { const char *v = getenv(name); return v ? atoi(v) : dflt; }
@@ -176,6 +196,14 @@ struct Knobs {
     // the run before anything is opened (run_basetype asks parse_counts_quals where its refusals stand; -1 here).  Default 128: the
     // accumulators of bvc_site_acc_create / _create_depth, as before the knob
     const int counts_quals = parse_counts_quals(getenv("BVC_HOST_COUNTS_QUALS"));
+    // --tmp-format counts only (every other format ignores them; unset, nothing changes): counts files (counts_file.h,
+    // docs/COUNTS_FILES.md).  BVC_HOST_COUNTS_LOAD=FILE[:FILE...]: before pass 1 every file's pieces are added into the accumulator
+    // (bvc_site_acc_add_packed) and every BAM a file records as counted is skipped in pass 1.  BVC_HOST_COUNTS_SAVE=FILE: after pass 1 the
+    // accumulator is packed in pieces of rows (bvc_site_acc_pack) and written to FILE with the list of every BAM counted, loaded ones
+    // included; the run then ends with status 0 and writes no .vcf.gz or .cvg.gz -- the counts analogue of --load.  An empty value or an
+    // empty name in the list ends the run before anything is opened (run_basetype asks the parse rules where its refusals stand)
+    const std::string counts_save = getenv("BVC_HOST_COUNTS_SAVE") ? getenv("BVC_HOST_COUNTS_SAVE") : "";
+    const std::vector<std::string> counts_load = [] { std::vector<std::string> f; parse_counts_load(getenv("BVC_HOST_COUNTS_LOAD"), f); return f; }();
     const bool two_byte_tiles =set("BVC_HOST_TWO_BYTE_TILES");              // set: never one byte per observation in the CPU parser's tiles
     const bool no_crc = set("BVC_HOST_NO_CRC");                              // set: the device does not check the CRC32 of the blocks it inflates
     // tests only: added to every base quality as it is read, so that data whose qualities stop at 41 can exercise the tiles that do not

@@ -33,9 +33,11 @@
 #include "../../include/bvc_popmatrix.h"
 #include "../../include/bvc_store.h"
 #include "../../include/bvc_bam_deflate.h"
+#include "../../include/bvc_site_acc_pack.h"
 #include "bam.h"
 #include "bam_blocks.h"
 #include "bam_gather.h"
+#include "counts_file.h"
 #include "feeds.h"
 #include "popmatrix.h"
 
@@ -79,7 +81,10 @@ static const char *BASETYPE_MESSAGE =
     "                           (BVC_HOST_STORE_GB caps the counts, then those batches; not with --group, --load, --keep_tmp\n"
     "                           or --gpus above 1; BVC_HOST_COUNTS_GROUPS=1 takes --group: 16 bytes a group and position more,\n"
     "                           32 distinct group names in the file at the most; BVC_HOST_COUNTS_QUALS=Q, a multiple of 4 in\n"
-    "                           4..128 [128]: 16 x Q bytes a position, and a base quality of Q or more ends the run)\n";
+    "                           4..128 [128]: 16 x Q bytes a position, and a base quality of Q or more ends the run;\n"
+    "                           BVC_HOST_COUNTS_SAVE=FILE: the class counts are written to FILE after the first pass and the run\n"
+    "                           ends there; BVC_HOST_COUNTS_LOAD=FILE[:FILE...]: such files are added before the first pass,\n"
+    "                           which skips the BAMs they record)\n";
 
 static const char *POPMATRIX_MESSAGE =
     "Commands: BaseVarC popmatrix\n"
@@ -477,12 +482,34 @@ struct CountsPass {
 struct GroupFile {
     std::vector<std::string> ids, groups, names;    // the lines in order; the distinct group names, sorted
 };
-static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
-                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run, const GroupFile *gf, int quals)
+// What the counts files of BVC_HOST_COUNTS_LOAD say of the run's BAMs, per BAM of --input: the file that records it as counted (-1: none,
+// pass 1 piles it up) and its sample name as that file has it
+struct LoadedCounts {
+    std::vector<std::string> files;
+    std::vector<int> file_of;
+    std::vector<std::string> sample;
+    std::atomic<int> piled{0};                      // batches pass 1 opened
+    int64_t skipped = 0, entries = 0, bytes = 0;
+};
+static void bt_r_counts(const std::vector<std::string> &all_bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+                        int32_t rg_s, int32_t rg_e, int nb, int bc, int ib, bvc_site_acc *acc, MemRun &run, const GroupFile *gf, int quals,
+                        LoadedCounts &loaded)
 {
+    const size_t a0 = (size_t)ib * bc, a1 = (ib == nb - 1) ? all_bams.size() : (size_t)(ib + 1) * bc;
+    // the batch's BAMs that no loaded file records: a batch without one is not opened, its names come from the files
+    std::vector<std::string> bams;
+    for (size_t b = a0; b < a1; ++b)
+        if (loaded.file_of[b] < 0) bams.push_back(all_bams[b]);
+    std::vector<std::string> &names_out = run.names[(size_t)ib];
+    names_out.clear();
+    if (bams.empty()) {
+        for (size_t b = a0; b < a1; ++b) names_out.push_back(loaded.sample[b]);
+        return;
+    }
+    ++loaded.piled;
     static thread_local LoadDevice dev;
     if (!dev.ctx && bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
-    const size_t b0 = (size_t)ib * bc, b1 = (ib == nb - 1) ? bams.size() : (size_t)(ib + 1) * bc, ns = b1 - b0;
+    const size_t b0 = 0, b1 = bams.size(), ns = b1 - b0;
     const int32_t beg0 = std::max(0, rg_s - 1 - 1000), end0 = rg_e + 1000;
     BamBatch batch;
     batch.open(bams, b0, b1, chr);
@@ -509,8 +536,106 @@ static void bt_r_counts(const std::vector<std::string> &bams, const std::vector<
     });
     for (size_t s = 0; s < ns; ++s)
         if (batch.rid[s] < 0 || status[s] == 1u) std::cerr << "warning: " << batch.sms[s] << " region " << opt::region << " is empty." << std::endl;
-    run.names[(size_t)ib] = batch.sms;
+    // (a batch with some BAMs recorded: the names are spliced in input order)
+    for (size_t b = a0, s = 0; b < a1; ++b) names_out.push_back(loaded.file_of[b] < 0 ? batch.sms[s++] : loaded.sample[b]);
     ++g_device_batches;
+}
+
+// The counts files of BVC_HOST_COUNTS_LOAD, opened and held against the run before anything is piled up: every refusal that a header can
+// decide is one line naming the file and the field.  The readers stay open for counts_files_add.
+struct CountsFileRun {
+    CountsFileMeta meta;                            // what a file of THIS run records (the BAM lists are filled when it is saved)
+    std::deque<CountsFileReader> readers;
+};
+static void counts_files_open(const std::vector<std::string> &files, const std::vector<std::string> &bams, CountsFileRun &cr, LoadedCounts &loaded)
+{
+    loaded.files = files;
+    loaded.file_of.assign(bams.size(), -1);
+    loaded.sample.assign(bams.size(), std::string());
+    std::unordered_map<std::string, size_t> index_of;
+    // (recorded BAMs are matched to --input by their path strings: with files to load, a path listed twice has no one line to match)
+    for (size_t b = 0; b < bams.size() && !files.empty(); ++b)
+        if (!index_of.insert({bams[b], b}).second)
+            throw std::runtime_error("ERROR: --input lists " + bams[b] + " twice, and BVC_HOST_COUNTS_LOAD matches the counts files' BAM lists to it by path");
+    const CountsFileMeta &want = cr.meta;
+    for (size_t f = 0; f < files.size(); ++f) {
+        cr.readers.emplace_back();
+        CountsFileMeta m;
+        std::string err;
+        if (!cr.readers.back().open(files[f], m, err)) throw std::runtime_error("ERROR: " + err);
+        auto refuse = [&](const std::string &field, const std::string &has, const std::string &run_has) {
+            throw std::runtime_error("ERROR: " + files[f] + ": the counts file's " + field + " is " + has + ", the run's is " + run_has);
+        };
+        auto join = [](const std::vector<std::string> &v) { std::string t; for (auto const &x : v) t += (t.empty() ? "" : ",") + x; return "[" + t + "]"; };
+        if (m.chrom != want.chrom) refuse("chromosome", m.chrom, want.chrom);
+        if (m.rg_s != want.rg_s || m.rg_e != want.rg_e)
+            refuse("range", std::to_string(m.rg_s) + "-" + std::to_string(m.rg_e), std::to_string(want.rg_s) + "-" + std::to_string(want.rg_e));
+        if (m.n_positions != want.n_positions) refuse("n_positions", std::to_string(m.n_positions), std::to_string(want.n_positions));
+        if (m.pos_hash != want.pos_hash) refuse("positions hash", std::to_string(m.pos_hash), std::to_string(want.pos_hash));
+        if (m.mapq != want.mapq) refuse("-q", std::to_string(m.mapq), std::to_string(want.mapq));
+        if (m.slots != want.slots) refuse("slots", std::to_string(m.slots), std::to_string(want.slots));
+        if (m.depth_groups != want.depth_groups) refuse("depth_groups", std::to_string(m.depth_groups), std::to_string(want.depth_groups));
+        if (m.groups != want.groups) refuse("group names", join(m.groups), join(want.groups));
+        for (size_t i = 0; i < m.bam_paths.size(); ++i) {
+            auto it = index_of.find(m.bam_paths[i]);
+            if (it == index_of.end()) throw std::runtime_error("ERROR: " + files[f] + ": the counts file's BAM list records " + m.bam_paths[i] + ", which is not in --input");
+            const size_t b = it->second;
+            if (loaded.file_of[b] >= 0)
+                throw std::runtime_error("ERROR: " + files[f] + ": the counts file's BAM list records " + m.bam_paths[i] + ", which " +
+                                         files[(size_t)loaded.file_of[b]] + " records too");
+            loaded.file_of[b] = (int)f;
+            loaded.sample[b] = m.bam_samples[i];
+            ++loaded.skipped;
+        }
+    }
+}
+// Every loaded file's pieces added into the new accumulator (bvc_site_acc_add_packed), in front of pass 1
+static void counts_files_add(bvc_ctx *ctx, bvc_site_acc *acc, int quals, CountsFileRun &cr, LoadedCounts &loaded)
+{
+    CountsPiece p;
+    std::string err;
+    for (size_t f = 0; f < cr.readers.size(); ++f) {
+        CountsFileReader &r = cr.readers[f];
+        int rc;
+        while ((rc = r.next(p, err)) == 1) {
+            // narrow rows (BVC_HOST_COUNTS_QUALS): a count the rows have no column for ends the run (one slot: cells 0..511 are counts)
+            for (size_t i = 0; i < p.cell.size() && quals < 128; ++i)
+                if (p.cell[i] < 512u && (int)(p.cell[i] & 127u) >= quals)
+                    throw std::runtime_error("ERROR: " + loaded.files[f] + ": the counts file holds a count of base quality " + std::to_string(p.cell[i] & 127u) +
+                                             " and the counts keep " + std::to_string(quals) + " quality columns, run with BVC_HOST_COUNTS_QUALS=128");
+            if (bvc_site_acc_add_packed(ctx, acc, p.t0, p.n, p.row_start.data(), p.cell.data(), p.count.data(), (int64_t)p.cell.size(), BVC_PTR_HOST) != BVC_OK)
+                throw std::runtime_error("ERROR: " + loaded.files[f] + ": the counts file's piece at row " + std::to_string(p.t0) + " is refused: " + bvc_last_error(ctx));
+        }
+        if (rc < 0) throw std::runtime_error("ERROR: " + err);
+        loaded.entries += r.entries();
+        loaded.bytes += r.bytes();
+    }
+    cr.readers.clear();
+}
+// The accumulator packed in pieces of rows (bvc_site_acc_pack: host memory stays bounded) and written to `path`
+static void counts_file_save(bvc_ctx *ctx, const bvc_site_acc *acc, size_t P, const std::string &path, const CountsFileMeta &meta, int64_t &entries, int64_t &bytes)
+{
+    const size_t rows = 65536;
+    CountsFileWriter w;
+    std::string err;
+    if (!w.open(path, meta, err)) throw std::runtime_error("ERROR: " + err);
+    std::vector<int64_t> row_start(rows + 1);
+    std::vector<uint16_t> cell;
+    std::vector<uint32_t> count;
+    for (size_t t0 = 0; t0 < P; t0 += rows) {
+        const size_t n = std::min(rows, P - t0);
+        int64_t need = 0;
+        int rc = bvc_site_acc_pack(ctx, acc, (int32_t)t0, (int32_t)n, row_start.data(), cell.data(), count.data(), (int64_t)cell.size(), &need, BVC_PTR_HOST);
+        if (rc == BVC_ACC_MORE) {
+            cell.resize((size_t)need); count.resize((size_t)need);
+            rc = bvc_site_acc_pack(ctx, acc, (int32_t)t0, (int32_t)n, row_start.data(), cell.data(), count.data(), (int64_t)cell.size(), &need, BVC_PTR_HOST);
+        }
+        bvc_check(ctx, rc);
+        if (!w.piece((int32_t)t0, (int32_t)n, row_start.data(), cell.data(), count.data(), err)) throw std::runtime_error("ERROR: " + err);
+    }
+    if (!w.close(err)) throw std::runtime_error("ERROR: " + err);
+    entries = w.entries();
+    bytes = w.bytes();
 }
 
 // ---- phase 2: temp batches -> tiles -> libbvc -> CVG/VCF (successor of bt_s + bt_f; the tiles' three stages: tile_runner.h, what
@@ -843,8 +968,10 @@ static void basetype_in_memory(const std::vector<std::string> &bams, const std::
 // positions from it; pass 2 piles the revisited positions -- the called ones, those with indel entries and their predecessors, a fraction of
 // a per cent -- up a second time into a store, as --tmp-format mem does for all of them, and the compute threads run on that store.  The
 // BAMs are gathered exactly twice whatever the cohort's size and the region's length; the accumulator and the store are never alive together.
+// With BVC_HOST_COUNTS_LOAD the accumulator starts from the loaded files' sum and pass 1 skips the BAMs they record; with
+// BVC_HOST_COUNTS_SAVE the run ends behind pass 1, the accumulator written to a counts file (returns true: nothing was computed).
 template <class Compute>
-static void basetype_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
+static bool basetype_counts(const std::vector<std::string> &bams, const std::vector<int32_t> &pv, const std::string &refseq, const std::string &chr,
                             int32_t rg_s, int32_t rg_e, int nb, int bc, int thread, const Knobs &knobs, const GroupFile *gf, double &t_loaded,
                             Compute compute)
 {
@@ -861,6 +988,16 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     MemRun run;
     run.names.resize((size_t)nb);
     run.sms.resize(bams.size());
+    // the counts files: what a file of this run records, and the loaded files held against it before anything is piled up
+    CountsFileRun cr;
+    LoadedCounts loaded;
+    cr.meta.chrom = chr; cr.meta.rg_s = rg_s; cr.meta.rg_e = rg_e; cr.meta.n_positions = (int32_t)P; cr.meta.mapq = opt::mapq;
+    cr.meta.pos_hash = counts_fnv1a64(pv.data(), P * sizeof(int32_t));
+    cr.meta.slots = 1; cr.meta.depth_groups = (uint32_t)G; cr.meta.n_quals = (uint32_t)Q;
+    if (gf) cr.meta.groups = gf->names;
+    counts_files_open(knobs.counts_load, bams, cr, loaded);
+    const bool files = !knobs.counts_load.empty() || !knobs.counts_save.empty();
+    int64_t saved_entries = 0, saved_bytes = 0;
     CountsPass cp;
     cp.pv = &pv;
     cp.tally.resize(P);
@@ -878,9 +1015,27 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
              : G     ? bvc_site_acc_create_depth(&acc.p, 0, (int32_t)P, (int32_t)G, budget)
                      : bvc_site_acc_create(&acc.p, 0, (int32_t)P, 0, budget)) != BVC_OK)
             throw std::runtime_error("ERROR: the device has no room: " + what + "; --tmp-format bin keeps the batches in files");
-        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run, gf, Q); });
         LoadDevice dev;
         if (bvc_create(&dev.ctx, 0) != BVC_OK) throw std::runtime_error("ERROR: no usable gfx950 device for libbvc");
+        counts_files_add(dev.ctx, acc.p, Q, cr, loaded);
+        run_pool(nb, thread, [&](int t) { bt_r_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, t, acc.p, run, gf, Q, loaded); });
+        bvc_site_acc_bytes(acc.p, &acc_bytes, nullptr);
+        if (!knobs.counts_save.empty()) {
+            // every BAM of --input is counted now, by a loaded file or by pass 1: the saved file holds the sum and the union of the lists
+            cr.meta.bam_paths = bams;
+            for (auto const &of_batch : run.names) cr.meta.bam_samples.insert(cr.meta.bam_samples.end(), of_batch.begin(), of_batch.end());
+            counts_file_save(dev.ctx, acc.p, P, knobs.counts_save, cr.meta, saved_entries, saved_bytes);
+        }
+        if (knobs.profile && files)
+            std::cerr << "[profile] main: counts files: " << knobs.counts_load.size() << " loaded (" << loaded.entries << " entries added, " << loaded.bytes
+                      << " bytes), " << loaded.skipped << " BAMs skipped, " << loaded.piled.load() << " of " << nb << " batches piled up in pass 1, "
+                      << (knobs.counts_save.empty() ? 0 : 1) << " saved (" << saved_entries << " entries written, " << saved_bytes
+                      << " bytes), accumulator " << acc_bytes << " bytes" << std::endl;
+        if (!knobs.counts_save.empty()) {
+            std::cout << "basetype counts saved -- " << knobs.counts_save << ": " << bams.size() << " BAMs, " << saved_entries << " entries, " << saved_bytes
+                      << " bytes" << std::endl;
+            return true;
+        }
         const size_t chunk = 8192;
         std::vector<int8_t> refs(chunk);
         std::vector<bvc_site_result> res(chunk);
@@ -892,7 +1047,6 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
             if (G) bvc_check(dev.ctx, bvc_site_acc_get_depth(dev.ctx, acc.p, (int32_t)t0, (int32_t)n, &cp.depth[t0 * G * 4]));
             for (size_t k = 0; k < n; ++k) called[t0 + k] = res[k].called != 0;
         }
-        bvc_site_acc_bytes(acc.p, &acc_bytes, nullptr);
     }
     if (gf) {
         // the names are known now: the groups that have a sample (read_groups' set, in its order) and each one's depth row
@@ -938,6 +1092,7 @@ static void basetype_counts(const std::vector<std::string> &bams, const std::vec
     std::cout << "basetype loading done -- " << ctime(&tim1);
     t_loaded = StageClock::now();
     compute(0, &m, 0, &cp);
+    return false;
 }
 
 static void run_basetype(int argc, char **argv)                          // src/BaseVarC.cpp:176-314
@@ -957,6 +1112,13 @@ static void run_basetype(int argc, char **argv)                          // src/
     // (BVC_HOST_COUNTS_QUALS acts with counts only; a value that is no multiple of 4 in 4..128 is refused here, before anything is opened)
     if (counts && parse_counts_quals(getenv("BVC_HOST_COUNTS_QUALS")) < 0)
         throw std::invalid_argument("ERROR: BVC_HOST_COUNTS_QUALS must be a multiple of 4 in 4..128");
+    // (BVC_HOST_COUNTS_LOAD and BVC_HOST_COUNTS_SAVE act with counts only; an empty name is refused here)
+    {
+        std::vector<std::string> files;
+        if (counts && !parse_counts_load(getenv("BVC_HOST_COUNTS_LOAD"), files))
+            throw std::invalid_argument("ERROR: BVC_HOST_COUNTS_LOAD must be FILE[:FILE...] without an empty name");
+        if (counts && parse_counts_save(getenv("BVC_HOST_COUNTS_SAVE")) < 0) throw std::invalid_argument("ERROR: BVC_HOST_COUNTS_SAVE must name a file");
+    }
     GroupFile group_file;
     if (counts_groups) {
         std::ifstream ifg(opt::group);
@@ -1041,8 +1203,9 @@ static void run_basetype(int argc, char **argv)                          // src/
     double t_loaded = 0, t_joined = 0;
     if (counts) {
         std::cerr << "begin to extract reads from bam" << std::endl;
-        basetype_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, counts_groups && !group_file.names.empty() ? &group_file : nullptr, t_loaded,
-                        compute);
+        if (basetype_counts(bams, pv, refseq, chr, rg_s, rg_e, nb, bc, thread, knobs, counts_groups && !group_file.names.empty() ? &group_file : nullptr,
+                            t_loaded, compute))
+            return;                                                      // (BVC_HOST_COUNTS_SAVE: the counts analogue of --load -- nothing to compute or merge)
         t_joined = StageClock::now();
     } else if (in_memory) {
         std::cerr << "begin to extract reads from bam" << std::endl;

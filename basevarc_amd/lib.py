@@ -196,6 +196,15 @@ SITE_ACC_QUALS_PROTOTYPES = {
     "bvc_site_acc_quals": (_int, [_vp, C.POINTER(_i32)]),
 }
 SITE_ACC_QUALS_EXPORTS = list(SITE_ACC_QUALS_PROTOTYPES)
+# The eleventh header, include/bvc_site_acc_pack.h (tests/test_site_acc_pack_abi.py compares the two), bound by bind() with the others: an
+# accumulator's rows as the (row_start, cell, count) entries of their non-zero words, and such entries added into an accumulator.
+SITE_ACC_PACK_PROTOTYPES = {
+    "bvc_site_acc_row_words": (_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "bvc_site_acc_pack": (_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _pi64, _u32]),
+    "bvc_site_acc_add_packed": (_int, [_vp, _vp, _i32, _i32, _vp, _vp, _vp, _i64, _u32]),
+}
+SITE_ACC_PACK_EXPORTS = list(SITE_ACC_PACK_PROTOTYPES)
+ACC_MORE = 2                # BVC_ACC_MORE (include/bvc_site_acc_pack.h): bvc_site_acc_pack wants more room for the entries
 STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a batch's slice one work item of the gather kernel copies
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
@@ -213,11 +222,12 @@ def library_path():
 
 def bind(cdll):
     """Gives every function of PROTOTYPES, BGZF_CODES_PROTOTYPES, BAM_PROTOTYPES, POPMATRIX_PROTOTYPES, BAM_TEXT_PROTOTYPES, STORE_PROTOTYPES,
-    BAM_DEFLATE_PROTOTYPES, BAM_COUNTS_PROTOTYPES, BAM_GROUP_DEPTH_PROTOTYPES and SITE_ACC_QUALS_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
+    BAM_DEFLATE_PROTOTYPES, BAM_COUNTS_PROTOTYPES, BAM_GROUP_DEPTH_PROTOTYPES, SITE_ACC_QUALS_PROTOTYPES and SITE_ACC_PACK_PROTOTYPES its restype / argtypes on `cdll` (libbvc.so or a variant build of it, a ctypes.CDLL).  A required symbol that the library lacks is an AttributeError."""
     for name, (restype, argtypes) in (list(PROTOTYPES.items()) + list(BGZF_CODES_PROTOTYPES.items()) + list(BAM_PROTOTYPES.items()) +
                                       list(POPMATRIX_PROTOTYPES.items()) + list(BAM_TEXT_PROTOTYPES.items()) + list(STORE_PROTOTYPES.items()) +
                                       list(BAM_DEFLATE_PROTOTYPES.items()) + list(BAM_COUNTS_PROTOTYPES.items()) +
-                                      list(BAM_GROUP_DEPTH_PROTOTYPES.items()) + list(SITE_ACC_QUALS_PROTOTYPES.items())):
+                                      list(BAM_GROUP_DEPTH_PROTOTYPES.items()) + list(SITE_ACC_QUALS_PROTOTYPES.items()) +
+                                      list(SITE_ACC_PACK_PROTOTYPES.items())):
         if name in OPTIONAL and not hasattr(cdll, name):
             continue
         fn = getattr(cdll, name)
@@ -1377,6 +1387,36 @@ class SiteAcc:
         d = np.zeros((max(n, 0), max(self.depth_groups, 1), 4), dtype=np.uint32)
         ctx._check(self._L.bvc_site_acc_get_depth(ctx._h, self._h, int(t0), n, _np_ptr(d) if n > 0 else None))
         return d
+
+    def row_words(self):
+        """bvc_site_acc_row_words: (W, slots, depth_groups) of the logical row (include/bvc_site_acc_pack.h)."""
+        w, sl, dg = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        rc = self._L.bvc_site_acc_row_words(self._h, C.byref(w), C.byref(sl), C.byref(dg))
+        if rc != 0:
+            raise BvcError(f"bvc_site_acc_row_words failed with code {rc}")
+        return w.value, sl.value, dg.value
+
+    def pack(self, ctx, t0=0, n=None):
+        """bvc_site_acc_pack, both steps: (row_start int64 [n + 1], cell uint16 [n_entries], count uint32 [n_entries]) of rows [t0, t0 + n)."""
+        n = self.n_positions - int(t0) if n is None else int(n)
+        rs = np.zeros(max(n, 0) + 1, dtype=np.int64)
+        need = C.c_int64(0)
+        rc = self._L.bvc_site_acc_pack(ctx._h, self._h, int(t0), n, _np_ptr(rs), None, None, 0, C.byref(need), BVC_PTR_HOST)
+        if rc not in (0, ACC_MORE):
+            ctx._check(rc)
+        cell, count = np.zeros(need.value, dtype=np.uint16), np.zeros(need.value, dtype=np.uint32)
+        if rc == ACC_MORE:
+            ctx._check(self._L.bvc_site_acc_pack(ctx._h, self._h, int(t0), n, _np_ptr(rs), _np_ptr(cell), _np_ptr(count), need.value, C.byref(need),
+                                                 BVC_PTR_HOST))
+        return rs, cell, count
+
+    def add_packed(self, ctx, row_start, cell, count, t0=0):
+        """bvc_site_acc_add_packed: the piece (row_start [n + 1], cell, count) ADDED into rows [t0, t0 + n)."""
+        rs, ce, co = _as(row_start, np.int64), _as(cell, np.uint16), _as(count, np.uint32)
+        if len(rs) < 1 or len(ce) != len(co):
+            raise ValueError("row_start must be [n + 1], and cell and count of one length")
+        ctx._check(self._L.bvc_site_acc_add_packed(ctx._h, self._h, int(t0), len(rs) - 1, _np_ptr(rs), _np_ptr(ce) if len(ce) else None,
+                                                   _np_ptr(co) if len(co) else None, len(ce), BVC_PTR_HOST))
 
     def lrt(self, ctx, ref_base, min_af, t0=0):
         """bvc_site_acc_lrt: stage 2 on rows [t0, t0 + len(ref_base)) where they lie.  Returns the site records (SITE_DTYPE), or with

@@ -14,6 +14,13 @@ position list of the test region, next to bvc_bam_pileup and bvc_bam_popmatrix o
                                                      # and from one more run of each with BVC_HOST_PROFILE=1 the accumulator's, the second
                                                      # pile-up's store's and mem's store's bytes
 
+  python tools/bam_counts_bench.py --pack [--repeats 5] [--out FILE]
+                                                     # (e) packed rows (include/bvc_site_acc_pack.h) on the accumulator of the test positions,
+                                                     # wide and at 40 columns with 5 groups: the entries and packed bytes beside the dense
+                                                     # bytes, bvc_site_acc_pack and bvc_site_acc_add_packed from device pointers, 8,192 rows
+                                                     # expanded (acc_expand_kernel) and a streaming read of as many bytes as each accumulator
+                                                     # holds; with --kernel-trace DIR: the size, place, scan, dry and add kernels of that run
+
 Every time it prints is the best wall-clock time of a device-pointer call with the context synchronised before and after (as
 tools/popmatrix_bench.py and tools/bam_pileup_bench.py take theirs).  At 100 samples that is launch and wait latency, not kernel time: a
 counts call is index + dry pass + scan + one wait + add pass.  The kernels' own times come from the same run under the profiler's kernel
@@ -89,6 +96,109 @@ def trace_report(a):
             f.write("\n".join(lines) + "\n")
 
 
+PACK_FORMS = (("wide", None, 0), ("40 columns, 5 groups", 40, 5))
+
+
+def pack_trace_report(a):
+    """The packed-rows kernels of one profiled --pack run: per kernel the dispatches in order, the wide accumulator's first."""
+    import csv
+    import glob
+    import statistics
+    files = glob.glob(os.path.join(a.kernel_trace, "**", "*kernel_trace.csv"), recursive=True)
+    if len(files) != 1:
+        raise SystemExit(f"one kernel trace expected under {a.kernel_trace}, found {len(files)}")
+    rows = list(csv.DictReader(open(files[0])))
+    P = 66615
+    dense = {"wide": P * 2096, "40 columns, 5 groups": P * (640 + 48 + 80)}
+    lines = Lines()
+    lines.append("# the packed-rows kernels of one profiled run (rocprofv3 --kernel-trace): min / median / max, microseconds; GB/s = the accumulator's dense "
+                 "bytes over the median")
+    for kernel in ("acc_pack_kernel<false>", "acc_pack_scan_kernel", "acc_pack_kernel<true>", "acc_add_packed_kernel<false>", "acc_first_fault_kernel",
+                   "acc_add_packed_kernel<true>"):
+        mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if kernel in r["Kernel_Name"])
+        if not mine or len(mine) % len(PACK_FORMS):
+            raise SystemExit(f"{kernel}: {len(mine)} dispatches in the trace")
+        k = len(mine) // len(PACK_FORMS)
+        for i, (form, _, _) in enumerate(PACK_FORMS):
+            us = [(e - b) / 1e3 for b, e in mine[i * k:(i + 1) * k]]
+            med = statistics.median(us)
+            rate = f"  {dense[form] / (med * 1e-6) / 1e9:7.0f} GB/s" if kernel.startswith("acc_pack_kernel") else ""
+            lines.append(f"  {kernel:30s} {form:22s} {min(us):8.1f} {med:8.1f} {max(us):8.1f}  ({len(us)} dispatches){rate}")
+    mine = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "acc_expand_kernel" in r["Kernel_Name"]]
+    if mine:
+        med = statistics.median(mine)
+        nbytes = 8192 * (16 * 40 + 2048)
+        lines.append(f"  {'acc_expand_kernel':30s} {'8,192 rows, 40 columns':22s} {min(mine):8.1f} {med:8.1f} {max(mine):8.1f}  ({len(mine)} dispatches)"
+                     f"  {nbytes / (med * 1e-6) / 1e9:7.0f} GB/s ({nbytes} bytes read and written)")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+def pack(a):
+    import ctypes as C
+    import numpy as np
+    import torch
+    from basevarc_amd import Context, SiteAcc
+    from tests import acc_pack_model as am
+    from tests import bam_group_depth_model as gm
+    from tests import bam_pileup_model as bm
+    from tests.test_bam_pileup_abi import bam_data_bytes, bam_data_call
+    contig, beg0, end0, mapq, pv, rg_s, refseq = bam_data_call()
+    data = bam_data_bytes()
+    rid = [refs.index(contig) for _, _, refs in data]
+    n, P = len(data), len(pv)
+    exp = bm.expected([(d[first:], True, r) for (d, first, _), r in zip(data, rid)], beg0, end0, mapq, pv, rg_s, refseq)
+    assert exp["rc"] == 0
+    labels = (np.arange(n) % 7).astype(np.uint8)
+    want_c, want_t, want_d = gm.fold_maps(exp["maps"], pv, labels, 5)
+    ctx = Context(0)
+    L = ctx._L
+    lines = Lines()
+    lines.append(f"# packed rows: tools/bam_counts_bench.py --pack, best of {a.repeats + 2} device-pointer calls, wall clock around a synchronised context")
+    lines.append(f"{n} samples, {P} positions, -q {mapq}; {int(want_c.sum())} counted observations")
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else None
+    for form, n_quals, G in PACK_FORMS:
+        rows = am.logical_rows(want_c.reshape(P, 512), want_t, want_d if G else None)
+        rs, cell, count = am.entries(rows)
+        E = len(cell)
+        with (SiteAcc.create_quals(0, P, n_quals, G) if n_quals else SiteAcc(0, P)) as acc, \
+                (SiteAcc.create_quals(0, P, n_quals, G) if n_quals else SiteAcc(0, P)) as sink:
+            acc.add_packed(ctx, rs, cell, count)
+            got = acc.pack(ctx)
+            assert all(np.array_equal(x, y) for x, y in zip(got, (rs, cell, count)))
+            used = acc.bytes()[0]
+            packed = 8 * (P + 1) + 6 * E
+            lines.append(f"{form}: {E} entries in {int((np.diff(rs) > 0).sum())} rows that hold any; packed {packed} bytes ({8 * (P + 1)} of row_start, {6 * E} of "
+                         f"entries), dense {used} bytes on the device, {P * (2048 + 48 + 16 * G)} through bvc_site_acc_get: {used / packed:.1f} x and "
+                         f"{P * (2048 + 48 + 16 * G) / packed:.1f} x")
+            d_rs = torch.zeros(P + 1, dtype=torch.int64, device="cuda")
+            d_cell = torch.zeros(E, dtype=torch.int16, device="cuda")
+            d_count = torch.zeros(E, dtype=torch.int32, device="cuda")
+            need = C.c_int64(0)
+            call = lambda: L.bvc_site_acc_pack(ctx._h, acc._h, 0, P, ptr(d_rs), ptr(d_cell), ptr(d_count), E, C.byref(need), 1)
+            assert call() == 0 and need.value == E
+            t = best_of(ctx, a.repeats, call)
+            assert np.array_equal(d_cell.cpu().numpy().view(np.uint16), cell) and np.array_equal(d_count.cpu().numpy().view(np.uint32), count)
+            lines.append(f"  bvc_site_acc_pack, device pointers (size pass, scan, one wait, place pass): {t * 1e3:8.3f} ms a call")
+            add = lambda: L.bvc_site_acc_add_packed(ctx._h, sink._h, 0, P, ptr(d_rs), ptr(d_cell), ptr(d_count), E, 1)
+            assert add() == 0
+            t = best_of(ctx, a.repeats, add)
+            lines.append(f"  bvc_site_acc_add_packed, device pointers (dry pass, first fault, one wait, add pass): {t * 1e3:8.3f} ms a call, {E} atomic adds")
+            if n_quals:
+                t = best_of(ctx, a.repeats, lambda: acc.get(ctx, 1000, 8192))
+                lines.append(f"  bvc_site_acc_get, 8,192 rows of {n_quals} columns expanded and brought to the host: {t * 1e3:8.3f} ms a call")
+            buf = torch.zeros(used // 4, dtype=torch.int32, device="cuda")
+            gbs = ctx.stream_read_gbs(buf, a.repeats)
+            lines.append(f"  a streaming read of {used} bytes: {used / gbs / 1e3:8.1f} us ({gbs:.0f} GB/s)")
+            del buf
+    ctx.close()
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def process(a):
     import re
     import subprocess
@@ -131,11 +241,15 @@ def main():
     ap.add_argument("--repeats", type=int, default=None)
     ap.add_argument("--copies", type=int, default=50)
     ap.add_argument("--process", action="store_true")
+    ap.add_argument("--pack", action="store_true", help="packed rows: bvc_site_acc_pack / bvc_site_acc_add_packed on the test positions' accumulator")
     ap.add_argument("--out", default=None)
     ap.add_argument("--depth", type=int, action="append", default=[], help="also bvc_bam_counts_depth with this many groups (may be given more than once)")
     ap.add_argument("--quals", type=int, action="append", default=[], help="also bvc_bam_counts_quals with this many quality columns, 0 and 5 groups (may be given more than once)")
     ap.add_argument("--kernel-trace", default=None, help="the directory of a rocprofv3 --kernel-trace run of this tool with the same --repeats, --depth and --quals")
     a = ap.parse_args()
+    if a.pack:
+        a.repeats = 5 if a.repeats is None else a.repeats
+        return pack_trace_report(a) if a.kernel_trace else pack(a)
     if a.kernel_trace:
         a.repeats = 5 if a.repeats is None else a.repeats
         return trace_report(a)
