@@ -225,20 +225,20 @@ hipError_t launch_acc_pack_scan(hipStream_t stream, int64_t n_rows, const uint32
     return hipGetLastError();
 }
 
-hipError_t launch_acc_add_packed(hipStream_t stream, bool add, int64_t n_rows, const AccRowShape &s, int32_t n_quals, const int64_t *row_start,
-                                 const uint16_t *cell, const uint32_t *count, int64_t n_entries, uint32_t *counts, ::bvc_bam_site_tally *tally,
-                                 uint32_t *depth, uint32_t *row_fault)
+hipError_t launch_acc_add_packed(hipStream_t stream, bool add, int64_t n_rows, const AccRowShape &s, const int64_t *row_start, const uint16_t *cell,
+                                 const uint32_t *count, int64_t n_entries, uint32_t *counts, ::bvc_bam_site_tally *tally, uint32_t *depth,
+                                 uint32_t *row_fault)
 {
-    if (n_rows < 0 || s.row0 < 0 || n_entries < 0 || n_quals < 4 || n_quals > 128 || (s.depth_groups > 0u && !depth)) return hipErrorInvalidValue;
+    if (n_rows < 0 || s.row0 < 0 || n_entries < 0 || s.q4 >= 32u || (s.depth_groups > 0u && !depth)) return hipErrorInvalidValue;
     if (n_rows == 0) return hipSuccess;
-    const uint32_t row_words = s.count_cells + 10u + 4u * s.depth_groups;
+    const uint32_t n_quals = s.q4 ? s.q4 * 4u : 128u, row_words = s.count_cells + 10u + 4u * s.depth_groups;
     uint32_t *const tw = reinterpret_cast<uint32_t *>(tally);
     if (add)
-        hipLaunchKernelGGL(acc_add_packed_kernel<true>, dim3(pack_grid(n_rows)), dim3(kPackThreads), 0, stream, n_rows, s, (uint32_t)n_quals, row_words,
-                           row_start, cell, count, n_entries, counts, tw, depth, row_fault);
+        hipLaunchKernelGGL(acc_add_packed_kernel<true>, dim3(pack_grid(n_rows)), dim3(kPackThreads), 0, stream, n_rows, s, n_quals, row_words, row_start,
+                           cell, count, n_entries, counts, tw, depth, row_fault);
     else
-        hipLaunchKernelGGL(acc_add_packed_kernel<false>, dim3(pack_grid(n_rows)), dim3(kPackThreads), 0, stream, n_rows, s, (uint32_t)n_quals, row_words,
-                           row_start, cell, count, n_entries, counts, tw, depth, row_fault);
+        hipLaunchKernelGGL(acc_add_packed_kernel<false>, dim3(pack_grid(n_rows)), dim3(kPackThreads), 0, stream, n_rows, s, n_quals, row_words, row_start,
+                           cell, count, n_entries, counts, tw, depth, row_fault);
     return hipGetLastError();
 }
 

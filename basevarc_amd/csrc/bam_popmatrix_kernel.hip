@@ -60,10 +60,8 @@ hipError_t launch_bam_popmatrix(hipStream_t stream, int32_t n_samples, const uin
                                 int32_t rg_s, int64_t refseq_len, const BamPileupScratch &s, uint8_t *matrix, int64_t row_stride, uint32_t *sample_status)
 {
     if (n_samples <= 0 || n_positions <= 0) return hipSuccess;
-    const int64_t chunks = ((int64_t)n_positions + kWave - 1) / kWave;
-    const dim3 grid((unsigned)((n_samples + kBamWaves - 1) / kBamWaves), (unsigned)(chunks < 1024 ? chunks : 1024));
-    hipLaunchKernelGGL(bam_popmatrix_kernel, grid, dim3(kBamThreads), 0, stream, n_samples, bam, bam_bytes, sample_off, sample_end, s.reads, s.runmax,
-                       s.n_reads, n_positions, positions, ref, alt, rg_s, refseq_len, matrix, row_stride, sample_status);
+    hipLaunchKernelGGL(bam_popmatrix_kernel, bam_sample_grid(n_samples, n_positions), dim3(kBamThreads), 0, stream, n_samples, bam, bam_bytes, sample_off,
+                       sample_end, s.reads, s.runmax, s.n_reads, n_positions, positions, ref, alt, rg_s, refseq_len, matrix, row_stride, sample_status);
     return hipGetLastError();
 }
 

@@ -1,8 +1,8 @@
 // bam_resolve_device.h -- what the kernels over a batch's inflated BAM records share (bam_pileup_kernel.hip, bam_popmatrix_kernel.hip,
-// bam_text_kernel.hip):
+// bam_text_kernel.hip, bam_counts_kernel.hip):
 // the byte loads (records lie at any byte address), the lane helpers, a sample's clamped byte range and resolve(), the per-position
 // rule of find_snp_at_pos / fetch_allele_type (host/bam.cpp) for ONE position over the read table bam_index_kernel leaves.  Device
-// code only; every function is inlined into its kernel.
+// code, every function inlined into its kernel, and the one grid formula of the sample-per-wavefront kernels.
 #ifndef BVC_BAM_RESOLVE_DEVICE_H
 #define BVC_BAM_RESOLVE_DEVICE_H
 
@@ -15,6 +15,13 @@ namespace {
 
 constexpr int kBamThreads = 256;                    // 4 wavefronts: 4 samples (index, pileup, popmatrix) or 4 positions (rows)
 constexpr int kBamWaves = kBamThreads / kWave;
+// (host side) the grid of the kernels that give a sample a wavefront and a position a lane: kBamWaves samples a workgroup in x, the
+// positions' chunks of 64 in y -- 1024 at most, more go round the kernel's loop
+inline dim3 bam_sample_grid(int32_t n_samples, int32_t n_positions)
+{
+    const int64_t chunks = ((int64_t)n_positions + kWave - 1) / kWave;
+    return dim3((unsigned)((n_samples + kBamWaves - 1) / kBamWaves), (unsigned)(chunks < 1024 ? chunks : 1024));
+}
 
 __device__ __forceinline__ uint32_t ld16(const uint8_t *__restrict__ p, int64_t at) { return (uint32_t)p[at] | ((uint32_t)p[at + 1] << 8); }
 __device__ __forceinline__ uint32_t ld32(const uint8_t *__restrict__ p, int64_t at)

@@ -11,7 +11,8 @@
 #include "../../include/bvc_bam_text.h"
 #include "../../include/bvc_popmatrix.h"
 
-// (BamCall, the checks and the two verdicts are declared in bvc_ctx.h: bvc_bam_counts.hip shares them)
+// (the checks, the staging of a host-pointer call's inputs (BamStage) and the two verdicts are declared in bvc_ctx.h: bvc_bam_counts.hip
+// shares them)
 int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_positions, int64_t refseq_len, int64_t records_cap)
 {
     if (n_samples < 0 || bam_bytes < 0 || n_positions < 0 || refseq_len < 0 || records_cap < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
@@ -68,6 +69,37 @@ int block_verdict(bvc_ctx *ctx, const std::vector<uint32_t> &block_status)
             std::snprintf(msg, sizeof msg, "BGZF block %lld: %s", (long long)i, block_status[i] == 10 ? "CRC32 mismatch" : "not valid deflate of its ISIZE bytes");
             return fail(ctx, BVC_ERR_DATA, msg);
         }
+    return BVC_OK;
+}
+
+void BamStage::take(Layout &L)
+{
+    const size_t ns = (size_t)h.n_samples, np = (size_t)h.n_positions, nb = (size_t)n_blocks;
+    u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
+    u_bam = L.take<uint8_t>((size_t)h.bam_bytes);
+    u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
+    u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
+    d_group = group ? L.take<uint8_t>(ns) : nullptr;
+    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
+}
+
+int BamStage::upload(bvc_ctx *ctx, PinIO &io)
+{
+    const size_t ns = (size_t)h.n_samples, np = (size_t)h.n_positions, nb = (size_t)n_blocks;
+    if (nb) {
+        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
+        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
+        // (the bytes between the blocks' outputs, if the caller left any, are no sample's: nothing reads them)
+        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
+        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
+    } else if (h.bam && h.bam_bytes)                // the records are the bulk: straight from the caller's memory (a DMA where it is page-locked)
+        BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, h.bam, (size_t)h.bam_bytes, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, io.h2d(u_off, h.off, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_end, h.end, ns * 8));
+    BVC_HIP_D(ctx, io.h2d(u_eof, h.eof, ns));
+    BVC_HIP_D(ctx, io.h2d(u_rid, h.rid, ns * 4));
+    if (group) BVC_HIP_D(ctx, io.h2d(d_group, group, ns));
+    BVC_HIP_D(ctx, io.h2d(u_pos, h.pos, np * 4));
     return BVC_OK;
 }
 
@@ -184,34 +216,16 @@ int bam_popmatrix_from_host(bvc_ctx *ctx, const BamCall &h, const uint8_t *comp,
     PinIO io(ctx);
     rc = io.reserve(ns * 21 + np * 6 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + nb * 4 + 1024);
     if (rc != BVC_OK) return rc;
-    uint8_t *u_comp, *u_bam, *u_eof, *u_ref, *u_alt; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
-    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
-        u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
-        u_bam = L.take<uint8_t>((size_t)h.bam_bytes);
-        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
-        u_pos = L.take<int32_t>(np); u_ref = L.take<uint8_t>(np); u_alt = L.take<uint8_t>(np); d_status = L.take<uint32_t>(ns);
-    });
-    if (rc != BVC_OK) return rc;
-    std::vector<uint32_t> block_status(nb);
-    if (nb) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
-        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
-        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
-    } else if (h.bam && h.bam_bytes)
-        BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, h.bam, (size_t)h.bam_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(ctx, io.h2d(u_off, h.off, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_end, h.end, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_eof, h.eof, ns));
-    BVC_HIP_D(ctx, io.h2d(u_rid, h.rid, ns * 4));
-    BVC_HIP_D(ctx, io.h2d(u_pos, h.pos, np * 4));
+    BamStage st(h, comp, comp_bytes, blocks, n_blocks);
+    uint8_t *u_ref, *u_alt;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { st.take(L); u_ref = L.take<uint8_t>(np); u_alt = L.take<uint8_t>(np); });
+    if (rc != BVC_OK || (rc = st.upload(ctx, io)) != BVC_OK) return rc;
     BVC_HIP_D(ctx, io.h2d(u_ref, h.pref, np));
     BVC_HIP_D(ctx, io.h2d(u_alt, h.palt, np));
-    BamCall c = h;
-    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos; c.pref = u_ref; c.palt = u_alt;
-    rc = run_bam_popmatrix(ctx, io, c, false, d_status, matrix, row_stride, sample_status);
+    st.c.pref = u_ref; st.c.palt = u_alt;
+    rc = run_bam_popmatrix(ctx, io, st.c, false, st.d_status, matrix, row_stride, sample_status);
     // the wait delivered the blocks' statuses too: a block that did not inflate outranks what the kernels made of its bytes
-    return block_verdict(ctx, block_status) != BVC_OK ? BVC_ERR_DATA : rc;
+    return block_verdict(ctx, st.block_status) != BVC_OK ? BVC_ERR_DATA : rc;
 }
 
 // The checks both entry points make before anything of the device is touched; fills what of the call they share.
@@ -226,9 +240,8 @@ int check_popmatrix(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_byt
     if ((n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) || (n_positions > 0 && (!positions || !ref || !alt)) ||
         (n_samples > 0 && n_positions > 0 && !matrix))
         return fail(ctx, BVC_ERR_ARG, "null data pointer");
-    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
-    c.eof = sample_eof; c.off = sample_off; c.end = sample_end; c.rid = rid; c.pos = positions; c.pref = ref; c.palt = alt;
-    c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
+    c = bam_call(n_samples, nullptr, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    c.pref = ref; c.palt = alt;
     return BVC_OK;
 }
 
@@ -256,30 +269,18 @@ int bam_pileup_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8_t *b
     PinIO io(ctx);
     rc = io.reserve(device ? 0 : ns * 21 + np * 4 + 1024, 64 + ns * 4 + (np + 1) * 4 + 1024);
     if (rc != BVC_OK) return rc;
-    BamCall c;
-    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
-    c.bam = bam; c.eof = sample_eof; c.ref = reinterpret_cast<const uint8_t *>(refseq); c.off = sample_off; c.end = sample_end; c.rid = rid;
-    c.pos = positions; c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
-    uint32_t *d_status = sample_status;
-    if (!device) {                                  // host pointers: the inputs live in the staging buffer for the length of the call
-        uint8_t *u_bam, *u_eof, *u_ref; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
-        rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
-            u_bam = L.take<uint8_t>((size_t)bam_bytes); u_ref = L.take<uint8_t>((size_t)refseq_len);
-            u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
-            u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
-        });
-        if (rc != BVC_OK) return rc;
-        // the records and the reference are the bulk: straight from the caller's memory (a DMA where it is page-locked)
-        if (bam_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, bam, (size_t)bam_bytes, hipMemcpyHostToDevice, ctx->stream));
-        if (refseq_len) BVC_HIP_D(ctx, hipMemcpyAsync(u_ref, refseq, (size_t)refseq_len, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
-        BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
-        BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
-        BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
-        BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
-        c.bam = u_bam; c.ref = u_ref; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
-    }
-    return run_bam_pileup(ctx, io, c, text, device, d_status, records, records_cap, records_needed, rec_start, sample_status);
+    BamCall c = bam_call(n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    c.ref = reinterpret_cast<const uint8_t *>(refseq);
+    if (device) return run_bam_pileup(ctx, io, c, text, true, sample_status, records, records_cap, records_needed, rec_start, sample_status);
+    // host pointers: the inputs live in the staging buffer for the length of the call
+    BamStage st(c, nullptr, 0, nullptr, 0);
+    uint8_t *u_ref;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { st.take(L); u_ref = L.take<uint8_t>((size_t)refseq_len); });
+    if (rc != BVC_OK || (rc = st.upload(ctx, io)) != BVC_OK) return rc;
+    // (the reference is bulk too: straight from the caller's memory)
+    if (refseq_len) BVC_HIP_D(ctx, hipMemcpyAsync(u_ref, refseq, (size_t)refseq_len, hipMemcpyHostToDevice, ctx->stream));
+    st.c.ref = u_ref;
+    return run_bam_pileup(ctx, io, st.c, text, false, st.d_status, records, records_cap, records_needed, rec_start, sample_status);
 }
 
 }  // namespace
@@ -308,36 +309,17 @@ int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8
     PinIO io(ctx);
     rc = io.reserve(ns * 21 + np * 4 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + (np + 1) * 4 + nb * 4 + 1024);
     if (rc != BVC_OK) return rc;
-    uint8_t *u_comp, *u_bam, *u_eof, *u_ref; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
-    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
-        u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
-        u_bam = L.take<uint8_t>((size_t)bam_bytes); u_ref = L.take<uint8_t>((size_t)refseq_len);
-        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns);
-        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
-    });
-    if (rc != BVC_OK) return rc;
-    std::vector<uint32_t> block_status(nb);
-    if (nb) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
-        // (the bytes between the blocks' outputs, if the caller left any, are no sample's: nothing reads them)
-        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
-        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
-    }
+    BamStage st(bam_call(n_samples, nullptr, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len),
+                comp, comp_bytes, blocks, n_blocks);
+    uint8_t *u_ref;
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { st.take(L); u_ref = L.take<uint8_t>((size_t)refseq_len); });
+    if (rc != BVC_OK || (rc = st.upload(ctx, io)) != BVC_OK) return rc;
     if (refseq_len) BVC_HIP_D(ctx, hipMemcpyAsync(u_ref, refseq, (size_t)refseq_len, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
-    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
-    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
-    BamCall c;
-    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
-    c.bam = u_bam; c.ref = u_ref; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos; c.bam_bytes = bam_bytes;
-    c.refseq_len = refseq_len;
+    st.c.ref = u_ref;
     // the pileup's first wait delivers the blocks' statuses too: a block that did not inflate (or failed its CRC32) outranks what the
     // kernels made of its bytes
-    rc = run_bam_pileup(ctx, io, c, text, false, d_status, records, records_cap, records_needed, rec_start, sample_status, sink);
-    if (block_verdict(ctx, block_status) != BVC_OK) {
+    rc = run_bam_pileup(ctx, io, st.c, text, false, st.d_status, records, records_cap, records_needed, rec_start, sample_status, sink);
+    if (block_verdict(ctx, st.block_status) != BVC_OK) {
         *records_needed = 0;
         return BVC_ERR_DATA;
     }

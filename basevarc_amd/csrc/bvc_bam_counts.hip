@@ -1,39 +1,24 @@
-// bvc_bam_counts.hip -- bvc_bam_counts, bvc_bam_counts_bgzf_acc and the accumulator bvc_site_acc (include/bvc_bam_counts.h): the inflated BAM
-// records of a batch of samples added into per-position class counts and tallies (bam_counts_kernel.hip).  The call's inputs (BamCall), their
-// checks and the verdicts on the statuses and the blocks are bvc_bam.hip's.  Order of work: index -> dry pass -> scan -> first wait ->
-// verdict -> add pass (-> second wait in the host forms): nothing is added unless the call returns BVC_OK.  The ninth header's calls
-// (include/bvc_bam_group_depth.h: bvc_bam_counts_depth, the accumulator's second kind) live here too: they are the same calls with one slot
-// of counts, the groups' depths beside it and bam_group_depth_kernel.hip as their add pass.  And the tenth header's
-// (include/bvc_site_acc_quals.h: bvc_bam_counts_quals, the accumulator's third kind): the same calls again with narrow rows of counts
-// [position][4][n_quals], bam_counts_quals_kernel.hip as both passes, one more verdict (status 5) behind the existing one, and
-// acc_expand_kernel between narrow rows and the callers of bvc_site_acc_get / bvc_site_acc_lrt.  And the eleventh header's
-// (include/bvc_site_acc_pack.h: bvc_site_acc_pack and bvc_site_acc_add_packed, beside bvc_site_acc_get): an accumulator's rows as the
-// entries of their non-zero words and back, acc_pack_kernel.hip -- size pass -> scan -> the wait for the total -> place pass, and dry pass
-// -> first fault -> the wait for the verdict -> add pass.
+// bvc_bam_counts.hip -- the inflated BAM records of a batch of samples added into per-position class counts and tallies
+// (bam_counts_kernel.hip), and the accumulator bvc_site_acc that keeps such counts on the device.  Every form of the call -- bvc_bam_counts
+// (include/bvc_bam_counts.h), bvc_bam_counts_depth (bvc_bam_group_depth.h), bvc_bam_counts_quals (bvc_site_acc_quals.h), and
+// bvc_bam_counts_bgzf_acc on any accumulator -- is one path that a CountsLayout (counts_layout.h) steers: index -> dry pass -> scan -> first
+// wait -> verdict (on narrow rows status 5 behind the others) -> add pass (-> second wait in the host forms); nothing is added unless the
+// call returns BVC_OK.  The call's inputs (BamCall), their checks, their staging (BamStage) and the verdicts on the statuses and the blocks
+// are bvc_bam.hip's.  Reading an accumulator: bvc_site_acc_get and bvc_site_acc_lrt (narrow rows pass through acc_expand_kernel), and
+// bvc_site_acc_pack / bvc_site_acc_add_packed (bvc_site_acc_pack.h; acc_pack_kernel.hip), its rows as the entries of their non-zero words
+// and back: size pass -> scan -> the wait for the total -> place pass, and dry pass -> first fault -> the wait for the verdict -> add pass.
 #include "bvc_ctx.h"
 #include "../../include/bvc_site_acc_pack.h"
 
 // An accumulator is no part of a context: its device memory is its own, and its bookkeeping is fixed when it is made (the adds are atomic).
 struct bvc_site_acc {
     int device = -1;
-    int32_t n_positions = 0, n_groups = 0;
+    int32_t n_positions = 0;
     int64_t budget = 0, used = 0;
-    int32_t depth_groups = 0;                        // the second kind (bvc_site_acc_create_depth): n_groups stays 0, one slot
-    uint32_t *d_counts = nullptr;                    // [n_positions][slots][512]
+    CountsLayout layout = CountsLayout::wide(0);
+    uint32_t *d_counts = nullptr;                    // [n_positions][layout.count_words()]
     bvc_bam_site_tally *d_tally = nullptr;           // [n_positions]
-    uint32_t *d_depth = nullptr;                     // [n_positions][depth_groups][4], the second and third kind
-    int32_t n_quals = 0;                             // > 0: the third kind (bvc_site_acc_create_quals) -- n_groups stays 0, one slot of
-                                                     // [4][n_quals] words, depth_groups 0..32
-    size_t slots() const { return n_groups > 0 ? (size_t)n_groups + 1 : 1; }
-    size_t row_words() const { return n_quals > 0 ? (size_t)n_quals * 4 : slots() * BVC_NCLASS; }
-    bool expanded() const { return n_quals > 0 && n_quals < 128; }   // its rows are not the [512] layout: acc_expand_kernel makes it
-    size_t logical_words() const { return slots() * BVC_NCLASS + 10 + (size_t)depth_groups * 4; }   // W of bvc_site_acc_pack.h
-    // rows from t0 on as acc_pack_kernel.hip's kernels see them (128 columns are stored as the wide layout stores them)
-    AccRowShape shape(int32_t t0) const
-    {
-        return AccRowShape{(int64_t)t0, (uint32_t)(row_words() / 4), expanded() ? (uint32_t)n_quals / 4u : 0u, (uint32_t)(slots() * BVC_NCLASS),
-                           (uint32_t)depth_groups};
-    }
+    uint32_t *d_depth = nullptr;                     // [n_positions][layout.depth_groups][4]
 };
 
 // Rows a call expands at a time into the context's scratch (bvc_site_acc_get, bvc_site_acc_lrt on narrow rows): 64 MiB of [512] rows
@@ -54,38 +39,51 @@ int check_rows(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t n)
     return BVC_OK;
 }
 
-int check_counts_groups(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of_sample, int32_t n_groups)
+// The labels' check of every form.  depth_form: the depths' forms with groups -- there is no such form without groups, and it words both
+// refusals its own way
+int check_labels(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of_sample, int32_t n_groups, bool depth_form)
 {
-    if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
-    if (n_groups > 0 && n_samples > 0 && !group_of_sample) return fail(ctx, BVC_ERR_ARG, "null group_of_sample with n_groups > 0");
+    if (n_groups < (depth_form ? 1 : 0) || n_groups > BVC_MAX_GROUPS)
+        return fail(ctx, BVC_ERR_ARG, depth_form ? "n_groups must be 1..32" : "n_groups must be 0..32");
+    if (n_groups > 0 && n_samples > 0 && !group_of_sample)
+        return fail(ctx, BVC_ERR_ARG, depth_form ? "null group_of_sample with samples present" : "null group_of_sample with n_groups > 0");
     return BVC_OK;
+}
+
+// What every entry point checks of the sample and position arguments (h: the caller's pointers) before anything of the device is touched.
+// n_groups: the groups the labels are compared with (CountsLayout::label_groups(), unchecked); a depth form names its labels behind the
+// null pointers, the others in front of them.
+int check_counts_call(bvc_ctx *ctx, const BamCall &h, const uint8_t *group_of_sample, int32_t n_groups, bool depth_form, const uint32_t *sample_status)
+{
+    int rc = check_sizes(ctx, h.n_samples, h.bam_bytes, h.n_positions, h.refseq_len, 0);
+    if (rc != BVC_OK) return rc;
+    if (!depth_form && (rc = check_labels(ctx, h.n_samples, group_of_sample, n_groups, false)) != BVC_OK) return rc;
+    if ((h.n_samples > 0 && (!h.off || !h.end || !h.eof || !h.rid || !sample_status)) || (h.n_positions > 0 && !h.pos))
+        return fail(ctx, BVC_ERR_ARG, "null data pointer");
+    return depth_form ? check_labels(ctx, h.n_samples, group_of_sample, n_groups, true) : BVC_OK;
 }
 
 // Index, dry pass, scan and the call's first wait, on inputs in device memory: the statuses (to sample_status on the host unless
 // out_device) and the verdict -- the blocks' first (blocks: their statuses come down with the same wait; may be null), then the samples'.
-// n_quals > 0: the narrow forms -- their dry pass also raises status 5, whose first sample comes down with the same wait and is judged
-// behind the existing verdict.
-int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_device, uint32_t *d_status, uint32_t *sample_status,
-                       const std::vector<uint32_t> *blocks, BamPileupScratch &S, int32_t n_quals = 0)
+// Narrow rows: their dry pass also raises status 5, whose first sample comes down with the same wait and is judged behind the existing
+// verdict.
+int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, const CountsLayout &layout, bool out_device, uint32_t *d_status,
+                       uint32_t *sample_status, const std::vector<uint32_t> *blocks, BamPileupScratch &S)
 {
     const size_t ns = (size_t)c.n_samples;
+    const bool narrow = layout.kind() == CountsKind::Narrow;
     int64_t *d_first5 = nullptr;
     int rc = carve(ctx, ctx->d_bam, 256, [&](Layout &L) {
         S = bam_popmatrix_scratch(L, c.bam_bytes, c.n_samples);
-        if (n_quals > 0) d_first5 = L.take<int64_t>(1);
+        if (narrow) d_first5 = L.take<int64_t>(1);
     });
     if (rc != BVC_OK) return rc;
     BVC_HIP_D(ctx, launch_bam_index(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.eof, c.rid, c.beg0, c.end0, c.min_mapq, S, d_status));
-    if (n_quals > 0)
-        BVC_HIP_D(ctx, launch_bam_counts_quals(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s,
-                                               c.refseq_len, nullptr, 0, n_quals, S, nullptr, nullptr, nullptr, d_status));
-    else
-        BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, false, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
-                                         nullptr, 0, S, nullptr, nullptr, d_status));
+    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, false, c, layout, S, CountsArrays{nullptr, nullptr, nullptr, nullptr}, d_status));
     BVC_HIP_D(ctx, launch_bam_scan(ctx->stream, 0, c.n_samples, S, d_status));
     int64_t head[4] = {0, 0, 0, 0}, first5 = 0x7FFFFFFF;
     BVC_HIP_D(ctx, io.d2h(head, S.head, sizeof head));
-    if (n_quals > 0) {
+    if (narrow) {
         BVC_HIP_D(ctx, launch_first_status(ctx->stream, c.n_samples, d_status, 5u, d_first5));
         BVC_HIP_D(ctx, io.d2h(&first5, d_first5, sizeof first5));
     }
@@ -97,125 +95,63 @@ int bam_counts_verdict(bvc_ctx *ctx, PinIO &io, const BamCall &c, bool out_devic
     if ((rc = status_verdict(ctx, head)) != BVC_OK || first5 == 0x7FFFFFFF) return rc;
     char msg[160];
     std::snprintf(msg, sizeof msg, "sample %lld: a base quality of %d or more, and the counts keep n_quals = %d quality columns", (long long)first5,
-                  (int)n_quals, (int)n_quals);
+                  (int)layout.n_quals, (int)layout.n_quals);
     return fail(ctx, BVC_ERR_DATA, msg);
 }
 
-// The add pass, enqueued on the context's stream.  d_depth: the depth form's array (one slot of counts, n_groups depth rows), else null.
-// n_quals > 0: the narrow forms (d_counts [P][4][n_quals]; d_depth null with n_groups 0).
-int bam_counts_add(bvc_ctx *ctx, const BamCall &c, const uint8_t *d_group, int32_t n_groups, const BamPileupScratch &S, uint32_t *d_counts,
-                   bvc_bam_site_tally *d_tally, uint32_t *d_depth, uint32_t *d_status, int32_t n_quals = 0)
+// bvc_bam_counts, bvc_bam_counts_depth and bvc_bam_counts_quals behind their own checks (check_counts_call among them): h and a are the
+// caller's pointers, device or host memory by flags.
+int bam_counts_call(bvc_ctx *ctx, const BamCall &h, const CountsLayout &layout, CountsArrays a, uint32_t *sample_status, uint32_t flags)
 {
-    if (n_quals > 0)
-        BVC_HIP_D(ctx, launch_bam_counts_quals(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s,
-                                               c.refseq_len, d_group, n_groups, n_quals, S, d_counts, d_tally, d_depth, d_status));
-    else if (d_depth)
-        BVC_HIP_D(ctx, launch_bam_counts_depth(ctx->stream, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
-                                               d_group, n_groups, S, d_counts, d_tally, d_depth));
-    else
-        BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, c.n_samples, c.bam, c.bam_bytes, c.off, c.end, c.n_positions, c.pos, c.rg_s, c.refseq_len,
-                                         d_group, n_groups, S, d_counts, d_tally, d_status));
-    return BVC_OK;
-}
-
-// The depth forms' own check of the labels: there is no form without groups
-int check_depth_groups(bvc_ctx *ctx, int32_t n_samples, const uint8_t *group_of_sample, int32_t n_groups)
-{
-    if (n_groups < 1 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 1..32");
-    if (n_samples > 0 && !group_of_sample) return fail(ctx, BVC_ERR_ARG, "null group_of_sample with samples present");
-    return BVC_OK;
-}
-
-// What both entry points check of the sample and position arguments before anything of the device is touched; fills what they share.
-int check_counts_call(bvc_ctx *ctx, BamCall &c, int32_t n_samples, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
-                      const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
-                      const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
-                      const uint32_t *sample_status)
-{
-    int rc = check_sizes(ctx, n_samples, bam_bytes, n_positions, refseq_len, 0);
-    if (rc != BVC_OK) return rc;
-    if ((rc = check_counts_groups(ctx, n_samples, group_of_sample, n_groups)) != BVC_OK) return rc;
-    if ((n_samples > 0 && (!sample_off || !sample_end || !sample_eof || !rid || !sample_status)) || (n_positions > 0 && !positions))
+    if ((h.bam_bytes > 0 && !h.bam) || (h.n_samples > 0 && h.n_positions > 0 && (!a.counts || !a.tally || (layout.depth_groups > 0u && !a.depth))))
         return fail(ctx, BVC_ERR_ARG, "null data pointer");
-    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
-    c.eof = sample_eof; c.off = sample_off; c.end = sample_end; c.rid = rid; c.pos = positions; c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
-    return BVC_OK;
-}
-
-// bvc_bam_counts (depth = false: counts [P][slots][512], group_depth unused) and bvc_bam_counts_depth (depth = true: counts [P][512] and
-// group_depth [P][n_groups][4]) are one call; so is bvc_bam_counts_quals (n_quals > 0: counts [P][4][n_quals]; depth says whether it has
-// groups, n_groups 0 is allowed).
-int bam_counts_call(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
-                    const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
-                    const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups, bool depth,
-                    uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags, int32_t n_quals = 0)
-{
-    if (!ctx) return BVC_ERR_ARG;
-    BamCall c;
-    int rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                               refseq_len, group_of_sample, depth ? 0 : n_groups, sample_status);
-    if (rc != BVC_OK) return rc;
-    if (depth && (rc = check_depth_groups(ctx, n_samples, group_of_sample, n_groups)) != BVC_OK) return rc;
-    if ((bam_bytes > 0 && !bam) || (n_samples > 0 && n_positions > 0 && (!counts || !tally || (depth && !group_depth))))
-        return fail(ctx, BVC_ERR_ARG, "null data pointer");
-    c.bam = bam;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t ns = (size_t)n_samples, np = (size_t)n_positions;
-    const bool labels = n_groups > 0 && ns > 0;
+    const size_t ns = (size_t)h.n_samples, np = (size_t)h.n_positions;
     BamPileupScratch S;
     PinIO io(ctx);
+    int rc;
     if (flags & BVC_PTR_DEVICE) {
         if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
-        rc = bam_counts_verdict(ctx, io, c, true, sample_status, sample_status, nullptr, S, n_quals);
-        return rc != BVC_OK ? rc : bam_counts_add(ctx, c, group_of_sample, n_groups, S, counts, tally, depth ? group_depth : nullptr, sample_status, n_quals);
+        if ((rc = bam_counts_verdict(ctx, io, h, layout, true, sample_status, sample_status, nullptr, S)) != BVC_OK) return rc;
+        BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, h, layout, S, a, sample_status));
+        return BVC_OK;
     }
-    if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
+    if ((rc = check_host_arrays(ctx, h.n_samples, h.off, h.end, h.bam_bytes, h.n_positions, h.pos)) != BVC_OK) return rc;
     if ((rc = io.reserve(ns * 22 + np * 4 + 1024, 64 + ns * 4 + 1024)) != BVC_OK) return rc;
     // host pointers: the inputs and the accumulators live in the staging buffer for the length of the call
-    const size_t row = n_quals > 0 ? (size_t)n_quals * 4 : (n_groups > 0 && !depth ? (size_t)n_groups + 1 : 1) * BVC_NCLASS;
-    const size_t cwords = ns ? np * row : 0, trows = ns ? np : 0;
-    const size_t dwords = depth && ns ? np * (size_t)n_groups * 4 : 0;
-    uint8_t *u_bam, *u_eof, *u_grp; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos; uint32_t *d_status, *d_counts, *d_depth; bvc_bam_site_tally *d_tally;
+    const size_t cwords = ns ? np * layout.count_words() : 0, trows = ns ? np : 0, dwords = ns ? np * layout.depth_groups * 4 : 0;
+    BamStage st(h, nullptr, 0, nullptr, 0, layout.label_groups() > 0u ? a.group_of_sample : nullptr);
+    CountsArrays d{nullptr, nullptr, nullptr, nullptr};
     rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
-        u_bam = L.take<uint8_t>((size_t)bam_bytes);
-        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns); u_grp = L.take<uint8_t>(ns);
-        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
-        d_counts = L.take<uint32_t>(cwords); d_tally = L.take<bvc_bam_site_tally>(trows); d_depth = L.take<uint32_t>(dwords);
+        st.take(L);
+        d.counts = L.take<uint32_t>(cwords); d.tally = L.take<bvc_bam_site_tally>(trows); d.depth = L.take<uint32_t>(dwords);
     });
-    if (rc != BVC_OK) return rc;
-    if (bam_bytes) BVC_HIP_D(ctx, hipMemcpyAsync(u_bam, bam, (size_t)bam_bytes, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
-    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
-    if (labels) BVC_HIP_D(ctx, io.h2d(u_grp, group_of_sample, ns));
-    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
-    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
-    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, nullptr, S, n_quals);
+    if (rc != BVC_OK || (rc = st.upload(ctx, io)) != BVC_OK) return rc;
+    d.group_of_sample = st.d_group;
+    rc = bam_counts_verdict(ctx, io, st.c, layout, false, st.d_status, sample_status, nullptr, S);
     if (rc != BVC_OK || cwords == 0) return rc;
     // the accumulators go up only now: a call that fails has not touched them
-    BVC_HIP_D(ctx, hipMemcpyAsync(d_counts, counts, cwords * 4, hipMemcpyHostToDevice, ctx->stream));
-    BVC_HIP_D(ctx, hipMemcpyAsync(d_tally, tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyHostToDevice, ctx->stream));
-    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(d_depth, group_depth, dwords * 4, hipMemcpyHostToDevice, ctx->stream));
-    if ((rc = bam_counts_add(ctx, c, u_grp, n_groups, S, d_counts, d_tally, depth ? d_depth : nullptr, d_status, n_quals)) != BVC_OK) return rc;
-    BVC_HIP_D(ctx, hipMemcpyAsync(counts, d_counts, cwords * 4, hipMemcpyDeviceToHost, ctx->stream));
-    BVC_HIP_D(ctx, hipMemcpyAsync(tally, d_tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
-    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(group_depth, d_depth, dwords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d.counts, a.counts, cwords * 4, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(d.tally, a.tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyHostToDevice, ctx->stream));
+    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(d.depth, a.depth, dwords * 4, hipMemcpyHostToDevice, ctx->stream));
+    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, st.c, layout, S, d, st.d_status));
+    BVC_HIP_D(ctx, hipMemcpyAsync(a.counts, d.counts, cwords * 4, hipMemcpyDeviceToHost, ctx->stream));
+    BVC_HIP_D(ctx, hipMemcpyAsync(a.tally, d.tally, trows * sizeof(bvc_bam_site_tally), hipMemcpyDeviceToHost, ctx->stream));
+    if (dwords) BVC_HIP_D(ctx, hipMemcpyAsync(a.depth, d.depth, dwords * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }
 
-// Every kind of accumulator is made here: depth_groups > 0 is the second kind (n_groups is then 0), n_quals > 0 the third (n_groups 0,
-// depth_groups 0..32)
-int site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t depth_groups, int64_t byte_budget, int32_t n_quals = 0)
+// Every kind of accumulator is made here
+int site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, const CountsLayout &layout, int64_t byte_budget)
 {
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return BVC_ERR_DEVICE; }
     bvc_site_acc *acc = new bvc_site_acc;
-    acc->device = device; acc->n_positions = n_positions; acc->n_groups = n_groups; acc->depth_groups = depth_groups; acc->n_quals = n_quals;
+    acc->device = device; acc->n_positions = n_positions; acc->layout = layout;
     acc->budget = byte_budget > 0 ? byte_budget : 0;
-    const size_t cbytes = (size_t)n_positions * acc->row_words() * 4, tbytes = (size_t)n_positions * sizeof(bvc_bam_site_tally);
-    const size_t dbytes = (size_t)n_positions * (size_t)depth_groups * 16;
-    acc->used = (int64_t)(cbytes + tbytes + dbytes);
+    const size_t cbytes = (size_t)n_positions * layout.count_words() * 4, tbytes = (size_t)n_positions * sizeof(bvc_bam_site_tally);
+    const size_t dbytes = (size_t)n_positions * layout.depth_groups * 16;
+    acc->used = (int64_t)((size_t)n_positions * layout.bytes_per_position());
     if (acc->budget > 0 && acc->used > acc->budget) { delete acc; return BVC_ERR_ALLOC; }
     if (n_positions > 0 &&
         (hipMalloc(reinterpret_cast<void **>(&acc->d_counts), cbytes) != hipSuccess || hipMalloc(reinterpret_cast<void **>(&acc->d_tally), tbytes) != hipSuccess ||
@@ -239,8 +175,11 @@ int bvc_bam_counts(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t 
                    const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
                    uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *sample_status, uint32_t flags)
 {
-    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                           refseq_len, group_of_sample, n_groups, false, counts, tally, nullptr, sample_status, flags);
+    if (!ctx) return BVC_ERR_ARG;
+    const BamCall h = bam_call(n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    const int rc = check_counts_call(ctx, h, group_of_sample, n_groups, false, sample_status);
+    if (rc != BVC_OK) return rc;
+    return bam_counts_call(ctx, h, CountsLayout::wide(n_groups), CountsArrays{counts, tally, nullptr, group_of_sample}, sample_status, flags);
 }
 
 int bvc_bam_counts_depth(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
@@ -248,8 +187,11 @@ int bvc_bam_counts_depth(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, in
                          const int32_t *positions, int32_t rg_s, int64_t refseq_len, const uint8_t *group_of_sample, int32_t n_groups,
                          uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
 {
-    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                           refseq_len, group_of_sample, n_groups, true, counts, tally, group_depth, sample_status, flags);
+    if (!ctx) return BVC_ERR_ARG;
+    const BamCall h = bam_call(n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    const int rc = check_counts_call(ctx, h, group_of_sample, n_groups, true, sample_status);
+    if (rc != BVC_OK) return rc;
+    return bam_counts_call(ctx, h, CountsLayout::with_depth(n_groups), CountsArrays{counts, tally, group_depth, group_of_sample}, sample_status, flags);
 }
 
 int bvc_bam_counts_quals(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
@@ -258,11 +200,12 @@ int bvc_bam_counts_quals(bvc_ctx *ctx, int32_t n_samples, const uint8_t *bam, in
                          uint32_t *counts, bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status, uint32_t flags)
 {
     if (!ctx) return BVC_ERR_ARG;
-    if (!quals_ok(n_quals)) return fail(ctx, BVC_ERR_ARG, "n_quals must be a multiple of 4 in 4..128");
+    if (!CountsLayout::quals_ok(n_quals)) return fail(ctx, BVC_ERR_ARG, "n_quals must be a multiple of 4 in 4..128");
     if (n_groups < 0 || n_groups > BVC_MAX_GROUPS) return fail(ctx, BVC_ERR_ARG, "n_groups must be 0..32");
-    return bam_counts_call(ctx, n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                           refseq_len, n_groups > 0 ? group_of_sample : nullptr, n_groups, n_groups > 0, counts, tally, group_depth, sample_status, flags,
-                           n_quals);
+    const BamCall h = bam_call(n_samples, bam, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    const int rc = check_counts_call(ctx, h, group_of_sample, n_groups, n_groups > 0, sample_status);
+    if (rc != BVC_OK) return rc;
+    return bam_counts_call(ctx, h, CountsLayout::narrow(n_quals, n_groups), CountsArrays{counts, tally, group_depth, group_of_sample}, sample_status, flags);
 }
 
 int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
@@ -270,7 +213,7 @@ int bvc_site_acc_create(bvc_site_acc **out, int device, int32_t n_positions, int
     if (!out) return BVC_ERR_ARG;
     *out = nullptr;
     if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
-    return site_acc_create(out, device, n_positions, n_groups, 0, byte_budget);
+    return site_acc_create(out, device, n_positions, CountsLayout::wide(n_groups), byte_budget);
 }
 
 int bvc_site_acc_create_depth(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int64_t byte_budget)
@@ -278,21 +221,21 @@ int bvc_site_acc_create_depth(bvc_site_acc **out, int device, int32_t n_position
     if (!out) return BVC_ERR_ARG;
     *out = nullptr;
     if (n_positions < 0 || n_groups < 1 || n_groups > BVC_MAX_GROUPS) return BVC_ERR_ARG;
-    return site_acc_create(out, device, n_positions, 0, n_groups, byte_budget);
+    return site_acc_create(out, device, n_positions, CountsLayout::with_depth(n_groups), byte_budget);
 }
 
 int bvc_site_acc_create_quals(bvc_site_acc **out, int device, int32_t n_positions, int32_t n_groups, int32_t n_quals, int64_t byte_budget)
 {
     if (!out) return BVC_ERR_ARG;
     *out = nullptr;
-    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS || !quals_ok(n_quals)) return BVC_ERR_ARG;
-    return site_acc_create(out, device, n_positions, 0, n_groups, byte_budget, n_quals);
+    if (n_positions < 0 || n_groups < 0 || n_groups > BVC_MAX_GROUPS || !CountsLayout::quals_ok(n_quals)) return BVC_ERR_ARG;
+    return site_acc_create(out, device, n_positions, CountsLayout::narrow(n_quals, n_groups), byte_budget);
 }
 
 int bvc_site_acc_quals(const bvc_site_acc *acc, int32_t *n_quals)
 {
     if (!acc || !n_quals) return BVC_ERR_ARG;
-    *n_quals = acc->n_quals > 0 ? acc->n_quals : 128;
+    *n_quals = (int32_t)acc->layout.n_quals;
     return BVC_OK;
 }
 
@@ -323,49 +266,23 @@ int bvc_bam_counts_bgzf_acc(bvc_ctx *ctx, int32_t n_samples, const uint8_t *comp
     int rc = check_acc(ctx, acc);
     if (rc != BVC_OK) return rc;
     if (n_positions != acc->n_positions) return fail(ctx, BVC_ERR_ARG, "n_positions is not the accumulator's");
-    BamCall c;
-    rc = check_counts_call(ctx, c, n_samples, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s,
-                           refseq_len, group_of_sample, acc->n_groups, sample_status);
-    if (rc != BVC_OK) return rc;
-    const int32_t dg = acc->depth_groups;                               // (> 0: the second kind, whose n_groups is 0)
-    if (dg > 0 && (rc = check_depth_groups(ctx, n_samples, group_of_sample, dg)) != BVC_OK) return rc;
+    const CountsLayout &layout = acc->layout;
+    const BamCall h = bam_call(n_samples, nullptr, bam_bytes, sample_off, sample_end, sample_eof, rid, beg0, end0, min_mapq, n_positions, positions, rg_s, refseq_len);
+    if ((rc = check_counts_call(ctx, h, group_of_sample, (int32_t)layout.label_groups(), layout.depth_groups > 0u, sample_status)) != BVC_OK) return rc;
     if (comp_bytes < 0 || n_blocks < 0) return fail(ctx, BVC_ERR_ARG, "negative size");
     if (n_blocks > 0 && (!comp || !blocks)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if ((rc = check_blocks(ctx, blocks, n_blocks, comp_bytes, bam_bytes)) != BVC_OK) return rc;
     if ((rc = check_host_arrays(ctx, n_samples, sample_off, sample_end, bam_bytes, n_positions, positions)) != BVC_OK) return rc;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t ns = (size_t)n_samples, np = (size_t)n_positions, nb = (size_t)n_blocks;
-    const bool labels = (acc->n_groups > 0 || dg > 0) && ns > 0;
     PinIO io(ctx);
     if ((rc = io.reserve(ns * 22 + np * 4 + nb * sizeof(bvc_bgzf_block) + 1024, 64 + ns * 4 + nb * 4 + 1024)) != BVC_OK) return rc;
-    uint8_t *u_comp, *u_bam, *u_eof, *u_grp; bvc_bgzf_block *u_blk; uint32_t *u_bst, *d_status; int64_t *u_off, *u_end; int32_t *u_rid, *u_pos;
-    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
-        u_comp = L.take<uint8_t>((size_t)comp_bytes, 16); u_blk = L.take<bvc_bgzf_block>(nb); u_bst = L.take<uint32_t>(nb);
-        u_bam = L.take<uint8_t>((size_t)bam_bytes);
-        u_off = L.take<int64_t>(ns); u_end = L.take<int64_t>(ns); u_eof = L.take<uint8_t>(ns); u_rid = L.take<int32_t>(ns); u_grp = L.take<uint8_t>(ns);
-        u_pos = L.take<int32_t>(np); d_status = L.take<uint32_t>(ns);
-    });
-    if (rc != BVC_OK) return rc;
-    std::vector<uint32_t> block_status(nb);
-    if (nb) {
-        BVC_HIP_D(ctx, hipMemcpyAsync(u_comp, comp, (size_t)comp_bytes, hipMemcpyHostToDevice, ctx->stream));
-        BVC_HIP_D(ctx, io.h2d(u_blk, blocks, nb * sizeof(bvc_bgzf_block)));
-        BVC_HIP_D(ctx, launch_inflate(ctx->stream, u_comp, u_blk, n_blocks, u_bam, u_bst));
-        BVC_HIP_D(ctx, io.d2h(block_status.data(), u_bst, nb * 4));
-    }
-    BVC_HIP_D(ctx, io.h2d(u_off, sample_off, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_end, sample_end, ns * 8));
-    BVC_HIP_D(ctx, io.h2d(u_eof, sample_eof, ns));
-    BVC_HIP_D(ctx, io.h2d(u_rid, rid, ns * 4));
-    if (labels) BVC_HIP_D(ctx, io.h2d(u_grp, group_of_sample, ns));
-    BVC_HIP_D(ctx, io.h2d(u_pos, positions, np * 4));
-    c.bam = u_bam; c.off = u_off; c.end = u_end; c.eof = u_eof; c.rid = u_rid; c.pos = u_pos;
+    BamStage st(h, comp, comp_bytes, blocks, n_blocks, layout.label_groups() > 0u ? group_of_sample : nullptr);
+    rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) { st.take(L); });
+    if (rc != BVC_OK || (rc = st.upload(ctx, io)) != BVC_OK) return rc;
     BamPileupScratch S;
-    rc = bam_counts_verdict(ctx, io, c, false, d_status, sample_status, &block_status, S, acc->n_quals);
-    if (rc != BVC_OK) return rc;
-    if ((rc = bam_counts_add(ctx, c, u_grp, dg > 0 ? dg : acc->n_groups, S, acc->d_counts, acc->d_tally, dg > 0 ? acc->d_depth : nullptr, d_status,
-                             acc->n_quals)) != BVC_OK)
-        return rc;
+    if ((rc = bam_counts_verdict(ctx, io, st.c, layout, false, st.d_status, sample_status, &st.block_status, S)) != BVC_OK) return rc;
+    BVC_HIP_D(ctx, launch_bam_counts(ctx->stream, true, st.c, layout, S, CountsArrays{acc->d_counts, acc->d_tally, acc->d_depth, st.d_group}, st.d_status));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
 }
@@ -379,15 +296,15 @@ int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     if (n > 0 && !tally) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if (n == 0) return BVC_OK;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t rw = acc->row_words();
-    if (counts && acc->expanded()) {
+    const size_t rw = acc->layout.count_words();
+    if (counts && acc->layout.expanded()) {
         // narrow rows: a bounded piece at a time is expanded into the context's scratch and comes down from there
         const int32_t piece = n < kExpandRows ? n : kExpandRows;
         uint32_t *d_wide;
         if ((rc = carve(ctx, ctx->d_acc, 256, [&](Layout &L) { d_wide = L.take<uint32_t>((size_t)piece * BVC_NCLASS); })) != BVC_OK) return rc;
         for (int32_t k = 0; k < n; k += piece) {
             const int32_t m = n - k < piece ? n - k : piece;
-            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, acc->n_quals, acc->d_counts + ((size_t)t0 + (size_t)k) * rw, d_wide));
+            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, (int32_t)acc->layout.n_quals, acc->d_counts + ((size_t)t0 + (size_t)k) * rw, d_wide));
             BVC_HIP_D(ctx, hipMemcpyAsync(counts + (size_t)k * BVC_NCLASS, d_wide, (size_t)m * BVC_NCLASS * 4, hipMemcpyDeviceToHost, ctx->stream));
         }
     } else if (counts)
@@ -400,9 +317,9 @@ int bvc_site_acc_get(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
 int bvc_site_acc_row_words(const bvc_site_acc *acc, int32_t *row_words, int32_t *slots, int32_t *depth_groups)
 {
     if (!acc) return BVC_ERR_ARG;
-    if (row_words) *row_words = (int32_t)acc->logical_words();
-    if (slots) *slots = (int32_t)acc->slots();
-    if (depth_groups) *depth_groups = acc->depth_groups;
+    if (row_words) *row_words = (int32_t)acc->layout.logical_words();
+    if (slots) *slots = (int32_t)acc->layout.slots;
+    if (depth_groups) *depth_groups = (int32_t)acc->layout.depth_groups;
     return BVC_OK;
 }
 
@@ -431,7 +348,7 @@ int bvc_site_acc_pack(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t
         if (!dev) d_row_start = L.take<int64_t>(nr + 1);
     });
     if (rc != BVC_OK) return rc;
-    const AccRowShape s = acc->shape(t0);
+    const AccRowShape s = acc->layout.row_shape(t0);
     PinIO io(ctx);
     if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
     BVC_HIP_D(ctx, launch_acc_pack(ctx->stream, false, n, s, acc->d_counts, acc->d_tally, acc->d_depth, d_row_n, nullptr, nullptr, nullptr));
@@ -488,12 +405,12 @@ int bvc_site_acc_add_packed(bvc_ctx *ctx, bvc_site_acc *acc, int32_t t0, int32_t
         }
         d_row_start = u_rs; d_cell = u_cell; d_count = u_count;
     }
-    const AccRowShape s = acc->shape(t0);
-    const int32_t nq = acc->expanded() ? acc->n_quals : 128;
+    const AccRowShape s = acc->layout.row_shape(t0);
+    const int nq = (int)acc->layout.n_quals, row_words = (int)acc->layout.logical_words();
     PinIO io(ctx);
     if ((rc = io.reserve(0, 64 + 1024)) != BVC_OK) return rc;
     // dry pass -> first fault -> the one wait, for the verdict: nothing is added unless the whole piece is sound
-    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, false, n, s, nq, d_row_start, d_cell, d_count, n_entries, nullptr, nullptr, acc->d_depth, d_fault));
+    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, false, n, s, d_row_start, d_cell, d_count, n_entries, nullptr, nullptr, acc->d_depth, d_fault));
     BVC_HIP_D(ctx, launch_acc_first_fault(ctx->stream, n, d_fault, d_first));
     int64_t first[2] = {0, 0};
     BVC_HIP_D(ctx, io.d2h(first, d_first, sizeof first));
@@ -507,17 +424,15 @@ int bvc_site_acc_add_packed(bvc_ctx *ctx, bvc_site_acc *acc, int32_t t0, int32_t
             std::snprintf(msg, sizeof msg, "row %lld: row_start must start at 0, never decrease and end at n_entries = %lld", t, (long long)n_entries);
             break;
         case kAccFaultCell:
-            std::snprintf(msg, sizeof msg, "row %lld: a cell of %d or more, and the accumulator's row has %d words", t, (int)acc->logical_words(),
-                          (int)acc->logical_words());
+            std::snprintf(msg, sizeof msg, "row %lld: a cell of %d or more, and the accumulator's row has %d words", t, row_words, row_words);
             break;
         case kAccFaultOrder: std::snprintf(msg, sizeof msg, "row %lld: the cells of a row must ascend strictly", t); break;
         default:
-            std::snprintf(msg, sizeof msg, "row %lld: a count of a base quality of %d or more, and the counts keep n_quals = %d quality columns", t, (int)nq,
-                          (int)nq);
+            std::snprintf(msg, sizeof msg, "row %lld: a count of a base quality of %d or more, and the counts keep n_quals = %d quality columns", t, nq, nq);
         }
         return fail(ctx, BVC_ERR_DATA, msg);
     }
-    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, true, n, s, nq, d_row_start, d_cell, d_count, n_entries, acc->d_counts, acc->d_tally, acc->d_depth,
+    BVC_HIP_D(ctx, launch_acc_add_packed(ctx->stream, true, n, s, d_row_start, d_cell, d_count, n_entries, acc->d_counts, acc->d_tally, acc->d_depth,
                                          nullptr));
     if (!dev) BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
@@ -528,12 +443,12 @@ int bvc_site_acc_get_depth(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, in
     if (!ctx) return BVC_ERR_ARG;
     int rc = check_acc(ctx, acc);
     if (rc != BVC_OK) return rc;
-    if (acc->depth_groups <= 0) return fail(ctx, BVC_ERR_ARG, "the accumulator keeps no group depths (bvc_site_acc_create_depth makes one that does)");
+    if (acc->layout.depth_groups == 0u) return fail(ctx, BVC_ERR_ARG, "the accumulator keeps no group depths (bvc_site_acc_create_depth makes one that does)");
     if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
     if (n > 0 && !group_depth) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if (n == 0) return BVC_OK;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t rw = (size_t)acc->depth_groups * 4;
+    const size_t rw = (size_t)acc->layout.depth_groups * 4;
     BVC_HIP_D(ctx, hipMemcpyAsync(group_depth, acc->d_depth + (size_t)t0 * rw, (size_t)n * rw * 4, hipMemcpyDeviceToHost, ctx->stream));
     BVC_HIP_D(ctx, wait_stream(ctx));
     return BVC_OK;
@@ -546,13 +461,13 @@ int bvc_site_acc_lrt(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     int rc = check_acc(ctx, acc);
     if (rc != BVC_OK) return rc;
     if ((rc = check_rows(ctx, acc, t0, n)) != BVC_OK) return rc;
-    const int32_t ng = acc->n_groups;
+    const int32_t ng = (int32_t)acc->layout.slots - 1;         // the groups that have a slot of their own
     if (n > 0 && (!ref_base || !results || (ng > 0 && !grp_results))) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if (n == 0) return BVC_OK;
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     // the rows stay where they are: only ref_base goes up and the records come down, through the staging buffer
     int8_t *d_r; bvc_site_result *d_res; bvc_group_result *d_gres; uint32_t *d_wide;
-    const int32_t piece = !acc->expanded() ? 0 : n < kExpandRows ? n : kExpandRows;      // narrow rows: expanded a piece at a time
+    const int32_t piece = !acc->layout.expanded() ? 0 : n < kExpandRows ? n : kExpandRows;      // narrow rows: expanded a piece at a time
     rc = carve(ctx, ctx->d_stage[0], 256, [&](Layout &L) {
         d_r = L.take<int8_t>((size_t)n);
         d_res = L.take<bvc_site_result>((size_t)n);
@@ -561,12 +476,13 @@ int bvc_site_acc_lrt(bvc_ctx *ctx, const bvc_site_acc *acc, int32_t t0, int32_t 
     });
     if (rc != BVC_OK) return rc;
     BVC_HIP_D(ctx, hipMemcpyAsync(d_r, ref_base, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
-    const uint32_t *rows = acc->d_counts + (size_t)t0 * acc->row_words();
+    const size_t rw = acc->layout.count_words();
+    const uint32_t *rows = acc->d_counts + (size_t)t0 * rw;
     if (piece > 0) {
         // (the stream orders a piece's stage 2 in front of the next piece's expansion into the same scratch)
         for (int32_t k = 0; k < n && rc == BVC_OK; k += piece) {
             const int32_t m = n - k < piece ? n - k : piece;
-            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, acc->n_quals, rows + (size_t)k * acc->row_words(), d_wide));
+            BVC_HIP_D(ctx, launch_acc_expand(ctx->stream, m, (int32_t)acc->layout.n_quals, rows + (size_t)k * rw, d_wide));
             rc = bvc_lrt_hist(ctx, m, d_wide, d_r + k, min_af, nullptr, nullptr, d_res + k, BVC_PTR_DEVICE);
         }
     } else if (ng > 0) {

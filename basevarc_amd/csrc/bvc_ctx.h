@@ -350,14 +350,37 @@ int bam_pileup_bgzf_call(bool text, bvc_ctx *ctx, int32_t n_samples, const uint8
                          const char *refseq, int64_t refseq_len, uint8_t *records, int64_t records_cap, int64_t *records_needed,
                          uint32_t *rec_start, uint32_t *sample_status, BatchSink *sink = nullptr);
 
-// bvc_bam.hip, shared with bvc_bam_counts.hip: a call's inputs where the kernels read them (device memory) and its sizes ...
-struct BamCall {
-    int32_t n_samples = 0, n_positions = 0, beg0 = 0, end0 = 0, min_mapq = 0, rg_s = 0;
-    const uint8_t *bam = nullptr, *eof = nullptr, *ref = nullptr;   // ref: the reference's text (the pileup only)
-    const uint8_t *pref = nullptr, *palt = nullptr;                 // the positions' REF and ALT characters (the matrix only)
-    const int64_t *off = nullptr, *end = nullptr;
-    const int32_t *rid = nullptr, *pos = nullptr;
-    int64_t bam_bytes = 0, refseq_len = 0;
+// bvc_bam.hip, shared with bvc_bam_counts.hip: a call's inputs (BamCall, bvc_internal.h) from the arguments every entry point has ...
+inline BamCall bam_call(int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off, const int64_t *sample_end,
+                        const uint8_t *sample_eof, const int32_t *rid, int32_t beg0, int32_t end0, int32_t min_mapq, int32_t n_positions,
+                        const int32_t *positions, int32_t rg_s, int64_t refseq_len)
+{
+    BamCall c;
+    c.n_samples = n_samples; c.n_positions = n_positions; c.beg0 = beg0; c.end0 = end0; c.min_mapq = min_mapq; c.rg_s = rg_s;
+    c.bam = bam; c.eof = sample_eof; c.off = sample_off; c.end = sample_end; c.rid = rid; c.pos = positions; c.bam_bytes = bam_bytes; c.refseq_len = refseq_len;
+    return c;
+}
+// ... the way of a host-pointer call's inputs into the staging buffer: take() among the caller's own takes of one carve, then upload(),
+// which enqueues on the context's stream the bulk (the BGZF bytes, else the inflated records) straight from the caller's memory, the
+// arrays through io, and with blocks the inflate and the blocks' statuses on their way down (the call's first wait delivers them) ...
+struct BamStage {
+    BamCall c;                              // the call with bam and the sample and position arrays where the kernels read them
+    uint32_t *d_status = nullptr;           // [n_samples]
+    uint8_t *d_group = nullptr;             // [n_samples]: the labels (null without group_of_sample)
+    std::vector<uint32_t> block_status;     // [n_blocks]
+    // host: the caller's pointers; comp / blocks: its BGZF blocks (host.bam is then unused); group_of_sample may be null
+    BamStage(const BamCall &host, const uint8_t *comp, int64_t comp_bytes, const bvc_bgzf_block *blocks, int64_t n_blocks,
+             const uint8_t *group_of_sample = nullptr)
+        : c(host), block_status((size_t)n_blocks), h(host), comp(comp), group(group_of_sample), blocks(blocks), comp_bytes(comp_bytes), n_blocks(n_blocks) {}
+    void take(Layout &L);
+    int upload(bvc_ctx *ctx, PinIO &io);
+private:
+    const BamCall h;
+    const uint8_t *comp, *group;
+    const bvc_bgzf_block *blocks;
+    int64_t comp_bytes, n_blocks;
+    uint8_t *u_comp = nullptr, *u_bam = nullptr, *u_eof = nullptr; bvc_bgzf_block *u_blk = nullptr; uint32_t *u_bst = nullptr;
+    int64_t *u_off = nullptr, *u_end = nullptr; int32_t *u_rid = nullptr, *u_pos = nullptr;
 };
 // ... the checks made before anything of the device is touched (strict: the positions ascend strictly; else they may repeat) ...
 int check_sizes(bvc_ctx *ctx, int32_t n_samples, int64_t bam_bytes, int32_t n_positions, int64_t refseq_len, int64_t records_cap);

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "../../include/bvc.h"
+#include "counts_layout.h"
 
 struct bvc_bam_site_tally;              // include/bvc_bam_counts.h
 
@@ -317,45 +318,40 @@ hipError_t launch_bam_popmatrix(hipStream_t stream, int32_t n_samples, const uin
                                 const int64_t *sample_end, int32_t n_positions, const int32_t *positions, const uint8_t *ref, const uint8_t *alt,
                                 int32_t rg_s, int64_t refseq_len, const BamPileupScratch &s, uint8_t *matrix, int64_t row_stride, uint32_t *sample_status);
 
-// bam_counts_kernel.hip: the same records added into class counts [position][slot][512] and tallies [position] (include/bvc_bam_counts.h,
-// bvc_bam_counts).  launch_bam_index as above, the scratch is bam_popmatrix_scratch; add = false: the dry pass, which only raises status 4
-// (nothing of counts, tally or group_of_sample is read); add = true: the adds.  launch_bam_scan with n_positions = 0 leaves head[1..3].
-hipError_t launch_bam_counts(hipStream_t stream, bool add, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
-                             const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
-                             const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
-                             ::bvc_bam_site_tally *tally, uint32_t *sample_status);
-// bam_group_depth_kernel.hip: the add pass with ONE slot of counts [position][512] and the groups' depths [position][n_groups][4] beside it
-// (include/bvc_bam_group_depth.h, bvc_bam_counts_depth); n_groups 1..32, a label >= n_groups adds no depth.  Its dry pass is
-// launch_bam_counts(add = false).
-hipError_t launch_bam_counts_depth(hipStream_t stream, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
-                                   const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
-                                   const uint8_t *group_of_sample, int32_t n_groups, const BamPileupScratch &s, uint32_t *counts,
-                                   ::bvc_bam_site_tally *tally, uint32_t *group_depth);
-// bam_counts_quals_kernel.hip: both passes with NARROW rows of counts [position][4][n_quals] (include/bvc_site_acc_quals.h,
-// bvc_bam_counts_quals); n_quals a multiple of 4 in 4..128, n_groups 0..32 (0: group_of_sample and group_depth are not read).  add = false:
-// the dry pass, which raises status 4 and status 5 (4 where both hold) and reads nothing of the three arrays; add = true: the adds, none
-// for a quality >= n_quals.  launch_first_status leaves in out[0] the first sample of status `which` (0x7FFFFFFF: none);
-// launch_acc_expand turns rows [n_rows][4][n_quals] into [n_rows][512] with zeros in the columns >= n_quals (both 16-byte aligned).
-inline bool quals_ok(int32_t n_quals) { return n_quals >= 4 && n_quals <= 128 && n_quals % 4 == 0; }
-hipError_t launch_bam_counts_quals(hipStream_t stream, bool add, int32_t n_samples, const uint8_t *bam, int64_t bam_bytes, const int64_t *sample_off,
-                                   const int64_t *sample_end, int32_t n_positions, const int32_t *positions, int32_t rg_s, int64_t refseq_len,
-                                   const uint8_t *group_of_sample, int32_t n_groups, int32_t n_quals, const BamPileupScratch &s, uint32_t *counts,
-                                   ::bvc_bam_site_tally *tally, uint32_t *group_depth, uint32_t *sample_status);
+// A call over a batch's inflated BAM records: its inputs where the kernels read them (device memory; in the host-pointer forms the caller's
+// arrays until they are staged) and its sizes
+struct BamCall {
+    int32_t n_samples = 0, n_positions = 0, beg0 = 0, end0 = 0, min_mapq = 0, rg_s = 0;
+    const uint8_t *bam = nullptr, *eof = nullptr, *ref = nullptr;   // ref: the reference's text (the pileup only)
+    const uint8_t *pref = nullptr, *palt = nullptr;                 // the positions' REF and ALT characters (the matrix only)
+    const int64_t *off = nullptr, *end = nullptr;
+    const int32_t *rid = nullptr, *pos = nullptr;
+    int64_t bam_bytes = 0, refseq_len = 0;
+};
+
+// bam_counts_kernel.hip: the same records added into class counts and tallies [position] of any CountsLayout (counts_layout.h;
+// include/bvc_bam_counts.h, bvc_bam_group_depth.h, bvc_site_acc_quals.h).  launch_bam_index as above, the scratch is bam_popmatrix_scratch.
+// add = false: the dry pass, which raises status 4 and on narrow rows status 5 (4 where both hold) and reads nothing of the arrays;
+// add = true: the adds -- counts [slots][512] or [4][n_quals] a position (none for a quality >= n_quals), the tally, and depth
+// [depth_groups][4] where the layout has groups' depths; group_of_sample is read where label_groups() > 0, a label >= that adds to the last
+// slot or to no depth.  launch_bam_scan with n_positions = 0 leaves head[1..3]; launch_first_status leaves in out[0] the first sample of
+// status `which` (0x7FFFFFFF: none); launch_acc_expand turns rows [n_rows][4][n_quals] into [n_rows][512] with zeros in the columns
+// >= n_quals (both 16-byte aligned).
+struct CountsArrays { uint32_t *counts; ::bvc_bam_site_tally *tally; uint32_t *depth; const uint8_t *group_of_sample; };
+hipError_t launch_bam_counts(hipStream_t stream, bool add, const BamCall &c, const CountsLayout &layout, const BamPileupScratch &s, CountsArrays a,
+                             uint32_t *sample_status);
 hipError_t launch_first_status(hipStream_t stream, int32_t n_samples, const uint32_t *sample_status, uint32_t which, int64_t *out);
 hipError_t launch_acc_expand(hipStream_t stream, int64_t n_rows, int32_t n_quals, const uint32_t *narrow, uint32_t *wide);
 
 // acc_pack_kernel.hip: an accumulator's rows <-> (row_start, cell, count) entries of their logical rows (include/bvc_site_acc_pack.h).  The
-// rows a launch works on as the kernels see them: row0 is the first of them in the accumulator's arrays, count_pieces the 16-byte pieces of
-// a position's counts as they are STORED (slots x 128, or n_quals for narrow rows, whose q4 = n_quals / 4; q4 = 0: the wide layout),
-// count_cells the LOGICAL count cells (slots x 512).
-struct AccRowShape { int64_t row0; uint32_t count_pieces, q4, count_cells, depth_groups; };
+// rows a launch works on are an AccRowShape (counts_layout.h, CountsLayout::row_shape).
 enum : uint32_t { kAccFaultRowStart = 1, kAccFaultCell = 2, kAccFaultOrder = 3, kAccFaultQual = 4 };   // a row's fault in row_fault
 // place = false: row_n [n_rows] (nothing of row_start, cell or count is touched); place = true: cell and count through row_start [n_rows + 1]
 hipError_t launch_acc_pack(hipStream_t stream, bool place, int64_t n_rows, const AccRowShape &s, const uint32_t *counts, const ::bvc_bam_site_tally *tally,
                            const uint32_t *depth, uint32_t *row_n, const int64_t *row_start, uint16_t *cell, uint32_t *count);
 hipError_t launch_acc_pack_scan(hipStream_t stream, int64_t n_rows, const uint32_t *row_n, int64_t *row_start);
-// add = false: row_fault [n_rows] (nothing is added); add = true: the adds (row_fault unused).  n_quals: the columns stored, 128 for wide rows
-hipError_t launch_acc_add_packed(hipStream_t stream, bool add, int64_t n_rows, const AccRowShape &s, int32_t n_quals, const int64_t *row_start,
+// add = false: row_fault [n_rows] (nothing is added); add = true: the adds (row_fault unused)
+hipError_t launch_acc_add_packed(hipStream_t stream, bool add, int64_t n_rows, const AccRowShape &s, const int64_t *row_start,
                                  const uint16_t *cell, const uint32_t *count, int64_t n_entries, uint32_t *counts, ::bvc_bam_site_tally *tally,
                                  uint32_t *depth, uint32_t *row_fault);
 // out[0] = the first row whose fault is not 0 (0x7FFFFFFFFFFFFFFF: none), out[1] = that fault

@@ -3,6 +3,7 @@ exported, in the binding's eighth table and refuse a null context or accumulator
 new kernel is built from its own source without private memory, scratch, flat addressing or spills, in the product and the diagnostic
 build; and the model (tests/bam_counts_model.py) folds a hand-made batch as the header says."""
 import ctypes as C
+import functools
 import os
 import re
 import sys
@@ -96,17 +97,34 @@ def test_the_tally_is_forty_eight_bytes_in_the_header_the_binding_and_the_model(
     assert bl.NCLASS == cm.NCLASS == 512
 
 
-def test_the_kernel_is_built_from_its_own_source_without_private_memory_or_flat_addressing():
+COUNTS_SOURCE = "bam_counts_kernel.hip"
+# the five instantiations of the one kernel (CountsKind 0 Slots, 1 Depth, 2 Narrow: no dry pass of Depth's own) and the two beside them
+COUNTS_KERNELS = {f"bam_counts_kernel<{add}, (bvc::CountsKind){kind}>" for add, kind in (("false", 0), ("false", 2), ("true", 0), ("true", 1), ("true", 2))} | \
+    {"first_status_kernel", "acc_expand_kernel"}
+
+
+@functools.lru_cache(maxsize=None)
+def check_the_counts_kernels():
+    """The one check of the three headers' kernel source, in the product and the diagnostic build (made once a session): exactly the seven
+    kernels, none with private memory, scratch, flat addressing, spills or MFMA; one resolve without text and no LDS in the source."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import isa_report
     from basevarc_amd import build as b
-    assert "bam_counts_kernel.hip" in b.SOURCES and "bvc_bam_counts.hip" in b.SOURCES and "bam_counts_kernel.hip" in isa_report.DEVICE_SOURCES
-    assert any(d.endswith("bvc_bam_counts.h") for d in b.DEPS)
+    assert COUNTS_SOURCE in b.SOURCES and COUNTS_SOURCE in isa_report.DEVICE_SOURCES and set(isa_report.DEVICE_SOURCES) <= set(b.SOURCES)
+    text = open(os.path.join(ROOT, "basevarc_amd", "csrc", COUNTS_SOURCE)).read()
+    assert text.count("resolve<false>(") == 1 and "__shared__" not in text
     for flags in ((), ("-DBVC_POISON", "-DBVC_CHECK_LDS")):
-        rows = {re.match(r"(?:bvc::)?([\w<>]+)", k["pretty"]).group(1): k for k in isa_report.kernels_of(isa_report.assembly("bam_counts_kernel.hip", flags))}
-        assert set(rows) == {"bam_counts_kernel<false>", "bam_counts_kernel<true>"}, sorted(rows)
+        rows = {re.match(r"(?:bvc::)?(\w+(?:<[^>]*>)?)", k["pretty"]).group(1): k for k in isa_report.kernels_of(isa_report.assembly(COUNTS_SOURCE, flags))}
+        assert set(rows) == COUNTS_KERNELS, sorted(rows)
         for name, k in rows.items():
             assert k["private"] == 0 and k["scratch"] == 0 and k["flat"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["mfma"] == 0, (name, k)
+
+
+def test_the_kernel_is_built_from_its_own_source_without_private_memory_or_flat_addressing():
+    from basevarc_amd import build as b
+    assert "bvc_bam_counts.hip" in b.SOURCES
+    assert any(d.endswith("bvc_bam_counts.h") for d in b.DEPS)
+    check_the_counts_kernels()
 
 
 def test_the_model_folds_a_hand_made_batch_as_the_header_says():

@@ -70,15 +70,12 @@ def test_the_library_the_header_and_the_binding_know_the_entry_points():
 
 
 def test_the_new_source_is_built_and_in_the_isa_reports_list():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_report
     from basevarc_amd import build as b
-    src = "bam_counts_quals_kernel.hip"
-    assert src in b.SOURCES and src in isa_report.DEVICE_SOURCES and set(isa_report.DEVICE_SOURCES) <= set(b.SOURCES)
+    from tests import test_bam_counts_abi as t8
     assert any(d.endswith("bvc_site_acc_quals.h") for d in b.DEPS)
-    text = open(os.path.join(ROOT, "basevarc_amd", "csrc", src)).read()
-    assert "resolve<false>(" in text and "__shared__" not in text
-    for kernel in ("bam_counts_quals_kernel", "first_status_kernel", "acc_expand_kernel"):
+    t8.check_the_counts_kernels()                     # (bam_counts_kernel.hip: both passes are bam_counts_kernel<ADD, Narrow>)
+    text = open(os.path.join(ROOT, "basevarc_amd", "csrc", t8.COUNTS_SOURCE)).read()
+    for kernel in ("bam_counts_kernel", "first_status_kernel", "acc_expand_kernel"):
         assert kernel in text, kernel
 
 
@@ -89,6 +86,36 @@ def test_the_byte_formula_and_what_it_buys():
     assert qm.acc_bytes(66615, 40, 5) == 66615 * (640 + 48 + 80)
     # 288 GB hold about 137 million wide positions; chromosome 1 (248,956,422 bp) takes 203 GB at 48 columns
     assert 288e9 // 2096 == 137404580 and 203e9 < qm.acc_bytes(248956422, 48) < 204e9 and qm.acc_bytes(248956422, 128) > 288e9
+    assert [q for q in range(-4, 140) if qm.quals_ok(q)] == list(range(4, 129, 4))
+
+
+def test_the_layouts_sizes_are_the_models_and_the_headers(tmp_path):
+    """csrc/counts_layout.h in a stand-alone program (tests/cpp/counts_layout_main.cpp) built with -fsanitize=address,undefined: every kind's
+    sizes against tests/bam_counts_quals_model.py, tests/acc_pack_model.py and the closed forms of the three headers."""
+    from tests import acc_pack_model as pm
+    exe = str(tmp_path / "counts_layout")
+    subprocess.check_call(["g++", "-std=c++11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan",
+                           "-fno-omit-frame-pointer", "-Wall", "-Wextra", "-I", os.path.join(ROOT, "basevarc_amd", "csrc"),
+                           os.path.join(ROOT, "tests", "cpp", "counts_layout_main.cpp"), "-o", exe])
+    r = subprocess.run([exe], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=60)
+    text = r.stdout.decode(errors="replace")
+    assert r.returncode == 0, text[-4000:]
+    lines = text.splitlines()
+    want = [("wide", g, 128) for g in (0, 1, 5, 32)] + [("with_depth", g, 128) for g in (1, 5, 32)] + \
+        [("narrow", g, q) for q in (4, 40, 124, 128) for g in (0, 5, 32)]
+    assert len(lines) == len(want) + 1 == 20
+    for line, (kind, g, q) in zip(lines, want):
+        head, _, tail = line.partition(" -> ")
+        assert head.split() == [kind, str(g), str(q)], line
+        count_words, logical_words, bytes_per_position, expanded, label_groups = (int(x) for x in tail.split())
+        slots, depth_groups = (g + 1 if g else 1, 0) if kind == "wide" else (1, g)
+        assert count_words == slots * 4 * q and logical_words == pm.row_words(slots, depth_groups) == slots * 512 + 10 + 4 * depth_groups, line
+        assert bytes_per_position == 4 * count_words + 48 + 16 * depth_groups and expanded == (q < 128) and label_groups == g, line
+        if kind == "wide":
+            assert count_words == slots * 512 and bytes_per_position == slots * 2048 + 48, line
+        else:
+            assert count_words == 4 * q and bytes_per_position == qm.acc_bytes(1, q, g), line
+    assert lines[-1].split() == ["quals_ok"] + [str(q) for q in range(4, 129, 4)]
     assert [q for q in range(-4, 140) if qm.quals_ok(q)] == list(range(4, 129, 4))
 
 

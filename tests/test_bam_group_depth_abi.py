@@ -84,19 +84,10 @@ def test_the_library_the_header_and_the_binding_know_the_entry_points():
 
 
 def test_the_kernel_is_one_built_from_its_own_source_without_private_memory_or_flat_addressing():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    import isa_report
     from basevarc_amd import build as b
-    src = "bam_group_depth_kernel.hip"
-    assert src in b.SOURCES and src in isa_report.DEVICE_SOURCES and set(isa_report.DEVICE_SOURCES) <= set(b.SOURCES)
+    from tests import test_bam_counts_abi as t8
     assert any(d.endswith("bvc_bam_group_depth.h") for d in b.DEPS)
-    text = open(os.path.join(ROOT, "basevarc_amd", "csrc", src)).read()
-    assert "resolve<false>(" in text and "__shared__" not in text
-    for flags in ((), ("-DBVC_POISON", "-DBVC_CHECK_LDS")):
-        rows = {re.match(r"(?:bvc::)?([\w<>]+)", k["pretty"]).group(1): k for k in isa_report.kernels_of(isa_report.assembly(src, flags))}
-        assert set(rows) == {"bam_counts_depth_kernel"}, sorted(rows)
-        k = rows["bam_counts_depth_kernel"]
-        assert k["private"] == 0 and k["scratch"] == 0 and k["flat"] == 0 and k["vgpr_spill"] == 0 and k["sgpr_spill"] == 0 and k["mfma"] == 0, k
+    t8.check_the_counts_kernels()                     # (bam_counts_kernel.hip: the add pass is bam_counts_kernel<true, Depth>)
 
 
 def test_the_model_folds_the_hand_made_batch_as_the_header_says():

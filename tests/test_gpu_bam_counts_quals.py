@@ -1,4 +1,4 @@
-"""bvc_bam_counts_quals and the accumulator's third kind on the device (bam_counts_quals_kernel.hip, bvc_bam_counts.hip; GPU), word for word
+"""bvc_bam_counts_quals and the accumulator's third kind on the device (bam_counts_kernel.hip, bvc_bam_counts.hip; GPU), word for word
 against the plain model (tests/bam_counts_quals_model.py: the wide call's counts cut to the first n_quals quality columns of each base, the
 ninth header's depth rows, sample status 5).
 

@@ -1,4 +1,4 @@
-"""bvc_bam_counts_depth, bvc_site_acc_create_depth and bvc_site_acc_get_depth on the device (bam_group_depth_kernel.hip, bvc_bam_counts.hip; GPU)
+"""bvc_bam_counts_depth, bvc_site_acc_create_depth and bvc_site_acc_get_depth on the device (bam_counts_kernel.hip, bvc_bam_counts.hip; GPU)
 against the plain model (tests/bam_group_depth_model.py: what tests/bam_counts_model.py says the grouped call adds, folded into one slot of
 counts and the groups' depths per base).
 

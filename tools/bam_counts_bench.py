@@ -69,27 +69,28 @@ def trace_report(a):
     lines = Lines()
     lines.append(f"# the add passes' kernel times of one profiled run (rocprofv3 --kernel-trace), {calls} dispatches a form: min / median / max, microseconds")
     narrow = [f"bvc_bam_counts_quals, n_quals {q}, n_groups {g}" for q in a.quals for g in (0, 5)]
-    for kernel, forms in (("bam_counts_kernel<true>", ["bvc_bam_counts, n_groups 0", "bvc_bam_counts, n_groups 5"]),
-                          ("bam_counts_depth_kernel", [f"bvc_bam_counts_depth, n_groups {g}" for g in a.depth]),
-                          ("bam_counts_quals_kernel<true>", narrow),
+    # the instantiations of bam_counts_kernel<ADD, CountsKind> (0 Slots, 1 Depth, 2 Narrow) as the trace names them
+    for kernel, forms in (("bam_counts_kernel<true, (bvc::CountsKind)0>", ["bvc_bam_counts, n_groups 0", "bvc_bam_counts, n_groups 5"]),
+                          ("bam_counts_kernel<true, (bvc::CountsKind)1>", [f"bvc_bam_counts_depth, n_groups {g}" for g in a.depth]),
+                          ("bam_counts_kernel<true, (bvc::CountsKind)2>", narrow),
                           # the dry passes, every form's pooled: the wide one serves bvc_bam_counts and bvc_bam_counts_depth
-                          ("bam_counts_kernel<false>", ["the dry pass of the wide forms"] * (2 + len(a.depth))),
-                          ("bam_counts_quals_kernel<false>", ["the dry pass of the narrow forms"] * len(narrow))):
+                          ("bam_counts_kernel<false, (bvc::CountsKind)0>", ["the dry pass of the wide forms"] * (2 + len(a.depth))),
+                          ("bam_counts_kernel<false, (bvc::CountsKind)2>", ["the dry pass of the narrow forms"] * len(narrow))):
         mine = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"])) for r in rows if kernel in r["Kernel_Name"])
         if len(mine) != calls * len(forms):
             raise SystemExit(f"{kernel}: {len(mine)} dispatches in the trace, {calls * len(forms)} expected")
         if len(set(forms)) == 1 and len(forms) > 1:                # (pooled: one line for all of them)
             us = [(e - b) / 1e3 for b, e in mine]
-            lines.append(f"  {kernel:30s} {forms[0]:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}  ({len(us)} dispatches)")
+            lines.append(f"  {kernel:46s} {forms[0]:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}  ({len(us)} dispatches)")
             continue
         for i, form in enumerate(forms):
             us = [(e - b) / 1e3 for b, e in mine[i * calls:(i + 1) * calls]]
-            lines.append(f"  {kernel:30s} {form:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}")
+            lines.append(f"  {kernel:46s} {form:44s} {min(us):8.1f} {statistics.median(us):8.1f} {max(us):8.1f}")
     mine = [(int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3 for r in rows if "acc_expand_kernel" in r["Kernel_Name"]]
     if mine:
         q = a.quals[0]
         gbs = 8192 * (16 * q + 2048) / (statistics.median(mine) * 1e-6) / 1e9
-        lines.append(f"  {'acc_expand_kernel':30s} {f'8,192 rows of {q} columns, {len(mine)} dispatches':44s} {min(mine):8.1f} {statistics.median(mine):8.1f} {max(mine):8.1f}"
+        lines.append(f"  {'acc_expand_kernel':46s} {f'8,192 rows of {q} columns, {len(mine)} dispatches':44s} {min(mine):8.1f} {statistics.median(mine):8.1f} {max(mine):8.1f}"
                      f"  ({8192 * (16 * q + 2048)} bytes read and written: {gbs:.0f} GB/s at the median)")
     if a.out:
         with open(a.out, "w") as f:

@@ -19,7 +19,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "basevarc_amd", "csrc")
-DEVICE_SOURCES = ["hist_kernel.hip", "counts_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip", "site_stats_kernel.hip", "vcf_samples_kernel.hip", "bgzf_deflate_kernel.hip", "bgzf_dynamic_kernel.hip", "bgzf_fields_kernel.hip", "bam_pileup_kernel.hip", "bam_popmatrix_kernel.hip", "bam_text_kernel.hip", "store_kernel.hip", "bam_counts_kernel.hip", "bam_group_depth_kernel.hip", "bam_counts_quals_kernel.hip", "acc_pack_kernel.hip"]
+DEVICE_SOURCES = ["hist_kernel.hip", "counts_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip", "site_stats_kernel.hip", "vcf_samples_kernel.hip", "bgzf_deflate_kernel.hip", "bgzf_dynamic_kernel.hip", "bgzf_fields_kernel.hip", "bam_pileup_kernel.hip", "bam_popmatrix_kernel.hip", "bam_text_kernel.hip", "store_kernel.hip", "bam_counts_kernel.hip", "acc_pack_kernel.hip"]
 
 
 def assembly(source, extra_flags=()):
