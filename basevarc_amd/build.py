@@ -7,7 +7,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libbvc.so")
 SOURCES = ["bvc_context.hip", "bvc_lrt.hip", "bvc_pileup.hip", "bvc_counts.hip", "bvc_stats.hip", "bvc_vcf.hip", "bvc_bgzf.hip", "bvc_bam.hip", "bvc_store.hip", "bvc_bam_deflate.hip", "bvc_bam_counts.hip", "hist_kernel.hip", "counts_kernel.hip", "em_kernel.hip", "em_items.hip", "synth_kernel.hip", "pileup_kernel.hip", "inflate_kernel.hip", "site_stats_kernel.hip", "vcf_samples_kernel.hip", "bgzf_deflate_kernel.hip", "bgzf_dynamic_kernel.hip", "bgzf_fields_kernel.hip", "bam_pileup_kernel.hip", "bam_popmatrix_kernel.hip", "bam_text_kernel.hip", "store_kernel.hip", "bam_counts_kernel.hip", "acc_pack_kernel.hip"]
-DEPS = ["bvc_ctx.h", "bvc_device.h", "bvc_internal.h", "counts_layout.h", "bam_resolve_device.h", "crc32_device.h", "bgzf_deflate_device.h", "bgzf_codes_device.h", "bgzf_dynamic_device.h", "bgzf_fields_device.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h"), os.path.join("..", "..", "include", "bvc_bgzf_codes.h"), os.path.join("..", "..", "include", "bvc_bam.h"), os.path.join("..", "..", "include", "bvc_popmatrix.h"), os.path.join("..", "..", "include", "bvc_bam_text.h"), os.path.join("..", "..", "include", "bvc_store.h"), os.path.join("..", "..", "include", "bvc_bam_deflate.h"), os.path.join("..", "..", "include", "bvc_bam_counts.h"), os.path.join("..", "..", "include", "bvc_bam_group_depth.h"), os.path.join("..", "..", "include", "bvc_site_acc_quals.h"), os.path.join("..", "..", "include", "bvc_site_acc_pack.h")]
+DEPS = ["bvc_ctx.h", "bvc_device.h", "bvc_internal.h", "counts_layout.h", "bam_resolve_device.h", "crc32_device.h", "bgzf_deflate_device.h", "bgzf_codes_device.h", "bgzf_dynamic_device.h", "bgzf_fields_device.h", "bgzf_block_kernel.h", "em_common.h", "synth_tables.inc", os.path.join("..", "..", "include", "bvc.h"), os.path.join("..", "..", "include", "bvc_bgzf_codes.h"), os.path.join("..", "..", "include", "bvc_bam.h"), os.path.join("..", "..", "include", "bvc_popmatrix.h"), os.path.join("..", "..", "include", "bvc_bam_text.h"), os.path.join("..", "..", "include", "bvc_store.h"), os.path.join("..", "..", "include", "bvc_bam_deflate.h"), os.path.join("..", "..", "include", "bvc_bam_counts.h"), os.path.join("..", "..", "include", "bvc_bam_group_depth.h"), os.path.join("..", "..", "include", "bvc_site_acc_quals.h"), os.path.join("..", "..", "include", "bvc_site_acc_pack.h")]
 
 
 def code_sha16(path=None):
@@ -55,9 +55,10 @@ COMMON_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", 
 PER_SOURCE_FLAGS = {"em_items.hip": ["-mllvm", "-disable-machine-licm"],
                     # the one-wavefront-per-site kernels: 46-64 SGPR spills (to VGPR lanes) with the pass, 15-38 without, fewer VGPRs
                     "em_kernel.hip": ["-mllvm", "-disable-machine-licm"],
-                    # the block kernel with the code builder inlined into it: 128 VGPRs and 3 of them spilled with the pass, 77 and none without
+                    # the deflate block kernel with the code builder inlined into it (bgzf_block_kernel<false, true>): 128 VGPRs and 3 of them
+                    # spilled with the pass, 77 and none without
                     "bgzf_dynamic_kernel.hip": ["-mllvm", "-disable-machine-licm"],
-                    # the field parse's kernels: the same builder inlined into the dynamic one of the two
+                    # the field parse's two instantiations: the same builder inlined into the dynamic one of the two
                     "bgzf_fields_kernel.hip": ["-mllvm", "-disable-machine-licm"]}
 
 

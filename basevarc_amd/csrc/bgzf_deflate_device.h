@@ -1,5 +1,4 @@
-// bgzf_deflate_device.h -- what the block kernels of the device deflate encoder share (bgzf_deflate_kernel.hip: fixed code or stored;
-// bgzf_dynamic_kernel.hip: a code of the block's own as well; bgzf_fields_kernel.hip: both behind another pass A): the layout of a
+// bgzf_deflate_device.h -- what every instantiation of the device deflate encoder's block kernel runs (bgzf_block_kernel.h): the layout of a
 // workgroup's LDS, the input's way into it, passes A (matches) and B (path), the fixed code, the workgroup scan of pass C and the
 // block's way out to its staging slot.  The passes are described at the top of bgzf_deflate_kernel.hip.  Every function is inlined into its kernel; all of a workgroup's 1024 threads call each of them.
 #pragma once
@@ -28,8 +27,6 @@ static_assert(kBdTabWords * 4 >= (int)kBdIn && kBdBitWords * 32 >= (int)kBdIn &&
 static_assert((kBdInWords + kBdTabWords + 2 * kBdBitWords + 32) * 4 <= 160 * 1024, "one workgroup's LDS");
 static_assert(kBdIn % 64 == 0 && kBdIn / 64 <= kBdThreads, "64 positions a thread in pass C");
 static_assert(kBdWays == 16 && kBdRound == 256, "the packing of the table's and the round's cells");
-
-struct BlockDesc { int64_t src; uint32_t len; uint32_t pad; };
 
 // the four bytes at byte address a of an LDS word array (any alignment)
 __device__ __forceinline__ uint32_t ld32(const uint32_t *w, uint32_t a)

@@ -5,14 +5,14 @@
 // block, the block's input and its match tables in LDS (144 KiB: one workgroup a CU).  Five launches:
 //   bgzf_plan_kernel     block b of the call -> (source, length): piece i holds blocks first_block[i] .. first_block[i + 1], of which
 //                        those behind the piece's real length are empty (the host may know an upper bound of a length only)
-//   bgzf_deflate_kernel  the block, written to its own 64 KiB slot of a staging buffer, and its size (tuning key "bgzf_codes" = 1:
-//                        bgzf_deflate_dynamic_kernel of bgzf_dynamic_kernel.hip in its place; "bgzf_parse" = 1: the kernels of
-//                        bgzf_fields_kernel.hip, with another pass A; the passes they share are in bgzf_deflate_device.h)
+//   bgzf_block_kernel    the block, written to its own 64 KiB slot of a staging buffer, and its size (bgzf_block_kernel.h: one template
+//                        for both parses and both codes.  <false, false>, the default, is instantiated here; tuning keys "bgzf_codes" = 1
+//                        and "bgzf_parse" = 1 choose among the other three, which bgzf_dynamic_kernel.hip and bgzf_fields_kernel.hip hold)
 //   bgzf_crc_kernel      CRC32 of the block's input into its trailer: one wavefront a block, crc32_device.h
 //   bgzf_scan_kernel     exclusive prefix sums of the sizes: where each block goes, comp_off of every piece
 //   bgzf_pack_kernel     the blocks laid down one after the other, no gaps
 //
-// The deflate kernel, per block:
+// The block kernel, per block (pass A as the general parse has it; the field parse's is described in bgzf_fields_device.h):
 //   A  MATCHES.  The positions are taken in rounds of 256, in order, four lanes a position.  Candidates for position p come from
 //      - a table of 16 ways x 2048 hash values (hash of the four bytes at p): way (r mod 16) holds the LARGEST position of round r' = r
 //        (mod 16), r' < current, with that hash -- written with atomicMax after the round's look-ups, so a cell never depends on the
@@ -33,10 +33,12 @@
 //      word are shared with its neighbours; OR does not depend on order).  If the image would be larger than the stored form the block
 //      is stored instead.  The workgroup copies header, image and ISIZE to the staging slot.
 // Every LDS index that comes from data (hash values, candidate positions, bit offsets) is bounded before use.
-#include "bgzf_deflate_device.h"
+#include "bgzf_block_kernel.h"
 #include "crc32_device.h"
 
 namespace bvc {
+
+template __global__ void bgzf_block_kernel<false, false>(const uint8_t *, const BlockDesc *, int64_t, uint8_t *, uint32_t *, uint32_t *, uint32_t);
 
 // desc[b] of every block of the call: piece i = the one with first_block[i] <= b < first_block[i + 1].
 __global__ __launch_bounds__(256) void bgzf_plan_kernel(
@@ -55,38 +57,6 @@ __global__ __launch_bounds__(256) void bgzf_plan_kernel(
         d.len = left <= 0 ? 0u : (left < (int64_t)kBdIn ? (uint32_t)left : kBdIn);
         d.pad = 0u;
         desc[b] = d;
-    }
-}
-
-__global__ __launch_bounds__(kBdThreads) void bgzf_deflate_kernel(
-    const uint8_t *__restrict__ data, const BlockDesc *__restrict__ desc, int64_t n_blocks, uint8_t *__restrict__ staging,
-    uint32_t *__restrict__ bsize, uint32_t *__restrict__ match_rows)
-{
-    BVC_POISON_LDS();
-    __shared__ __attribute__((aligned(16))) uint32_t s_in[kBdInWords];
-    __shared__ __attribute__((aligned(16))) uint32_t s_tab[kBdTabWords];
-    __shared__ uint32_t s_first[kBdBitWords];
-    __shared__ uint32_t s_path[kBdBitWords];
-    __shared__ uint32_t s_scan[32];
-    const uint32_t tid = threadIdx.x;
-    uint32_t *const match = match_rows + (size_t)blockIdx.x * kBdIn;
-    // (pass C: the image of the output lies in s_in; passes B and C: the bytes of s_tab are the literal, or length - 3)
-    uint32_t *const s_ism = s_first;                                          // passes B and C: bit p = position p holds a match
-
-    for (int64_t blk = blockIdx.x; blk < n_blocks; blk += gridDim.x) {       // (workgroup-uniform)
-        const uint32_t n = desc[blk].len < kBdIn ? desc[blk].len : kBdIn;
-        uint8_t *const slot = staging + (size_t)blk * kBdSlot;
-        if (n == 0u) {
-            if (tid == 0u) bsize[blk] = 0u;
-            continue;
-        }
-        bd_load(s_in, s_tab, s_first, data + desc[blk].src, n, tid);
-        bd_matches(s_in, s_tab, s_first, match, n, tid);
-        bd_path(s_in, s_tab, s_ism, s_path, match, n, tid);
-
-        const uint32_t bs = bd_fixed_block(slot, s_in, s_tab, s_ism, s_path, s_scan, match, n, tid);     // ---- C: bits
-        if (tid == 0u) bsize[blk] = bs;
-        __syncthreads();                                                      // the LDS belongs to the next block from here
     }
 }
 
@@ -178,7 +148,7 @@ BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_b
     BgzfDeflateScratch s;
     s.first_block = L.take<int64_t>((size_t)n_pieces + 1);
     s.block_off = L.take<int64_t>(nb + 1);
-    s.desc = L.take<char>(nb * sizeof(BlockDesc));
+    s.desc = L.take<BlockDesc>(nb);
     s.bsize = L.take<uint32_t>(nb);
     s.match_rows = L.take<uint32_t>(grid * kBdIn);
     s.staging = L.take<uint8_t>(nb * kBdSlot);
@@ -186,20 +156,25 @@ BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_b
     return s;
 }
 
-hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
-                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int cuts, int codes, int parse)
+// The tuning keys as the launches read them: the one place where they become a mode.
+BgzfMode bgzf_mode(const LaunchState &ls)
 {
-    BlockDesc *const desc = reinterpret_cast<BlockDesc *>(s.desc);
+    return {ls.bgzf_parse == 1, ls.bgzf_codes == 1, ls.bgzf_cuts == 1 ? kBfDelimsSpaceNewline : kBfDelimsTabColon};
+}
+
+hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, const BgzfMode &mode)
+{
     if (n_blocks > 0) {
         const unsigned grid = (unsigned)(n_blocks < kBgzfDeflateGrid ? n_blocks : kBgzfDeflateGrid);
         hipLaunchKernelGGL(bgzf_plan_kernel, dim3((unsigned)((n_blocks + 255) / 256 < 1024 ? (n_blocks + 255) / 256 : 1024)), dim3(256), 0, stream,
-                           n_pieces, piece_off, piece_len, s.first_block, n_blocks, desc);
-        if (parse == 1) launch_bgzf_deflate_field_blocks(stream, grid, codes, cuts, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
-        else if (codes == 1) launch_bgzf_deflate_dynamic_blocks(stream, grid, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
-        else hipLaunchKernelGGL(bgzf_deflate_kernel, dim3(grid), dim3(kBdThreads), 0, stream, data, desc, n_blocks, s.staging, s.bsize, s.match_rows);
+                           n_pieces, piece_off, piece_len, s.first_block, n_blocks, s.desc);
+        if (mode.fields || mode.dynamic) launch_bgzf_blocks_other(stream, grid, mode, data, s.desc, n_blocks, s.staging, s.bsize, s.match_rows);
+        else hipLaunchKernelGGL((bgzf_block_kernel<false, false>), dim3(grid), dim3(kBdThreads), 0, stream, data, s.desc, n_blocks, s.staging, s.bsize,
+                                s.match_rows, mode.delims);
         const uintptr_t a = reinterpret_cast<uintptr_t>(data);
         hipLaunchKernelGGL(bgzf_crc_kernel, dim3((unsigned)(n_blocks < 65536 ? n_blocks : 65536)), dim3(kWave), 0, stream,
-                           reinterpret_cast<const uint8_t *>(a & ~(uintptr_t)15), (uint32_t)(a & 15u), desc, n_blocks, s.bsize, s.staging);
+                           reinterpret_cast<const uint8_t *>(a & ~(uintptr_t)15), (uint32_t)(a & 15u), s.desc, n_blocks, s.bsize, s.staging);
     }
     // (with no block at all it still writes comp_off: all zero)
     hipLaunchKernelGGL(bgzf_scan_kernel, dim3(1), dim3(1024), 0, stream, n_blocks, s.bsize, s.block_off, n_pieces, s.first_block, comp_off);

@@ -1,5 +1,5 @@
-// bgzf_dynamic_device.h -- what the block kernels with a Huffman code of the block's own share (bgzf_dynamic_kernel.hip behind the general
-// parse, bgzf_fields_kernel.hip behind the field parse): everything behind pass B -- counts, lengths, the choice among stored, fixed and
+// bgzf_dynamic_device.h -- what the block kernel runs with a Huffman code of the block's own (bgzf_block_kernel.h, DYNAMIC, behind either
+// parse): everything behind pass B -- counts, lengths, the choice among stored, fixed and
 // dynamic, the bits, the slot.  The steps are described at the top of bgzf_dynamic_kernel.hip.  Inlined into its kernel; all of a
 // workgroup's 1024 threads call it.
 #pragma once

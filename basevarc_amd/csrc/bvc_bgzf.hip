@@ -1,5 +1,6 @@
-// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip; with tuning key
-// "bgzf_codes" = 1 the block kernel of bgzf_dynamic_kernel.hip, with "bgzf_parse" = 1 those of bgzf_fields_kernel.hip), and bvc_bgzf_code_lengths: that kernel's code-length builder on its own.
+// bvc_bgzf.hip -- bvc_bgzf_deflate: byte ranges deflated into finished BGZF blocks on the device (bgzf_deflate_kernel.hip; tuning keys
+// "bgzf_codes", "bgzf_parse" and "bgzf_cuts" choose the block kernel's instantiation, bgzf_block_kernel.h), and bvc_bgzf_code_lengths: the
+// dynamic code's code-length builder on its own.
 // bvc_pileup_sample_bgzf (bvc_pileup.hip) hands a tile's sample columns to the same kernels where they are made.
 #include "bvc_ctx.h"
 #include "../../include/bvc_bgzf_codes.h"
@@ -18,8 +19,7 @@ int bgzf_deflate_device(bvc_ctx *ctx, PinIO &io, int64_t n_pieces, const uint8_t
     // a call that returns with its launches in flight must not leave a transfer out of the page-locked buffer in flight too: the next
     // call on the context fills that buffer at once.  (The stream holds nothing but this copy here: its caller has just waited.)
     if (wait_for_upload) BVC_HIP_D(ctx, wait_stream(ctx));
-    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, ctx->ls.bgzf_cuts,
-                                       ctx->ls.bgzf_codes, ctx->ls.bgzf_parse));
+    BVC_HIP_D(ctx, launch_bgzf_deflate(ctx->stream, n_pieces, d_data, d_off, d_len, n_blocks, scr, d_comp, comp_cap, d_comp_off, bgzf_mode(ctx->ls)));
     return BVC_OK;
 }
 
@@ -63,28 +63,32 @@ int bvc_bgzf_deflate(bvc_ctx *ctx, int64_t n_pieces, const uint8_t *data, const 
     BVC_HIP(ctx, hipSetDevice(ctx->device));
     const size_t np = (size_t)n_pieces;
     PinIO io(ctx);
-    int64_t total = 0, need = 0;
-    if (flags & BVC_PTR_DEVICE) {
-        if (n_pieces == 0) { BVC_HIP(ctx, hipMemsetAsync(comp_off, 0, 8, ctx->stream)); return BVC_OK; }
+    const bool device = (flags & BVC_PTR_DEVICE) != 0;
+    if (n_pieces == 0) {                                          // (no piece: nothing below could refuse the call)
+        if (device) BVC_HIP(ctx, hipMemsetAsync(comp_off, 0, 8, ctx->stream)); else comp_off[0] = 0;
+        return BVC_OK;
+    }
+    int rc;
+    std::vector<int64_t> down;                                    // the device form: the pieces' offsets, then their lengths, on the host
+    const int64_t *h_off = piece_off, *h_len = piece_len;
+    if (device) {
         // the wait of the device form: the launches and the scratch are sized from the pieces' lengths
-        int rc = io.reserve((np + 1) * 8 + 64, 2 * np * 8 + 128);
+        rc = io.reserve((np + 1) * 8 + 64, 2 * np * 8 + 128);
         if (rc != BVC_OK) return rc;
-        std::vector<int64_t> off(np), len(np);
-        BVC_HIP_D(ctx, io.d2h(off.data(), piece_off, np * 8));
-        BVC_HIP_D(ctx, io.d2h(len.data(), piece_len, np * 8));
+        down.resize(2 * np);
+        h_off = down.data(); h_len = down.data() + np;
+        BVC_HIP_D(ctx, io.d2h(down.data(), piece_off, np * 8));
+        BVC_HIP_D(ctx, io.d2h(down.data() + np, piece_len, np * 8));
         BVC_HIP_D(ctx, wait_stream(ctx));
         io.deliver();
-        if (!sum_pieces(n_pieces, off.data(), len.data(), &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
-        if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
-        if (need > comp_cap) return fail_cap(ctx, "comp_cap", comp_cap, "the bounds of the pieces", need);
-        return bgzf_deflate_device(ctx, io, n_pieces, data, piece_off, piece_len, len.data(), comp, comp_cap, comp_off, true);
     }
-    if (!sum_pieces(n_pieces, piece_off, piece_len, &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
+    int64_t total = 0, need = 0;
+    if (!sum_pieces(n_pieces, h_off, h_len, &total, &need)) return fail(ctx, BVC_ERR_ARG, "a negative piece_off or piece_len");
     if ((total > 0 && !data) || (need > 0 && !comp)) return fail(ctx, BVC_ERR_ARG, "null data pointer");
     if (need > comp_cap) return fail_cap(ctx, "comp_cap", comp_cap, "the bounds of the pieces", need);
-    if (n_pieces == 0) { comp_off[0] = 0; return BVC_OK; }
+    if (device) return bgzf_deflate_device(ctx, io, n_pieces, data, piece_off, piece_len, h_len, comp, comp_cap, comp_off, true);
     uint8_t *d_data, *d_comp; int64_t *d_off, *d_len, *d_coff;
-    int rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
+    rc = carve(ctx, ctx->d_bgzf_io, 256, [&](Layout &L) {
         d_data = L.take<uint8_t>((size_t)total, 16);
         d_off = L.take<int64_t>(np);
         d_len = L.take<int64_t>(np);

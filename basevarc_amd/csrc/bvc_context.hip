@@ -374,21 +374,14 @@ int bvc_debug_report(bvc_ctx *ctx, uint32_t *out24, int reset)
     BVC_HIP(ctx, debug_read_hist(out24, reset != 0));
     BVC_HIP(ctx, debug_read_wave_engine(out24 + 8, reset != 0));
     BVC_HIP(ctx, debug_read_items(out24 + 16, reset != 0));
-    uint32_t pl[8];                                              // pileup_kernel.hip: folded into the histogram unit's count
-    BVC_HIP(ctx, debug_read_pileup(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_inflate(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_site_stats(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_vcf_samples(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_bgzf_deflate(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_bgzf_dynamic(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
-    BVC_HIP(ctx, debug_read_bgzf_fields(pl, reset != 0));
-    if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
+    // the other translation units: folded into the histogram unit's count, the first violation kept
+    hipError_t (*const folded[])(uint32_t *, bool) = {debug_read_pileup, debug_read_inflate, debug_read_site_stats, debug_read_vcf_samples,
+                                                      debug_read_bgzf_deflate, debug_read_bgzf_dynamic, debug_read_bgzf_fields};
+    for (auto *read : folded) {
+        uint32_t pl[8];
+        BVC_HIP(ctx, read(pl, reset != 0));
+        if (pl[0]) { if (out24[0] == 0) for (int i = 1; i < 8; ++i) out24[i] = pl[i]; out24[0] += pl[0]; }
+    }
     return BVC_OK;
 }
 #endif

@@ -42,10 +42,10 @@ struct LaunchState {
                                    // log-likelihood shows that it cannot be the level's first minimum (em_items.hip, site_decide); 0 = it always runs
     int stats_log2c = 2;           // site_stats_kernel: 2^n LDS copies of its 1536 counters (0..4; 2 = 30 KiB with the folded counters: four
                                    // 512-thread workgroups a CU, as many as its 32 wavefronts hold; measured, profiles/site_stats/README.txt)
-    int bgzf_codes = 0;            // device deflate: 0 = fixed code or stored (bgzf_deflate_kernel), 1 = the smallest of stored, fixed and a code of
-                                   // the block's own (bgzf_deflate_dynamic_kernel).  Not a launch policy: it changes the bytes
+    int bgzf_codes = 0;            // device deflate: 0 = fixed code or stored (bd_fixed_block), 1 = the smallest of stored, fixed and a code of
+                                   // the block's own (bd_dynamic_block).  Not a launch policy: it changes the bytes
     int bgzf_parse = 0;            // device deflate: 0 = the general parse (a search at every position, bd_matches), 1 = the field parse for
-                                   // tab-separated text (bd_field_matches, bgzf_fields_kernel.hip).  Independent of bgzf_codes; it changes the bytes
+                                   // tab-separated text (bd_field_matches, bgzf_fields_device.h).  Independent of bgzf_codes; it changes the bytes
     int bgzf_cuts = 0;             // the field parse (bgzf_parse = 1; nothing otherwise): what ends a field -- 0 = a tab or a colon, 1 = a space or a
                                    // newline (the text temp batches' lines).  It changes the bytes
     int dbg_levels = 0;            // BVC_DBG_LEVELS (timing only, records wrong): cut region_kernel short after a phase; 0 = run all
@@ -255,21 +255,20 @@ hipError_t launch_vcf_samples(hipStream_t stream, int64_t n_sites, const int64_t
 // blocks first_block[i] .. first_block[i + 1] of the call (first_block [n_pieces + 1] in the scratch, filled by the caller: from the
 // pieces' lengths or from upper bounds of them -- a block behind a piece's real length is empty and takes no byte); comp_off
 // [n_pieces + 1] and the packed blocks are written on the stream.  Nothing is packed when the blocks do not fit comp_cap.
-constexpr int kBgzfDeflateGrid = 256;    // workgroups of bgzf_deflate_kernel: a call of more blocks sends each round its loop again
-struct BgzfDeflateScratch { int64_t *first_block, *block_off; char *desc; uint32_t *bsize, *match_rows; uint8_t *staging; };
+constexpr int kBgzfDeflateGrid = 256;    // workgroups of bgzf_block_kernel: a call of more blocks sends each round its loop again
+struct BlockDesc { int64_t src; uint32_t len; uint32_t pad; };               // a block of the call: where its input starts in `data`, its bytes
+struct BgzfDeflateScratch { int64_t *first_block, *block_off; BlockDesc *desc; uint32_t *bsize, *match_rows; uint8_t *staging; };
+// Which instantiation of bgzf_block_kernel (bgzf_block_kernel.h) a call launches -- fields: the field parse, dynamic: a code of the block's own
+// as well -- and the two bytes that end a field, as the field parse takes them.  bgzf_mode makes it from the
+// tuning keys "bgzf_parse", "bgzf_codes" and "bgzf_cuts".
+struct BgzfMode { bool fields, dynamic; uint32_t delims; };
+BgzfMode bgzf_mode(const LaunchState &ls);
 size_t bgzf_deflate_scratch_bytes(int64_t n_pieces, int64_t n_blocks);
 BgzfDeflateScratch bgzf_deflate_scratch(void *buf, int64_t n_pieces, int64_t n_blocks, Layout *sized = nullptr);
 hipError_t launch_bgzf_deflate(hipStream_t stream, int64_t n_pieces, const uint8_t *data, const int64_t *piece_off, const int64_t *piece_len,
-                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, int cuts, int codes, int parse);
-// bgzf_dynamic_kernel.hip: the block kernel of codes = 1 (launch_bgzf_deflate launches it in bgzf_deflate_kernel's place; desc: its block
-// table), and the code-length builder on counts of the caller's: lengths[set][s] from counts[set][s], device pointers
-void launch_bgzf_deflate_dynamic_blocks(hipStream_t stream, unsigned grid, const uint8_t *data, const char *desc, int64_t n_blocks, uint8_t *staging,
-                                        uint32_t *bsize, uint32_t *match_rows);
+                               int64_t n_blocks, const BgzfDeflateScratch &s, uint8_t *comp, int64_t comp_cap, int64_t *comp_off, const BgzfMode &mode);
+// bgzf_dynamic_kernel.hip: the code-length builder on counts of the caller's: lengths[set][s] from counts[set][s], device pointers
 hipError_t launch_bgzf_code_lengths(hipStream_t stream, int64_t n_sets, const uint32_t *counts, int32_t n_symbols, int32_t limit, uint8_t *lengths);
-// bgzf_fields_kernel.hip: the block kernels of parse = 1, with the fixed code (codes = 0) or a code of the block's own (codes = 1);
-// cuts: what ends a field (0: a tab or a colon, 1: a space or a newline)
-void launch_bgzf_deflate_field_blocks(hipStream_t stream, unsigned grid, int codes, int cuts, const uint8_t *data, const char *desc, int64_t n_blocks,
-                                      uint8_t *staging, uint32_t *bsize, uint32_t *match_rows);
 
 // inflate_kernel.hip: raw deflate of whole BGZF blocks, one wavefront per block; status[i] != 0: block i is not valid deflate of isize bytes
 hipError_t launch_inflate(hipStream_t stream, const uint8_t *comp, const bvc_bgzf_block *blocks, int64_t n_blocks, uint8_t *out, uint32_t *status);

@@ -209,7 +209,7 @@ STORE_CHUNK = 16384         # BVC_STORE_CHUNK (include/bvc_store.h): bytes of a 
 STORE_GRID = 1024           # workgroups of store_gather_kernel at most (csrc/bvc_internal.h, kStoreGrid): more items go round its loop
 BAM_MORE = 2                # BVC_BAM_MORE (include/bvc.h): bvc_bam_pileup wants more bytes of a sample, or more room for the records
 BGZF_BLOCK_INPUT = 65280    # input bytes of every block of a piece but its last (include/bvc.h, BVC_BGZF_BLOCK_INPUT)
-BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
+BGZF_DEFLATE_GRID = 256     # workgroups of bgzf_block_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid): more blocks go round its loop
 OPTIONAL = ("bvc_debug_report",)                                # bound where the library has them
 EXPORTS = [name for name in PROTOTYPES if name not in OPTIONAL]   # what every build of the library exports
 

@@ -1,14 +1,18 @@
 """The hand-built catalogue of byte ranges the device deflate encoder is walked over (tests/test_gpu_bgzf_deflate.py): the smallest inputs
 at which an encoder can go wrong, and the three sample-column texts its output size is judged on.  Nothing here needs a device."""
+import functools
 import os
+import re
+import sys
 import zlib
 
 import numpy as np
 
 from tests import vcf_samples_cases as vc
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 B = 65280                                                          # input bytes of a block (include/bvc.h)
-GRID = 256                                                         # workgroups of bgzf_deflate_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid)
+GRID = 256                                                         # workgroups of bgzf_block_kernel (csrc/bvc_internal.h, kBgzfDeflateGrid)
 LEN_BASE = (3, 4, 5, 6, 7, 8, 9, 10, 11, 13, 15, 17, 19, 23, 27, 31, 35, 43, 51, 59, 67, 83, 99, 115, 131, 163, 195, 227, 258)
 DIST_BASE = (1, 2, 3, 4, 5, 7, 9, 13, 17, 25, 33, 49, 65, 97, 129, 193, 257, 385, 513, 769, 1025, 1537, 2049, 3073, 4097, 6145, 8193, 12289,
              16385, 24577)
@@ -88,3 +92,34 @@ def zlib_size(data, level):
         c = zlib.compressobj(level, zlib.DEFLATED, -15)
         total += len(c.compress(data[at:at + B]) + c.flush()) + 26
     return total
+
+
+# ---- the block kernel's sources as the CPU-side tests read them (tests/test_bgzf_*_abi.py, tests/test_bam_deflate_abi.py)
+BLOCK_KERNELS = {(fields, dynamic): "bgzf_block_kernel<%s, %s>" % (str(fields).lower(), str(dynamic).lower())
+                 for fields in (False, True) for dynamic in (False, True)}
+
+
+@functools.lru_cache(maxsize=None)
+def source_rows(source):
+    """{kernel: its row of tools/isa_report.py} of one source of csrc, compiled once with the flags the library is built with."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import isa_report
+    return {k["pretty"].split("::")[-1]: k for k in isa_report.kernels_of(isa_report.assembly(source))}
+
+
+def assert_the_mode_is_built_in_one_place():
+    """The three tuning keys of the encoder reach the launches as one BgzfMode, made from the context's LaunchState by one function: no
+    other line of csrc reads a key, and every call hands the launch that function's result.  (tests/test_bgzf_fields_abi.py and tests/test_bam_deflate_abi.py ask it.)"""
+    csrc = os.path.join(ROOT, "basevarc_amd", "csrc")
+    texts = {f: re.sub(r"//[^\n]*", "", open(os.path.join(csrc, f)).read()) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
+    made = re.search(r"BgzfMode bgzf_mode\(const LaunchState &ls\)\s*\{\s*return \{ls\.bgzf_parse == 1, ls\.bgzf_codes == 1, "
+                     r"ls\.bgzf_cuts == 1 \? kBfDelimsSpaceNewline : kBfDelimsTabColon\};\s*\}", texts["bgzf_deflate_kernel.hip"])
+    assert made, "bgzf_mode"
+    for key in ("bgzf_parse", "bgzf_codes", "bgzf_cuts"):
+        # its declaration in LaunchState, its row of the table of keys, and the one read
+        reads = {f: len(re.findall(r"(?:\.|->|::)" + key + r"\b", text)) for f, text in texts.items()}
+        assert {f: n for f, n in reads.items() if n} == {"bvc_context.hip": 1, "bgzf_deflate_kernel.hip": 1}, (key, reads)
+    assert "kBfDelims" not in "".join(text for f, text in texts.items() if f not in ("bgzf_deflate_kernel.hip", "bgzf_fields_device.h"))
+    assert re.search(r"launch_bgzf_deflate\([^;]*d_comp_off, bgzf_mode\(ctx->ls\)\)\);", texts["bvc_bgzf.hip"])
+    assert sum(text.count("bgzf_mode(") for text in texts.values()) == 3          # declared, defined, called
+    assert sum(len(re.findall(r"\blaunch_bgzf_deflate\(", text)) for text in texts.values()) == 3

@@ -95,9 +95,12 @@ def test_the_key_is_declared_beside_bgzf_parse():
     assert re.search(r'\{"bgzf_cuts", "BVC_BGZF_CUTS", 0, 1, 1, 0, &LaunchState::bgzf_cuts\}', context)
     # the rows the existing tests pin stay as they are, and the pair of bytes is carried into both kernels as an argument
     assert re.search(r'\{"bgzf_parse", "BVC_BGZF_PARSE", 0, 1, 1, 0, &LaunchState::bgzf_parse\}', context)
-    assert re.search(r"ctx->ls\.bgzf_cuts,\s*ctx->ls\.bgzf_codes,\s*ctx->ls\.bgzf_parse\)", read("basevarc_amd", "csrc", "bvc_bgzf.hip"))
-    kernels = read("basevarc_amd", "csrc", "bgzf_fields_kernel.hip")
-    assert kernels.count("uint32_t *__restrict__ match_rows, uint32_t delims)") == 2 and kernels.count("match, n, tid, delims);") == 2
+    dc.assert_the_mode_is_built_in_one_place()                               # all three keys, bgzf_cuts as the pair of bytes
+    # the one block kernel takes the pair as its last argument, whatever it is instantiated with, and hands it to the field parse
+    kernel = read("basevarc_amd", "csrc", "bgzf_block_kernel.h")
+    assert kernel.count("uint32_t *__restrict__ match_rows, uint32_t delims)") == 1 and kernel.count("match, n, tid, delims);") == 1
+    assert read("basevarc_amd", "csrc", "bgzf_dynamic_kernel.hip").count("bsize, match_rows, mode.delims);") == 1
+    assert read("basevarc_amd", "csrc", "bgzf_deflate_kernel.hip").count("s.match_rows, mode.delims);") == 1
     device = read("basevarc_amd", "csrc", "bgzf_fields_device.h")
     assert "kBfDelimsTabColon = 0x09u | (0x3Au << 8)" in device and "kBfDelimsSpaceNewline = 0x20u | (0x0Au << 8)" in device
     assert "bgzf_cuts" in read("docs", "BGZF_FIELDS.md")

@@ -73,18 +73,21 @@ def test_the_kernels_are_built_from_their_own_source_under_the_rules_of_every_ke
     import isa_report
     from basevarc_amd import build as b
     assert "bgzf_dynamic_kernel.hip" in b.SOURCES and "bgzf_dynamic_kernel.hip" in isa_report.DEVICE_SOURCES
-    assert {"bgzf_deflate_device.h", "bgzf_codes_device.h"} <= set(b.DEPS)
-    flags = tuple(b.PER_SOURCE_FLAGS.get("bgzf_dynamic_kernel.hip", []))
-    rows = {k["pretty"].split("::")[-1]: k for k in isa_report.kernels_of(isa_report.assembly("bgzf_dynamic_kernel.hip", extra_flags=flags))}
-    assert set(rows) == {"bgzf_deflate_dynamic_kernel", "bgzf_code_lengths_kernel"}, sorted(rows)
+    assert {"bgzf_deflate_device.h", "bgzf_codes_device.h", "bgzf_block_kernel.h"} <= set(b.DEPS)
+    # the general parse's dynamic instantiation, and the flag it is built with: on this source, not on the fixed one's
+    assert b.PER_SOURCE_FLAGS.get("bgzf_dynamic_kernel.hip") == ["-mllvm", "-disable-machine-licm"] and "bgzf_deflate_kernel.hip" not in b.PER_SOURCE_FLAGS
+    rows = dc.source_rows("bgzf_dynamic_kernel.hip")
+    assert set(rows) == {dc.BLOCK_KERNELS[False, True], "bgzf_code_lengths_kernel"}, sorted(rows)
     for name, k in rows.items():
         assert k["private"] == 0 and k["scratch"] == 0 and k["flat"] == 0 and k["vgpr_spill"] == 0 and k["mfma"] == 0, (name, k)
-    assert 128 * 1024 < rows["bgzf_deflate_dynamic_kernel"]["lds"] <= 160 * 1024
-    # the passes are shared with the fixed kernel's source, not copied
+        assert k["vgprs"] <= 128, (name, k["vgprs"])                      # sixteen wavefronts a CU: 128 registers a lane at the most
+    assert 128 * 1024 < rows[dc.BLOCK_KERNELS[False, True]]["lds"] <= 160 * 1024
+    # the passes are shared with the fixed kernel's source, not copied: both sources hold the one template, which holds the device headers
     fixed = open(os.path.join(ROOT, "basevarc_amd", "csrc", "bgzf_deflate_kernel.hip")).read()
     dynamic = open(os.path.join(ROOT, "basevarc_amd", "csrc", "bgzf_dynamic_kernel.hip")).read()
     for text in (fixed, dynamic):
-        assert '#include "bgzf_deflate_device.h"' in text and "atomicMax(" not in text and "hash_of(" not in text
+        assert '#include "bgzf_block_kernel.h"' in text and "atomicMax(" not in text and "hash_of(" not in text
+    assert '#include "bgzf_deflate_device.h"' in open(os.path.join(ROOT, "basevarc_amd", "csrc", "bgzf_block_kernel.h")).read()
 
 
 # ---- the model's reader and writer against zlib

@@ -36,7 +36,7 @@ def test_the_key_is_declared_and_the_host_program_reads_its_knob():
     assert '"bgzf_parse"' in header and "BVC_BGZF_PARSE" in header
     # the key takes 0 and 1 and refuses 2: lo 0, hi 1, step 1, default 0 (bvc_set_tuning itself needs a device: tests/test_gpu_bgzf_fields.py)
     assert re.search(r'\{"bgzf_parse", "BVC_BGZF_PARSE", 0, 1, 1, 0, &LaunchState::bgzf_parse\}', read("basevarc_amd", "csrc", "bvc_context.hip"))
-    assert re.search(r"ctx->ls\.bgzf_codes,\s*ctx->ls\.bgzf_parse\)", read("basevarc_amd", "csrc", "bvc_bgzf.hip"))
+    dc.assert_the_mode_is_built_in_one_place()
     knobs = read("basevarc_amd", "host", "knobs.h")
     assert re.search(r'device_deflate_fields = num\("BVC_HOST_DEVICE_DEFLATE_FIELDS", 0\) != 0 && device_deflate;', knobs)
     assert re.search(r'knobs\.device_deflate_fields && bvc_set_tuning\(tr\.ctx, "bgzf_parse", 1\)', read("basevarc_amd", "host", "main.cpp"))
@@ -50,8 +50,13 @@ def test_the_kernels_are_in_the_library():
     from basevarc_amd import lib as bl
     b.build(force=b.needs_build())
     blob = open(bl.library_path(), "rb").read()
+    # the four instantiations of the one block kernel, as their mangled names spell them, and none of the kernels they replaced
+    for fields in (b"Lb0E", b"Lb1E"):
+        for dynamic in (b"Lb0E", b"Lb1E"):
+            assert b"17bgzf_block_kernelI" + fields + dynamic + b"E" in blob, (fields, dynamic)
+    assert blob.count(b"_ZN3bvc17bgzf_block_kernelI") == blob.count(b"_ZN3bvc17bgzf_block_kernelILb") > 0      # (no other arguments)
     for kernel in (b"bgzf_deflate_fields_kernel", b"bgzf_deflate_fields_dynamic_kernel", b"bgzf_deflate_kernel", b"bgzf_deflate_dynamic_kernel"):
-        assert b"%d%s" % (len(kernel), kernel) in blob, kernel            # (as its mangled name spells it)
+        assert b"%d%s" % (len(kernel), kernel) not in blob, kernel
 
 
 def test_the_kernels_are_built_from_their_own_source_under_the_rules_of_every_kernel():
@@ -59,26 +64,31 @@ def test_the_kernels_are_built_from_their_own_source_under_the_rules_of_every_ke
     import isa_report
     from basevarc_amd import build as b
     assert "bgzf_fields_kernel.hip" in b.SOURCES and "bgzf_fields_kernel.hip" in isa_report.DEVICE_SOURCES
-    assert {"bgzf_deflate_device.h", "bgzf_codes_device.h", "bgzf_dynamic_device.h", "bgzf_fields_device.h"} <= set(b.DEPS)
-    flags = tuple(b.PER_SOURCE_FLAGS.get("bgzf_fields_kernel.hip", []))
-    rows = {k["pretty"].split("::")[-1]: k for k in isa_report.kernels_of(isa_report.assembly("bgzf_fields_kernel.hip", extra_flags=flags))}
-    assert set(rows) == {"bgzf_deflate_fields_kernel", "bgzf_deflate_fields_dynamic_kernel"}, sorted(rows)
-    for name, k in rows.items():
-        assert k["private"] == 0 and k["scratch"] == 0 and k["flat"] == 0 and k["vgpr_spill"] == 0 and k["mfma"] == 0, (name, k)
-        assert k["vgprs"] <= 128, (name, k["vgprs"])                      # sixteen wavefronts a CU: 128 registers a lane at the most
+    assert b.PER_SOURCE_FLAGS.get("bgzf_fields_kernel.hip") == ["-mllvm", "-disable-machine-licm"]
+    assert {"bgzf_deflate_device.h", "bgzf_codes_device.h", "bgzf_dynamic_device.h", "bgzf_fields_device.h", "bgzf_block_kernel.h"} <= set(b.DEPS)
+    rows = dc.source_rows("bgzf_fields_kernel.hip")
+    assert set(rows) == {dc.BLOCK_KERNELS[True, False], dc.BLOCK_KERNELS[True, True]}, sorted(rows)
+    fixed, dynamic = rows[dc.BLOCK_KERNELS[True, False]], rows[dc.BLOCK_KERNELS[True, True]]
+    for k in (fixed, dynamic):
+        assert k["private"] == 0 and k["scratch"] == 0 and k["flat"] == 0 and k["vgpr_spill"] == 0 and k["mfma"] == 0, k
+        assert k["vgprs"] <= 128, k                                       # sixteen wavefronts a CU: 128 registers a lane at the most
     # the heads' bitmap and a round's best matches: 9 KiB beside what the general parse's kernels hold; one workgroup a CU either way
-    assert 147600 + 8192 + 1024 == rows["bgzf_deflate_fields_kernel"]["lds"] < rows["bgzf_deflate_fields_dynamic_kernel"]["lds"] <= 160 * 1024
-    # everything behind pass A is shared with the general parse's kernels, not copied
-    fields = read("basevarc_amd", "csrc", "bgzf_fields_kernel.hip")
+    assert 147600 + 8192 + 1024 == fixed["lds"] < dynamic["lds"] <= 160 * 1024
+    # nothing is copied: the block's way through the passes is written once, in the template, and no source calls a pass itself
+    template = read("basevarc_amd", "csrc", "bgzf_block_kernel.h")
     for header in ("bgzf_deflate_device.h", "bgzf_dynamic_device.h", "bgzf_fields_device.h"):
-        assert f'#include "{header}"' in fields
-    for call in ("bd_load(", "bd_field_matches(", "bd_path(", "bd_fixed_block(", "bd_dynamic_block(", "BVC_POISON_LDS()"):
-        assert call in fields, call
-    for other in ("bgzf_deflate_kernel.hip", "bgzf_dynamic_kernel.hip"):
-        text = read("basevarc_amd", "csrc", other)
-        assert "bd_matches(" in text and "bd_field_matches(" not in text
-    assert "bd_fixed_block(" in read("basevarc_amd", "csrc", "bgzf_deflate_kernel.hip")
-    assert "bd_dynamic_block(" in read("basevarc_amd", "csrc", "bgzf_dynamic_kernel.hip")
+        assert f'#include "{header}"' in template
+    csrc = os.path.join(ROOT, "basevarc_amd", "csrc")
+    texts = {f: read("basevarc_amd", "csrc", f) for f in os.listdir(csrc) if f.endswith((".hip", ".h"))}
+    for call in ("bd_load(", "bd_path(", "BVC_POISON_LDS()", "bd_matches(", "bd_field_matches(", "bd_fixed_block(", "bd_dynamic_block("):
+        assert template.count(call) == 1, call
+    for call in ("bd_load(", "bd_path(", "bd_matches(", "bd_field_matches(", "bd_fixed_block(", "bd_dynamic_block("):
+        # the template, and the device header that defines the pass
+        assert len([f for f, text in texts.items() if call in text]) == 2, call
+    assert "bd_field_matches(" in texts["bgzf_fields_device.h"]
+    for source in ("bgzf_deflate_kernel.hip", "bgzf_dynamic_kernel.hip", "bgzf_fields_kernel.hip"):
+        assert '#include "bgzf_block_kernel.h"' in texts[source]
+        assert "atomicMax(" not in texts[source] and "hash_of(" not in texts[source] and "s_in" not in texts[source]
 
 
 # ---- the model

@@ -1,4 +1,4 @@
-"""The device deflate encoder with tuning key "bgzf_parse" at 1 (bgzf_fields_kernel.hip; GPU), at both values of "bgzf_codes".  The
+"""The device deflate encoder with tuning key "bgzf_parse" at 1 (bgzf_block_kernel<true, *>, bgzf_fields_device.h; GPU), at both values of "bgzf_codes".  The
 pieces of tests/bgzf_fields_cases.py and the catalogue of tests/bgzf_deflate_cases.py go through the block walker, from host and from
 device pointers (device pieces at odd addresses); every block is held, byte for byte, against the encoding
 (tests/bgzf_dynamic_model.encode) of the symbols the plain Python model of the rule gives (tests/bgzf_fields_model.py,

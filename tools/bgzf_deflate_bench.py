@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
-"""bgzf_deflate_kernel alone (bvc_bgzf_deflate, device pointers): the rate at which sample-column text becomes BGZF blocks.
+"""The device deflate encoder alone (bvc_bgzf_deflate, device pointers; bgzf_deflate_kernel.hip): the rate at which sample-column text becomes BGZF blocks.
 
   python tools/bgzf_deflate_bench.py [--samples 100000] [--codes 0|1] [--parse 0|1] [--out profiles/vcf_deflate/kernel.txt]
 
---codes: the context's tuning key "bgzf_codes" (1: bgzf_deflate_dynamic_kernel, each block the smallest of stored, fixed and dynamic).
---parse 1: the tuning key "bgzf_parse" at 1 (the field parse, bgzf_fields_kernel.hip) AGAINST 0 in the same run: every row is timed at
+--codes: the context's tuning key "bgzf_codes" (1: the block kernel's dynamic instantiations, bgzf_block_kernel<*, true>: each block the smallest of stored, fixed and dynamic).
+--parse 1: the tuning key "bgzf_parse" at 1 (the field parse, bgzf_block_kernel<true, *>) AGAINST 0 in the same run: every row is timed at
 both values in turn -- key 0, key 1, key 0, ... -- and key 1's row ends with its time and its size against key 0's.
 
 The texts are the three of tests/bgzf_deflate_cases.py (one called site's sample columns at coverage 0.10, 0.01 and 1.0), each as one
